@@ -1,20 +1,29 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: Mvoxels/s of end-to-end KpSiftAlgorithm on a 512^3 fp32 volume.
 
-    python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]      (N>1: launched by torch.distributed.run)
 
 A "step" is one full CSIFT3D::KpSiftAlgorithm (Gaussian/DoG pyramid, extrema, orientation,
 descriptors) on one synthetic 512^3 volume that is ALREADY resident and normalised in HBM (the
 reference does copy + normalise in the constructor too, outside KpSiftAlgorithm).  With N ranks every
 GPU processes its own 512^3 volume (BASELINE.json configs[4], independent volumes => weak scaling, no
-data-path collective); value = N * 512^3 * K / max-over-ranks time.
+data-path collective); value = N * 512^3 * K / max-over-ranks time, ms_per_step = that time / K.
+
+A plain run does only what that figure needs: set up, warm up, time the K steps, write the outputs if asked, print the JSON line
+(headline fields, the per-stage times of the timed steps and what is derived from them).  --full adds every side measurement below,
+each of which takes runs of its own: the roofline's every-level-built timing and copy ceiling, constructor and GetKeypoints timings,
+the non-aligned / thin / other-parameter legs, the CPU baseline + parity, the matcher and two-volume pipeline, and the slab leg.
+
+--dump-outputs DIR writes what the last timed step computed -- the arrays GetKeypoints() hands a caller -- as DIR/*.npy:
+kp_<field>.npy for every keypoint field (float32; octave and level as float64) and descriptors.npy (float32, keypoints x 768).
+Above 64 MB in all, a fixed seeded sample of keypoint rows is written, with its row numbers in sample_rows.npy.  Rank 0 only.
 
     python bench.py --workload slab [--slab-dims 1024x1024x512] [--sim-ranks R]
 
 times BASELINE.json configs[3] instead: ONE volume sharded as z-slabs over the N ranks (3dsift_amd/slab.py: halo
 exchange + all-reduce over RCCL; strong scaling, N=1 is the plain single-GPU extractor on the whole volume).
 --sim-ranks R runs R simulated ranks on one GPU (functional check / redundancy accounting, not a speed claim).
-A default N>1 run appends the slab measurement as "slab": {...} to its JSON line: "native" (the library's C++ driver, first class),
+A --full N>1 run appends the slab measurement as "slab": {...} to its JSON line: "native" (the library's C++ driver, first class),
 "python" (3dsift_amd/slab.py over torch.distributed), each behind a watchdog and with speedup_vs_n1 against the committed N = 1 record.
 
 The JSON line also carries
@@ -22,12 +31,12 @@ The JSON line also carries
                 (52 B x pyramid voxels: two DoG levels per octave and the last Gaussian level are not built)
                 / HIP-event time of that stage on the library's own stream, against the 8 TB/s HBM3E peak;
                 frac_every_level_built is SURVEY.md 8d's work as defined (every level built and written, 68 B per
-                pyramid voxel), timed in its own runs
+                pyramid voxel), timed in its own runs (--full)
   descriptor    the descriptor stage (half of the step): keypoints/s, window voxels/s, and the VALU-issue roofline
                 of k_describe (wave-instructions from the committed PMC profile of the same kernel sources)
   cpu_baseline  the CPU oracle (our restatement of the reference, OpenMP) timed on this host on a
-                bounded sample of the same workload
-  parity        the GPU result on that sample checked against the oracle
+                bounded sample of the same workload (--full)
+  parity        the GPU result on that sample checked against the oracle (--full)
 """
 import argparse
 import importlib
@@ -226,6 +235,30 @@ def run_slab(dims, world, rank, local, dev, steps, warmup, sim_ranks=0, seed=432
     return res
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # --dump-outputs: all files together, .npy headers included
+DUMP_SAMPLE_SEED = 2024
+
+
+def dump_outputs(dirname, kp, desc):
+    """--dump-outputs: the keypoints and descriptors GetKeypoints() returned, one .npy per keypoint field (float32; the integer fields
+    as float64) + descriptors.npy (float32).  Beyond DUMP_LIMIT_BYTES a fixed seeded sample of the rows, their numbers in sample_rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    cols = {f: (np.float64 if kp.dtype[f].base.kind in "iu" else np.float32) for f in kp.dtype.names}
+    row_bytes = sum(np.dtype(t).itemsize * int(np.prod(kp.dtype[f].shape)) for f, t in cols.items()) + 4 * desc.shape[1]
+    budget = DUMP_LIMIT_BYTES - 256 * (len(cols) + 2)
+    rows_file = os.path.join(dirname, "sample_rows.npy")
+    if len(kp) * row_bytes > budget:
+        k = budget // (row_bytes + 8)
+        rows = np.sort(np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED)).choice(len(kp), k, replace=False))
+        kp, desc = kp[rows], desc[rows]
+        np.save(rows_file, rows.astype(np.float64))
+    elif os.path.exists(rows_file):
+        os.remove(rows_file)
+    for f, t in cols.items():
+        np.save(os.path.join(dirname, f"kp_{f}.npy"), np.ascontiguousarray(kp[f]).astype(t))
+    np.save(os.path.join(dirname, "descriptors.npy"), np.ascontiguousarray(desc, np.float32))
+
+
 def guarded(fn, seconds):
     """run fn() in a thread; (result, None) or (None, reason) when it raised or did not finish in time"""
     import threading
@@ -272,7 +305,12 @@ def main():
     ap.add_argument("--rank-threads", type=int, default=0, help="with --native on ONE GPU: that many rank threads sharing the GPU over the copy transport (the multi-threaded driver without a second GPU)")
     ap.add_argument("--ghost", action="store_true", help="with --native: octave 0 on ghost zones (SIFT3D_SHARDED_GHOST_OCTAVE0): recomputed instead of exchanged level by level")
     ap.add_argument("--whole-windows", action="store_true", help="with --native: whole descriptor windows on the wide plane halos (r05's default)")
+    ap.add_argument("--full", action="store_true", help="also take every side measurement (roofline runs, CPU baseline, parity, other shapes and "
+                                                        "parameters, matcher, slab leg); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (keypoints, descriptors) as DIR/*.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "volumes":
+        ap.error("--dump-outputs applies to the default workload (--workload volumes)")
 
     import torch
 
@@ -335,6 +373,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     dt = s3d_dist.max_over_ranks(dt, device=dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *ex.GetKeypoints())
     kp, _ = ex.GetKeypoints(with_desc=False)
     nkp = len(kp)
     next_ = len(ex.extrema())
@@ -389,25 +429,26 @@ def main():
     # ... and SURVEY 8d's work AS DEFINED, timed ("work moved out of the timed region earns no credit" -- the default
     # build leaves G[nd], DoG[0] and DoG[nd-1] to the detection stage): the same extractor with every Gaussian and DoG level built and
     # written (hooks glast_eager + dog_eager), its pyramid stage against the 68 B per pyramid voxel of that accounting.
-    try:
-        if not (rank == 0 and world == 1):
-            raise RuntimeError("measured at N = 1 only")
-        with capi.hook("glast_eager", 1), capi.hook("dog_eager", 1):
-            exe = capi.CSIFT3D(None, device=local, device_ptr=vol.data_ptr(), shape=(n, n, n))
-            te = []
-            for _ in range(2 + 5):
-                exe.run_stages(1)
-                te.append(exe.m_timer["d_BuildGSS"] + exe.m_timer["d_BuildDOG"])
-            exe.close()
-        t_eager = float(np.median(te[2:]))
-        # scalars of the roofline object itself, so that the as-defined figure travels wherever the line's roofline is quoted
-        out["roofline"]["frac_every_level_built"] = 68.0 * pv / t_eager / 1e9 / HBM_PEAK_GBS
-        out["roofline"]["seconds_every_level_built"] = t_eager
-        out["roofline"]["bytes_every_level_built"] = 68.0 * pv
-        out["roofline"]["every_level_built_note"] = ("all 6 Gaussian + 5 DoG levels of every octave built and written (hooks glast_eager, dog_eager): "
-                                                     "SURVEY 8d's 68 B per pyramid voxel with nothing deferred to detection")
-    except Exception as e:  # noqa: BLE001 -- a side measurement
-        out["roofline"]["every_level_built_note"] = f"not measured: {type(e).__name__}: {e}"
+    if args.full:
+        try:
+            if not (rank == 0 and world == 1):
+                raise RuntimeError("measured at N = 1 only")
+            with capi.hook("glast_eager", 1), capi.hook("dog_eager", 1):
+                exe = capi.CSIFT3D(None, device=local, device_ptr=vol.data_ptr(), shape=(n, n, n))
+                te = []
+                for _ in range(2 + 5):
+                    exe.run_stages(1)
+                    te.append(exe.m_timer["d_BuildGSS"] + exe.m_timer["d_BuildDOG"])
+                exe.close()
+            t_eager = float(np.median(te[2:]))
+            # scalars of the roofline object itself, so that the as-defined figure travels wherever the line's roofline is quoted
+            out["roofline"]["frac_every_level_built"] = 68.0 * pv / t_eager / 1e9 / HBM_PEAK_GBS
+            out["roofline"]["seconds_every_level_built"] = t_eager
+            out["roofline"]["bytes_every_level_built"] = 68.0 * pv
+            out["roofline"]["every_level_built_note"] = ("all 6 Gaussian + 5 DoG levels of every octave built and written (hooks glast_eager, dog_eager): "
+                                                         "SURVEY 8d's 68 B per pyramid voxel with nothing deferred to detection")
+        except Exception as e:  # noqa: BLE001 -- a side measurement
+            out["roofline"]["every_level_built_note"] = f"not measured: {type(e).__name__}: {e}"
     # ---- descriptor stage (keypoints/s and window-voxels/s, not an HBM fraction) + the VALU-issue roofline of k_describe
     if stage["d_Extraction"] > 0 and nkp:
         wv = descriptor_window_voxels(kp)
@@ -433,7 +474,7 @@ def main():
         out["descriptor"] = dsc
     out["debug_counters"] = ex.debug_counters()
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # ---- measured device-copy ceiling beside the spec peak: the library's float4 copy kernel on 1 GiB, read + write counted
         # (the MI355X guide measures 6.29 TB/s with such a kernel)
         copy_gbs = capi.copy_bandwidth(1 << 30, 5, local)
@@ -461,7 +502,7 @@ def main():
                                    "GBs": round(nkp * (768 * 4 + 168) / min(tg) / 1e9, 1),
                                    "into_freshly_allocated_arrays": round(min(tg2) * 1e3, 3),
                                    "note": "sift3d_get_keypoints into arrays the caller has touched; the second figure adds the page faults of two new numpy arrays"}
-    if rank == 0 and world == 1 and not args.no_nonaligned:
+    if args.full and rank == 0 and world == 1 and not args.no_nonaligned:
         # ---- a volume whose width and height are NOT multiples of the 32 x 32 tile of the level kernel (not part of `value`): the
         # pyramid stage priced like the headline's, per pyramid voxel
         def leg(dims, **params):
@@ -510,7 +551,7 @@ def main():
                                                 "pyramid_ns_per_voxel_vs_headline": lg["pyramid_ns_per_pyramid_voxel"] / (t_pyr / pv * 1e9)}
             except Exception as e:  # noqa: BLE001 -- a side leg
                 out["other_parameters"][tag] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_cpu and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and args.cpu_sample > 0:
         # ---- CPU baseline + parity on a bounded sample: the [0:s]^3 crop of the same volume ----
         import oracle_lib as ol  # test infrastructure, used here ONLY as the timed baseline / checker
 
@@ -579,7 +620,7 @@ def main():
         out["parity"] = {"sample_keypoints_gpu": len(gkp), "sample_keypoints_cpu": len(okp), "same_keypoint_set": bool(same),
                          "descriptor_rms": rms, "worst_keypoint_rms": worst_kp, "worst_element_abs": worst_abs,
                          "bars": "2e-5 RMS per keypoint, 1e-4 per element (tests/hipcheck.py)"}
-    if rank == 0 and world == 1 and not args.no_match:
+    if args.full and rank == 0 and world == 1 and not args.no_match:
         # ---- BASELINE configs[2] leg (not part of `value`): second volume = the same blobs shifted by one voxel in x,
         # extract, then muBruteMatcher::enhancedMatch on the device-resident descriptors; the score GEMM is the one MFMA
         # kernel of the path (v_mfma_f32_32x32x2_f32), priced against the dense f32 matrix peak
@@ -676,14 +717,14 @@ def main():
                                "rank0_matched": npairs}
     slab_attempted, slab_err = False, None
     SLAB_STEPS, SLAB_WARMUP = 10, 3
-    if world == 1 and rank == 0 and not args.no_slab_leg:
+    if args.full and world == 1 and rank == 0 and not args.no_slab_leg:
         # BASELINE configs[3] at N = 1: the same 1024x1024x512 volume on ONE GPU through the plain extractor -- the denominator of the
         # 1 -> N speed-up the north star asks for, in the default driver record (r04; VERDICT r03 missing #2)
         ex.close(); del vol
         torch.cuda.empty_cache()
         res, slab_err = guarded(lambda: run_slab(parse_dims(args.slab_dims), 1, 0, local, dev, SLAB_STEPS, SLAB_WARMUP), 240)
         out["slab"] = dict(res, n=1, steps=SLAB_STEPS, warmup=SLAB_WARMUP) if slab_err is None else {"error": slab_err}
-    if world > 1 and not args.no_slab_leg:
+    if args.full and world > 1 and not args.no_slab_leg:
         # BASELINE configs[3] next to the headline number: one 1024x1024x512 volume over the same GPUs.  No multi-GPU box exists in development:
         # every leg runs behind a watchdog and, whatever happens, the headline line is printed.
         #   slab.native (first class since r06)  the library's own driver (csrc/sharded.hip): one process, one host thread per GPU, RCCL

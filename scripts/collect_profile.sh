@@ -25,10 +25,10 @@ k["kernel_source_sha"] = j["kernel_source_sha"]
 json.dump(k, open(sys.argv[2], "w"), indent=1)
 PY
 cp $REPO/profiles/pmc_k_describe_512.json $OUT/${TAG}_pmc_k_describe_512.json
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -- python3 $REPO/bench.py --steps 5 --warmup 2 --cpu-sample 0 > $OUT/${TAG}_bench_under_rocprof.json 2> /tmp/prof_$TAG.err || true
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -- python3 $REPO/bench.py --full --steps 5 --warmup 2 --cpu-sample 0 > $OUT/${TAG}_bench_under_rocprof.json 2> /tmp/prof_$TAG.err || true
 f=$(find /tmp/prof_$TAG -name "*kernel_stats.csv" | head -1)
 cp "$f" $OUT/${TAG}_rocprofv3_kernel_stats.csv
-python3 $REPO/bench.py > $OUT/${TAG}_bench.json 2> /dev/null
+python3 $REPO/bench.py --full > $OUT/${TAG}_bench.json 2> /dev/null
 # the N = 1 record of configs[3] (the bench line's "slab" block) stamped with the kernel sources: a --gpus N run forms slab.speedup_vs_1gpu from it
 python3 - $OUT/${TAG}_bench.json $REPO/profiles/slab_1gpu.json $REPO <<'PY'
 import importlib, json, sys

@@ -27,16 +27,6 @@ def orc():
 
 
 @pytest.fixture(scope="session")
-def ref():
-    """The real reference (only where oracle/_ref was built, i.e. where /root/reference exists)."""
-    import oracle_lib as ol
-
-    if not ol.available("ref"):
-        pytest.skip("oracle/_ref/libref3dsift.so not built (no /root/reference on this machine)")
-    return ol.load("ref")
-
-
-@pytest.fixture(scope="session")
 def synth():
     import importlib
 

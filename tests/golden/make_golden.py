@@ -28,8 +28,10 @@ Fixture inventory (the reference has no golden vec
                     float arrays the reference's readNiiFile (oracle/_ref/librefnii.so) returns for them
 
   g10_sift_kp.npz   a key-point coordinate list written by the reference's write_sift_kp and read back by its read_sift_kp (8f-4)
+  g11_vs_ref.npz    the reference's results on the fresh seeded inputs of tests/test_oracle_vs_ref.py: level hashes, extrema,
+                    keypoints + descriptors (three pipelines, one wide-kernel run) and muBruteMatcher on stored descriptor sets
 
-    python tests/golden/make_golden.py g1 g9 g10     # only these
+    python tests/golden/make_golden.py g1 g9 g10 g11     # only these
 """
 import hashlib
 import importlib
@@ -218,6 +220,78 @@ def make_g10():
     print("g10:", len(xyz), "points,", len(blob), "bytes; first lines:", blob.decode().splitlines()[:2], "last:", blob.decode().splitlines()[-1])
 
 
+G11_PIPELINE = [((36, 44, 52), 21, 0.02), ((64, 32, 48), 22, 0.0), ((17, 33, 20), 23, 0.05)]
+G11_WIDE = dict(shape=(96, 100, 104), seed=41, noise=0.02, params=dict(num_kp_levels=1, sigma_default=2.1))
+G11_MATCH = dict(shape=(48, 48, 48), seed=31, shift=(0.0, 1.0, 0.0), modes=(1, 2, 3), thresholds=(0.7, 0.85, 1.0))
+
+
+def g11_level_hashes(ex, octaves, ngss, ndog, crop):
+    """sha256 of the bits of every Gaussian / DoG level; crop=True drops the [1:-1]^3 shell of the last level of an octave of <= 9
+    voxels on a side, which the reference reads out of bounds (undefined there)"""
+    h = []
+    for o in range(octaves):
+        for kind, n, get in (("gss", ngss, ex.gss), ("dog", ndog, ex.dog)):
+            for i in range(n):
+                lv = np.ascontiguousarray(get(o, i), np.float32)
+                shell = crop and min(lv.shape) <= 9 and i == n - 1
+                h.append(f"{kind}_{o}_{i}:" + interior_mask_hash(lv.view(np.uint32), shell))
+    return np.array(h)
+
+
+G11_EXTREMA_FIELDS = ("x", "y", "z", "scale", "octave", "level")
+
+
+def g11_extrema(e):
+    """the fields an extremum has when the extrema list is built (the reference leaves the others uninitialised at that stage)"""
+    out = np.zeros(len(e), [(f, e.dtype[f]) for f in G11_EXTREMA_FIELDS])
+    for f in G11_EXTREMA_FIELDS:
+        out[f] = e[f]
+    return out
+
+
+def make_g11(ref):
+    """G11: the reference's results on the inputs of tests/test_oracle_vs_ref.py (fresh seeded volumes beyond G3..G8): level hashes,
+    extrema, keypoints + descriptors of three full pipelines and of a wide-kernel one (octaves 0 and 1), and muBruteMatcher on descriptor
+    sets of our restatement (stored: the inputs the reference matched)."""
+    orc = ol.load("orc")
+    g = {}
+    for j, (shape, seed, noise) in enumerate(G11_PIPELINE):
+        vol = synth.blobs(shape, seed=seed, noise=noise)
+        ex = ref.extractor(vol).run(5)
+        g[f"p{j}_vol_sha"] = sha(vol)
+        g[f"p{j}_noct"] = np.int32(ex.num_octaves)
+        g[f"p{j}_hashes"] = g11_level_hashes(ex, ex.num_octaves, 6, 5, crop=True)
+        g[f"p{j}_extrema"] = g11_extrema(ex.extrema())
+        g[f"p{j}_kp"], g[f"p{j}_desc"] = ex.keypoints()
+        ex.close()
+    w = G11_WIDE
+    vol = synth.blobs(w["shape"], seed=w["seed"], noise=w["noise"])
+    ex = ref.extractor(vol, **w["params"]).run(5)
+    g["w_vol_sha"] = sha(vol)
+    g["w_noct"] = np.int32(ex.num_octaves)
+    g["w_hashes"] = g11_level_hashes(ex, 2, 4, 3, crop=False)
+    e = ex.extrema()
+    g["w_extrema"] = g11_extrema(e[e["octave"] < 2])
+    kp, desc = ex.keypoints()
+    m = kp["octave"] < 2
+    g["w_kp"], g["w_desc"] = kp[m], desc[m]
+    ex.close()
+    m = G11_MATCH
+    va = synth.blobs(m["shape"], seed=m["seed"])
+    vb = synth.blobs(m["shape"], seed=m["seed"], shift=m["shift"])
+    ka, da = orc.extractor(va).run(5).keypoints()
+    kb, db = orc.extractor(vb).run(5).keypoints()
+    xa = np.stack([ka["rx"], ka["ry"], ka["rz"]], 1)
+    xb = np.stack([kb["rx"], kb["ry"], kb["rz"]], 1)
+    g.update(m_da=da, m_xa=xa, m_db=db, m_xb=xb)
+    for mode in m["modes"]:
+        for thr in m["thresholds"]:
+            for k, v in ref.match(da, xa, db, xb, thr, mode).items():
+                g[f"m_m{mode}_t{int(round(thr * 100))}_{k}"] = v
+    np.savez_compressed(os.path.join(HERE, "g11_vs_ref.npz"), **g)
+    print("g11:", ", ".join(f"p{j} {len(g[f'p{j}_kp'])} kp" for j in range(len(G11_PIPELINE))), f"; wide {len(g['w_kp'])} kp; match {len(da)} x {len(db)}")
+
+
 def main():
     only = set(sys.argv[1:])
     ref = ol.load("ref")
@@ -228,7 +302,9 @@ def main():
         make_g9()
     if not only or "g10" in only:
         make_g10()
-    if only and not (only - {"g1", "g9", "g10"}):
+    if not only or "g11" in only:
+        make_g11(ref)
+    if only and not (only - {"g1", "g9", "g10", "g11"}):
         return
     out = {}
 

@@ -1,7 +1,7 @@
 """The C++ drop-in shell (3dsift_amd/host, namespace CPUSIFT) and its loaders.
 
-CPU: it builds, the reference's own Example.cpp compiles and links UNCHANGED against our headers
-(only where /root/reference exists), readNiiFile / ReadMatrixFromDisk parse files written by numpy.
+CPU: it builds, a caller written with the include paths and calls of the reference's demo compiles and links against our
+headers, readNiiFile / ReadMatrixFromDisk parse files written by numpy.
 GPU: the demo program runs the reference's flow end to end (extract x2 -> enhancedMatch)."""
 import ctypes as C
 import gzip
@@ -25,14 +25,54 @@ def shell():
     return C.CDLL(os.path.join(PKG, "libsift3d.so"))
 
 
+# A caller written the way the reference's demo program is: its three include paths, resolved from the root of the header tree
+# (-I3dsift_amd/host), and the calls of its flow -- readNiiFile, CSIFT3DFactory::CreateCSIFT3D, KpSiftAlgorithm, GetKeypoints,
+# muBruteMatcher::enhancedMatch, delete[] of the volumes and delete of the extractors.
+USER_PROGRAM = r"""
+#include "Include/cSIFT3D.h"
+#include "Include/Util/readNii.h"
+#include "Include/cMatcher.h"
+#include <cstdio>
+#include <vector>
+
+int main(int argc, char **argv) {
+    if (argc < 3) return 2;
+    int nx, ny, nz, mx, my, mz;
+    float *ref = readNiiFile(argv[1], nx, ny, nz);
+    if (!ref) return 1;
+    float *tar = readNiiFile(argv[2], mx, my, mz);
+    if (!tar) { delete[] ref; return 1; }
+    auto sift_ref = CPUSIFT::CSIFT3DFactory::CreateCSIFT3D(ref, nx, ny, nz);
+    sift_ref->KpSiftAlgorithm();
+    std::vector<CPUSIFT::Keypoint> kp_ref = sift_ref->GetKeypoints();
+    CPUSIFT::CSIFT3D *sift_tar = CPUSIFT::CSIFT3DFactory::CreateCSIFT3D(tar, mx, my, mz);
+    sift_tar->KpSiftAlgorithm();
+    auto kp_tar = sift_tar->GetKeypoints();
+    CPUSIFT::muBruteMatcher matcher;
+    std::vector<CPUSIFT::Cvec> ref_xyz, tar_xyz;
+    const float threshold = 0.85f;
+    matcher.enhancedMatch(ref_xyz, tar_xyz, kp_ref, kp_tar, threshold);
+    printf("%zu %zu %zu\n", kp_ref.size(), kp_tar.size(), ref_xyz.size());
+    delete[] ref;
+    delete[] tar;
+    delete sift_ref;
+    delete sift_tar;
+    return 0;
+}
+"""
+
+
 def test_reference_example_compiles_unchanged(shell):
-    src = "/root/reference/3DSIFT/Example.cpp"
-    if not os.path.exists(src):
-        pytest.skip("reference tree not present on this machine")
+    """A user's unchanged code compiles and links against OUR header tree: the include paths and calls of the reference's demo
+    (USER_PROGRAM above), built the way INTEGRATION.md tells its users to.  Run on files that do not exist it must stop at
+    readNiiFile (exit code 1): the program loads against the two libraries and the reader reports the failure."""
     with tempfile.TemporaryDirectory() as t:
-        os.symlink(src, os.path.join(t, "Example.cpp"))  # so "Include/..." resolves to OUR headers, not the reference's
-        subprocess.check_call(["g++", "-std=c++14", "-I" + os.path.join(PKG, "host"), "-o", os.path.join(t, "a.out"),
-                               os.path.join(t, "Example.cpp"), "-L" + PKG, "-lsift3d", "-lsift3d_hip", "-Wl,-rpath," + PKG])
+        src, exe = os.path.join(t, "Example.cpp"), os.path.join(t, "a.out")
+        open(src, "w").write(USER_PROGRAM)
+        subprocess.check_call(["g++", "-std=c++14", "-I" + os.path.join(PKG, "host"), "-o", exe,
+                               src, "-L" + PKG, "-lsift3d", "-lsift3d_hip", "-Wl,-rpath," + PKG])
+        r = subprocess.run([exe, os.path.join(t, "missing_a.nii"), os.path.join(t, "missing_b.nii")], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 1, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
 
 
 def nifti1(vol, dtype, code, big_endian=False):

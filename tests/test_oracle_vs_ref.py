@@ -1,34 +1,53 @@
-"""CPU tests, only where /root/reference was compiled into oracle/_ref: our restatement against
-the untouched reference on fresh seeded inputs (beyond the committed goldens)."""
+"""CPU tests: our restatement against what the untouched reference produced on fresh seeded inputs (beyond the other goldens).
+The reference's results are stored in tests/golden/g11_vs_ref.npz (tests/golden/make_golden.py g11): level hashes, extrema,
+keypoints, descriptors and matcher outputs, compared bit for bit."""
+import hashlib
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+from make_golden import G11_MATCH, G11_PIPELINE, G11_WIDE, g11_level_hashes  # noqa: E402
+
+from conftest import golden  # noqa: E402
 
 
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-@pytest.mark.parametrize("shape,seed,noise", [((36, 44, 52), 21, 0.02), ((64, 32, 48), 22, 0.0), ((17, 33, 20), 23, 0.05)])
-def test_full_pipeline_matches_reference(orc, ref, synth, shape, seed, noise):
+def sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+@pytest.fixture(scope="module")
+def g11():
+    return golden("g11_vs_ref.npz")
+
+
+def check_hashes(got, want):
+    assert len(got) == len(want)
+    for h, w in zip(got, want):
+        assert h == w, h.split(":")[0]
+
+
+@pytest.mark.parametrize("shape,seed,noise", G11_PIPELINE)
+def test_full_pipeline_matches_reference(orc, synth, g11, shape, seed, noise):
+    p = f"p{G11_PIPELINE.index((shape, seed, noise))}_"
     vol = synth.blobs(shape, seed=seed, noise=noise)
-    a = ref.extractor(vol).run(5)
+    assert sha(vol) == str(g11[p + "vol_sha"])
     b = orc.extractor(vol).run(5)
-    assert a.num_octaves == b.num_octaves
-    for o in range(a.num_octaves):
-        for i in range(6):
-            ga, gb = a.gss(o, i), b.gss(o, i)
-            if min(ga.shape) <= 9 and i == 5:  # reference reads out of bounds there (undefined shell)
-                ga, gb = ga[1:-1, 1:-1, 1:-1], gb[1:-1, 1:-1, 1:-1]
-            assert np.array_equal(bits(ga), bits(gb)), ("gss", o, i)
-        for i in range(5):
-            da, db = a.dog(o, i), b.dog(o, i)
-            if min(da.shape) <= 9 and i == 4:
-                da, db = da[1:-1, 1:-1, 1:-1], db[1:-1, 1:-1, 1:-1]
-            assert np.array_equal(bits(da), bits(db)), ("dog", o, i)
-    ea, eb = a.extrema(), b.extrema()
+    assert b.num_octaves == int(g11[p + "noct"])
+    # every Gaussian / DoG level (the [1:-1]^3 interior of the last level of an octave of <= 9 voxels: the reference reads out of
+    # bounds there)
+    check_hashes(g11_level_hashes(b, b.num_octaves, 6, 5, crop=True), g11[p + "hashes"])
+    ea, eb = g11[p + "extrema"], b.extrema()
+    assert len(ea) == len(eb)
     for f in ("x", "y", "z", "scale", "octave", "level"):
         assert np.array_equal(ea[f], eb[f]), f
-    ka, da_ = a.keypoints()
+    ka, da_ = g11[p + "kp"], g11[p + "desc"]
     kb, db_ = b.keypoints()
     assert len(ka) == len(kb)
     for f in ("x", "y", "z", "scale", "octave", "level", "rx", "ry", "rz", "win", "eigvalue", "Rotation", "str_tensor"):
@@ -36,46 +55,49 @@ def test_full_pipeline_matches_reference(orc, ref, synth, shape, seed, noise):
     assert np.array_equal(bits(da_), bits(db_))
 
 
-def test_wide_kernels_match_reference(orc, ref, synth):
+def test_wide_kernels_match_reference(orc, synth, g11):
     """num_kp_levels = 1 with a wide sigma: Gaussian kernels of up to 89 taps (the product accepts up to 129 since late r04; the
     restatement had a 64-tap buffer).  Octaves 0 and 1 (lines of at least 48 voxels): pyramid, extrema and keypoints of the restatement
     against the untouched reference.  From octave 2 on the kernel (hw 44) is wider than the line and the reference reads out of bounds
     -- undefined there, like its 8^3 octaves with the default parameters -- so those octaves are not compared."""
-    vol = synth.blobs((96, 100, 104), seed=41, noise=0.02)
-    params = dict(num_kp_levels=1, sigma_default=2.1)
-    a = ref.extractor(vol, **params).run(5)
-    b = orc.extractor(vol, **params).run(5)
-    assert a.num_octaves == b.num_octaves and a.num_octaves >= 2
-    for o in range(2):
-        for i in range(4):
-            assert np.array_equal(bits(a.gss(o, i)), bits(b.gss(o, i))), ("gss", o, i)
-        for i in range(3):
-            assert np.array_equal(bits(a.dog(o, i)), bits(b.dog(o, i))), ("dog", o, i)
-    ea, eb = a.extrema(), b.extrema()
-    ea, eb = ea[ea["octave"] < 2], eb[eb["octave"] < 2]
+    w = G11_WIDE
+    vol = synth.blobs(w["shape"], seed=w["seed"], noise=w["noise"])
+    assert sha(vol) == str(g11["w_vol_sha"])
+    b = orc.extractor(vol, **w["params"]).run(5)
+    assert b.num_octaves == int(g11["w_noct"]) and b.num_octaves >= 2
+    check_hashes(g11_level_hashes(b, 2, 4, 3, crop=False), g11["w_hashes"])
+    ea, eb = g11["w_extrema"], b.extrema()
+    eb = eb[eb["octave"] < 2]
     assert len(ea) == len(eb) and len(ea) > 0
     for f in ("x", "y", "z", "scale", "octave", "level"):
         assert np.array_equal(ea[f], eb[f]), f
-    ka, da_ = a.keypoints()
+    ka, da_ = g11["w_kp"], g11["w_desc"]
     kb, db_ = b.keypoints()
-    ma, mb = ka["octave"] < 2, kb["octave"] < 2
-    ka, da_, kb, db_ = ka[ma], da_[ma], kb[mb], db_[mb]
+    mb = kb["octave"] < 2
+    kb, db_ = kb[mb], db_[mb]
     assert len(ka) == len(kb)
     for f in ("x", "y", "z", "scale", "octave", "level", "rx", "ry", "rz", "win", "eigvalue", "Rotation", "str_tensor"):
         assert np.array_equal(ka[f], kb[f]), f
     assert np.array_equal(bits(da_), bits(db_))
 
 
-def test_matcher_matches_reference(orc, ref, synth):
-    va = synth.blobs((48, 48, 48), seed=31)
-    vb = synth.blobs((48, 48, 48), seed=31, shift=(0.0, 1.0, 0.0))
+def test_matcher_matches_reference(orc, synth, g11):
+    m = G11_MATCH
+    va = synth.blobs(m["shape"], seed=m["seed"])
+    vb = synth.blobs(m["shape"], seed=m["seed"], shift=m["shift"])
     ka, da = orc.extractor(va).run(5).keypoints()
     kb, db = orc.extractor(vb).run(5).keypoints()
     xa = np.stack([ka["rx"], ka["ry"], ka["rz"]], 1)
     xb = np.stack([kb["rx"], kb["ry"], kb["rz"]], 1)
     assert len(ka) > 5 and len(kb) > 5
-    for mode in (1, 2, 3):
-        for thr in (0.7, 0.85, 1.0):
-            r, o = ref.match(da, xa, db, xb, thr, mode), orc.match(da, xa, db, xb, thr, mode)
-            for k in r:
-                assert np.array_equal(r[k], o[k]), (mode, thr, k)
+    # the descriptor sets the reference matched are the restatement's of these volumes
+    for got, key in ((da, "m_da"), (xa, "m_xa"), (db, "m_db"), (xb, "m_xb")):
+        assert np.array_equal(bits(got), bits(g11[key])), key
+    for mode in m["modes"]:
+        for thr in m["thresholds"]:
+            o = orc.match(da, xa, db, xb, thr, mode)
+            pre = f"m_m{mode}_t{int(round(thr * 100))}_"
+            keys = [k[len(pre):] for k in g11.files if k.startswith(pre)]
+            assert keys
+            for k in keys:
+                assert np.array_equal(g11[pre + k], o[k]), (mode, thr, k)
