@@ -36,6 +36,8 @@ SYMBOLS = [
     "sift3d_get_extrema", "sift3d_get_orientation_codes", "sift3d_gaussian_smooth", "sift3d_downsample", "sift3d_dog_sub", "sift3d_conv_axis",
     "sift3d_orient_keypoint", "sift3d_describe_keypoint", "sift3d_match",
     "sift3d_match_handles",
+    # detection options: the 80-neighbour rule and the sub-voxel refinement
+    "sift3d_default_detect_options", "sift3d_set_detect_options", "sift3d_get_detect_options", "sift3d_get_refined",
     "sift3d_device_count", "sift3d_error_string", "sift3d_last_error",
     # multi-GPU sharding (z-slabs of octave 0 + seeded replicated tail)
     "sift3d_slab_min_halo", "sift3d_slab_arena_floats", "sift3d_slab_create", "sift3d_slab_buffer", "sift3d_slab_upload",
@@ -71,6 +73,19 @@ SHARDED_GHOST_OCTAVE0 = 8
 class Params(C.Structure):
     _fields_ = [("num_kp_levels", C.c_int), ("sigma_default", C.c_float), ("sigma_n_default", C.c_float),
                 ("peak_thresh", C.c_float), ("max_eig_thres", C.c_float), ("corner_thresh", C.c_float)]
+
+
+class DetectOptions(C.Structure):
+    """sift3d_detect_options (include/sift3d_hip.h)"""
+    _fields_ = [("neighbours", C.c_int), ("refine", C.c_int), ("max_offset", C.c_float), ("contrast_thresh", C.c_float),
+                ("edge_ratio", C.c_float), ("reserved", C.c_int * 3)]
+
+
+assert C.sizeof(DetectOptions) == 32
+
+# sift3d_refined: refined coordinates / scale, the fit's offset (dx, dy, dz, ds) and D(x^)
+REFINED_DTYPE = np.dtype([("rx", "<f4"), ("ry", "<f4"), ("rz", "<f4"), ("scale", "<f4"), ("offset", "<f4", (4,)), ("contrast", "<f4")])
+assert REFINED_DTYPE.itemsize == 36
 
 
 class SlabDesc(C.Structure):
@@ -129,6 +144,11 @@ def lib():
                                    C.c_int, C.c_int, _ip, _ip, _fp, _fp, _fp, _ip, C.POINTER(C.c_double)]
         L.sift3d_match_handles.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int, _ip, _ip, _fp, _fp, _fp, _ip, C.POINTER(C.c_double)]
         L.sift3d_device_count.argtypes = [_ip]
+        L.sift3d_default_detect_options.argtypes = [C.POINTER(DetectOptions)]
+        L.sift3d_default_detect_options.restype = None
+        L.sift3d_set_detect_options.argtypes = [C.c_void_p, C.POINTER(DetectOptions)]
+        L.sift3d_get_detect_options.argtypes = [C.c_void_p, C.POINTER(DetectOptions)]
+        L.sift3d_get_refined.argtypes = [C.c_void_p, C.c_void_p]
         _sz = C.POINTER(C.c_size_t)
         L.sift3d_slab_min_halo.argtypes = [C.POINTER(Params), _ip]
         L.sift3d_slab_arena_floats.argtypes = [C.POINTER(SlabDesc), C.POINTER(Params), _sz]
@@ -251,6 +271,18 @@ def face_lookup(grad3, route=0, device=0):
     face = np.zeros(len(g), np.int32); bary = np.zeros((len(g), 3), np.float32)
     _check(lib().sift3d_debug_face_lookup(_f(g), len(g), int(route), face.ctypes.data_as(_ip), _f(bary), device))
     return face, bary
+
+
+def default_detect_options():
+    """sift3d_default_detect_options as a dict (needs no GPU)"""
+    o = DetectOptions()
+    lib().sift3d_default_detect_options(C.byref(o))
+    return _options_dict(o)
+
+
+def _options_dict(o):
+    return {"neighbours": o.neighbours, "refine": bool(o.refine), "max_offset": o.max_offset, "contrast_thresh": o.contrast_thresh,
+            "edge_ratio": o.edge_ratio}
 
 
 def device_count():
@@ -391,6 +423,27 @@ class CSIFT3D:
     def export_device(self, desc_ptr, xyz_ptr=None):
         """D2D copy of the results into caller-owned device buffers (n*768, n*3 floats)"""
         _check(lib().sift3d_export_device(self._h, C.c_void_p(int(desc_ptr)), C.c_void_p(int(xyz_ptr)) if xyz_ptr else None))
+
+    # --- detection options (no reference counterpart; include/sift3d_hip.h, sift3d_set_detect_options) -----------------------
+    def set_detect_options(self, neighbours=8, refine=False, max_offset=0.5, contrast_thresh=0.0, edge_ratio=0.0):
+        """the extremum rule of the next run: neighbours 8 (the reference's, default) or 80; refine: sub-voxel quadratic fit with its
+        rejection tests.  Raises Sift3dError on a refusal (bad values, a run in flight, a slab / seeded handle)."""
+        o = DetectOptions(int(neighbours), int(refine), float(max_offset), float(contrast_thresh), float(edge_ratio))
+        _check(lib().sift3d_set_detect_options(self._h, C.byref(o)))
+        return self
+
+    def detect_options(self):
+        o = DetectOptions()
+        _check(lib().sift3d_get_detect_options(self._h, C.byref(o)))
+        return _options_dict(o)
+
+    def refined(self):
+        """REFINED_DTYPE records of the last run's keypoints, GetKeypoints() order (the run must have had refine on)"""
+        n = C.c_int(0)
+        _check(lib().sift3d_num_keypoints(self._h, C.byref(n)))
+        out = np.zeros(max(n.value, 1), REFINED_DTYPE)  # (the call checks its state even for zero keypoints)
+        _check(lib().sift3d_get_refined(self._h, out.ctypes.data))
+        return out[:n.value]
 
     def debug_counters(self):
         """{list_regrows, desc_second_passes, match_exact_rows}: how often the rare paths ran (sift3d_debug_counters)"""

@@ -45,6 +45,7 @@ static void free_lists(sift3d_ctx *c) {
 	hipFree(c->d_prov); c->d_prov = nullptr;
 	hipFree(c->d_prov2); c->d_prov2 = nullptr;
 	hipFree(c->dsplit.gacc); c->dsplit = DescSplit{};
+	hipFree(c->d_refined); c->d_refined = nullptr; c->refined_cap = 0;
 }
 
 int alloc_lists(sift3d_ctx *c, unsigned ext_cap) {
@@ -99,6 +100,17 @@ extern "C" void sift3d_default_params(sift3d_params *p) {
 	p->peak_thresh = 0.1f;
 	p->max_eig_thres = 0.9f;
 	p->corner_thresh = 0.4f;
+}
+
+// No reference counterpart (generalises IsExtrema_neighbor, Src/cSIFT3D.cc:884-911): the reference's 8-neighbour rule, no fit
+extern "C" void sift3d_default_detect_options(sift3d_detect_options *o) {
+	if (!o) return;
+	memset(o, 0, sizeof(*o));
+	o->neighbours = 8;
+	o->refine = 0;
+	o->max_offset = 0.5f;
+	o->contrast_thresh = 0.0f;
+	o->edge_ratio = 0.0f;
 }
 
 extern "C" int sift3d_device_count(int *n) {
@@ -241,6 +253,7 @@ int create_common(sift3d_handle *out, const CreateCfg &cfg, const sift3d_params 
 	sift3d_ctx *c = new sift3d_ctx();
 	c->device = device;
 	if (params) c->p = *params; else sift3d_default_params(&c->p);
+	sift3d_default_detect_options(&c->dopt);
 	if (c->p.num_kp_levels < 1 || c->p.num_kp_levels > 5) { delete c; set_last_error("num_kp_levels must be in [1,5]"); return SIFT3D_ERR_ARG; }
 	c->nx = cfg.nx; c->ny = cfg.ny; c->nz = cfg.nz;
 	c->octave_base = cfg.octave_base; c->seeded = cfg.seeded;
@@ -514,6 +527,11 @@ static int run_prepare(sift3d_ctx *c, int &upto) {
 	// it is not built at all; those voxels get the value from k_lazy_next (DetectLevels::lazy_src).  SIFT3D_HOOK_GLAST_EAGER builds it.
 	const bool glast_eager = hook(SIFT3D_HOOK_GLAST_EAGER) != 0;
 	c->g_last_elide = c->dog_elide && !glast_eager && c->use_fused && 2 * (2 * c->taps[c->ng - 1].hw + 1) <= kLazySlots;
+	// detection options (sift3d_set_detect_options): the full neighbourhood and the fit read 3x3 blocks of DoG[0] and DoG[nd-1], so
+	// such a run builds every level; a default handle keeps the elisions above unchanged
+	c->run_full = c->dopt.neighbours == 80 || c->dopt.refine != 0;
+	c->run_refine = c->dopt.refine != 0;
+	if (c->run_full) { c->dog_elide = false; c->g_last_elide = false; }
 	c->g_last_built.assign((size_t)std::max(1, c->noct), 0);
 	c->n_regrow = 0;
 	return SIFT3D_OK;
@@ -523,6 +541,11 @@ static int run_enqueue(sift3d_ctx *c, int upto, bool part_orient) {
 	int rc = set_device(c->device);
 	if (rc) return rc;
 	hipStream_t st = c->stream;
+	if (c->run_refine && upto >= 4 && c->refined_cap < c->kp_cap) {  // (first refining run, or the lists were regrown)
+		hipFree(c->d_refined); c->d_refined = nullptr; c->refined_cap = 0;
+		S3D_HIP(hipMalloc(&c->d_refined, sizeof(sift3d_refined) * (size_t)c->kp_cap));
+		c->refined_cap = c->kp_cap;
+	}
 	if (c->dsplit_dirty && c->dsplit.gacc) {  // (a run cut short by an error may have left partial sums / arrival counts behind)
 		S3D_HIP(hipMemsetAsync(c->dsplit.gacc, 0, sizeof(int) * (size_t)c->dsplit.cap * (kDesc + 8 + 1), st));
 		c->dsplit_dirty = false;
@@ -678,6 +701,10 @@ static int run_enqueue(sift3d_ctx *c, int upto, bool part_orient) {
 		std::vector<DetectLevels> DLs((size_t)c->noct);
 		const int nl = c->nd - 2;  // DoG levels 1 .. nd-2 (Src/cSIFT3D.cc:376)
 		const Taps *lt = c->g_last_elide ? &c->taps[c->ng - 1] : nullptr;
+		DetectOpts dopt;
+		dopt.neighbours = c->dopt.neighbours; dopt.refine = c->dopt.refine;
+		dopt.max_offset = c->dopt.max_offset; dopt.contrast_thresh = c->dopt.contrast_thresh; dopt.edge_ratio = c->dopt.edge_ratio;
+		const DetectOpts *dop = c->run_full ? &dopt : nullptr;  // null: the reference rule (k_mark)
 		if (upto >= 3)
 			for (int o = 0; o < c->noct; o++) {
 				DetectLevels &DL = DLs[(size_t)o];
@@ -701,7 +728,7 @@ static int run_enqueue(sift3d_ctx *c, int upto, bool part_orient) {
 		if (early) {
 			const Level &C0 = c->dog[(size_t)0 * c->nd + 1];
 			S3D_HIP(hipEventRecord(c->ev_det_fork, st));  // octave 0's pyramid is complete (the main stream is its stream)
-			launch_detect_mark(DLs[0], nl, C0.nx, C0.ny, C0.zr_all(), c->p.peak_thresh, 0 + c->octave_base, c->det, st, lt);
+			launch_detect_mark(DLs[0], nl, C0.nx, C0.ny, C0.zr_all(), c->p.peak_thresh, 0 + c->octave_base, c->det, st, lt, dop);
 			S3D_HIP(hipStreamWaitEvent(sb, c->ev_det_fork, 0));
 			// (octave 1 too: its levels are in sb's own order only when neither the chain stream nor the small-octave launch took them)
 			for (int o = 1; o < c->noct; o++) S3D_HIP(hipStreamWaitEvent(sb, c->ev_done[o], 0));
@@ -730,7 +757,7 @@ static int run_enqueue(sift3d_ctx *c, int upto, bool part_orient) {
 				for (int o = 1; o < c->noct; o++) {
 					const Level &C = c->dog[(size_t)o * c->nd + 1];
 					if (own && o >= 2) S3D_HIP(hipStreamWaitEvent(sc, c->ev_done[o], 0));
-					launch_detect_mark(DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), c->p.peak_thresh, o + c->octave_base, c->det_o[(size_t)o], o == 1 ? sb : sc, lt);
+					launch_detect_mark(DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), c->p.peak_thresh, o + c->octave_base, c->det_o[(size_t)o], o == 1 ? sb : sc, lt, dop);
 				}
 				S3D_HIP(hipEventRecord(c->ev_det_join, sb));
 				if (sc != sb) { S3D_HIP(hipEventRecord(c->ev_det_join2, sc)); S3D_HIP(hipStreamWaitEvent(sb, c->ev_det_join2, 0)); S3D_HIP(hipEventRecord(c->ev_det_join, sb)); }
@@ -739,7 +766,7 @@ static int run_enqueue(sift3d_ctx *c, int upto, bool part_orient) {
 			for (int o = 0; o < c->noct; o++) {
 				const Level &C = c->dog[(size_t)o * c->nd + 1];
 				const DetectBufs &b = (two && o > 0) ? c->det_o[(size_t)o] : c->det;
-				if (!(two && o > 0) && !(early && o == 0)) launch_detect_mark(DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), c->p.peak_thresh, o + c->octave_base, b, st, lt);
+				if (!(two && o > 0) && !(early && o == 0)) launch_detect_mark(DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), c->p.peak_thresh, o + c->octave_base, b, st, lt, dop);
 				if (two && o == 1) S3D_HIP(hipStreamWaitEvent(st, c->ev_det_join, 0));
 				if (two && o > 0 && c->noct - 1 <= 8) rest.push_back(DetectEmitItem{&DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), o + c->octave_base, &b});
 				else launch_detect_emit(DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), o + c->octave_base, b, c->d_ext, c->ext_cap, st);
@@ -760,6 +787,17 @@ static int run_enqueue(sift3d_ctx *c, int upto, bool part_orient) {
 			                c->part_world, c->d_order, c->d_nkp, c->d_nkp + 1, st, c->desc_lut_lds, &c->dsplit);
 		}
 		if (upto >= 4) launch_finalize(c->d_ext, c->d_total, c->ext_cap, upto >= 5, c->d_kpout, c->d_xyz, c->kp_cap, st);
+		if (upto >= 4 && c->run_refine) {  // refined records of the accepted keypoints (timed with the descriptor stage)
+			DogTable T;
+			memset(&T, 0, sizeof(T));
+			T.octave_base = c->octave_base;
+			for (int o = 0; o < c->noct && o < kDogTabOct; o++) {
+				const Level &D0 = c->dog[(size_t)o * c->nd];
+				T.nx[o] = D0.nx; T.ny[o] = D0.ny;
+				for (int i = 0; i < c->nd && i < kDogTabLv; i++) T.d[o][i] = c->dog[(size_t)o * c->nd + i].d;
+			}
+			launch_refine(c->d_ext, c->d_total, c->ext_cap, c->kp_cap, T, c->p.num_kp_levels, c->d_refined, st);
+		}
 		S3D_HIP(hipEventRecord(c->ev[5], st));
 		// total, overflow, nkp, describe work counter, describe second passes -> pinned host words
 		S3D_HIP(hipMemcpyAsync(c->h_words, c->d_total, sizeof(unsigned) * 5, hipMemcpyDeviceToHost, st));
@@ -791,6 +829,7 @@ static int run_finish(sift3d_ctx *c, int upto, bool &again) {
 		c->n_kp = upto >= 4 ? host_words[2] : 0;
 		c->n_desc_redo = upto >= 5 ? (int)host_words[4] : 0;
 		c->stage = upto;
+		c->last_refine = c->run_refine && upto >= 4;
 		float ms = 0;
 		auto dt = [&](int a, int b) { hipEventElapsedTime(&ms, c->ev[a], c->ev[b]); return (double)ms * 1e-3; };
 		c->times[0] = dt(0, 5); c->times[1] = 0; c->times[2] = dt(0, 1); c->times[3] = dt(1, 2);
@@ -928,6 +967,41 @@ extern "C" int sift3d_match_handles(sift3d_handle ref, sift3d_handle tar, double
 		td = ref->d_peer; tx = ref->d_peer + (size_t)m * kDesc;
 	}
 	return sift3d_match(ref->d_desc, ref->d_xyz, n, td, tx, m, thresHold, mode, 1, ref->device, gIdx, sIdx, gDist, sDist, pairs6, npairs, seconds);
+}
+
+// No reference counterpart (generalises IsExtrema_neighbor, Src/cSIFT3D.cc:884-911): see include/sift3d_hip.h
+extern "C" int sift3d_set_detect_options(sift3d_handle c, const sift3d_detect_options *o) {
+	if (!c || !o) { set_last_error("sift3d_set_detect_options: null argument"); return SIFT3D_ERR_ARG; }
+	if (c->slab || c->seeded) { set_last_error("sift3d_set_detect_options: only plain single-volume handles (sift3d_create) take detection options"); return SIFT3D_ERR_ARG; }
+	if (c->pending) { set_last_error("sift3d_set_detect_options: the handle has an asynchronous run in flight: call sift3d_wait first"); return SIFT3D_ERR_STATE; }
+	if (o->neighbours != 8 && o->neighbours != 80) { set_last_error("sift3d_set_detect_options: neighbours must be 8 or 80"); return SIFT3D_ERR_ARG; }
+	if (o->refine != 0 && o->refine != 1) { set_last_error("sift3d_set_detect_options: refine must be 0 or 1"); return SIFT3D_ERR_ARG; }
+	if (!isfinite(o->max_offset) || !isfinite(o->contrast_thresh) || !isfinite(o->edge_ratio)) {
+		set_last_error("sift3d_set_detect_options: thresholds must be finite");
+		return SIFT3D_ERR_ARG;
+	}
+	if (o->reserved[0] || o->reserved[1] || o->reserved[2]) { set_last_error("sift3d_set_detect_options: reserved words must be 0"); return SIFT3D_ERR_ARG; }
+	if (c->noct > kDogTabOct || c->nd > kDogTabLv) { set_last_error("sift3d_set_detect_options: too many octaves / levels for the refinement table"); return SIFT3D_ERR_ARG; }
+	c->dopt = *o;
+	return SIFT3D_OK;
+}
+
+// No reference counterpart (generalises Src/cSIFT3D.cc:884-911)
+extern "C" int sift3d_get_detect_options(sift3d_handle c, sift3d_detect_options *o) {
+	if (!c || !o) return SIFT3D_ERR_ARG;
+	*o = c->dopt;
+	return SIFT3D_OK;
+}
+
+// No reference counterpart (generalises Src/cSIFT3D.cc:884-911): the refined records of the last completed run, slot order
+extern "C" int sift3d_get_refined(sift3d_handle c, sift3d_refined *out) {
+	if (!c || !out) return SIFT3D_ERR_ARG;
+	if (c->pending) { int wrc = sift3d_wait(c); if (wrc) return wrc; }  // an asynchronous run in flight is completed first
+	if (!c->last_refine || c->stage < 4) { set_last_error("sift3d_get_refined: the last completed run did not refine its keypoints"); return SIFT3D_ERR_STATE; }
+	if (c->n_kp == 0) return SIFT3D_OK;
+	int rc = set_device(c->device);
+	if (rc) return rc;
+	return staged_d2h(out, c->d_refined, sizeof(sift3d_refined) * (size_t)c->n_kp, c->device, c->own_stream);
 }
 
 extern "C" int sift3d_num_octaves(sift3d_handle c, int *n) {

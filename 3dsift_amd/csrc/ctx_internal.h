@@ -95,6 +95,14 @@ struct sift3d_ctx {
 	std::vector<Taps> taps;  // per GSS level index within an octave
 	Taps base_taps{};
 
+	// sift3d_set_detect_options (plain contexts only): dopt = the options of the next run; run_opts = those of the run enqueued last
+	// (set by run_prepare: a non-default run materialises every DoG level and the last Gaussian level); last_refine = the last
+	// COMPLETED run refined its keypoints (d_refined holds n_kp records, sized kp_cap and reallocated behind a list regrow)
+	sift3d_detect_options dopt{};
+	bool run_full = false, run_refine = false, last_refine = false;
+	sift3d_refined *d_refined = nullptr;
+	unsigned refined_cap = 0;
+
 	bool use_fused = true;  // SIFT3D_HOOK_SEPARABLE forces the generic three-pass kernels (parity cross-check)
 	int n_regrow = 0, n_desc_redo = 0;  // sift3d_debug_counters: list regrows / second descriptor passes of the last run
 

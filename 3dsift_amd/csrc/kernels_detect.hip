@@ -707,7 +707,8 @@ __global__ void __launch_bounds__(kThreads) k_emit_multi(EmitMulti M, DevKp *__r
 // first half of an octave's detection: the ballot masks of the strict extrema (k_mark) and the parked candidates of the lazy level
 // (k_lazy_next).  Octaves with their own scratch (DetectBufs) can run this half concurrently.
 void launch_detect_mark(const DetectLevels &L, int nlevels, int nx, int ny, const ZRange &zr, float peak_thresh, int octave,
-                        const DetectBufs &b, hipStream_t st, const Taps *lazy_taps) {
+                        const DetectBufs &b, hipStream_t st, const Taps *lazy_taps, const DetectOpts *opt) {
+	if (opt) { launch_mark_full(L, nlevels, nx, ny, zr, kRows, peak_thresh, *opt, b, st); return; }  // sift3d_set_detect_options
 	const int nyb = (ny + kRows - 1) / kRows;
 	const int nzl = zr.zo1 - zr.zo0;
 	if (nzl <= 0) return;

@@ -193,8 +193,23 @@ struct DetectLevels {
 	float scale[kMaxKpLevels];
 };
 constexpr int kLazySlots = 52;  // k_lazy_next: 2 * (2 hw + 1) source slots per axis (boundary voxels) fit for hw <= 12 (r06; 36 / hw <= 8 before)
+// the opt-in rules of sift3d_set_detect_options (kernels_detect_full.hip); num_kp_levels: the refined scale's 2^(ds / num_kp_levels)
+struct DetectOpts {
+	int neighbours = 8, refine = 0;
+	float max_offset = 0.5f, contrast_thresh = 0.0f, edge_ratio = 0.0f;
+};
+// opt != null: k_mark_full instead of k_mark + the lazy kernels (every DoG level of the octave is materialised)
 void launch_detect_mark(const DetectLevels &L, int nlevels, int nx, int ny, const ZRange &zr, float peak_thresh, int octave,
-                        const DetectBufs &b, hipStream_t st, const Taps *lazy_taps);
+                        const DetectBufs &b, hipStream_t st, const Taps *lazy_taps, const DetectOpts *opt = nullptr);
+void launch_mark_full(const DetectLevels &L, int nlevels, int nx, int ny, const ZRange &zr, int rows, float peak_thresh, const DetectOpts &opt,
+                      const DetectBufs &b, hipStream_t st);
+// DoG levels by (octave - octave_base, level) for k_refine
+constexpr int kDogTabOct = 12, kDogTabLv = 8;
+struct DogTable {
+	const float *d[kDogTabOct][kDogTabLv];
+	int nx[kDogTabOct], ny[kDogTabOct];
+	int octave_base;
+};
 void launch_detect_emit(const DetectLevels &L, int nlevels, int nx, int ny, const ZRange &zr, int octave, const DetectBufs &b, DevKp *out,
                         unsigned cap, hipStream_t st);
 struct DetectEmitItem { const DetectLevels *L; int nlevels, nx, ny; ZRange zr; int octave; const DetectBufs *b; };
@@ -279,6 +294,9 @@ void launch_describe(const DevKp *kps, const unsigned *d_count, unsigned cap, co
                      const int *order, const unsigned *d_nkp, unsigned *d_work /* device counter, zeroed by the launch */,
                      hipStream_t st, bool lut_in_lds = true, const DescSplit *split = nullptr);
 void launch_face_lookup(const float *d_g3, int n, int route, int *d_face, float *d_bary3, hipStream_t st);  // sift3d_debug_face_lookup
+// refined records of the accepted keypoints (slot order), kernels_detect_full.hip
+void launch_refine(const DevKp *kps, const unsigned *d_count, unsigned cap, unsigned kp_cap, const DogTable &T, int num_kp_levels,
+                   sift3d_refined *out, hipStream_t st);
 void launch_finalize(const DevKp *kps, const unsigned *d_count, unsigned cap, int transposed,
                      sift3d_keypoint *d_out, float *d_xyz, unsigned kp_cap, hipStream_t st);
 

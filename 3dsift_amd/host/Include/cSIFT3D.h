@@ -131,6 +131,23 @@ public:
 	SIFT_LIBRARY_API std::vector<TexImage> *GET_DOG();
 	SIFT_LIBRARY_API std::vector<std::vector<Keypoint>> *GET_LEVEL();
 
+	// extension (no reference counterpart; generalises IsExtrema_neighbor, Src/cSIFT3D.cc:884-911): the extremum rule of the next
+	// KpSiftAlgorithm -- neighbours 8 (the reference's, default) or 80 (Lowe's 3x3x3x3 test), refine = sub-voxel quadratic fit with
+	// offset / contrast / edge rejection (fields as sift3d_detect_options of include/sift3d_hip.h).  Call it before KpSiftAlgorithm.
+	// false (options unchanged): bad values, a run in flight, or an extractor sharded over several GPUs (SIFT3D_DEVICES).  Keypoint
+	// records and descriptors stay those of the integer voxel; the refined positions come from GetRefinedCoordinates / GetRefinedScales.
+	struct DetectOptions {
+		int neighbours = 8;
+		int refine = 0;
+		float max_offset = 0.5f;
+		float contrast_thresh = 0.0f;
+		float edge_ratio = 0.0f;
+	};
+	SIFT_LIBRARY_API bool SetDetectOptions(const DetectOptions &o);
+	// extension: refined (rx, ry, rz) / refined scale of the keypoints, GetKeypoints() order; empty when the last run did not refine
+	SIFT_LIBRARY_API std::vector<Cvec> GetRefinedCoordinates();
+	SIFT_LIBRARY_API std::vector<float> GetRefinedScales();
+
 	// extension: device-resident descriptors / coordinates for a matcher that never leaves the GPU
 	SIFT_LIBRARY_API bool GetDeviceResults(const float **d_desc, const float **d_xyz, int *n, int *device);
 	// extension: the live extractor whose GetKeypoints() produced `kp` unchanged (same count, descriptor

@@ -340,6 +340,40 @@ void CSIFT3D::Wait() {
 		m_timer.d_Detect = t[4]; m_timer.d_AssignOrientation = t[5]; m_timer.d_Extraction = t[6]; m_timer.d_release = t[7];
 	}
 }
+bool CSIFT3D::SetDetectOptions(const DetectOptions &o) {
+	if (impl->sh) {
+		fprintf(stderr, "[3dsift_amd] SetDetectOptions: this extractor shards its volume over several GPUs (SIFT3D_DEVICES / SIFT3D_SIM_RANKS); "
+		                "detection options need a single-GPU extractor -- the defaults stay\n");
+		return false;
+	}
+	if (!need_single("SetDetectOptions", impl->h, impl->sh)) return false;
+	sift3d_detect_options d;
+	sift3d_default_detect_options(&d);
+	d.neighbours = o.neighbours; d.refine = o.refine; d.max_offset = o.max_offset; d.contrast_thresh = o.contrast_thresh; d.edge_ratio = o.edge_ratio;
+	const int rc = sift3d_set_detect_options(impl->h, &d);
+	complain("SetDetectOptions", rc);
+	return rc == SIFT3D_OK;
+}
+static std::vector<sift3d_refined> refined_of(sift3d_handle h, int stage) {
+	std::vector<sift3d_refined> r;
+	int n = 0;
+	if (!h || stage < 4 || sift3d_num_keypoints(h, &n) != SIFT3D_OK || n <= 0) return r;
+	r.resize((size_t)n);
+	if (sift3d_get_refined(h, r.data()) != SIFT3D_OK) r.clear();  // (the last run did not refine: empty, no message)
+	return r;
+}
+std::vector<Cvec> CSIFT3D::GetRefinedCoordinates() {
+	Wait();
+	std::vector<Cvec> out;
+	for (const sift3d_refined &r : refined_of(impl->h, impl->stage)) out.push_back(Cvec(r.rx, r.ry, r.rz));
+	return out;
+}
+std::vector<float> CSIFT3D::GetRefinedScales() {
+	Wait();
+	std::vector<float> out;
+	for (const sift3d_refined &r : refined_of(impl->h, impl->stage)) out.push_back(r.scale);
+	return out;
+}
 void CSIFT3D::Initialize() {}
 void CSIFT3D::Build_Gaussian_Scale_Space() { if (need_single("Build_Gaussian_Scale_Space", impl->h, impl->sh)) run_to(this, impl->h, 1, impl->stage, impl->fetched, m_timer); }
 void CSIFT3D::Build_DOG_Scale_Space() { if (need_single("Build_DOG_Scale_Space", impl->h, impl->sh)) run_to(this, impl->h, 2, impl->stage, impl->fetched, m_timer); }

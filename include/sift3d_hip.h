@@ -348,6 +348,60 @@ int sift3d_sharded_traffic(sift3d_sharded_handle h, double *halo_bytes /* [world
 const char *sift3d_sharded_error(sift3d_sharded_handle h);
 int sift3d_sharded_destroy(sift3d_sharded_handle h);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Detection options of a plain single-volume handle (no reference counterpart: the reference has one extremum rule,
+ * IsExtrema_neighbor, Src/cSIFT3D.cc:884-911 -- 8 neighbours: +-x, +-y, +-z in the level and the centre voxel of the levels
+ * above and below -- and integer keypoint coordinates).  The defaults are that rule, bit for bit.
+ *   neighbours 80: a voxel of DoG level l must be strictly above (maximum) or strictly below (minimum) all 26 neighbours in
+ *   level l and all 27 voxels of levels l-1 and l+1 (Lowe's scale-space extremum); threshold, voxel range, keypoint levels and
+ *   emit order as in the 8-neighbour rule, so its extrema are a subsequence of the 8-neighbour extrema.
+ *   refine 1 (either neighbourhood): a quadratic fit in (x, y, z, s), s = DoG level index, on the 3x3x3x3 block around the
+ *   extremum, all in fp64 from the fp32 DoG samples: g_i = 0.5 (D+ - D-), H_ii = (D+ + D-) - 2 D0, H_ij = 0.25 (((D++ - D+-) - D-+) + D--),
+ *   delta = -H^-1 g by Gaussian elimination with partial pivoting (axis order x, y, z, s; the first largest |pivot| of the column),
+ *   contrast D(x^) = D0 + 0.5 g.delta.  A candidate is REJECTED (it is not an extremum) when a pivot is exactly 0, when
+ *   max_offset > 0 and some |delta_i| > max_offset, when contrast_thresh > 0 and |D(x^)| < contrast_thresh * max|level| (fp32
+ *   product, like peak_thresh), or when edge_ratio = r > 0 and the spatial 3x3 block of H fails tr det > 0 && tr^3 / det < (2r+1)^3 / r^2
+ *   (Allaire et al. 2008).  Keypoints are never moved to another voxel: their records, orientation frames and descriptors are
+ *   those of the integer voxel, bit for bit as in a default run; the refined position comes separately (sift3d_get_refined).
+ * Only plain handles (sift3d_create) take options: z-slab and seeded contexts refuse them with SIFT3D_ERR_ARG.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct sift3d_detect_options {
+	int neighbours;        /* 8 (reference rule, default) or 80 */
+	int refine;            /* 0 (default) or 1 */
+	float max_offset;      /* default 0.5; <= 0: no offset test */
+	float contrast_thresh; /* default 0 (off); relative to max|level| like peak_thresh */
+	float edge_ratio;      /* default 0 (off) */
+	int reserved[3];       /* must be 0 */
+} sift3d_detect_options;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_detect_options) == 32, "sift3d_detect_options must be 32 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_detect_options, refine) == 4 && offsetof(sift3d_detect_options, max_offset) == 8 &&
+                     offsetof(sift3d_detect_options, contrast_thresh) == 12 && offsetof(sift3d_detect_options, edge_ratio) == 16 &&
+                     offsetof(sift3d_detect_options, reserved) == 20, "sift3d_detect_options field offsets");
+
+/* refined position of one keypoint (fp64 results rounded to fp32 once): rx = (x + delta_x) * 2^octave -- the factor of
+ * sift3d_keypoint.rx --, likewise ry, rz; scale = keypoint scale * 2^(delta_s / num_kp_levels) */
+typedef struct sift3d_refined {
+	float rx, ry, rz;      /* refined coordinates, same units as sift3d_keypoint.rx */
+	float scale;           /* refined scale */
+	float offset[4];       /* dx, dy, dz, ds in the keypoint's octave / level units */
+	float contrast;        /* D(x^) */
+} sift3d_refined;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_refined) == 36, "sift3d_refined must be 36 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_refined, scale) == 12 && offsetof(sift3d_refined, offset) == 16 && offsetof(sift3d_refined, contrast) == 32,
+                     "sift3d_refined field offsets");
+
+/* No reference counterpart (generalises IsExtrema_neighbor, Src/cSIFT3D.cc:884-911): the defaults above; needs no GPU. */
+void sift3d_default_detect_options(sift3d_detect_options *o);
+/* No reference counterpart (generalises Src/cSIFT3D.cc:884-911): the options of the next run of a plain handle.
+ * SIFT3D_ERR_STATE while an asynchronous run is in flight; SIFT3D_ERR_ARG for neighbours not 8 / 80, refine not 0 / 1, a
+ * non-finite threshold, a non-zero reserved word, or a z-slab / seeded handle. */
+int sift3d_set_detect_options(sift3d_handle h, const sift3d_detect_options *o);
+/* No reference counterpart (generalises Src/cSIFT3D.cc:884-911): the options the next run will use. */
+int sift3d_get_detect_options(sift3d_handle h, sift3d_detect_options *o);
+/* No reference counterpart (generalises Src/cSIFT3D.cc:884-911): num_keypoints records in sift3d_get_keypoints order.
+ * SIFT3D_ERR_STATE unless the last completed run had refine on and reached the orientation stage. */
+int sift3d_get_refined(sift3d_handle h, sift3d_refined *out);
+
 /* Test hooks, rare-path counters and the unit-level debug entry points live in include/sift3d_hip_test.h: this header is the
  * product boundary only. */
 const char *sift3d_error_string(int code);
