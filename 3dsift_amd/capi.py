@@ -38,6 +38,8 @@ SYMBOLS = [
     "sift3d_match_handles",
     # detection options: the 80-neighbour rule and the sub-voxel refinement
     "sift3d_default_detect_options", "sift3d_set_detect_options", "sift3d_get_detect_options", "sift3d_get_refined",
+    # RANSAC affine fits of matched pairs, global and per point
+    "sift3d_default_ransac_options", "sift3d_fit_affine", "sift3d_fit_affine_local",
     "sift3d_device_count", "sift3d_error_string", "sift3d_last_error",
     # multi-GPU sharding (z-slabs of octave 0 + seeded replicated tail)
     "sift3d_slab_min_halo", "sift3d_slab_arena_floats", "sift3d_slab_create", "sift3d_slab_buffer", "sift3d_slab_upload",
@@ -86,6 +88,20 @@ assert C.sizeof(DetectOptions) == 32
 # sift3d_refined: refined coordinates / scale, the fit's offset (dx, dy, dz, ds) and D(x^)
 REFINED_DTYPE = np.dtype([("rx", "<f4"), ("ry", "<f4"), ("rz", "<f4"), ("scale", "<f4"), ("offset", "<f4", (4,)), ("contrast", "<f4")])
 assert REFINED_DTYPE.itemsize == 36
+
+
+class RansacOptions(C.Structure):
+    """sift3d_ransac_options (include/sift3d_hip.h)"""
+    _fields_ = [("iterations", C.c_int), ("inlier_thresh", C.c_float), ("seed", C.c_uint), ("refine", C.c_int), ("min_det", C.c_float),
+                ("reserved", C.c_int * 3)]
+
+
+assert C.sizeof(RansacOptions) == 32
+
+# sift3d_affine_fit: final transform, the best hypothesis's minimal-sample transform, status and counts
+FIT_DTYPE = np.dtype([("A", "<f8", (12,)), ("hyp", "<f8", (12,)), ("status", "<i4"), ("candidates", "<i4"), ("best_hypothesis", "<i4"),
+                      ("best_count", "<i4"), ("inliers", "<i4"), ("rms", "<f4"), ("reserved", "<i4", (2,))])
+assert FIT_DTYPE.itemsize == 224
 
 
 class SlabDesc(C.Structure):
@@ -149,6 +165,12 @@ def lib():
         L.sift3d_set_detect_options.argtypes = [C.c_void_p, C.POINTER(DetectOptions)]
         L.sift3d_get_detect_options.argtypes = [C.c_void_p, C.POINTER(DetectOptions)]
         L.sift3d_get_refined.argtypes = [C.c_void_p, C.c_void_p]
+        L.sift3d_default_ransac_options.argtypes = [C.POINTER(RansacOptions)]
+        L.sift3d_default_ransac_options.restype = None
+        L.sift3d_fit_affine.argtypes = [C.c_void_p, C.c_int, C.POINTER(RansacOptions), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_double)]
+        L.sift3d_fit_affine_local.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(RansacOptions), C.c_int,
+                                              C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         _sz = C.POINTER(C.c_size_t)
         L.sift3d_slab_min_halo.argtypes = [C.POINTER(Params), _ip]
         L.sift3d_slab_arena_floats.argtypes = [C.POINTER(SlabDesc), C.POINTER(Params), _sz]
@@ -283,6 +305,76 @@ def default_detect_options():
 def _options_dict(o):
     return {"neighbours": o.neighbours, "refine": bool(o.refine), "max_offset": o.max_offset, "contrast_thresh": o.contrast_thresh,
             "edge_ratio": o.edge_ratio}
+
+
+def default_ransac_options():
+    """sift3d_default_ransac_options as a dict (needs no GPU)"""
+    o = RansacOptions()
+    lib().sift3d_default_ransac_options(C.byref(o))
+    return {"iterations": o.iterations, "inlier_thresh": o.inlier_thresh, "seed": o.seed, "refine": o.refine, "min_det": o.min_det}
+
+
+def _ransac_options(opts):
+    o = RansacOptions()
+    lib().sift3d_default_ransac_options(C.byref(o))
+    for k, v in opts.items():
+        if k not in ("iterations", "inlier_thresh", "seed", "refine", "min_det"):
+            raise TypeError(f"unknown RANSAC option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def _rows(a, width, name):
+    """(pointer, rows, keep-alive, on_device) of an (n, width) float32 numpy array or a contiguous float32 device tensor"""
+    if hasattr(a, "data_ptr") and getattr(a, "is_cuda", False):
+        if str(a.dtype) != "torch.float32" or not a.is_contiguous() or (a.numel() and a.shape[-1] != width):
+            raise ValueError(f"{name}: a contiguous float32 (n, {width}) device tensor is needed")
+        return C.c_void_p(a.data_ptr()), a.numel() // width, a, 1
+    h = np.ascontiguousarray(a, np.float32).reshape(-1, width)
+    return h.ctypes.data_as(C.c_void_p), len(h), h, 0
+
+
+def _fit_dict(f):
+    return {"A": f["A"].reshape(f.shape + (3, 4)).copy(), "hyp": f["hyp"].reshape(f.shape + (3, 4)).copy(), "status": f["status"].copy(),
+            "candidates": f["candidates"].copy(), "best_hypothesis": f["best_hypothesis"].copy(), "best_count": f["best_count"].copy(),
+            "inliers": f["inliers"].copy(), "rms": f["rms"].copy()}
+
+
+def fit_affine(pairs, device=0, **opts):
+    """sift3d_fit_affine: RANSAC affine t = L r + b over all rows of pairs ((n, 6) float32: ref rx ry rz, tar rx ry rz; numpy or a
+    device tensor).  Returns the fit's fields (A and hyp as (3, 4) float64, scalars as Python numbers), the inlier mask (bool [n])
+    and the device seconds."""
+    o = _ransac_options(opts)
+    pp, n, keep, on_dev = _rows(pairs, 6, "pairs")
+    out = np.zeros((), FIT_DTYPE)
+    mask = np.zeros(max(n, 1), np.uint8)
+    sec = C.c_double(0)
+    _check(lib().sift3d_fit_affine(pp, n, C.byref(o), on_dev, int(device), out.ctypes.data_as(C.c_void_p), mask.ctypes.data_as(C.c_void_p),
+                                   C.byref(sec)))
+    d = {k: (v if k in ("A", "hyp") else v.item()) for k, v in _fit_dict(out).items()}
+    d["mask"] = mask[:n].astype(bool)
+    d["seconds"] = sec.value
+    return d
+
+
+def fit_affine_local(pairs, points, k=32, radius=0.0, device=0, **opts):
+    """sift3d_fit_affine_local: one RANSAC affine per query point ((m, 3) reference coordinates) on its k nearest pairs (within radius
+    when radius > 0).  Returns per-point arrays (A, hyp: (m, 3, 4); status, counts, rms: (m,)), neighbours (m, k) int32 (-1 padded)
+    and the device seconds."""
+    o = _ransac_options(opts)
+    pp, n, keep_p, dev_p = _rows(pairs, 6, "pairs")
+    qp, m, keep_q, dev_q = _rows(points, 3, "points")
+    if dev_p != dev_q:
+        raise ValueError("pairs and points must both be host arrays or both device tensors")
+    out = np.zeros(max(m, 1), FIT_DTYPE)
+    nb = np.zeros((max(m, 1), max(int(k), 1)), np.int32)
+    sec = C.c_double(0)
+    _check(lib().sift3d_fit_affine_local(pp, n, qp, m, int(k), float(radius), C.byref(o), dev_p, int(device), out.ctypes.data_as(C.c_void_p),
+                                         nb.ctypes.data_as(C.c_void_p), C.byref(sec)))
+    d = _fit_dict(out[:m])
+    d["neighbours"] = nb[:m].copy()
+    d["seconds"] = sec.value
+    return d
 
 
 def device_count():

@@ -314,6 +314,15 @@ int match_rows_device(const float *d_a, const int *d_row_ids, int nrows, const f
                       void *d_part, float *d_gd, float *d_sd, int *d_gi, int *d_si, const MatchGuard &g, hipStream_t st);
 int match_redo_rows();  // rows the last sift3d_match re-scored exactly (near-tie guard)
 
+// ---- kernels_ransac.hip: RANSAC affine fits (sift3d_fit_affine / sift3d_fit_affine_local, include/sift3d_hip.h) ----------------
+uint32_t ransac_seed(uint32_t seed);  // s = fmix32(seed ^ 0x9E3779B9)
+// d_hyp: 12 * H doubles, d_count: H ints (scratch); d_out: one record, d_mask: n bytes
+void launch_ransac_global(const float *d_pairs, int n, int H, uint32_t s, double tau2, double min_det, int refine, double *d_hyp, int *d_count,
+                          sift3d_affine_fit *d_out, unsigned char *d_mask, hipStream_t st);
+// d_out: m records; d_nbrs: m * k ints or null
+void launch_ransac_local(const float *d_pairs, int n, const float *d_pts, int m, int k, float r2, int H, uint32_t s, double tau2, double min_det,
+                         int refine, sift3d_affine_fit *d_out, int *d_nbrs, hipStream_t st);
+
 // code-object preload of the translation units whose kernels would otherwise be loaded by the first KpSiftAlgorithm of a process
 void preload_march_kernels();
 void preload_small_kernels();

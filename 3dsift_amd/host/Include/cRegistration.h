@@ -1,0 +1,46 @@
+// cRegistration.h -- RANSAC affine fits of matched keypoints (no reference counterpart): the step after enhancedMatch, on the GPU.
+// Over sift3d_fit_affine / sift3d_fit_affine_local (include/sift3d_hip.h, which states the numerical contract).  Both functions take
+// exactly the two std::vector<Cvec> that muBruteMatcher::enhancedMatch fills (refMatch[i] <-> tarMatch[i]).
+#ifndef S3D_HOST_CREGISTRATION_H
+#define S3D_HOST_CREGISTRATION_H
+
+#include <vector>
+
+#include "Util/common.h"
+#include "cSIFT3D.h"
+
+namespace CPUSIFT {
+
+struct SIFT_LIBRARY_API RansacOptions {
+	int iterations = 0;          // hypotheses per problem; 0 = 4096 global, 256 local; at most 65536
+	float inlier_thresh = 3.0f;  // tau, in full-resolution voxels
+	unsigned seed = 1;
+	int refine = 1;              // least-squares refit rounds on the inliers, 0..4
+	float min_det = 1.0f;        // a sample (or an inlier covariance) with |det| below this is degenerate
+};
+
+// t = L r + b, row-major A = [L | b]; status 0 ok, 1 fewer than 4 candidates, 2 every hypothesis degenerate, 3 refit singular,
+// -1 the call failed (message on stderr, like muBruteMatcher)
+struct SIFT_LIBRARY_API AffineFit {
+	double A[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+	double hyp[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // the best minimal-sample hypothesis
+	int status = -1;
+	int candidates = 0, best_hypothesis = -1, best_count = 0, inliers = 0;
+	float rms = 0.f;
+	double seconds = 0;  // device time of the call
+
+	// the transform applied to a point, its displacement L p + b - p and the displacement gradient L - I (row-major 3x3)
+	Cvec Apply(const Cvec &p) const;
+	Cvec Displacement(const Cvec &p) const;
+	void Gradient(double G[9]) const;
+};
+
+// one fit over all pairs; inlierMask (optional) gets 1 / 0 per pair
+SIFT_LIBRARY_API AffineFit EstimateAffine(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, const RansacOptions &opts = RansacOptions(),
+                                          std::vector<int> *inlierMask = nullptr);
+// one fit per point (reference coordinates) on its k nearest pairs by reference position (within radius when radius > 0), k in 4..64
+SIFT_LIBRARY_API std::vector<AffineFit> EstimateLocalAffine(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, const std::vector<Cvec> &points,
+                                                            int k = 32, float radius = 0, const RansacOptions &opts = RansacOptions());
+
+}  // namespace CPUSIFT
+#endif

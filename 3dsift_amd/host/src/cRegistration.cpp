@@ -1,0 +1,95 @@
+// cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine over sift3d_fit_affine / sift3d_fit_affine_local (include/sift3d_hip.h).
+#include "../Include/cRegistration.h"
+
+#include <cstdio>
+#include <cstring>
+
+#include "../../../include/sift3d_hip.h"
+
+namespace CPUSIFT {
+
+namespace {
+sift3d_ransac_options to_c(const RansacOptions &o) {
+	sift3d_ransac_options c;
+	sift3d_default_ransac_options(&c);
+	c.iterations = o.iterations;
+	c.inlier_thresh = o.inlier_thresh;
+	c.seed = o.seed;
+	c.refine = o.refine;
+	c.min_det = o.min_det;
+	return c;
+}
+void from_c(const sift3d_affine_fit &f, double sec, AffineFit &a) {
+	memcpy(a.A, f.A, sizeof(a.A));
+	memcpy(a.hyp, f.hyp, sizeof(a.hyp));
+	a.status = f.status;
+	a.candidates = f.candidates;
+	a.best_hypothesis = f.best_hypothesis;
+	a.best_count = f.best_count;
+	a.inliers = f.inliers;
+	a.rms = f.rms;
+	a.seconds = sec;
+}
+std::vector<float> pairs6(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, size_t n) {
+	std::vector<float> p(6 * (n ? n : 1));
+	for (size_t i = 0; i < n; i++) {
+		p[6 * i] = ref[i].x; p[6 * i + 1] = ref[i].y; p[6 * i + 2] = ref[i].z;
+		p[6 * i + 3] = tar[i].x; p[6 * i + 4] = tar[i].y; p[6 * i + 5] = tar[i].z;
+	}
+	return p;
+}
+}  // namespace
+
+Cvec AffineFit::Apply(const Cvec &p) const {
+	double v[3];
+	for (int i = 0; i < 3; i++) v[i] = A[4 * i] * p.x + A[4 * i + 1] * p.y + A[4 * i + 2] * p.z + A[4 * i + 3];
+	return Cvec((float)v[0], (float)v[1], (float)v[2]);
+}
+Cvec AffineFit::Displacement(const Cvec &p) const {
+	const Cvec t = Apply(p);
+	return Cvec(t.x - p.x, t.y - p.y, t.z - p.z);
+}
+void AffineFit::Gradient(double G[9]) const {
+	for (int i = 0; i < 3; i++)
+		for (int j = 0; j < 3; j++) G[3 * i + j] = A[4 * i + j] - (i == j ? 1.0 : 0.0);
+}
+
+AffineFit EstimateAffine(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, const RansacOptions &opts, std::vector<int> *inlierMask) {
+	AffineFit a;
+	const size_t n = ref.size() < tar.size() ? ref.size() : tar.size();
+	const std::vector<float> p = pairs6(ref, tar, n);
+	const sift3d_ransac_options o = to_c(opts);
+	std::vector<unsigned char> mask(n ? n : 1);
+	sift3d_affine_fit f;
+	double sec = 0;
+	const int rc = sift3d_fit_affine(p.data(), (int)n, &o, 0, GetDevice(), &f, mask.data(), &sec);
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] EstimateAffine: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		if (inlierMask) inlierMask->assign(n, 0);
+		return a;
+	}
+	from_c(f, sec, a);
+	if (inlierMask) inlierMask->assign(mask.begin(), mask.begin() + n);
+	return a;
+}
+
+std::vector<AffineFit> EstimateLocalAffine(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, const std::vector<Cvec> &points, int k, float radius,
+                                           const RansacOptions &opts) {
+	const size_t n = ref.size() < tar.size() ? ref.size() : tar.size(), m = points.size();
+	std::vector<AffineFit> res(m);
+	const std::vector<float> p = pairs6(ref, tar, n);
+	std::vector<float> q(3 * (m ? m : 1));
+	for (size_t i = 0; i < m; i++) { q[3 * i] = points[i].x; q[3 * i + 1] = points[i].y; q[3 * i + 2] = points[i].z; }
+	const sift3d_ransac_options o = to_c(opts);
+	std::vector<sift3d_affine_fit> f(m ? m : 1);
+	double sec = 0;
+	const int rc = sift3d_fit_affine_local(p.data(), (int)n, q.data(), (int)m, k, radius, &o, 0, GetDevice(), f.data(), nullptr, &sec);
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] EstimateLocalAffine: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return res;
+	}
+	for (size_t i = 0; i < m; i++) from_c(f[i], sec, res[i]);
+	return res;
+}
+
+}  // namespace CPUSIFT

@@ -402,6 +402,80 @@ int sift3d_get_detect_options(sift3d_handle h, sift3d_detect_options *o);
  * SIFT3D_ERR_STATE unless the last completed run had refine on and reached the orientation stage. */
 int sift3d_get_refined(sift3d_handle h, sift3d_refined *out);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * RANSAC affine fits of matched keypoints (no reference counterpart: the step every caller of enhancedMatch writes next; Rister et al.,
+ * "Volumetric Image Registration From Invariant Keypoints").  Input: pairs6, n rows of (ref rx, ry, rz, tar rx, ry, rz) fp32 -- what
+ * sift3d_match / sift3d_match_handles return, or any other source of pairs.  A fit is a 3x4 affine t = L r + b.
+ *   sift3d_fit_affine: ONE problem whose candidates are all n pairs (problem index p = 0).
+ *   sift3d_fit_affine_local: m problems, one per query point q (reference coordinates, p = point index); the candidates of q are the
+ *   k nearest pairs by reference position (optionally within `radius`).  Displacement at q: L q + b - q; its gradient: L - I.
+ * Numerical contract (fp64 on the fp32 inputs, every expression evaluated in the order written, no FMA contraction, no sqrt before the
+ * inlier decision; tests/ransac_ref.py restates it and checks the GPU bit for bit):
+ *   Sampler: the 4 draws of hypothesis h (0 <= h < H) of problem p over c >= 4 candidates, uint32 arithmetic mod 2^32, with
+ *     fmix32(x) = x ^= x>>16; x *= 0x85ebca6b; x ^= x>>13; x *= 0xc2b2ae35; x ^= x>>16  (murmur3 finaliser):
+ *     s = fmix32(seed ^ 0x9E3779B9);  u_j = fmix32(fmix32(s + p) + (4h + j));  i_j = (uint32)(((uint64)u_j * c) >> 32);
+ *     while i_j equals an earlier draw of the hypothesis: i_j = (i_j + 1 == c) ? 0 : i_j + 1.
+ *     Indices are positions in the problem's candidate list: pair order (global), neighbour order (local).
+ *   Minimal solve: samples P0..P3 (ref), T0..T3 (tar); column k-1 of the 3x3 M is P_k - P0, N likewise from T;
+ *     cofactor C_rc = +-(M[r1][c1] M[r2][c2] - M[r1][c2] M[r2][c1]) (r1 < r2 the other rows, c1 < c2 the other columns, the sign
+ *     (-1)^(r+c) applied by negation); det = (M00 C00 + M01 C01) + M02 C02; DEGENERATE unless |det| >= min_det (NaN: degenerate);
+ *     inv_ij = C_ji / det; L_ij = (N_i0 inv_0j + N_i1 inv_1j) + N_i2 inv_2j; b_i = T0_i - ((L_i0 P0x + L_i1 P0y) + L_i2 P0z).
+ *   Scoring of a candidate (r, t): e_i = (((L_i0 rx + L_i1 ry) + L_i2 rz) + b_i) - t_i; d2 = (e0 e0 + e1 e1) + e2 e2;
+ *     inlier iff d2 <= (double)tau * (double)tau.
+ *   Best hypothesis: the non-degenerate one with the most inliers, ties to the smallest h; none: status 2.
+ *   Refit (`refine` rounds): on the current inlier set (at least 4, else stop) the means rbar, tbar, Cov = sum (r - rbar)(r - rbar)^T,
+ *     S = sum (t - tbar)(r - rbar)^T, L = S Cov^-1 (the cofactor inverse above, L_ij = (S_i0 inv_0j + S_i1 inv_1j) + S_i2 inv_2j),
+ *     b = tbar - L rbar (as b_i above); |det Cov| < min_det (or NaN): stop, keep the previous transform, status 3.  Re-scored after
+ *     every accepted round.  Sums run in a fixed order of the implementation: two calls give the same bits (checked to tolerance).
+ *   Local neighbours of q: fp32 d2_i = (dx dx + dy dy) + dz dz, dx = r_x - q_x; the candidates are the k smallest (d2_i, i) in
+ *     lexicographic order among the pairs with d2_i <= radius * radius (fp32; radius <= 0: no limit; a NaN d2_i never qualifies),
+ *     listed in that order; 4 <= k <= 64; fewer than 4 candidates: status 1.
+ * Results: A = the final transform; hyp = the best hypothesis's minimal-sample transform (bit exact); inliers / rms (sqrt of the mean
+ * d2, fp32) over the final inlier set, which the mask holds.  Status 1 / 2 leave A, hyp zero, best_hypothesis -1 and the mask empty:
+ * they are results of a successful call, not errors.  SIFT3D_ERR_ARG (checked before any device call): n < 0, m < 0, k outside
+ * 4..64, iterations outside 0..65536, refine outside 0..4, tau or min_det negative or not finite, radius not finite, a non-zero
+ * reserved word, a NULL pointer that is needed (options may be NULL: defaults).  on_device != 0: pairs6 / points3 are device pointers
+ * on `device`; outputs are host memory, filled by one copy at the end.  *seconds (may be NULL): device time of the call (HIP events).
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct sift3d_ransac_options {
+	int iterations;        /* hypotheses per problem; 0 = default: 4096 global, 256 local; max 65536 */
+	float inlier_thresh;   /* tau, in rx units (full-resolution voxels); default 3.0 */
+	unsigned seed;         /* default 1 */
+	int refine;            /* refit rounds 0..4, default 1 */
+	float min_det;         /* default 1.0 */
+	int reserved[3];       /* must be 0 */
+} sift3d_ransac_options;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_ransac_options) == 32, "sift3d_ransac_options must be 32 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_ransac_options, inlier_thresh) == 4 && offsetof(sift3d_ransac_options, seed) == 8 &&
+                     offsetof(sift3d_ransac_options, refine) == 12 && offsetof(sift3d_ransac_options, min_det) == 16 &&
+                     offsetof(sift3d_ransac_options, reserved) == 20, "sift3d_ransac_options field offsets");
+
+typedef struct sift3d_affine_fit {
+	double A[12];          /* final transform, row-major 3x4: [L | b] */
+	double hyp[12];        /* the best hypothesis's minimal-sample transform (bit exact against the contract) */
+	int status;            /* 0 ok, 1 fewer than 4 candidates, 2 every hypothesis degenerate, 3 refit singular */
+	int candidates;        /* pairs the problem drew from (n, or the neighbours found) */
+	int best_hypothesis;   /* h of the best hypothesis, -1 with status 1 / 2 */
+	int best_count;        /* its inliers */
+	int inliers;           /* inliers of A */
+	float rms;             /* sqrt(mean d2) over the final inliers */
+	int reserved[2];
+} sift3d_affine_fit;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_affine_fit) == 224, "sift3d_affine_fit must be 224 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_affine_fit, hyp) == 96 && offsetof(sift3d_affine_fit, status) == 192 &&
+                     offsetof(sift3d_affine_fit, candidates) == 196 && offsetof(sift3d_affine_fit, best_hypothesis) == 200 &&
+                     offsetof(sift3d_affine_fit, best_count) == 204 && offsetof(sift3d_affine_fit, inliers) == 208 &&
+                     offsetof(sift3d_affine_fit, rms) == 212 && offsetof(sift3d_affine_fit, reserved) == 216, "sift3d_affine_fit field offsets");
+
+/* the defaults above; needs no GPU */
+void sift3d_default_ransac_options(sift3d_ransac_options *o);
+/* the global fit; inlier_mask: n bytes (1 inlier of A, 0 not), may be NULL */
+int sift3d_fit_affine(const float *pairs6, int n, const sift3d_ransac_options *o, int on_device, int device, sift3d_affine_fit *out,
+                      unsigned char *inlier_mask, double *seconds);
+/* m local fits; out: m records; neighbours: m*k pair indices in candidate order, -1 padded, may be NULL */
+int sift3d_fit_affine_local(const float *pairs6, int n, const float *points3, int m, int k, float radius, const sift3d_ransac_options *o,
+                            int on_device, int device, sift3d_affine_fit *out, int *neighbours, double *seconds);
+
 /* Test hooks, rare-path counters and the unit-level debug entry points live in include/sift3d_hip_test.h: this header is the
  * product boundary only. */
 const char *sift3d_error_string(int code);
