@@ -61,7 +61,7 @@ void launch_copy16(const float *src, float *dst, size_t nfloats, hipStream_t st)
 }
 
 // ---------------------------------------------------------------------------------------------
-// The simulated transport of the z-slab driver (csrc/sharded.hip, all ranks on one GPU): the "sends" of one exchange step -- up to
+// The device copies of the z-slab driver (csrc/sharded.hip: simulated ranks, rank threads on one GPU): the moves of one exchange step -- up to
 // kCopySegs plane ranges -- as ONE launch instead of one hipMemcpyAsync each (a level of eight simulated ranks posted 42 copies of a few
 // planes: ~500 copy launches per step on the one stream the ranks share), and the MAX "all-reduce" of the DoG maxima on the device.
 // ---------------------------------------------------------------------------------------------
@@ -90,11 +90,11 @@ __global__ void __launch_bounds__(64) k_max_merge(MaxMerge a) {
 	const int i = threadIdx.x;
 	if (i >= a.n) return;
 	float m = 0.0f;
-	for (int r = 0; r < a.np; r++) m = fmaxf(m, a.p[r][i]);
-	for (int r = 0; r < a.np; r++) a.p[r][i] = m;
+	for (int r = 0; r < a.nin; r++) m = fmaxf(m, a.in[r][i]);
+	for (int r = 0; r < a.nout; r++) a.out[r][i] = m;
 }
 void launch_max_merge(const MaxMerge &a, hipStream_t st) {
-	if (a.np > 0 && a.n > 0) hipLaunchKernelGGL(k_max_merge, dim3(1), dim3(64), 0, st, a);
+	if (a.nin > 0 && a.nout > 0 && a.n > 0) hipLaunchKernelGGL(k_max_merge, dim3(1), dim3(64), 0, st, a);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -20,19 +20,17 @@
 //                     and descriptors dealt and all-reduced): eight times the pyramid and the extrema of the tail for an eighth of its descriptors.
 //   no read-backs     (r06) detection and orientation of every sharded octave are enqueued before the first count is read; the first round's
 //                     finish leaves its count of flagged records in pinned memory and is only looked at when everything else is enqueued.
-// Transport:
-//   RCCL   one host thread per GPU, three communicators per rank (urgent / deferred / tail: operations of one communicator must be
-//          issued in the same order on every rank, and the three flows run concurrently; the tail's carries the gather of the seed level
-//          alone), point-to-point ncclSend / ncclRecv between
-//          z-neighbours over xGMI inside ncclGroupStart / End, on the rank's own streams: no host synchronisation between the
-//          levels.  librccl is opened at run time (dlopen), so the library loads on hosts without it.
-//          Failure protocol (r04): the first rank (or tail thread) whose step fails aborts EVERY communicator of the handle
-//          (ncclCommAbort), so that z-neighbours blocked in a receive / reduction kernel return instead of wedging the process; the
-//          handle is then dead -- sift3d_sharded_run returns an error from now on, the caller destroys it and, if it wants to go on,
-//          starts a fresh process (nothing is restarted in place).
-//   SIM    all ranks in this process on ONE GPU and one stream: the sends of an exchange step are one copy launch (kernels_pyramid.hip
-//          k_copy_segments), the MAX reduction a device kernel.  This is how the 1-GPU test boxes check the driver (same code, same
-//          plan) against the single-volume result, and how the work of eight ranks is added up on one GPU (bench.py --sim-ranks).
+// Transport: the pipeline builds lists of moves (source rank / pointer -> destination rank / pointer, bytes) and hands them to post() on a
+// lane (urgent / deferred halos of a sharded octave, the tail's gather: a send stream, a receive stream and a communicator per rank); post()
+// and reduce_dogmax() are the only places where the three transports differ, for_ranks() the only place that starts rank threads.
+//   SIM     every rank in one thread on ONE GPU, a shared stream per octave: the moves of a post are one copy launch (k_copy_segments), the
+//           MAX a device kernel.  How the 1-GPU test boxes check the plan against the single-volume result (bench.py --sim-ranks).
+//   COPIES  one thread per rank (a device may be named several times): a send is an event + address in the mailbox of the rank pair, a
+//           receive waits for it and copies (one copy launch on one device, a peer copy between devices).
+//   RCCL    one thread per GPU, one group of ncclSend / ncclRecv per post on the lane's communicator (2 S + 1 per rank: operations of one
+//           communicator are issued in one order on every rank, the lanes run concurrently); librccl is opened at run time (dlopen).
+//   Failure protocol (r04): the first rank (or tail thread) whose step fails aborts EVERY communicator (ncclCommAbort) and wakes every
+//   mailbox, so that no peer stays blocked; the handle is then dead -- the caller destroys it (nothing is restarted in place).
 //
 // 3dsift_amd/slab.py drives the same C-ABI slab contexts from python over torch.distributed; this file is what the C++ user gets:
 // CSIFT3DFactory::CreateCSIFT3D with SIFT3D_DEVICES=0,1,...,7 (3dsift_amd/host/src/cSIFT3D.cpp).
@@ -62,6 +60,8 @@ namespace {
 
 enum { KIND_INPUT = 0, KIND_GSS = 1, KIND_DOG = 2 };
 struct Transfer { int src, dst, kind, idx, zg0, zg1, stage; };
+struct Move { int src, dst; const void *sp; void *dp; size_t bytes; };  // sp valid where src is local, dp where dst is local; bytes > 0
+enum class Transport { Sim, Copies, Rccl };
 typedef std::vector<std::pair<int, int>> Bounds;
 
 // ---- planning (halo / window plans as in 3dsift_amd/slab.py, which the CPU tests cover; the slab boundaries: weighted, see slab_bounds_weighted) ----
@@ -233,8 +233,8 @@ struct Worker {  // the sharded octaves of one rank (+ the tail's extractor on t
 	int rank = 0, device = 0;
 	// r06: every sharded octave has a stream of its own (sstream[s]; stream == sstream[0]) -- octave s + 1 only depends on the seed level octave
 	// s decimates (ev_next[s]), and its launches are small and latency-bound: they run beside the machine-filling launches of the octave
-	// above, as the octaves of the single-GPU extractor do -- and, for RCCL, a stream for its deferred halos and a pair of communicators
-	// (operations of one communicator are issued in one order; the octaves' flows interleave freely)
+	// above, as the octaves of the single-GPU extractor do -- and a stream for its deferred halos (simulated ranks: the shared stream itself) and,
+	// for RCCL, a pair of communicators (operations of one communicator are issued in one order; the octaves' flows interleave freely)
 	hipStream_t stream = nullptr;
 	std::vector<hipStream_t> sstream, sdstream;
 	hipStream_t tstream = nullptr;                    // tail rank: the stream of the tail's extractor (the seed level is gathered on it)
@@ -258,7 +258,7 @@ struct Worker {  // the sharded octaves of one rank (+ the tail's extractor on t
 	int tail_rc = 0;
 	std::string tail_err;
 	// copy transport: the events this rank has recorded for its sends in the current step (reused from step to step: a step ends with every
-	// stream of every rank drained), and where its peers' DoG maxima land
+	// stream of every rank drained), and every rank's DoG maxima (its own exported into slot `rank`, the peers' copied into theirs)
 	std::vector<hipEvent_t> evp;
 	size_t evp_i = 0;
 	std::vector<float *> dogmax_in;  // per stage: world x 8 floats (device)
@@ -289,7 +289,7 @@ struct PartStage {
 
 struct sift3d_sharded {
 	int nx = 0, ny = 0, nz = 0, world = 1, S = 1, halo = 0, noct = 0, levels = 3, ng = 6;
-	bool sim = false;
+	Transport tr = Transport::Rccl;
 	sift3d_params p{};
 	std::vector<int> devices;
 	std::vector<Worker> workers;
@@ -321,14 +321,11 @@ struct sift3d_sharded {
 	std::atomic<bool> failed{false};
 	std::atomic<bool> comms_aborted{false};  // abort_all ran: the communicators are gone (their pointers are left alone)
 	std::shared_timed_mutex comm_mu;
-	// r06, the COPY transport (SIFT3D_SHARDED_COPY_TRANSPORT): the same rank threads, streams and plan as the RCCL transport, but a "send" is a message
-	// -- an event recorded on the sender's stream behind the producer + the source address -- in the mailbox of the (sender, receiver) pair, and a
-	// "receive" waits for the message (host), makes its stream wait for the event and copies (one copy launch per exchange step on one device,
-	// hipMemcpyPeerAsync between devices).  Both sides walk the same transfer list in the same order, so a FIFO per pair matches them.  A step
-	// writes every buffer it sends from once, and ends with every rank's streams drained: a sender never overwrites what a peer still reads.
-	// `devices` may name one device several times: N rank THREADS on one GPU -- what a one-GPU box can run of the multi-threaded driver.
+	// r06, the COPY transport (SIFT3D_SHARDED_COPY_TRANSPORT): a "send" is a message -- an event recorded on the sender's stream behind the
+	// producer + the source address -- in the mailbox of the (sender, receiver) pair.  Both sides walk the same move list in the same order, so a
+	// FIFO per pair matches them.  A step writes every buffer it sends from once, and ends with every rank's streams drained: a sender never
+	// overwrites what a peer still reads.  `devices` may name one device several times: N rank THREADS on one GPU.
 	bool ghost0 = false;  // SIFT3D_SHARDED_GHOST_OCTAVE0: octave 0's levels on ghost zones, nothing of octave 0 is exchanged
-	bool copies = false;
 	struct Msg { hipEvent_t ev; const void *p; };
 	struct Mailbox { std::mutex mu; std::condition_variable cv; std::deque<Msg> q; };
 	std::unique_ptr<Mailbox[]> mail;  // [src * world + dst]
@@ -351,8 +348,8 @@ void set_err(W &w, const std::string &msg) {
 // reduction or a broadcast whose partner will never arrive.  The exclusive lock is awaited for a bounded time only: a peer stuck
 // INSIDE a call (connection set-up waiting for the rank that failed) holds it shared, and aborting under it is what frees that peer.
 void abort_all(sift3d_sharded *H) {
-	if (H->sim || H->failed.exchange(true)) return;
-	if (H->copies) {  // (no communicators: the flag alone frees the ranks that wait for a message or at a rendezvous)
+	if (H->tr == Transport::Sim || H->failed.exchange(true)) return;
+	if (H->tr == Transport::Copies) {  // (no communicators: the flag alone frees the ranks that wait for a message or at a rendezvous)
 		for (int i = 0; i < H->world * H->world; i++) H->mail[(size_t)i].cv.notify_all();
 		return;
 	}
@@ -372,7 +369,47 @@ void abort_all(sift3d_sharded *H) {
 }
 #define SH_LIVE(H, w) do { if ((H)->failed.load()) { set_err((w), "aborted: another rank failed"); return SIFT3D_ERR_STATE; } } while (0)
 
-// ---- the copy transport's three moves --------------------------------------------------------------------------------------------
+// what the ranks do, f(ws): SIM one call with every worker, in this thread; otherwise one thread per rank, and the first rank that fails aborts
+// the others.  The cause goes to `why`: the first rank whose error is its own, not "aborted: another rank failed".
+template <class F>
+int for_ranks(sift3d_sharded *H, F f, std::string &why) {
+	std::vector<Worker *> all;
+	for (Worker &w : H->workers) all.push_back(&w);
+	if (H->tr == Transport::Sim) {
+		const int rc = f(all);
+		if (rc) for (Worker *w : all) if (!w->err.empty()) { why = w->err; break; }
+		return rc;
+	}
+	std::vector<int> rcs(all.size(), SIFT3D_OK);
+	std::vector<std::thread> th;
+	for (Worker *w : all)
+		th.emplace_back([&, w] {
+			std::vector<Worker *> ws{w};
+			rcs[(size_t)w->rank] = f(ws);
+			if (rcs[(size_t)w->rank] != SIFT3D_OK) abort_all(H);  // frees the z-neighbours blocked in a receive / reduction with this rank
+		});
+	for (auto &t : th) t.join();
+	for (int pass = 0; pass < 2; pass++)
+		for (Worker *w : all)
+			if (rcs[(size_t)w->rank] && (pass == 1 || w->err.compare(0, 8, "aborted:") != 0)) {
+				why = "rank " + std::to_string(w->rank) + ": " + w->err;
+				return rcs[(size_t)w->rank];
+			}
+	return SIFT3D_OK;
+}
+
+// ---- moving data: lanes, the copy transport's mailboxes, post() -----------------------------------------------------------------
+// A lane gives every rank a send stream, a receive stream and a communicator.  urgent(s) / deferred(s): the rank's stream / deferred stream of
+// sharded octave s and that octave's communicators.  TAIL: the senders' stream of the last sharded octave (which decimates their pieces of the
+// tail's seed level), the tail rank's tail stream, the tail's communicator.
+struct Lane {
+	enum Kind { URGENT, DEFERRED, TAIL } kind;
+	int s;
+	hipStream_t send(const Worker &w) const { return kind == DEFERRED ? w.sdstream[(size_t)s] : w.sstream[(size_t)s]; }
+	hipStream_t recv(const Worker &w) const { return kind == TAIL ? w.tstream : send(w); }
+	ncclComm_t comm(const Worker &w) const { return kind == TAIL ? w.c_tail : kind == DEFERRED ? w.c_deferred[(size_t)s] : w.c_urgent[(size_t)s]; }
+};
+
 // an event of this rank, recorded on `st` (behind everything the rank has enqueued there)
 int mb_mark(Worker &w, hipStream_t st, hipEvent_t &ev) {
 	if (w.evp_i == w.evp.size()) {
@@ -405,209 +442,164 @@ int mb_take(sift3d_sharded *H, Worker &w, int src, hipStream_t st, const void *&
 	p = m.p;
 	return SIFT3D_OK;
 }
-// n bytes from a peer's buffer into this rank's, on this rank's stream: collected into `cs` on one device, a peer copy between devices
-int mb_copy(sift3d_sharded *H, Worker &w, int src, const void *sp, void *dp, size_t bytes, CopySegs &cs, hipStream_t st) {
-	const int sdev = H->workers[(size_t)src].device;
-	if (!bytes) return SIFT3D_OK;
-	if (sdev != w.device) { SH_HIP(w, hipMemcpyPeerAsync(dp, w.device, sp, sdev, bytes, st)); return SIFT3D_OK; }
-	if (bytes & 3) { SH_HIP(w, hipMemcpyAsync(dp, sp, bytes, hipMemcpyDeviceToDevice, st)); return SIFT3D_OK; }
-	cs.src[cs.n] = static_cast<const float *>(sp); cs.dst[cs.n] = static_cast<float *>(dp); cs.floats[cs.n] = bytes / 4; cs.n++;
-	if (cs.n == kCopySegs) { launch_copy_segments(cs, st); cs.n = 0; }
-	return SIFT3D_OK;
-}
 
-// posts the transfers this set of local workers takes part in.  SIM: device copies on the shared stream.  RCCL: one group of
-// sends / receives of the one local rank on `comm` / `stream` of the given flow (0 urgent, 1 deferred).
-int exchange(sift3d_sharded *H, std::vector<Worker *> &ws, const std::vector<Transfer> &ts, int flow) {
-	if (ts.empty()) return SIFT3D_OK;
-	const size_t sgi = (size_t)ts[0].stage;  // (a call's transfers belong to one sharded octave)
-	if (H->sim) {
-		Worker &w0 = *ws[0];
-		hipStream_t sst = w0.sstream[sgi];
-		CopySegs cs;
-		for (const Transfer &t : ts) {
-			if (H->solo && t.dst != w0.rank) continue;  // (solo: only what this rank RECEIVES; its neighbours' buffers hold the last full run's planes)
-			Stage &s = H->workers[(size_t)t.src].stages[(size_t)t.stage], &d = H->workers[(size_t)t.dst].stages[(size_t)t.stage];
-			float *sp = s.view(t.kind, t.idx, t.zg0, t.zg1), *dp = d.view(t.kind, t.idx, t.zg0, t.zg1);
-			if (!sp || !dp) { set_err(w0, "halo transfer outside a level buffer"); return SIFT3D_ERR_STATE; }
-			cs.src[cs.n] = sp; cs.dst[cs.n] = dp; cs.floats[cs.n] = s.plane * (size_t)(t.zg1 - t.zg0); cs.n++;
-			if (cs.n == kCopySegs) { launch_copy_segments(cs, sst); cs.n = 0; }
-		}
-		launch_copy_segments(cs, sst);
-		SH_HIP(w0, hipGetLastError());
+// device copies into buffers of rank w on one stream: word ranges on one device collected into k_copy_segments launches, odd byte counts as plain
+// copies (never: planes, records, histograms and masses are words), a peer copy between devices
+struct CopyBatch {
+	Worker &w;
+	hipStream_t st;
+	CopySegs cs;
+	int add(const void *sp, int sdev, void *dp, size_t bytes) {
+		if (sdev != w.device) { SH_HIP(w, hipMemcpyPeerAsync(dp, w.device, sp, sdev, bytes, st)); return SIFT3D_OK; }
+		if (bytes & 3) { SH_HIP(w, hipMemcpyAsync(dp, sp, bytes, hipMemcpyDeviceToDevice, st)); return SIFT3D_OK; }
+		cs.src[cs.n] = static_cast<const float *>(sp); cs.dst[cs.n] = static_cast<float *>(dp); cs.floats[cs.n] = bytes / 4; cs.n++;
+		if (cs.n == kCopySegs) { launch_copy_segments(cs, st); cs.n = 0; }
 		return SIFT3D_OK;
 	}
-	Worker &w = *ws[0];
-	hipStream_t st = flow ? w.sdstream[sgi] : w.sstream[sgi];
-	bool any = false, sends = false;
-	for (const Transfer &t : ts) { any = any || t.src == w.rank || t.dst == w.rank; sends = sends || t.src == w.rank; }
-	if (!any) return SIFT3D_OK;
-	if (H->copies) {
-		SH_LIVE(H, w);
-		hipEvent_t ev = nullptr;
-		int rc;
-		if (sends && (rc = mb_mark(w, st, ev)) != SIFT3D_OK) return rc;
-		for (const Transfer &t : ts) {  // every send first (none of them waits), then the receives
-			if (t.src != w.rank) continue;
-			float *p = w.stages[(size_t)t.stage].view(t.kind, t.idx, t.zg0, t.zg1);
-			if (!p) { set_err(w, "halo transfer outside a level buffer"); return SIFT3D_ERR_STATE; }
-			mb_post(H, w.rank, t.dst, ev, p);
-		}
-		CopySegs cs;
-		for (const Transfer &t : ts) {
-			if (t.dst != w.rank) continue;
-			Stage &s = w.stages[(size_t)t.stage];
-			float *p = s.view(t.kind, t.idx, t.zg0, t.zg1);
-			if (!p) { set_err(w, "halo transfer outside a level buffer"); return SIFT3D_ERR_STATE; }
-			const void *sp = nullptr;
-			if ((rc = mb_take(H, w, t.src, st, sp)) != SIFT3D_OK) return rc;
-			if ((rc = mb_copy(H, w, t.src, sp, p, sizeof(float) * s.plane * (size_t)(t.zg1 - t.zg0), cs, st)) != SIFT3D_OK) return rc;
-		}
+	int flush() {
 		launch_copy_segments(cs, st);
+		cs.n = 0;
 		SH_HIP(w, hipGetLastError());
 		return SIFT3D_OK;
 	}
-	ncclComm_t comm = flow ? w.c_deferred[sgi] : w.c_urgent[sgi];
+};
+
+// posts the moves the ranks ws take part in, on a lane: the one place where the transports move data.
+//   SIM     every rank is in ws: every move in one batch on the lane's (shared) send stream; a solo re-run only what the solo rank receives
+//           (its neighbours' buffers hold what the last full run left there)
+//   COPIES  one mark if the rank sends anything, every send posted, then every receive taken and copied, in list order
+//   RCCL    one group of the rank's sends and receives, in list order
+int post(sift3d_sharded *H, std::vector<Worker *> &ws, const std::vector<Move> &moves, Lane lane) {
+	Worker &w = *ws[0];
+	int rc;
+	if (H->tr == Transport::Sim) {
+		CopyBatch b{w, lane.send(w)};
+		for (const Move &m : moves)
+			if (!(H->solo && m.dst != w.rank) && (rc = b.add(m.sp, w.device, m.dp, m.bytes)) != SIFT3D_OK) return rc;
+		return b.flush();
+	}
+	bool sends = false, recvs = false;
+	for (const Move &m : moves) { sends = sends || m.src == w.rank; recvs = recvs || m.dst == w.rank; }
+	if (!sends && !recvs) return SIFT3D_OK;
+	if (H->tr == Transport::Copies) {
+		SH_LIVE(H, w);
+		hipEvent_t ev = nullptr;
+		if (sends && (rc = mb_mark(w, lane.send(w), ev)) != SIFT3D_OK) return rc;
+		for (const Move &m : moves) if (m.src == w.rank) mb_post(H, w.rank, m.dst, ev, m.sp);
+		CopyBatch b{w, lane.recv(w)};
+		for (const Move &m : moves) {
+			const void *sp = nullptr;
+			if (m.dst == w.rank && ((rc = mb_take(H, w, m.src, b.st, sp)) != SIFT3D_OK || (rc = b.add(sp, H->workers[(size_t)m.src].device, m.dp, m.bytes)) != SIFT3D_OK))
+				return rc;
+		}
+		return b.flush();
+	}
 	std::shared_lock<std::shared_timed_mutex> live(H->comm_mu);
 	SH_LIVE(H, w);
+	const ncclComm_t comm = lane.comm(w);
 	SH_NCCL(w, g_rccl.GroupStart());
-	for (const Transfer &t : ts) {
-		if (t.src != w.rank && t.dst != w.rank) continue;
-		Stage &s = w.stages[(size_t)t.stage];
-		float *p = s.view(t.kind, t.idx, t.zg0, t.zg1);
-		if (!p) { (void)g_rccl.GroupEnd(); set_err(w, "halo transfer outside a level buffer"); return SIFT3D_ERR_STATE; }
-		const size_t cnt = s.plane * (size_t)(t.zg1 - t.zg0);
-		if (t.src == w.rank) SH_NCCL(w, g_rccl.Send(p, cnt, ncclFloat, t.dst, comm, st));
-		else SH_NCCL(w, g_rccl.Recv(p, cnt, ncclFloat, t.src, comm, st));
+	for (const Move &m : moves) {
+		if (m.src == w.rank) SH_NCCL(w, g_rccl.Send(m.sp, m.bytes, ncclInt8, m.dst, comm, lane.send(w)));
+		else if (m.dst == w.rank) SH_NCCL(w, g_rccl.Recv(m.dp, m.bytes, ncclInt8, m.src, comm, lane.recv(w)));
 	}
 	SH_NCCL(w, g_rccl.GroupEnd());
 	return SIFT3D_OK;
 }
 
-// in-place MAX over the ranks of n device floats per worker (non-negative values: the DoG maxima), stream ordered for RCCL
-int allreduce_max_dev(sift3d_sharded *H, std::vector<Worker *> &ws, int stage, int n) {
-	if (H->sim && H->solo) return SIFT3D_OK;  // (the rank's buffer still holds the global maxima of the last full run: run_local skips the export)
-	if (H->sim) {
-		Worker &w0 = *ws[0];
-		if ((int)ws.size() <= kMaxMergePtrs && n <= 64) {  // on the device, in the shared stream's order (no host round trip)
-			MaxMerge mm;
-			for (Worker *w : ws) mm.p[mm.np++] = w->dogmax[(size_t)stage];
-			mm.n = n;
-			launch_max_merge(mm, w0.sstream[(size_t)stage]);
-			SH_HIP(w0, hipGetLastError());
-			return SIFT3D_OK;
-		}
-		std::vector<float> m((size_t)n, 0.f), t((size_t)n);
-		SH_HIP(w0, hipStreamSynchronize(w0.sstream[(size_t)stage]));
-		for (Worker *w : ws) {
-			SH_HIP(w0, hipMemcpy(t.data(), w->dogmax[(size_t)stage], sizeof(float) * n, hipMemcpyDeviceToHost));
-			for (int i = 0; i < n; i++) m[(size_t)i] = std::max(m[(size_t)i], t[(size_t)i]);
-		}
-		for (Worker *w : ws) SH_HIP(w0, hipMemcpy(w->dogmax[(size_t)stage], m.data(), sizeof(float) * n, hipMemcpyHostToDevice));
-		return SIFT3D_OK;
+// plane transfers of one sharded octave as moves, resolved through Stage::view for the ranks in ws only (view fills its map lazily: a rank thread
+// never calls it on another rank's stage; a solo re-run reads its neighbours' planes as the last full run left them), and posted
+int post_halos(sift3d_sharded *H, std::vector<Worker *> &ws, const std::vector<Transfer> &ts, Lane lane) {
+	if (ts.empty()) return SIFT3D_OK;
+	const size_t o = (size_t)ts[0].stage;  // (a call's transfers belong to one sharded octave)
+	std::vector<Stage *> mine((size_t)H->world, nullptr);
+	for (Worker *w : ws) mine[(size_t)w->rank] = &w->stages[o];
+	std::vector<Stage *> from = mine;
+	if (H->solo) for (Worker &w : H->workers) from[(size_t)w.rank] = &w.stages[o];
+	std::vector<Move> mv;
+	for (const Transfer &t : ts) {
+		Stage *s = from[(size_t)t.src], *d = mine[(size_t)t.dst];
+		if (!mine[(size_t)t.src] && !d) continue;
+		const void *sp = s ? s->view(t.kind, t.idx, t.zg0, t.zg1) : nullptr;
+		void *dp = d ? d->view(t.kind, t.idx, t.zg0, t.zg1) : nullptr;
+		if ((s && !sp) || (d && !dp)) { set_err(*ws[0], "halo transfer outside a level buffer"); return SIFT3D_ERR_STATE; }
+		mv.push_back(Move{t.src, t.dst, sp, dp, sizeof(float) * (s ? s : d)->plane * (size_t)(t.zg1 - t.zg0)});
 	}
-	Worker &w = *ws[0];
-	if (H->copies) {
-		// every rank's n values into this rank's scratch, then the MAX over them and its own (a peer's array may already hold ITS merge: a maximum
-		// of maxima, the same result)
-		SH_LIVE(H, w);
-		hipStream_t st = w.sstream[(size_t)stage];
-		hipEvent_t ev = nullptr;
-		int rc = mb_mark(w, st, ev);
-		if (rc) return rc;
-		for (int r = 0; r < H->world; r++) if (r != w.rank) mb_post(H, w.rank, r, ev, w.dogmax[(size_t)stage]);
-		MaxMerge mm;
-		mm.p[mm.np++] = w.dogmax[(size_t)stage];
-		mm.n = n;
-		for (int r = 0; r < H->world; r++) {
-			if (r == w.rank) continue;
-			const void *sp = nullptr;
-			if ((rc = mb_take(H, w, r, st, sp)) != SIFT3D_OK) return rc;
-			float *slot = w.dogmax_in[(size_t)stage] + (size_t)r * 8;
-			const int sdev = H->workers[(size_t)r].device;
-			if (sdev != w.device) SH_HIP(w, hipMemcpyPeerAsync(slot, w.device, sp, sdev, sizeof(float) * (size_t)n, st));
-			else SH_HIP(w, hipMemcpyAsync(slot, sp, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, st));
-			mm.p[mm.np++] = slot;
-		}
-		launch_max_merge(mm, st);
-		SH_HIP(w, hipGetLastError());
-		return SIFT3D_OK;
-	}
-	std::shared_lock<std::shared_timed_mutex> live(H->comm_mu);
-	SH_LIVE(H, w);
-	SH_NCCL(w, g_rccl.AllReduce(w.dogmax[(size_t)stage], w.dogmax[(size_t)stage], (size_t)n, ncclFloat, ncclMax, w.c_urgent[(size_t)stage], w.sstream[(size_t)stage]));
-	return SIFT3D_OK;
+	return post(H, ws, mv, lane);
 }
 
 // The tail's seed level = the owned planes of all ranks, in rank order, gathered ON THE TAIL RANK straight into level 0 of its seeded
-// extractor, on that extractor's stream.  The tail rank's own planes were decimated in place.
-int gather_seed(sift3d_sharded *H, std::vector<Worker *> &ws) {
+// extractor (the tail rank's own planes are decimated in place).  The pointers are written once, at creation: any thread may read them.
+std::vector<Move> seed_moves(sift3d_sharded *H) {
 	const size_t pl = (size_t)H->sx * H->sy;
-	std::vector<size_t> off((size_t)H->world + 1, 0);
-	for (int r = 0; r < H->world; r++) off[(size_t)r + 1] = off[(size_t)r] + pl * (size_t)H->counts2[(size_t)r];
-	Worker *tw = nullptr;
-	for (Worker *w : ws) if (w->rank == H->tail_rank) tw = w;
-	const size_t sl = (size_t)H->S - 1;  // the last sharded octave decimates the tail's seed level: on its stream
-	if (H->sim) {
-		Worker &w0 = *ws[0];
-		if (!tw && H->solo) return SIFT3D_OK;  // (a solo rank that is not the tail rank: its piece was decimated, the send costs the GPU nothing)
-		if (!tw) { set_err(w0, "no tail rank among the simulated ranks"); return SIFT3D_ERR_STATE; }
-		CopySegs cs;
-		std::vector<Worker *> srcs = ws;
-		if (H->solo) { srcs.clear(); for (Worker &w : H->workers) srcs.push_back(&w); }  // (the other ranks' pieces of the last full run)
-		for (Worker *w : srcs) {
-			const size_t cnt = off[(size_t)w->rank + 1] - off[(size_t)w->rank];
-			if (w == tw || !cnt) continue;
-			cs.src[cs.n] = w->seed_mine; cs.dst[cs.n] = tw->seed_dst + off[(size_t)w->rank]; cs.floats[cs.n] = cnt; cs.n++;
-			if (cs.n == kCopySegs) { launch_copy_segments(cs, w0.sstream[sl]); cs.n = 0; }
-		}
-		launch_copy_segments(cs, w0.sstream[sl]);
-		SH_HIP(w0, hipEventRecord(tw->ev_seed, w0.sstream[sl]));
-		SH_HIP(w0, hipStreamWaitEvent(tw->tstream, tw->ev_seed, 0));
-		return SIFT3D_OK;
+	float *dst = H->workers[(size_t)H->tail_rank].seed_dst;
+	std::vector<Move> mv;
+	for (int r = 0; r < H->world; r++) {
+		const size_t n = pl * (size_t)H->counts2[(size_t)r];
+		if (r != H->tail_rank && n) mv.push_back(Move{r, H->tail_rank, H->workers[(size_t)r].seed_mine, dst, sizeof(float) * n});
+		dst += n;
 	}
-	Worker &w = *ws[0];
-	if (H->copies) {
-		SH_LIVE(H, w);
-		int rc;
-		if (&w != tw) {  // behind the decimation on that octave's stream
-			hipEvent_t ev = nullptr;
-			if (off[(size_t)w.rank + 1] == off[(size_t)w.rank]) return SIFT3D_OK;
-			if ((rc = mb_mark(w, w.sstream[sl], ev)) != SIFT3D_OK) return rc;
-			mb_post(H, w.rank, H->tail_rank, ev, w.seed_mine);
-			return SIFT3D_OK;
+	return mv;
+}
+
+// The DoG maxima of sharded octave s made global (threshold of Detect_KeyPoints, Src/cSIFT3D.cc:379-384): every rank exports its own, the MAX
+// over the ranks is formed, every rank imports it.
+//   SIM     the max of every rank's array into all of them, on the device (through the host for more ranks than one launch takes); a solo re-run
+//           only imports (its array still holds the last full run's global maxima)
+//   COPIES  a rank exports into its slot of dogmax_in, posts that slot to its peers (whose copies land in their own slots) and merges every
+//           slot into dogmax, which no peer reads
+//   RCCL    an in-place ncclAllReduce of dogmax
+int reduce_dogmax(sift3d_sharded *H, std::vector<Worker *> &ws, int s) {
+	const size_t o = (size_t)s, n = 8;
+	const bool copies = H->tr == Transport::Copies;
+	auto mine = [&](Worker &w) { return copies ? w.dogmax_in[o] + (size_t)w.rank * n : w.dogmax[o]; };
+	if (!H->solo) for (Worker *w : ws) { SH_HIP(*w, hipSetDevice(w->device)); SH_ABI(*w, sift3d_slab_export_dogmax_device(w->stages[o].ctx, mine(*w))); }
+	Worker &w0 = *ws[0];
+	int rc;
+	switch (H->tr) {
+	case Transport::Sim:
+		if (H->solo) break;
+		if (ws.size() <= (size_t)kMaxMergePtrs) {
+			MaxMerge mm;
+			for (Worker *w : ws) { mm.in[mm.nin++] = w->dogmax[o]; mm.out[mm.nout++] = w->dogmax[o]; }
+			mm.n = (int)n;
+			launch_max_merge(mm, w0.sstream[o]);
+			SH_HIP(w0, hipGetLastError());
+			break;
 		}
-		CopySegs cs;
-		for (int r = 0; r < H->world; r++) {
-			const size_t cnt = off[(size_t)r + 1] - off[(size_t)r];
-			if (r == w.rank || !cnt) continue;
-			const void *sp = nullptr;
-			if ((rc = mb_take(H, w, r, w.tstream, sp)) != SIFT3D_OK) return rc;
-			if ((rc = mb_copy(H, w, r, sp, w.seed_dst + off[(size_t)r], sizeof(float) * cnt, cs, w.tstream)) != SIFT3D_OK) return rc;
+		{
+			std::vector<float> m(n, 0.f), t(n);
+			SH_HIP(w0, hipStreamSynchronize(w0.sstream[o]));
+			for (Worker *w : ws) {
+				SH_HIP(w0, hipMemcpy(t.data(), w->dogmax[o], sizeof(float) * n, hipMemcpyDeviceToHost));
+				for (size_t i = 0; i < n; i++) m[i] = std::max(m[i], t[i]);
+			}
+			for (Worker *w : ws) SH_HIP(w0, hipMemcpy(w->dogmax[o], m.data(), sizeof(float) * n, hipMemcpyHostToDevice));
 		}
-		launch_copy_segments(cs, w.tstream);
-		SH_HIP(w, hipGetLastError());
-		SH_HIP(w, hipEventRecord(w.ev_seed, w.sstream[sl]));
-		SH_HIP(w, hipStreamWaitEvent(w.tstream, w.ev_seed, 0));
-		return SIFT3D_OK;
+		break;
+	case Transport::Copies: {
+		std::vector<Move> mv;
+		for (int r = 0; r < H->world; r++)
+			if (r != w0.rank) {
+				mv.push_back(Move{w0.rank, r, mine(w0), nullptr, sizeof(float) * n});
+				mv.push_back(Move{r, w0.rank, nullptr, w0.dogmax_in[o] + (size_t)r * n, sizeof(float) * n});
+			}
+		if ((rc = post(H, ws, mv, Lane{Lane::URGENT, s})) != SIFT3D_OK) return rc;
+		MaxMerge mm;
+		for (int r = 0; r < H->world; r++) mm.in[mm.nin++] = w0.dogmax_in[o] + (size_t)r * n;
+		mm.out[mm.nout++] = w0.dogmax[o];
+		mm.n = (int)n;
+		launch_max_merge(mm, w0.sstream[o]);
+		SH_HIP(w0, hipGetLastError());
+		break;
 	}
-	{
+	case Transport::Rccl: {
 		std::shared_lock<std::shared_timed_mutex> live(H->comm_mu);
-		SH_LIVE(H, w);
-		if (&w != tw) {
-			const size_t cnt = off[(size_t)w.rank + 1] - off[(size_t)w.rank];
-			if (cnt) SH_NCCL(w, g_rccl.Send(w.seed_mine, cnt, ncclFloat, H->tail_rank, w.c_tail, w.sstream[sl]));  // behind the decimation on that octave's stream
-			return SIFT3D_OK;
-		}
-		SH_NCCL(w, g_rccl.GroupStart());
-		for (int r = 0; r < H->world; r++) {
-			const size_t cnt = off[(size_t)r + 1] - off[(size_t)r];
-			if (r != w.rank && cnt) SH_NCCL(w, g_rccl.Recv(w.seed_dst + off[(size_t)r], cnt, ncclFloat, r, w.c_tail, w.tstream));
-		}
-		SH_NCCL(w, g_rccl.GroupEnd());
+		SH_LIVE(H, w0);
+		SH_NCCL(w0, g_rccl.AllReduce(w0.dogmax[o], w0.dogmax[o], n, ncclFloat, ncclMax, w0.c_urgent[o], w0.sstream[o]));
+		break;
 	}
-	SH_HIP(w, hipEventRecord(w.ev_seed, w.sstream[sl]));       // the tail rank's own planes (decimated in place on that octave's stream)
-	SH_HIP(w, hipStreamWaitEvent(w.tstream, w.ev_seed, 0));
+	}
+	for (Worker *w : ws) { SH_HIP(*w, hipSetDevice(w->device)); SH_ABI(*w, sift3d_slab_import_dogmax_device(w->stages[o].ctx, w->dogmax[o])); }
 	return SIFT3D_OK;
 }
 
@@ -644,7 +636,7 @@ int join_tail(std::vector<Worker *> &ws) {
 // ---- partial descriptor windows (r05, opt-in; the protocol of 3dsift_amd/slab.py _describe_partial) ---------------------
 // every rank thread of the RCCL transport arrives; values written before are visible to all after.  A dead handle lets the waiters go.
 int rendezvous(sift3d_sharded *H, Worker &w) {
-	if (H->sim) return SIFT3D_OK;
+	if (H->tr == Transport::Sim) return SIFT3D_OK;
 	std::unique_lock<std::mutex> lk(H->rv_mu);
 	const unsigned gen = H->rv_gen;
 	if (++H->rv_arrived == H->world) { H->rv_arrived = 0; H->rv_gen++; H->rv_cv.notify_all(); return SIFT3D_OK; }
@@ -659,56 +651,6 @@ int rendezvous(sift3d_sharded *H, Worker &w) {
 		}
 		H->rv_cv.wait_for(lk, std::chrono::milliseconds(20));
 	}
-	return SIFT3D_OK;
-}
-
-struct RawXfer { int src, dst; const void *sp; void *dp; size_t bytes; };  // sp valid where src is local, dp where dst is local
-
-int exchange_raw(sift3d_sharded *H, std::vector<Worker *> &ws, const std::vector<RawXfer> &ts, int stage) {
-	if (ts.empty()) return SIFT3D_OK;
-	if (H->sim) {
-		Worker &w0 = *ws[0];
-		hipStream_t sst = w0.sstream[(size_t)stage];
-		CopySegs cs;
-		for (const RawXfer &t : ts) {
-			if (!t.bytes) continue;
-			if (t.bytes & 3) { SH_HIP(w0, hipMemcpyAsync(t.dp, t.sp, t.bytes, hipMemcpyDeviceToDevice, sst)); continue; }  // (never: records, histograms and masses are words)
-			cs.src[cs.n] = static_cast<const float *>(t.sp); cs.dst[cs.n] = static_cast<float *>(t.dp); cs.floats[cs.n] = t.bytes / 4; cs.n++;
-			if (cs.n == kCopySegs) { launch_copy_segments(cs, sst); cs.n = 0; }
-		}
-		launch_copy_segments(cs, sst);
-		SH_HIP(w0, hipGetLastError());
-		return SIFT3D_OK;
-	}
-	Worker &w = *ws[0];
-	if (H->copies) {
-		SH_LIVE(H, w);
-		hipStream_t st = w.sstream[(size_t)stage];
-		hipEvent_t ev = nullptr;
-		int rc;
-		bool sends = false;
-		for (const RawXfer &t : ts) sends = sends || (t.src == w.rank && t.bytes);
-		if (sends && (rc = mb_mark(w, st, ev)) != SIFT3D_OK) return rc;
-		for (const RawXfer &t : ts) if (t.src == w.rank && t.bytes) mb_post(H, w.rank, t.dst, ev, t.sp);
-		CopySegs cs;
-		for (const RawXfer &t : ts) {
-			if (t.dst != w.rank || !t.bytes) continue;
-			const void *sp = nullptr;
-			if ((rc = mb_take(H, w, t.src, st, sp)) != SIFT3D_OK) return rc;
-			if ((rc = mb_copy(H, w, t.src, sp, t.dp, t.bytes, cs, st)) != SIFT3D_OK) return rc;
-		}
-		launch_copy_segments(cs, st);
-		SH_HIP(w, hipGetLastError());
-		return SIFT3D_OK;
-	}
-	std::shared_lock<std::shared_timed_mutex> live(H->comm_mu);
-	SH_LIVE(H, w);
-	SH_NCCL(w, g_rccl.GroupStart());
-	for (const RawXfer &t : ts) {
-		if (t.src == w.rank) SH_NCCL(w, g_rccl.Send(t.sp, t.bytes, ncclInt8, t.dst, w.c_urgent[(size_t)stage], w.sstream[(size_t)stage]));
-		else if (t.dst == w.rank) SH_NCCL(w, g_rccl.Recv(t.dp, t.bytes, ncclInt8, t.src, w.c_urgent[(size_t)stage], w.sstream[(size_t)stage]));
-	}
-	SH_NCCL(w, g_rccl.GroupEnd());
 	return SIFT3D_OK;
 }
 
@@ -765,7 +707,7 @@ int partial_round(sift3d_sharded *H, std::vector<Worker *> &ws, int s, const std
 	for (size_t i = 0; i < ws.size(); i++) local[ws[i]->rank] = i;
 	auto is_local = [&](int r) { return local.count(r) != 0; };
 	const Bounds &bounds = ws[0]->stages[(size_t)s].bounds;
-	std::vector<RawXfer> ts;
+	std::vector<Move> ts;
 	for (int r = 0; r < H->world; r++)
 		for (int q : neigh[(size_t)r]) {
 			const size_t n = (size_t)counts[(size_t)r];
@@ -773,10 +715,10 @@ int partial_round(sift3d_sharded *H, std::vector<Worker *> &ws, int s, const std
 			if (H->solo && !is_local(q)) continue;  // (solo: only what this rank receives, from the lists the last full run left in its neighbours' scratch)
 			const PartLayout *Lr = is_local(r) ? &L[local[r]] : (H->solo ? &H->ps_last[(size_t)s].L[(size_t)r] : nullptr);
 			PartLayout *Lq = is_local(q) ? &L[local[q]] : nullptr;
-			ts.push_back(RawXfer{r, q, Lr ? Lr->recs : nullptr, Lq ? Lq->recs_in[r] : nullptr, n * rb});
-			if (second) ts.push_back(RawXfer{r, q, Lr ? Lr->units : nullptr, Lq ? Lq->units_in[r] : nullptr, n * 4});
+			ts.push_back(Move{r, q, Lr ? Lr->recs : nullptr, Lq ? Lq->recs_in[r] : nullptr, n * rb});
+			if (second) ts.push_back(Move{r, q, Lr ? Lr->units : nullptr, Lq ? Lq->units_in[r] : nullptr, n * 4});
 		}
-	int rc = exchange_raw(H, ws, ts, s);
+	int rc = post(H, ws, ts, Lane{Lane::URGENT, s});
 	if (rc) return rc;
 	for (size_t i = 0; i < ws.size(); i++) {
 		Worker &w = *ws[i];
@@ -802,10 +744,10 @@ int partial_round(sift3d_sharded *H, std::vector<Worker *> &ws, int s, const std
 			if (!n || (!is_local(r) && !is_local(q))) continue;
 			if (H->solo && !is_local(r)) continue;
 			PartLayout *Lq = is_local(q) ? &L[local[q]] : (H->solo ? &H->ps_last[(size_t)s].L[(size_t)q] : nullptr), *Lr = is_local(r) ? &L[local[r]] : nullptr;
-			ts.push_back(RawXfer{q, r, Lq ? Lq->part_h[r] : nullptr, Lr ? Lr->got_h[q] : nullptr, n * 768 * 4});
-			ts.push_back(RawXfer{q, r, Lq ? Lq->part_m[r] : nullptr, Lr ? Lr->got_m[q] : nullptr, n * 4});
+			ts.push_back(Move{q, r, Lq ? Lq->part_h[r] : nullptr, Lr ? Lr->got_h[q] : nullptr, n * 768 * 4});
+			ts.push_back(Move{q, r, Lq ? Lq->part_m[r] : nullptr, Lr ? Lr->got_m[q] : nullptr, n * 4});
 		}
-	rc = exchange_raw(H, ws, ts, s);
+	rc = post(H, ws, ts, Lane{Lane::URGENT, s});
 	if (rc) return rc;
 	for (size_t i = 0; i < ws.size(); i++) {
 		Worker &w = *ws[i];
@@ -915,7 +857,7 @@ int run_local(sift3d_sharded *H, std::vector<Worker *> &ws) {
 			const int urgent_h = i + 1 < ng ? H->hws[(size_t)i + 1] + 1 : 0;  // planes p-hw-1 .. p+hw of the next level's z-march
 			const bool ghost = H->ghost0 && s == 0;  // (ghost zones: this octave's slabs computed what they would receive)
 			// urgent: ordered behind the level kernel on the rank's stream, in front of the next level
-			int rc = ghost ? SIFT3D_OK : exchange(H, ws, halo_transfers(bounds, nzs, KIND_GSS, i, 0, urgent_h, s), 0);
+			int rc = ghost ? SIFT3D_OK : post_halos(H, ws, halo_transfers(bounds, nzs, KIND_GSS, i, 0, urgent_h, s), Lane{Lane::URGENT, s});
 			if (rc) return rc;
 			// deferred: the wider keypoint-window halo of G[1..levels] and the DoG plane behind it, on the deferred flow
 			std::vector<Transfer> late;
@@ -925,13 +867,12 @@ int run_local(sift3d_sharded *H, std::vector<Worker *> &ws) {
 				late.insert(late.end(), dg.begin(), dg.end());
 			}
 			if (!late.empty()) {
-				if (!H->sim)
-					for (Worker *w : ws) {  // the deferred stream picks up behind the level kernel
+				for (Worker *w : ws)
+					if (w->sdstream[(size_t)s] != w->sstream[(size_t)s]) {  // a deferred stream of its own picks up behind the level kernel
 						SH_HIP(*w, hipEventRecord(w->ev_level[(size_t)s], w->sstream[(size_t)s]));
 						SH_HIP(*w, hipStreamWaitEvent(w->sdstream[(size_t)s], w->ev_level[(size_t)s], 0));
 					}
-				rc = exchange(H, ws, late, 1);
-				if (rc) return rc;
+				if ((rc = post_halos(H, ws, late, Lane{Lane::DEFERRED, s})) != SIFT3D_OK) return rc;
 			}
 			if (i == H->levels && s + 1 < H->noct) {
 				// G[s+1][0] = DownSample_3D(G[s][levels]) (Src/cSIFT3D.cc:293-296, 321-344), owned planes only: straight into the next
@@ -951,25 +892,28 @@ int run_local(sift3d_sharded *H, std::vector<Worker *> &ws) {
 				}
 				if (s + 1 < H->S)
 					for (Worker *w : ws) { SH_HIP(*w, hipSetDevice(w->device)); SH_HIP(*w, hipEventRecord(w->ev_next[(size_t)s], w->sstream[(size_t)s])); }
-				// the octaves behind the sharded ones, once, on the tail rank: the seed level gathered, the whole pipeline enqueued by a thread of its own
+				// the octaves behind the sharded ones, once, on the tail rank: the seed level gathered on its tail stream, which then waits for the
+				// tail rank's own planes (decimated in place on this octave's stream); the whole pipeline enqueued by a thread of its own
 				if (s + 1 == H->S && has_tail) {
-					if ((rc = gather_seed(H, ws)) != SIFT3D_OK) return rc;
+					if ((rc = post(H, ws, seed_moves(H), Lane{Lane::TAIL, s})) != SIFT3D_OK) return rc;
+					for (Worker *w : ws)
+						if (w->rank == H->tail_rank) {
+							SH_HIP(*w, hipEventRecord(w->ev_seed, w->sstream[(size_t)s]));
+							SH_HIP(*w, hipStreamWaitEvent(w->tstream, w->ev_seed, 0));
+						}
 					if ((rc = start_tail(H, ws)) != SIFT3D_OK) return rc;
 				}
 			}
 		}
-		// DoG maxima -> global (threshold of Detect_KeyPoints, Src/cSIFT3D.cc:379-384)
-		if (!H->solo) for (Worker *w : ws) { SH_HIP(*w, hipSetDevice(w->device)); SH_ABI(*w, sift3d_slab_export_dogmax_device(w->stages[(size_t)s].ctx, w->dogmax[(size_t)s])); }
-		int rc = allreduce_max_dev(H, ws, s, 8);
+		int rc = reduce_dogmax(H, ws, s);
 		if (rc) return rc;
-		for (Worker *w : ws) { SH_HIP(*w, hipSetDevice(w->device)); SH_ABI(*w, sift3d_slab_import_dogmax_device(w->stages[(size_t)s].ctx, w->dogmax[(size_t)s])); }
 		// extrema + orientation of this octave right behind its pyramid, BEFORE the next octave's levels are enqueued: on the GPU they then run
 		// beside the next octaves' small level launches.  (Enqueued behind every octave's pyramid -- the order until late r06 -- octave 0's masks
 		// started when the LAST octave's levels had been placed, 0.25 ms after its own pyramid had ended: profiles/r06x_solo3_all.txt.)  The counts
 		// are read further down, when every octave's launches are in the queues.
 		for (Worker *w : ws) {
 			SH_HIP(*w, hipSetDevice(w->device));
-			if (!H->sim) {  // the octave's deferred halos are complete before its detection reads them
+			if (w->sdstream[(size_t)s] != w->sstream[(size_t)s]) {  // the octave's deferred halos are complete before its detection reads them
 				SH_HIP(*w, hipEventRecord(w->ev_def[(size_t)s], w->sdstream[(size_t)s]));
 				SH_HIP(*w, hipStreamWaitEvent(w->sstream[(size_t)s], w->ev_def[(size_t)s], 0));
 			}
@@ -1026,7 +970,7 @@ int run_local(sift3d_sharded *H, std::vector<Worker *> &ws) {
 			}
 			rc = partial_stage_second(H, ws, s, PS[(size_t)s]);
 		}
-		if (H->sim && !H->solo && rc == SIFT3D_OK) H->ps_last = PS;  // (simulated ranks: what a solo re-run of one rank reads its neighbours' lists from)
+		if (ws.size() == (size_t)H->world && !H->solo && rc == SIFT3D_OK) H->ps_last = PS;  // (every rank here: what a solo re-run of one reads its neighbours' lists from)
 	}
 	if (rc != SIFT3D_OK) abort_all(H);  // (peers may sit in a receive waiting for this rank)
 	// the tail's run is completed whatever happened above (an extractor with a run in flight must not be destroyed under it)
@@ -1086,7 +1030,8 @@ void destroy_worker(Worker &w, int phase, bool comms_aborted) {
 		}
 		w.c_urgent.clear(); w.c_deferred.clear(); w.c_tail = nullptr;
 	} else {
-		for (hipStream_t st : w.sdstream) if (st) (void)hipStreamDestroy(st);
+		for (size_t o = 0; o < w.sdstream.size(); o++)  // (simulated ranks: the deferred lane is the shared stream, destroyed once below)
+			if (w.sdstream[o] && w.sdstream[o] != w.sstream[o]) (void)hipStreamDestroy(w.sdstream[o]);
 		if (w.tstream) (void)hipStreamDestroy(w.tstream);
 		if (w.own_stream) for (hipStream_t st : w.sstream) if (st) (void)hipStreamDestroy(st);
 		w.sstream.clear(); w.sdstream.clear(); w.tstream = w.stream = nullptr;
@@ -1125,10 +1070,10 @@ extern "C" int sift3d_sharded_create_ex(sift3d_sharded_handle *out, const float 
 	auto fail = [&](int rc, const std::string &why) { set_last_error(why); sift3d_sharded_destroy(H); return rc; };
 	H->nx = nx; H->ny = ny; H->nz = nz;
 	if (params) H->p = *params; else sift3d_default_params(&H->p);
-	H->sim = sim_ranks > 0;
-	H->world = H->sim ? sim_ranks : ndev;
-	H->copies = !H->sim && (flags & SIFT3D_SHARDED_COPY_TRANSPORT) != 0;
-	if (H->copies) {
+	const bool sim = sim_ranks > 0;
+	H->tr = sim ? Transport::Sim : (flags & SIFT3D_SHARDED_COPY_TRANSPORT) ? Transport::Copies : Transport::Rccl;
+	H->world = sim ? sim_ranks : ndev;
+	if (H->tr == Transport::Copies) {
 		if (H->world > kMaxMergePtrs) return fail(SIFT3D_ERR_ARG, "the copy transport takes at most " + std::to_string(kMaxMergePtrs) + " ranks");
 		H->mail.reset(new sift3d_sharded::Mailbox[(size_t)H->world * (size_t)H->world]);
 		// peer access between the devices of ranks that exchange (every pair: the DoG maxima travel between all of them), so that the peer copies go
@@ -1136,7 +1081,7 @@ extern "C" int sift3d_sharded_create_ex(sift3d_sharded_handle *out, const float 
 		for (int i = 0; i < ndev; i++)
 			for (int j = 0; j < ndev; j++)
 				if (devices[i] != devices[j] && hipSetDevice(devices[i]) == hipSuccess) { (void)hipDeviceEnablePeerAccess(devices[j], 0); (void)hipGetLastError(); }
-	} else if (!H->sim) {
+	} else if (H->tr == Transport::Rccl) {
 		for (int i = 0; i < ndev; i++)
 			for (int j = 0; j < i; j++)
 				if (devices[i] == devices[j]) return fail(SIFT3D_ERR_ARG, "RCCL takes one rank per device (several ranks on one device: SIFT3D_SHARDED_COPY_TRANSPORT, or simulated ranks)");
@@ -1226,7 +1171,7 @@ extern "C" int sift3d_sharded_create_ex(sift3d_sharded_handle *out, const float 
 	}
 	H->halo = H->stage_halo[0];
 	H->need.assign((size_t)S, std::vector<int>());
-	if (!H->sim && !H->copies) {
+	if (H->tr == Transport::Rccl) {
 		std::lock_guard<std::mutex> lk(g_rccl_mu);
 		std::string e;
 		if (!g_rccl.load(e)) return fail(SIFT3D_ERR_STATE, e);
@@ -1235,22 +1180,23 @@ extern "C" int sift3d_sharded_create_ex(sift3d_sharded_handle *out, const float 
 	std::vector<hipStream_t> shared;  // simulated ranks share ONE stream per sharded octave: their "sends" are copies ordered on it
 	for (int r = 0; r < H->world; r++) {
 		Worker &w = H->workers[(size_t)r];
-		w.rank = r; w.device = H->sim ? devices[0] : devices[r];
+		w.rank = r; w.device = sim ? devices[0] : devices[r];
 #define CR_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(SIFT3D_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
 #define CR_ABI(call) do { int r_ = (call); if (r_ != SIFT3D_OK) return fail(r_, std::string(#call) + ": " + sift3d_last_error()); } while (0)
 		CR_HIP(hipSetDevice(w.device));
-		if (H->sim && !shared.empty()) w.sstream = shared;
+		if (sim && !shared.empty()) w.sstream = shared;
 		else {
 			w.sstream.assign((size_t)S, nullptr);
 			for (int o = 0; o < S; o++) CR_HIP(hipStreamCreateWithFlags(&w.sstream[(size_t)o], hipStreamNonBlocking));
 			w.own_stream = true;
-			if (H->sim) shared = w.sstream;
+			if (sim) shared = w.sstream;
 		}
 		w.stream = w.sstream[0];
 		w.sdstream.assign((size_t)S, nullptr);
 		w.ev_level.assign((size_t)S, nullptr); w.ev_def.assign((size_t)S, nullptr); w.ev_next.assign((size_t)S, nullptr);
 		for (int o = 0; o < S; o++) {
-			if (!H->sim) CR_HIP(hipStreamCreateWithFlags(&w.sdstream[(size_t)o], hipStreamNonBlocking));
+			if (sim) w.sdstream[(size_t)o] = w.sstream[(size_t)o];  // (the deferred lane of simulated ranks is the shared stream)
+			else CR_HIP(hipStreamCreateWithFlags(&w.sdstream[(size_t)o], hipStreamNonBlocking));
 			CR_HIP(hipEventCreateWithFlags(&w.ev_level[(size_t)o], hipEventDisableTiming));
 			CR_HIP(hipEventCreateWithFlags(&w.ev_def[(size_t)o], hipEventDisableTiming));
 			CR_HIP(hipEventCreateWithFlags(&w.ev_next[(size_t)o], hipEventDisableTiming));
@@ -1278,7 +1224,7 @@ extern "C" int sift3d_sharded_create_ex(sift3d_sharded_handle *out, const float 
 			CR_HIP(hipMalloc(&dm, sizeof(float) * 8));
 			CR_HIP(hipMemset(dm, 0, sizeof(float) * 8));
 			w.dogmax.push_back(dm);
-			if (H->copies) {
+			if (H->tr == Transport::Copies) {
 				float *di = nullptr;
 				CR_HIP(hipMalloc(&di, sizeof(float) * 8 * (size_t)H->world));
 				CR_HIP(hipMemset(di, 0, sizeof(float) * 8 * (size_t)H->world));
@@ -1336,7 +1282,7 @@ extern "C" int sift3d_sharded_create_ex(sift3d_sharded_handle *out, const float 
 	}
 	H->kp_count.assign((size_t)S, std::vector<int>((size_t)H->world, 0));
 	H->redo_count = H->kp_count;
-	if (!H->sim && !H->copies) {
+	if (H->tr == Transport::Rccl) {
 		// communicators over the same devices: per sharded octave one for its urgent halos, reductions and window exchange and one for its
 		// deferred halos; one for the gather of the tail's seed level
 		std::vector<ncclComm_t> c((size_t)H->world);
@@ -1361,58 +1307,31 @@ extern "C" int sift3d_sharded_create_ex(sift3d_sharded_handle *out, const float 
 	// z-neighbours, and more: the host has the whole volume)
 	auto up0 = [&](const Stage &st) { return H->ghost0 ? std::max(0, st.z0 - H->stage_halo[0]) : st.z0; };
 	auto up1 = [&](const Stage &st) { return H->ghost0 ? std::min(nz, st.z1 + H->stage_halo[0]) : st.z1; };
-	if (H->sim) {
-		for (Worker &w : H->workers) {
-			CR_HIP(hipSetDevice(w.device));
-			Stage &st = w.stages[0];
-			CR_ABI(sift3d_slab_upload(st.ctx, volume + pl * (size_t)up0(st), up0(st), up1(st), 0));
-			CR_ABI(sift3d_slab_input_absmax(st.ctx, &lmax[(size_t)w.rank]));
+	// one host thread per GPU: every rank stages its own slab through its device's pinned pool (csrc/staging.hip), so the constructor's H2D
+	// scales with the number of GPUs instead of running the slabs one after the other
+	std::string why;
+	int rc = for_ranks(H, [&](std::vector<Worker *> &ws) -> int {
+		for (Worker *w : ws) {
+			Stage &st = w->stages[0];
+			SH_HIP(*w, hipSetDevice(w->device));
+			SH_ABI(*w, sift3d_slab_upload(st.ctx, volume + pl * (size_t)up0(st), up0(st), up1(st), 0));
+			SH_ABI(*w, sift3d_slab_input_absmax(st.ctx, &lmax[(size_t)w->rank]));
 		}
-	} else {
-		// one host thread per GPU: every rank stages its own slab through its device's pinned pool (csrc/staging.hip), so the
-		// constructor's H2D scales with the number of GPUs instead of running the slabs one after the other
-		std::vector<std::thread> th;
-		std::vector<int> rcs((size_t)H->world, SIFT3D_OK);
-		std::vector<std::string> errs((size_t)H->world);
-		for (int r = 0; r < H->world; r++)
-			th.emplace_back([&, r] {
-				Worker &w = H->workers[(size_t)r];
-				Stage &st = w.stages[0];
-				int rc = hipSetDevice(w.device) == hipSuccess ? SIFT3D_OK : SIFT3D_ERR_HIP;
-				if (rc == SIFT3D_OK) rc = sift3d_slab_upload(st.ctx, volume + pl * (size_t)up0(st), up0(st), up1(st), 0);
-				if (rc == SIFT3D_OK) rc = sift3d_slab_input_absmax(st.ctx, &lmax[(size_t)r]);
-				if (rc != SIFT3D_OK) errs[(size_t)r] = sift3d_last_error();  // (the error text is thread-local)
-				rcs[(size_t)r] = rc;
-			});
-		for (auto &t : th) t.join();
-		for (int r = 0; r < H->world; r++) if (rcs[(size_t)r]) return fail(rcs[(size_t)r], "slab upload of rank " + std::to_string(r) + ": " + errs[(size_t)r]);
-	}
+		return SIFT3D_OK;
+	}, why);
+	if (rc) return fail(rc, "slab upload failed: " + why);
 	for (float v : lmax) gmax = std::max(gmax, v);  // (one process holds every rank: the MAX all-reduce is a host loop)
 	for (Worker &w : H->workers) { CR_HIP(hipSetDevice(w.device)); CR_ABI(sift3d_slab_input_scale(w.stages[0].ctx, gmax)); }
 	if (!H->ghost0) {
 		const std::vector<Transfer> ts = halo_transfers(b, nz, KIND_INPUT, 0, 0, H->hws[0] + 1, 0);
-		int rc = SIFT3D_OK;
-		if (H->sim) {
-			std::vector<Worker *> ws;
-			for (Worker &w : H->workers) ws.push_back(&w);
-			rc = exchange(H, ws, ts, 0);
-			if (rc == SIFT3D_OK && hipStreamSynchronize(H->workers[0].stream) != hipSuccess) rc = SIFT3D_ERR_HIP;
-		} else {
-			std::vector<std::thread> th;
-			std::vector<int> rcs((size_t)H->world, SIFT3D_OK);
-			for (int r = 0; r < H->world; r++)
-				th.emplace_back([&, r] {
-					Worker &w = H->workers[(size_t)r];
-					std::vector<Worker *> ws{&w};
-					(void)hipSetDevice(w.device);
-					rcs[(size_t)r] = exchange(H, ws, ts, 0);
-					if (rcs[(size_t)r] != SIFT3D_OK) abort_all(H);
-					else if (hipStreamSynchronize(w.stream) != hipSuccess) rcs[(size_t)r] = SIFT3D_ERR_HIP;
-				});
-			for (auto &t : th) t.join();
-			for (int v : rcs) if (v) rc = v;
-		}
-		if (rc) return fail(rc, "input halo exchange failed: " + H->workers[0].err);
+		rc = for_ranks(H, [&](std::vector<Worker *> &ws) -> int {
+			for (Worker *w : ws) SH_HIP(*w, hipSetDevice(w->device));
+			const int prc = post_halos(H, ws, ts, Lane{Lane::URGENT, 0});
+			if (prc) return prc;
+			for (Worker *w : ws) SH_HIP(*w, hipStreamSynchronize(w->stream));
+			return SIFT3D_OK;
+		}, why);
+		if (rc) return fail(rc, "input halo exchange failed: " + why);
 	}
 #undef CR_HIP
 #undef CR_ABI
@@ -1428,31 +1347,11 @@ extern "C" int sift3d_sharded_run(sift3d_sharded_handle H) {
 		return SIFT3D_ERR_STATE;
 	}
 	const auto t0 = std::chrono::steady_clock::now();
-	int rc = SIFT3D_OK;
 	H->ran = false;
-	if (H->sim) {
-		std::vector<Worker *> ws;
-		for (Worker &w : H->workers) ws.push_back(&w);
-		rc = run_local(H, ws);
-		if (rc) for (Worker &w : H->workers) if (!w.err.empty()) { H->err = w.err; break; }
-	} else {
-		std::vector<std::thread> th;
-		std::vector<int> rcs((size_t)H->world, SIFT3D_OK);
-		for (int r = 0; r < H->world; r++)
-			th.emplace_back([&, r] {
-				std::vector<Worker *> ws{&H->workers[(size_t)r]};
-				H->workers[(size_t)r].evp_i = 0;  // (copy transport: the last step's events are free again, every stream has drained)
-				rcs[(size_t)r] = run_local(H, ws);
-				if (rcs[(size_t)r] != SIFT3D_OK) abort_all(H);  // frees the z-neighbours blocked in a receive / reduction with this rank
-			});
-		for (auto &t : th) t.join();
-		// the rank that failed FIRST carries the cause; the others report "aborted: another rank failed"
-		for (int pass = 0; pass < 2 && rc == SIFT3D_OK; pass++)
-			for (int r = 0; r < H->world; r++) {
-				const std::string &e = H->workers[(size_t)r].err;
-				if (rcs[(size_t)r] && (pass == 1 || e.compare(0, 8, "aborted:") != 0)) { rc = rcs[(size_t)r]; H->err = "rank " + std::to_string(r) + ": " + e; break; }
-			}
-	}
+	const int rc = for_ranks(H, [&](std::vector<Worker *> &ws) -> int {
+		for (Worker *w : ws) w->evp_i = 0;  // (copy transport: the last step's events are free again, every stream has drained)
+		return run_local(H, ws);
+	}, H->err);
 	if (rc) { set_last_error(H->err); return rc; }
 	// like the single-GPU extractor's, the results stay on the devices until they are asked for (sift3d_sharded_get_keypoints)
 	H->times[0] = H->times[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1595,7 +1494,7 @@ extern "C" int sift3d_sharded_plan(sift3d_sharded_handle H, int *partial_windows
 // its transfers wait for.  Results are not touched (the rank recomputes what it held).  Partial windows only.
 extern "C" int sift3d_test_sharded_time_rank(sift3d_sharded_handle H, int rank, double *seconds) {
 	if (!H || !seconds || rank < 0 || rank >= H->world) return SIFT3D_ERR_ARG;
-	if (!H->sim || !H->ran || H->ps_last.size() != (size_t)H->S) { set_last_error("needs a simulated extractor that has run"); return SIFT3D_ERR_STATE; }
+	if (H->tr != Transport::Sim || !H->ran || H->ps_last.size() != (size_t)H->S) { set_last_error("needs a simulated extractor that has run"); return SIFT3D_ERR_STATE; }
 	Worker &w = H->workers[(size_t)rank];
 	if (hipSetDevice(w.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return SIFT3D_ERR_HIP;
 	std::vector<Worker *> ws{&w};

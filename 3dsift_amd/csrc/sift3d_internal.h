@@ -136,10 +136,11 @@ bool march_applicable(int nx, int ny, int nzg, const Taps &t);
 bool launch_march_level(const float *src, float *dst, float *dog, unsigned *dogmax, int nx, int ny, const ZRange &zr, const Taps &t,
                         hipStream_t st, int plan_slots = 0, int prio = 0, const MarchHalf *half = nullptr);
 void launch_copy16(const float *src, float *dst, size_t nfloats, hipStream_t st);  // float4 copy (bandwidth ceiling probe)
-// simulated transport of the z-slab driver (sharded.hip): one exchange step's plane ranges in one launch; MAX over np arrays of n <= 64 floats, in place in all of them
+// z-slab driver (sharded.hip): one exchange step's plane ranges in one launch; MAX over nin arrays of n <= 64 floats into each of nout arrays
+// (an output may also be an input: every thread reads and writes its own element only)
 constexpr int kCopySegs = 32, kMaxMergePtrs = 16;
 struct CopySegs { const float *src[kCopySegs]; float *dst[kCopySegs]; size_t floats[kCopySegs]; int n = 0; };
-struct MaxMerge { float *p[kMaxMergePtrs]; int np = 0, n = 0; };
+struct MaxMerge { const float *in[kMaxMergePtrs]; float *out[kMaxMergePtrs]; int nin = 0, nout = 0, n = 0; };
 void launch_copy_segments(const CopySegs &a, hipStream_t st);
 void launch_max_merge(const MaxMerge &a, hipStream_t st);
 // ---- kernels_small.hip: every level of the SMALL octaves (16^3-class and below) in one launch of one workgroup ----
