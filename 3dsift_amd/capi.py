@@ -40,6 +40,8 @@ SYMBOLS = [
     "sift3d_default_detect_options", "sift3d_set_detect_options", "sift3d_get_detect_options", "sift3d_get_refined",
     # RANSAC affine fits of matched pairs, global and per point
     "sift3d_default_ransac_options", "sift3d_fit_affine", "sift3d_fit_affine_local",
+    # IC-GN displacement refinement (digital volume correlation)
+    "sift3d_default_icgn_options", "sift3d_icgn_init_from_fits", "sift3d_icgn",
     "sift3d_device_count", "sift3d_error_string", "sift3d_last_error",
     # multi-GPU sharding (z-slabs of octave 0 + seeded replicated tail)
     "sift3d_slab_min_halo", "sift3d_slab_arena_floats", "sift3d_slab_create", "sift3d_slab_buffer", "sift3d_slab_upload",
@@ -102,6 +104,20 @@ assert C.sizeof(RansacOptions) == 32
 FIT_DTYPE = np.dtype([("A", "<f8", (12,)), ("hyp", "<f8", (12,)), ("status", "<i4"), ("candidates", "<i4"), ("best_hypothesis", "<i4"),
                       ("best_count", "<i4"), ("inliers", "<i4"), ("rms", "<f4"), ("reserved", "<i4", (2,))])
 assert FIT_DTYPE.itemsize == 224
+
+
+class IcgnOptions(C.Structure):
+    """sift3d_icgn_options (include/sift3d_hip.h)"""
+    _fields_ = [("subset_radius", C.c_int), ("max_iterations", C.c_int), ("tolerance", C.c_float), ("interpolation", C.c_int),
+                ("reserved", C.c_int * 4)]
+
+
+assert C.sizeof(IcgnOptions) == 32
+
+# sift3d_icgn_result: p = (u, ux, uy, uz, v, vx, vy, vz, w, wx, wy, wz), zncc, last step, iterations, status
+ICGN_DTYPE = np.dtype([("p", "<f8", (12,)), ("zncc", "<f8"), ("last_step", "<f8"), ("iterations", "<i4"), ("status", "<i4"),
+                       ("reserved", "<i4", (2,))])
+assert ICGN_DTYPE.itemsize == 128
 
 
 class SlabDesc(C.Structure):
@@ -171,6 +187,11 @@ def lib():
                                         C.POINTER(C.c_double)]
         L.sift3d_fit_affine_local.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(RansacOptions), C.c_int,
                                               C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        L.sift3d_default_icgn_options.argtypes = [C.POINTER(IcgnOptions)]
+        L.sift3d_default_icgn_options.restype = None
+        L.sift3d_icgn_init_from_fits.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.sift3d_icgn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                  C.POINTER(IcgnOptions), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
         _sz = C.POINTER(C.c_size_t)
         L.sift3d_slab_min_halo.argtypes = [C.POINTER(Params), _ip]
         L.sift3d_slab_arena_floats.argtypes = [C.POINTER(SlabDesc), C.POINTER(Params), _sz]
@@ -375,6 +396,92 @@ def fit_affine_local(pairs, points, k=32, radius=0.0, device=0, **opts):
     d["neighbours"] = nb[:m].copy()
     d["seconds"] = sec.value
     return d
+
+
+ICGN_OPTIONS = ("subset_radius", "max_iterations", "tolerance", "interpolation")
+
+
+def default_icgn_options():
+    """sift3d_default_icgn_options as a dict (needs no GPU)"""
+    o = IcgnOptions()
+    lib().sift3d_default_icgn_options(C.byref(o))
+    return {k: getattr(o, k) for k in ICGN_OPTIONS}
+
+
+def _icgn_options(opts):
+    o = IcgnOptions()
+    lib().sift3d_default_icgn_options(C.byref(o))
+    for k, v in opts.items():
+        if k not in ICGN_OPTIONS:
+            raise TypeError(f"unknown IC-GN option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def icgn_init_from_fits(fits, points):
+    """sift3d_icgn_init_from_fits: (m, 12) float64 initial parameters from the dict fit_affine_local returns (A (m, 3, 4), status) at
+    the integer points ((m, 3) x, y, z); a failed fit gives a NaN row"""
+    A = np.asarray(fits["A"], np.float64).reshape(-1, 12)
+    f = np.zeros(max(len(A), 1), FIT_DTYPE)
+    f["A"][:len(A)] = A
+    f["status"][:len(A)] = np.asarray(fits["status"])
+    q = np.ascontiguousarray(points, np.int32).reshape(-1, 3)
+    if len(q) != len(A):
+        raise ValueError("one point per fit")
+    out = np.zeros((max(len(A), 1), 12), np.float64)
+    _check(lib().sift3d_icgn_init_from_fits(f.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p), len(A), out.ctypes.data_as(C.c_void_p)))
+    return out[:len(A)].copy()
+
+
+def icgn(ref, tar, points, init=None, device=0, **opts):
+    """sift3d_icgn: IC-GN refinement of the displacement at each point ((m, 3) int32 x, y, z of ref) from ref to tar.  ref / tar:
+    (nz, ny, nx) float32 numpy arrays or contiguous float32 device tensors, both of the same kind; init: (m, 12) float64 or None (zero).
+    Options: subset_radius, max_iterations, tolerance, interpolation (0 tricubic, 1 trilinear).  Returns p (m, 12), displacement
+    (m, 3) = (u, v, w), gradient (m, 3, 3) (rows u, v, w; columns x, y, z), zncc, last_step, iterations, status (m,) and the device
+    seconds."""
+    o = _icgn_options(opts)
+    dev = [hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) for a in (ref, tar)]
+    if dev[0] != dev[1]:
+        raise ValueError("ref and tar must both be numpy arrays or both device tensors")
+    vols, keep = [], []
+    if dev[0]:
+        import torch
+
+        for a, name in ((ref, "ref"), (tar, "tar")):
+            if a.dtype != torch.float32 or not a.is_contiguous() or a.dim() != 3:
+                raise ValueError(f"{name}: a contiguous float32 (nz, ny, nx) device tensor is needed")
+            vols.append((C.c_void_p(a.data_ptr()), a.shape))
+        q = torch.as_tensor(points, dtype=torch.int32, device=ref.device).reshape(-1, 3).contiguous()
+        m = q.shape[0]
+        ini = None if init is None else torch.as_tensor(init, dtype=torch.float64, device=ref.device).reshape(-1, 12).contiguous()
+        keep += [q, ini]
+        qp = C.c_void_p(q.data_ptr())
+        ip = None if ini is None else C.c_void_p(ini.data_ptr())
+    else:
+        for a, name in ((ref, "ref"), (tar, "tar")):
+            h = np.ascontiguousarray(a, np.float32)
+            if h.ndim != 3:
+                raise ValueError(f"{name}: a (nz, ny, nx) volume is needed")
+            keep.append(h)
+            vols.append((h.ctypes.data_as(C.c_void_p), h.shape))
+        q = np.ascontiguousarray(points, np.int32).reshape(-1, 3)
+        m = len(q)
+        ini = None if init is None else np.ascontiguousarray(init, np.float64).reshape(-1, 12)
+        keep += [q, ini]
+        qp = q.ctypes.data_as(C.c_void_p)
+        ip = None if ini is None else ini.ctypes.data_as(C.c_void_p)
+    if ini is not None and ini.shape[0] != m:
+        raise ValueError("init: one row of 12 per point")
+    (rp, (rz, ry, rx)), (tp, (tz, ty, tx)) = vols
+    out = np.zeros(max(m, 1), ICGN_DTYPE)
+    sec = C.c_double(0)
+    _check(lib().sift3d_icgn(rp, int(rx), int(ry), int(rz), tp, int(tx), int(ty), int(tz), qp, m, ip, C.byref(o), int(dev[0]), int(device),
+                             out.ctypes.data_as(C.c_void_p), C.byref(sec)))
+    out = out[:m]
+    p = out["p"].copy()
+    G = p.reshape(-1, 3, 4)[:, :, 1:].copy()
+    return {"p": p, "displacement": p[:, [0, 4, 8]].copy(), "gradient": G, "zncc": out["zncc"].copy(), "last_step": out["last_step"].copy(),
+            "iterations": out["iterations"].copy(), "status": out["status"].copy(), "seconds": sec.value}
 
 
 def device_count():

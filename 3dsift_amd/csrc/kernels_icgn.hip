@@ -1,0 +1,507 @@
+// kernels_icgn.hip -- IC-GN displacement refinement (sift3d_icgn, include/sift3d_hip.h, which states the numerical contract).
+// No reference counterpart.  One workgroup of 256 threads per point of interest (POI), two launches on one stream:
+//   k_icgn_prepare  the status 5 / 2 / 4 / 3 checks, Rm, dR and the constants of the subset: sum SD^T (R - Rm), sum SD^T and
+//                   H = sum SD^T SD (60 distinct sums: 6 gradient pairs x 10 monomials of (1, dx, dy, dz)), all accumulated in fp64;
+//                   the 12 x 12 fp64 Cholesky of H in LDS (a column per step, the trailing update spread over the workgroup) and
+//                   H^-1 by 12 column solves; a record per POI (IcgnState) for the second launch
+//   k_icgn_iterate  every iteration inside the launch: one pass over the subset per iteration gathers 15 sums at the current warp
+//                   (sum T', sum T'^2, sum R'T' and the 12 sums SD^T T', with T' = T(W) - Rm and R' = R - Rm), reduced in a fixed
+//                   order (xor butterfly in the wave, waves in index order); every thread then forms the same step from the sums
+//                   (fp64, redundantly: no broadcast and one barrier per pass), composes the warp, tests convergence and the 8 corners.
+//                   The pass after the last update gives zncc at the returned p.
+// SD is recomputed per voxel from R (6 cached loads; a 12-float table per voxel does not fit in LDS at r = 16).  Per-voxel arithmetic is
+// fp32 (positions relative to floor(q + u), so the fraction keeps its bits); per-thread sums are fp32 except sum T' and sum T'^2
+// (fp64: the variance is their difference); the reduction is fp64.  No float atomics: two calls give the same bits.
+#include "sift3d_internal.h"
+
+#include <math.h>
+
+namespace s3d {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kPrepSums = 86;  // dR^2, sum R', 12 sum SD, 12 sum SD R', 60 H pieces
+constexpr int kIterSums = 15;  // sum T', sum T'^2, 12 sum SD T', sum R'T'
+constexpr int kRun = -1;       // IcgnState::status: go on to the iteration
+
+struct IcgnState {
+	double hinv[144];  // H^-1, row-major
+	double c1[12];     // sum SD^T (R - Rm)
+	double c2[12];     // sum SD^T
+	double dr;         // dR
+	double sr;         // sum (R - Rm) as the iterate kernel forms R' (fp32 R - (float)Rm): zncc's correction term
+	float rm;          // (float)Rm, the shift of T and R in the iterate kernel
+	int status;        // kRun, or the final status the prepare kernel wrote
+};
+
+typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));  // 4 x-taps of T at dword alignment
+typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
+
+__device__ inline double wave_sum(double x) {
+	for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+	return x;
+}
+
+// the position of the subset offset d under p (fp64, the contract's order): q + F d + (u, v, w)
+__device__ inline void warp_point(const double p[12], const int q[3], double dx, double dy, double dz, double o[3]) {
+#pragma unroll
+	for (int a = 0; a < 3; a++) {
+		const double *g = p + 4 * a;
+		const double fx = (a == 0 ? 1.0 + g[1] : g[1]), fy = (a == 1 ? 1.0 + g[2] : g[2]), fz = (a == 2 ? 1.0 + g[3] : g[3]);
+		o[a] = ((double)q[a] + ((fx * dx + fy * dy) + fz * dz)) + g[0];
+	}
+}
+
+// every tap of the warped subset inside T: the 8 corners decide (a NaN position is outside)
+__device__ inline bool in_domain(const double p[12], const int q[3], int r, const IcgnVol &T, bool cubic) {
+	const int n[3] = {T.nx, T.ny, T.nz};
+	bool ok = true;
+#pragma unroll
+	for (int c = 0; c < 8; c++) {
+		double o[3];
+		warp_point(p, q, (c & 1) ? r : -r, (c & 2) ? r : -r, (c & 4) ? r : -r, o);
+#pragma unroll
+		for (int a = 0; a < 3; a++) {
+			const double f = floor(o[a]);
+			ok = ok && (cubic ? (f - 1.0 >= 0.0 && f + 2.0 <= (double)(n[a] - 1)) : (f >= 0.0 && f + 1.0 <= (double)(n[a] - 1)));
+		}
+	}
+	return ok;
+}
+
+// the linear subset index i of offset (dx, dy, dz) advances by kThreads: 256 = sz D^2 + sy D + sx, one carry per axis at most
+struct SubsetWalk {
+	int r, sx, sy, sz;
+	__device__ explicit SubsetWalk(int r_) : r(r_) {
+		const int D = 2 * r + 1;
+		sz = kThreads / (D * D);
+		sy = (kThreads - sz * D * D) / D;
+		sx = kThreads - sz * D * D - sy * D;
+	}
+	__device__ void start(int i, int &dx, int &dy, int &dz) const {
+		const int D = 2 * r + 1;
+		dz = i / (D * D) - r;
+		dy = (i / D) % D - r;
+		dx = i % D - r;
+	}
+	__device__ void next(int &dx, int &dy, int &dz) const {
+		const int D = 2 * r + 1;
+		dx += sx;
+		if (dx > r) { dx -= D; dy++; }
+		dy += sy;
+		if (dy > r) { dy -= D; dz++; }
+		dz += sz;
+	}
+};
+
+__device__ inline size_t vidx(const IcgnVol &V, int x, int y, int z) { return ((size_t)z * V.ny + y) * V.nx + x; }
+
+__device__ inline void write_result(sift3d_icgn_result *o, const double p[12], double zncc, double last, int it, int status) {
+#pragma unroll
+	for (int k = 0; k < 12; k++) o->p[k] = p[k];
+	o->zncc = zncc;
+	o->last_step = last;
+	o->iterations = it;
+	o->status = status;
+	o->reserved[0] = o->reserved[1] = 0;
+}
+
+// ---- prepare ---------------------------------------------------------------------------------------------------------------------
+
+__device__ inline int h_piece(int i, int j) {  // H(i, j) -> index into the 60 H pieces
+	int a = i >> 2, b = j >> 2, mi = i & 3, mj = j & 3;
+	if (a > b) { int t = a; a = b; b = t; }
+	if (mi > mj) { int t = mi; mi = mj; mj = t; }
+	const int pp = a == 0 ? b : (a == 1 ? 2 + b : 5);                          // (0,0) (0,1) (0,2) (1,1) (1,2) (2,2)
+	const int mm = mi == 0 ? mj : (mi == 1 ? 3 + mj : (mi == 2 ? 5 + mj : 9));  // (0,0..3) (1,1..3) (2,2..3) (3,3)
+	return pp * 10 + mm;
+}
+
+__global__ __launch_bounds__(kThreads) void k_icgn_prepare(IcgnVol R, IcgnVol T, const int *__restrict__ pts, const double *__restrict__ init,
+                                                          int r, int cubic, IcgnState *__restrict__ state, sift3d_icgn_result *__restrict__ out) {
+	__shared__ double red[kWaves][kPrepSums];
+	__shared__ double A[12][13];
+	__shared__ int s_fail;
+	const int poi = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+	const int q[3] = {pts[3 * poi], pts[3 * poi + 1], pts[3 * poi + 2]};
+	double p[12];
+	bool finite = true;
+#pragma unroll
+	for (int k = 0; k < 12; k++) {
+		p[k] = init ? init[12 * (size_t)poi + k] : 0.0;
+		finite = finite && isfinite(p[k]);
+	}
+	IcgnState *S = state + poi;
+	int status = kRun;
+	if (!finite) status = 5;
+	else if (q[0] - r - 1 < 0 || q[0] + r + 1 > R.nx - 1 || q[1] - r - 1 < 0 || q[1] + r + 1 > R.ny - 1 || q[2] - r - 1 < 0 ||
+	         q[2] + r + 1 > R.nz - 1)
+		status = 2;
+	if (status != kRun) {  // uniform: the whole workgroup leaves
+		if (tid == 0) {
+			S->status = status;
+			write_result(out + poi, p, 0.0, 0.0, 0, status);
+		}
+		return;
+	}
+	const int D = 2 * r + 1, N = D * D * D;
+	const SubsetWalk W(r);
+	const float *Rq = R.d + vidx(R, q[0], q[1], q[2]);
+	const int sy = R.nx, sz = R.nx * R.ny;
+	// pass 1: Rm
+	double s = 0.0;
+	{
+		int dx, dy, dz;
+		W.start(tid, dx, dy, dz);
+		for (int i = tid; i < N; i += kThreads) {
+			s += (double)Rq[dz * sz + dy * sy + dx];
+			W.next(dx, dy, dz);
+		}
+	}
+	s = wave_sum(s);
+	if (lane == 0) red[wv][0] = s;
+	__syncthreads();
+	const double Rm = (((red[0][0] + red[1][0]) + red[2][0]) + red[3][0]) / (double)N;
+	const float rmf = (float)Rm;
+	__syncthreads();
+	// pass 2: the constants
+	double acc[kPrepSums];
+#pragma unroll
+	for (int k = 0; k < kPrepSums; k++) acc[k] = 0.0;
+	{
+		int dx, dy, dz;
+		W.start(tid, dx, dy, dz);
+		for (int i = tid; i < N; i += kThreads) {
+			const float *c = Rq + (dz * sz + dy * sy + dx);
+			const float gxf = 0.5f * (c[1] - c[-1]), gyf = 0.5f * (c[sy] - c[-sy]), gzf = 0.5f * (c[sz] - c[-sz]);
+			const double rv = (double)c[0] - Rm;
+			const double g[3] = {(double)gxf, (double)gyf, (double)gzf};
+			const double v[4] = {1.0, (double)dx, (double)dy, (double)dz};
+			acc[0] += rv * rv;
+			acc[1] += (double)(c[0] - rmf);
+#pragma unroll
+			for (int a = 0; a < 3; a++)
+#pragma unroll
+				for (int k = 0; k < 4; k++) {
+					acc[2 + 4 * a + k] += g[a] * v[k];
+					acc[14 + 4 * a + k] += (g[a] * v[k]) * rv;
+				}
+			int pp = 0;
+#pragma unroll
+			for (int a = 0; a < 3; a++)
+#pragma unroll
+				for (int b = a; b < 3; b++, pp++) {
+					const double w = g[a] * g[b];
+					int mm = 0;
+#pragma unroll
+					for (int mi = 0; mi < 4; mi++)
+#pragma unroll
+						for (int mj = mi; mj < 4; mj++, mm++) acc[26 + pp * 10 + mm] += w * (v[mi] * v[mj]);
+				}
+			W.next(dx, dy, dz);
+		}
+	}
+#pragma unroll
+	for (int k = 0; k < kPrepSums; k++) {
+		const double x = wave_sum(acc[k]);
+		if (lane == 0) red[wv][k] = x;
+	}
+	__syncthreads();
+	if (tid < kPrepSums) red[0][tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+	__syncthreads();
+	const double dr = sqrt(red[0][0]);
+	if (tid < 144) {
+		const int i = tid / 12, j = tid % 12;
+		A[i][j] = red[0][26 + h_piece(i, j)];
+	}
+	if (tid == 0) s_fail = !(dr > 0.0);
+	__syncthreads();
+	bool fail = s_fail;
+	__syncthreads();  // every thread has read the flag before the first pivot may set it
+	// Cholesky H = L L^T in A's lower triangle, a column per step; the flag is read only between the barriers that follow its write
+	for (int k = 0; k < 12 && !fail; k++) {
+		if (tid == 0) {
+			const double d = A[k][k];
+			if (!(d > 0.0)) s_fail = 1;
+			A[k][k] = sqrt(d);
+		}
+		__syncthreads();
+		fail = s_fail;
+		if (fail) break;
+		if (tid > k && tid < 12) A[tid][k] = A[tid][k] / A[k][k];
+		__syncthreads();
+		if (tid < 144) {
+			const int i = tid / 12, j = tid % 12;
+			if (j > k && i >= j) A[i][j] = A[i][j] - A[i][k] * A[j][k];
+		}
+		__syncthreads();
+	}
+	if (fail) {
+		if (tid == 0) {
+			S->status = 4;
+			write_result(out + poi, p, 0.0, 0.0, 0, 4);
+		}
+		return;
+	}
+	// H^-1: thread c solves L y = e_c, then L^T x = y in place (registers, fully unrolled)
+	if (tid < 12) {
+		const int c = tid;
+		double y[12];
+#pragma unroll
+		for (int i = 0; i < 12; i++) {
+			double t = (i == c) ? 1.0 : 0.0;
+#pragma unroll
+			for (int j = 0; j < i; j++) t -= A[i][j] * y[j];
+			y[i] = t / A[i][i];
+		}
+#pragma unroll
+		for (int i = 11; i >= 0; i--) {
+			double t = y[i];
+#pragma unroll
+			for (int j = i + 1; j < 12; j++) t -= A[j][i] * y[j];
+			y[i] = t / A[i][i];
+		}
+#pragma unroll
+		for (int i = 0; i < 12; i++) S->hinv[12 * i + c] = y[i];
+		S->c2[c] = red[0][2 + c];
+		S->c1[c] = red[0][14 + c];
+	}
+	if (tid == 0) {
+		const bool dom = in_domain(p, q, r, T, cubic);
+		S->dr = dr;
+		S->sr = red[0][1];
+		S->rm = rmf;
+		S->status = dom ? kRun : 3;
+		if (!dom) write_result(out + poi, p, 0.0, 0.0, 0, 3);
+	}
+}
+
+// ---- iterate ---------------------------------------------------------------------------------------------------------------------
+
+// one pass over the subset at the warp p: the 15 sums, reduced (every thread returns the same values)
+template <bool CUBIC>
+__device__ inline void subset_pass(const IcgnVol &R, const IcgnVol &T, const int q[3], int r, float rmf, const double p[12],
+                                   double (*red)[kIterSums], double sums[kIterSums]) {
+	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+	const int D = 2 * r + 1, N = D * D * D;
+	const SubsetWalk W(r);
+	// position of offset d: c + o(d), c = floor(q + u) (integer), o = frac(q + u) + F d in fp32
+	int ci[3];
+	float cf[3], F[9];
+#pragma unroll
+	for (int a = 0; a < 3; a++) {
+		const double c = (double)q[a] + p[4 * a];
+		const double fl = floor(c);
+		ci[a] = (int)fl;
+		cf[a] = (float)(c - fl);
+#pragma unroll
+		for (int b = 0; b < 3; b++) F[3 * a + b] = (float)((a == b ? 1.0 : 0.0) + p[4 * a + 1 + b]);
+	}
+	const int lo = CUBIC ? 1 : 0;
+	const int hx = T.nx - (CUBIC ? 3 : 2), hy = T.ny - (CUBIC ? 3 : 2), hz = T.nz - (CUBIC ? 3 : 2);
+	const size_t tsy = (size_t)T.nx, tsz = (size_t)T.nx * T.ny;
+	const float *Rq = R.d + vidx(R, q[0], q[1], q[2]);
+	const int sy = R.nx, sz = R.nx * R.ny;
+	float acc[13];
+#pragma unroll
+	for (int k = 0; k < 13; k++) acc[k] = 0.f;
+	double sT = 0.0, sTT = 0.0;
+	int dx, dy, dz;
+	W.start(tid, dx, dy, dz);
+#pragma unroll 1
+	for (int i = tid; i < N; i += kThreads) {
+		const float fx = (float)dx, fy = (float)dy, fz = (float)dz;
+		float o[3];
+#pragma unroll
+		for (int a = 0; a < 3; a++) o[a] = cf[a] + ((F[3 * a] * fx + F[3 * a + 1] * fy) + F[3 * a + 2] * fz);
+		const float flx = floorf(o[0]), fly = floorf(o[1]), flz = floorf(o[2]);
+		const float tx = o[0] - flx, ty = o[1] - fly, tz = o[2] - flz;
+		// the clamp only guards memory: the corner test keeps every tap inside T up to fp32 rounding
+		const int gx = min(max(ci[0] + (int)flx, lo), hx), gy = min(max(ci[1] + (int)fly, lo), hy), gz = min(max(ci[2] + (int)flz, lo), hz);
+		float tv;
+		if (CUBIC) {
+			float w[3][4];
+			const float t3[3] = {tx, ty, tz};
+#pragma unroll
+			for (int a = 0; a < 3; a++) {
+				const float t = t3[a], t2 = t * t, tc = t2 * t;
+				w[a][0] = 0.5f * ((2.f * t2 - tc) - t);
+				w[a][1] = 0.5f * ((3.f * tc - 5.f * t2) + 2.f);
+				w[a][2] = 0.5f * ((4.f * t2 - 3.f * tc) + t);
+				w[a][3] = 0.5f * (tc - t2);
+			}
+			const float *b = T.d + (((size_t)(gz - 1) * T.ny + (gy - 1)) * T.nx + (gx - 1));
+			tv = 0.f;
+#pragma unroll
+			for (int k = 0; k < 4; k++) {
+				float zv = 0.f;
+#pragma unroll
+				for (int j = 0; j < 4; j++) {
+					const f4u v = *reinterpret_cast<const f4u *>(b + (k * tsz + j * tsy));
+					const float row = fmaf(w[0][3], v.w, fmaf(w[0][2], v.z, fmaf(w[0][1], v.y, w[0][0] * v.x)));
+					zv = fmaf(w[1][j], row, zv);
+				}
+				tv = fmaf(w[2][k], zv, tv);
+			}
+		} else {
+			const float *b = T.d + (((size_t)gz * T.ny + gy) * T.nx + gx);
+			const f2u a00 = *reinterpret_cast<const f2u *>(b), a01 = *reinterpret_cast<const f2u *>(b + tsy);
+			const f2u a10 = *reinterpret_cast<const f2u *>(b + tsz), a11 = *reinterpret_cast<const f2u *>(b + tsz + tsy);
+			const float r00 = fmaf(tx, a00.y - a00.x, a00.x), r01 = fmaf(tx, a01.y - a01.x, a01.x);
+			const float r10 = fmaf(tx, a10.y - a10.x, a10.x), r11 = fmaf(tx, a11.y - a11.x, a11.x);
+			const float z0 = fmaf(ty, r01 - r00, r00), z1 = fmaf(ty, r11 - r10, r10);
+			tv = fmaf(tz, z1 - z0, z0);
+		}
+		const float *c = Rq + (dz * sz + dy * sy + dx);
+		const float g[3] = {0.5f * (c[1] - c[-1]), 0.5f * (c[sy] - c[-sy]), 0.5f * (c[sz] - c[-sz])};
+		const float tp = tv - rmf, rp = c[0] - rmf;
+		sT += (double)tp;
+		sTT = fma((double)tp, (double)tp, sTT);
+		acc[12] = fmaf(rp, tp, acc[12]);
+#pragma unroll
+		for (int a = 0; a < 3; a++) {
+			const float gt = g[a] * tp;
+			acc[4 * a] += gt;
+			acc[4 * a + 1] = fmaf(gt, fx, acc[4 * a + 1]);
+			acc[4 * a + 2] = fmaf(gt, fy, acc[4 * a + 2]);
+			acc[4 * a + 3] = fmaf(gt, fz, acc[4 * a + 3]);
+		}
+		W.next(dx, dy, dz);
+	}
+	double v[kIterSums];
+	v[0] = sT;
+	v[1] = sTT;
+#pragma unroll
+	for (int k = 0; k < 13; k++) v[2 + k] = (double)acc[k];
+#pragma unroll
+	for (int k = 0; k < kIterSums; k++) {
+		const double x = wave_sum(v[k]);
+		if (lane == 0) red[wv][k] = x;
+	}
+	__syncthreads();
+#pragma unroll
+	for (int k = 0; k < kIterSums; k++) sums[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+}
+
+template <bool CUBIC>
+__global__ __launch_bounds__(kThreads) void k_icgn_iterate(IcgnVol R, IcgnVol T, const int *__restrict__ pts, const double *__restrict__ init,
+                                                          int r, int max_it, double tol, const IcgnState *__restrict__ state,
+                                                          sift3d_icgn_result *__restrict__ out) {
+	__shared__ double red[2][kWaves][kIterSums];  // by pass parity: one barrier per pass
+	__shared__ double cst[168];                   // H^-1, c1, c2: read in the solve only (not held in registers across the passes)
+	const int poi = blockIdx.x;
+	const IcgnState *S = state + poi;
+	if (S->status != kRun) return;  // the prepare kernel wrote the result
+	if (threadIdx.x < 168) cst[threadIdx.x] = threadIdx.x < 144 ? S->hinv[threadIdx.x] : (threadIdx.x < 156 ? S->c1[threadIdx.x - 144] : S->c2[threadIdx.x - 156]);
+	__syncthreads();
+	const int q[3] = {pts[3 * poi], pts[3 * poi + 1], pts[3 * poi + 2]};
+	double p[12];
+#pragma unroll
+	for (int k = 0; k < 12; k++) p[k] = init ? init[12 * (size_t)poi + k] : 0.0;
+	const double N = (double)((2 * r + 1) * (2 * r + 1) * (2 * r + 1)), dr = S->dr, sr = S->sr, r2 = (double)r * (double)r;
+	const float rmf = S->rm;
+	int it = 0, status = kRun;
+	double last = 0.0;
+	bool done = false;
+	for (int pass = 0;; pass++) {
+		double s[kIterSums];
+		subset_pass<CUBIC>(R, T, q, r, rmf, p, red[pass & 1], s);
+		// s: 0 sum T', 1 sum T'^2, 2..13 sum SD T', 14 sum R'T'
+		const double tm = s[0] / N;
+		const double dt2 = s[1] - s[0] * tm;
+		const bool flat = !(dt2 > 1e-10 * s[1]);  // dT = 0 to rounding
+		const double dt = flat ? 0.0 : sqrt(dt2);
+		const double zncc = flat ? 0.0 : (s[14] - tm * sr) / (dr * dt);
+		if (done) {
+			if (threadIdx.x == 0) write_result(out + poi, p, zncc, last, it, status);
+			return;
+		}
+		if (flat) {
+			if (threadIdx.x == 0) write_result(out + poi, p, 0.0, last, it, 4);
+			return;
+		}
+		const double k = dr / dt;
+		double b[12], dp[12];
+#pragma unroll
+		for (int j = 0; j < 12; j++) b[j] = cst[144 + j] - k * (s[2 + j] - tm * cst[156 + j]);
+		bool fin = true;
+#pragma unroll
+		for (int i = 0; i < 12; i++) {
+			double t = 0.0;
+#pragma unroll
+			for (int j = 0; j < 12; j++) t += cst[12 * i + j] * b[j];
+			dp[i] = -t;
+			fin = fin && isfinite(dp[i]);
+		}
+		double g2 = 0.0;
+#pragma unroll
+		for (int a = 0; a < 3; a++) g2 += (dp[4 * a + 1] * dp[4 * a + 1] + dp[4 * a + 2] * dp[4 * a + 2]) + dp[4 * a + 3] * dp[4 * a + 3];
+		last = sqrt(((dp[0] * dp[0] + dp[4] * dp[4]) + dp[8] * dp[8]) + r2 * g2);
+		// M(p) <- M(p) . M(dp)^-1: F <- F Fd^-1, t <- t - F Fd^-1 td
+		double Fd[9], Fp[9], inv[9];
+#pragma unroll
+		for (int a = 0; a < 3; a++)
+#pragma unroll
+			for (int c = 0; c < 3; c++) {
+				Fd[3 * a + c] = (a == c ? 1.0 : 0.0) + dp[4 * a + 1 + c];
+				Fp[3 * a + c] = (a == c ? 1.0 : 0.0) + p[4 * a + 1 + c];
+			}
+		inv[0] = Fd[4] * Fd[8] - Fd[5] * Fd[7];
+		inv[3] = -(Fd[3] * Fd[8] - Fd[5] * Fd[6]);
+		inv[6] = Fd[3] * Fd[7] - Fd[4] * Fd[6];
+		const double det = (Fd[0] * inv[0] + Fd[1] * inv[3]) + Fd[2] * inv[6];
+		if (!fin || !(det != 0.0) || !isfinite(det)) {
+			if (threadIdx.x == 0) write_result(out + poi, p, zncc, last, it, 6);
+			return;
+		}
+		inv[1] = -(Fd[1] * Fd[8] - Fd[2] * Fd[7]);
+		inv[4] = Fd[0] * Fd[8] - Fd[2] * Fd[6];
+		inv[7] = -(Fd[0] * Fd[7] - Fd[1] * Fd[6]);
+		inv[2] = Fd[1] * Fd[5] - Fd[2] * Fd[4];
+		inv[5] = -(Fd[0] * Fd[5] - Fd[2] * Fd[3]);
+		inv[8] = Fd[0] * Fd[4] - Fd[1] * Fd[3];
+#pragma unroll
+		for (int e = 0; e < 9; e++) inv[e] = inv[e] / det;
+		double pn[12], ti[3];
+#pragma unroll
+		for (int a = 0; a < 3; a++) ti[a] = -((inv[3 * a] * dp[0] + inv[3 * a + 1] * dp[4]) + inv[3 * a + 2] * dp[8]);
+#pragma unroll
+		for (int a = 0; a < 3; a++) {
+			pn[4 * a] = ((Fp[3 * a] * ti[0] + Fp[3 * a + 1] * ti[1]) + Fp[3 * a + 2] * ti[2]) + p[4 * a];
+#pragma unroll
+			for (int c = 0; c < 3; c++)
+				pn[4 * a + 1 + c] = ((Fp[3 * a] * inv[c] + Fp[3 * a + 1] * inv[3 + c]) + Fp[3 * a + 2] * inv[6 + c]) - (a == c ? 1.0 : 0.0);
+		}
+		if (!in_domain(pn, q, r, T, CUBIC)) {
+			if (threadIdx.x == 0) write_result(out + poi, p, zncc, last, it, 3);
+			return;
+		}
+#pragma unroll
+		for (int e = 0; e < 12; e++) p[e] = pn[e];
+		it++;
+		if (last < tol) {
+			status = 0;
+			done = true;
+		} else if (it >= max_it) {
+			status = 1;
+			done = true;
+		}
+	}
+}
+
+}  // namespace
+
+size_t icgn_state_bytes() { return sizeof(IcgnState); }
+
+void launch_icgn(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_init, int r, int max_it, double tol, int cubic, void *d_state,
+                 sift3d_icgn_result *d_out, hipStream_t st) {
+	IcgnState *S = static_cast<IcgnState *>(d_state);
+	hipLaunchKernelGGL(k_icgn_prepare, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, cubic, S, d_out);
+	if (cubic)
+		hipLaunchKernelGGL(k_icgn_iterate<true>, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out);
+	else
+		hipLaunchKernelGGL(k_icgn_iterate<false>, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out);
+}
+
+}  // namespace s3d

@@ -324,6 +324,17 @@ void launch_ransac_global(const float *d_pairs, int n, int H, uint32_t s, double
 void launch_ransac_local(const float *d_pairs, int n, const float *d_pts, int m, int k, float r2, int H, uint32_t s, double tau2, double min_det,
                          int refine, sift3d_affine_fit *d_out, int *d_nbrs, hipStream_t st);
 
+// ---- kernels_icgn.hip: IC-GN displacement refinement (sift3d_icgn, include/sift3d_hip.h) ---------------------------------------
+// a volume on the device: fp32 [z][y][x]
+struct IcgnVol {
+	const float *d;
+	int nx, ny, nz;
+};
+size_t icgn_state_bytes();  // per-POI scratch record of the prepare kernel
+// d_init: m * 12 doubles or null (zero); d_state: m * icgn_state_bytes(); d_out: m records
+void launch_icgn(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_init, int r, int max_it, double tol, int cubic, void *d_state,
+                 sift3d_icgn_result *d_out, hipStream_t st);
+
 // code-object preload of the translation units whose kernels would otherwise be loaded by the first KpSiftAlgorithm of a process
 void preload_march_kernels();
 void preload_small_kernels();

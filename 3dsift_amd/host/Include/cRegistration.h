@@ -1,5 +1,6 @@
-// cRegistration.h -- RANSAC affine fits of matched keypoints (no reference counterpart): the step after enhancedMatch, on the GPU.
-// Over sift3d_fit_affine / sift3d_fit_affine_local (include/sift3d_hip.h, which states the numerical contract).  Both functions take
+// cRegistration.h -- RANSAC affine fits of matched keypoints and IC-GN displacement refinement (no reference counterpart): the steps
+// after enhancedMatch, on the GPU.
+// Over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_icgn (include/sift3d_hip.h, which states the numerical contracts).  Both functions take
 // exactly the two std::vector<Cvec> that muBruteMatcher::enhancedMatch fills (refMatch[i] <-> tarMatch[i]).
 #ifndef S3D_HOST_CREGISTRATION_H
 #define S3D_HOST_CREGISTRATION_H
@@ -41,6 +42,34 @@ SIFT_LIBRARY_API AffineFit EstimateAffine(const std::vector<Cvec> &ref, const st
 // one fit per point (reference coordinates) on its k nearest pairs by reference position (within radius when radius > 0), k in 4..64
 SIFT_LIBRARY_API std::vector<AffineFit> EstimateLocalAffine(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, const std::vector<Cvec> &points,
                                                             int k = 32, float radius = 0, const RansacOptions &opts = RansacOptions());
+
+struct SIFT_LIBRARY_API IcgnOptions {
+	int subset_radius = 16;   // r: the subset is (2r+1)^3 voxels, 2..32
+	int max_iterations = 20;  // 1..100
+	float tolerance = 1e-3f;  // on ||dp||_r; 0 runs max_iterations updates
+	int interpolation = 0;    // 0 tricubic Keys (Catmull-Rom), 1 trilinear
+};
+
+// the refined first-order shape function at one point of interest: p = (u, ux, uy, uz, v, vx, vy, vz, w, wx, wy, wz) (include/sift3d_hip.h);
+// status 0 converged, 1 max_iterations reached, 2 subset outside ref, 3 warped subset outside tar, 4 flat subset, 5 init not finite,
+// 6 singular step, -1 the call failed (message on stderr, like EstimateAffine)
+struct SIFT_LIBRARY_API IcgnResult {
+	double p[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+	double zncc = 0, last_step = 0;
+	int iterations = 0;
+	int status = -1;
+	double seconds = 0;  // device time of the call
+
+	// (u, v, w) and the displacement gradient (row-major 3x3: rows u, v, w; columns x, y, z)
+	Cvec Displacement() const;
+	void Gradient(double G[9]) const;
+};
+
+// IC-GN refinement of the displacement from ref (nx x ny x nz, fp32, x fastest) to tar (tnx x tny x tnz) at integral points of ref,
+// starting from the local affine fits (one per point, e.g. EstimateLocalAffine at the same points) or from zero
+SIFT_LIBRARY_API std::vector<IcgnResult> RefineDisplacements(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
+                                                             const std::vector<Cvec> &points, const std::vector<AffineFit> *init = nullptr,
+                                                             const IcgnOptions &opts = IcgnOptions());
 
 }  // namespace CPUSIFT
 #endif

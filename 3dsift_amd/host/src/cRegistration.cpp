@@ -1,6 +1,8 @@
-// cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine over sift3d_fit_affine / sift3d_fit_affine_local (include/sift3d_hip.h).
+// cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine / RefineDisplacements over sift3d_fit_affine / sift3d_fit_affine_local /
+// sift3d_icgn (include/sift3d_hip.h).
 #include "../Include/cRegistration.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 
@@ -89,6 +91,66 @@ std::vector<AffineFit> EstimateLocalAffine(const std::vector<Cvec> &ref, const s
 		return res;
 	}
 	for (size_t i = 0; i < m; i++) from_c(f[i], sec, res[i]);
+	return res;
+}
+
+Cvec IcgnResult::Displacement() const { return Cvec((float)p[0], (float)p[4], (float)p[8]); }
+void IcgnResult::Gradient(double G[9]) const {
+	for (int i = 0; i < 3; i++)
+		for (int j = 0; j < 3; j++) G[3 * i + j] = p[4 * i + 1 + j];
+}
+
+std::vector<IcgnResult> RefineDisplacements(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
+                                            const std::vector<Cvec> &points, const std::vector<AffineFit> *init, const IcgnOptions &opts) {
+	const size_t m = points.size();
+	std::vector<IcgnResult> res(m);
+	std::vector<int> q(3 * (m ? m : 1));
+	for (size_t i = 0; i < m; i++) {
+		const float c[3] = {points[i].x, points[i].y, points[i].z};
+		for (int a = 0; a < 3; a++) {
+			if (!(std::floor(c[a]) == c[a]) || std::fabs(c[a]) > 2e9f) {
+				fprintf(stderr, "[3dsift_amd] RefineDisplacements: point %zu is not an integral voxel\n", i);
+				return res;
+			}
+			q[3 * i + a] = (int)c[a];
+		}
+	}
+	if (init && init->size() != m) {
+		fprintf(stderr, "[3dsift_amd] RefineDisplacements: %zu initial fits for %zu points\n", init->size(), m);
+		return res;
+	}
+	std::vector<double> p0;
+	if (init) {
+		std::vector<sift3d_affine_fit> f(m ? m : 1);
+		memset(f.data(), 0, sizeof(sift3d_affine_fit) * f.size());
+		for (size_t i = 0; i < m; i++) {
+			memcpy(f[i].A, (*init)[i].A, sizeof(f[i].A));
+			f[i].status = (*init)[i].status;
+		}
+		p0.assign(12 * (m ? m : 1), 0.0);
+		sift3d_icgn_init_from_fits(f.data(), q.data(), (int)m, p0.data());
+	}
+	sift3d_icgn_options o;
+	sift3d_default_icgn_options(&o);
+	o.subset_radius = opts.subset_radius;
+	o.max_iterations = opts.max_iterations;
+	o.tolerance = opts.tolerance;
+	o.interpolation = opts.interpolation;
+	std::vector<sift3d_icgn_result> r(m ? m : 1);
+	double sec = 0;
+	const int rc = sift3d_icgn(ref, nx, ny, nz, tar, tnx, tny, tnz, q.data(), (int)m, init ? p0.data() : nullptr, &o, 0, GetDevice(), r.data(), &sec);
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] RefineDisplacements: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return res;
+	}
+	for (size_t i = 0; i < m; i++) {
+		memcpy(res[i].p, r[i].p, sizeof(res[i].p));
+		res[i].zncc = r[i].zncc;
+		res[i].last_step = r[i].last_step;
+		res[i].iterations = r[i].iterations;
+		res[i].status = r[i].status;
+		res[i].seconds = sec;
+	}
 	return res;
 }
 

@@ -476,6 +476,76 @@ int sift3d_fit_affine(const float *pairs6, int n, const sift3d_ransac_options *o
 int sift3d_fit_affine_local(const float *pairs6, int n, const float *points3, int m, int k, float radius, const sift3d_ransac_options *o,
                             int on_device, int device, sift3d_affine_fit *out, int *neighbours, double *seconds);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * IC-GN displacement refinement for digital volume correlation (no reference counterpart: what the DVC users of the reference run on
+ * the initial guess of sift3d_fit_affine_local; Pan et al., inverse-compositional Gauss-Newton with a first-order shape function).
+ * Numerical contract (a tolerance contract, not bit for bit; tests/icgn_ref.py restates it in NumPy fp64):
+ *   Volumes: fp32, [z][y][x], x fastest (the layout of sift3d_create, the frame of a keypoint's rx, ry, rz).  The reference R and the
+ *     target T may differ in size.  A point of interest (POI) is an integer voxel q = (x, y, z) of R.
+ *   Shape function: p = (u, ux, uy, uz, v, vx, vy, vz, w, wx, wy, wz); the subset offset d maps to q + F d + (u, v, w) in T with
+ *     F = [[1+ux, uy, uz], [vx, 1+vy, vz], [wx, wy, 1+wz]]; M(p) = [[F, (u,v,w)^T], [0, 0, 0, 1]].  From an affine fit A = [L | b] at q:
+ *     (u, v, w) = L q + b - q, F = L (sift3d_icgn_init_from_fits).
+ *   Subset: d in [-r, r]^3, N = (2r+1)^3 voxels.  Gradient of R: fp32 central differences at integer voxels, Rx = 0.5f * (R[x+1] - R[x-1])
+ *     (y, z alike), so the subset plus a 1-voxel margin must lie inside R.  Steepest-descent row of a voxel:
+ *     SD = (Rx, Rx dx, Rx dy, Rx dz, Ry, Ry dx, Ry dy, Ry dz, Rz, Rz dx, Rz dy, Rz dz);  H = sum SD^T SD;  Rm = mean of R over the
+ *     subset;  dR = sqrt(sum (R - Rm)^2).
+ *   Interpolation of T: 0 (default) tricubic Keys convolution, a = -0.5 (Catmull-Rom), 64 taps, weights for the fraction t:
+ *     w-1 = (-t^3 + 2t^2 - t)/2, w0 = (3t^3 - 5t^2 + 2)/2, w1 = (-3t^3 + 4t^2 + t)/2, w2 = (t^3 - t^2)/2;  1 trilinear.  A position is in
+ *     the domain when every tap lies in T: floor(x) - 1 >= 0 and floor(x) + 2 <= n - 1 per axis (cubic), floor(x) >= 0 and
+ *     floor(x) + 1 <= n - 1 (linear).  The warped subset is the affine image of a box: its 8 corners decide.
+ *   Iteration: at the current p, Tm, dT = sqrt(sum (T(W) - Tm)^2) and the ZNSSD step
+ *     dp = -H^-1 sum SD^T [(R - Rm) - (dR/dT)(T(W) - Tm)];  then M(p) <- M(p) . M(dp)^-1, fp64.  Stop when
+ *     ||dp||_r = sqrt(du^2 + dv^2 + dw^2 + r^2 * (sum of the 9 squared gradient terms of dp)) < tolerance.  `iterations` counts the
+ *     updates applied; tolerance 0 runs exactly max_iterations updates (status 1).
+ *   zncc = sum (R - Rm)(T - Tm) / (dR dT), evaluated at the returned p.
+ *   Status per POI (results of a successful call, not errors), checked in this order:
+ *     5 init not finite;  2 subset + margin outside R;  4 flat subset (dR = 0, or H not positive definite: a Cholesky pivot <= 0 or NaN)
+ *       -- these three return the init as given, iterations 0, zncc 0;
+ *     3 warped subset outside T's domain, at the start (init, iterations 0, zncc 0) or after a step (the last in-domain p);
+ *     6 a non-finite dp or a singular M(dp) (the last p);  4 dT = 0 during the iteration, to rounding: dT^2 <= 1e-10 sum (T - Rm)^2
+ *       (the last p);
+ *     1 max_iterations reached without convergence (the last p);  0 converged (the final p).
+ *   Precision: per-voxel interpolation in fp32; the sums over the subset are formed with T shifted by Rm (ZNSSD does not change when T
+ *   is shifted) and reduced in a fixed order with no float atomics: two calls return the same bits.
+ * SIFT3D_ERR_ARG (checked before any device call): m < 0, a dimension < 1, an option outside its range or a non-zero reserved word,
+ * NULL ref / tar / out, NULL points3 with m > 0; m = 0 succeeds.  o may be NULL (defaults).  on_device != 0: ref, tar, points3 and
+ * init12 are device pointers on `device`; out is host memory, filled by one copy at the end.  *seconds (may be NULL): device time
+ * of the call (HIP events; the uploads of host inputs excluded).
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct sift3d_icgn_options {
+	int subset_radius;     /* r, 2..32, default 16 */
+	int max_iterations;    /* 1..100, default 20 */
+	float tolerance;       /* >= 0, finite, default 1e-3; 0: run max_iterations updates */
+	int interpolation;     /* 0 tricubic Keys (default), 1 trilinear */
+	int reserved[4];       /* must be 0 */
+} sift3d_icgn_options;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_icgn_options) == 32, "sift3d_icgn_options must be 32 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_icgn_options, max_iterations) == 4 && offsetof(sift3d_icgn_options, tolerance) == 8 &&
+                     offsetof(sift3d_icgn_options, interpolation) == 12 && offsetof(sift3d_icgn_options, reserved) == 16,
+                     "sift3d_icgn_options field offsets");
+
+typedef struct sift3d_icgn_result {
+	double p[12];          /* u ux uy uz v vx vy vz w wx wy wz */
+	double zncc;
+	double last_step;      /* ||dp||_r of the last computed step (0: none) */
+	int iterations;        /* updates applied */
+	int status;            /* the table above */
+	int reserved[2];
+} sift3d_icgn_result;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_icgn_result) == 128, "sift3d_icgn_result must be 128 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_icgn_result, zncc) == 96 && offsetof(sift3d_icgn_result, last_step) == 104 &&
+                     offsetof(sift3d_icgn_result, iterations) == 112 && offsetof(sift3d_icgn_result, status) == 116 &&
+                     offsetof(sift3d_icgn_result, reserved) == 120, "sift3d_icgn_result field offsets");
+
+/* the defaults above; needs no GPU */
+void sift3d_default_icgn_options(sift3d_icgn_options *o);
+/* host only: m rows of 12 initial parameters from m affine fits at the integer points (x, y, z); a fit with status != 0 gives a NaN
+ * row (POI status 5).  SIFT3D_ERR_ARG: m < 0, or a NULL pointer with m > 0. */
+int sift3d_icgn_init_from_fits(const sift3d_affine_fit *fits, const int *points3, int m, double *init12);
+/* m POIs (x, y, z int triples) refined between ref (rnx x rny x rnz) and tar (tnx x tny x tnz); init12: m*12 or NULL (zero) */
+int sift3d_icgn(const float *ref, int rnx, int rny, int rnz, const float *tar, int tnx, int tny, int tnz, const int *points3, int m,
+                const double *init12, const sift3d_icgn_options *o, int on_device, int device, sift3d_icgn_result *out, double *seconds);
+
 /* Test hooks, rare-path counters and the unit-level debug entry points live in include/sift3d_hip_test.h: this header is the
  * product boundary only. */
 const char *sift3d_error_string(int code);
