@@ -345,7 +345,7 @@ int create_common(sift3d_handle *out, const CreateCfg &cfg, const sift3d_params 
 	for (auto &L : c->gss) { L.d = p; p += al64(L.n()); }
 	for (auto &L : c->dog) { L.d = p; p += al64(L.n()); }
 
-	const size_t nwords = 1 + (size_t)std::max(1, c->noct * c->nd) + 8;  // ... + total, overflow, nkp, describe work counter, describe redo counter, orientation redo counter
+	const size_t nwords = 1 + (size_t)std::max(1, c->noct * c->nd) + 8 + 1;  // ... + total, overflow, nkp, describe work counter, describe redo counter, orientation redo counter; the last word: non-finite input flag
 	CHECKED(hipMalloc(&c->d_words, sizeof(unsigned) * nwords));
 	CHECKED(hipMemset(c->d_words, 0, sizeof(unsigned) * nwords));
 	CHECKED(hipHostMalloc(&c->h_words, sizeof(unsigned) * 8, hipHostMallocDefault));
@@ -450,9 +450,17 @@ extern "C" int sift3d_create(sift3d_handle *out, const float *volume, int nx, in
 		e = hipStreamSynchronize(c->up_stream);  // every chunk has landed: the kernels below run on the handle's stream
 	}
 	if (e == hipSuccess) {
-		launch_absmax(c->in.d, V0, c->d_inmax, c->stream);
+		unsigned *d_nonfinite = c->d_words + 1 + (size_t)std::max(1, c->noct * c->nd) + 8;
+		launch_absmax(c->in.d, V0, c->d_inmax, c->stream, d_nonfinite);
 		launch_scale_by_max(c->in.d, V0, c->d_inmax, c->stream);
-		e = hipStreamSynchronize(c->stream);
+		// A volume with a NaN or Inf voxel (k_absmax's flag; four bytes read behind the synchronisation this constructor ends with anyway)
+		// takes the generic three-pass kernels in their `exact` form for every Gaussian level, the last one included (no k_lazy_next): the
+		// fused, the one-workgroup and the lazy kernels use the interior shortcut tap * src[p - d], which is the reference's arithmetic on
+		// finite data only.  (The first and the last DoG level stay elided as in any run: the extremum test forms them as (hi - lo) * (-1)
+		// from the two Gaussian levels, the arithmetic of the stored levels.)
+		e = hipMemcpyAsync(&c->h_words[7], d_nonfinite, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream);
+		if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+		if (e == hipSuccess && c->h_words[7] != 0) { c->nonfinite = true; c->use_fused = false; }
 	}
 	if (e == hipSuccess) e = hipGetLastError();
 	if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); sift3d_destroy(c); *out = nullptr; return SIFT3D_ERR_HIP; }
@@ -503,9 +511,9 @@ static bool smooth_level(sift3d_ctx *c, int o, const float *src, const Level &ds
 		if (launch_march_level(src, dst.d, dog, dogmax, dst.nx, dst.ny, dst.zr_all(), t, st, plan_slots, prio, want_half ? &hf : nullptr))
 			return want_half;
 	}
-	launch_conv_axis(0, src, c->tmpA[o], dst.nx, dst.ny, dst.nz, t, nullptr, nullptr, nullptr, st);
-	launch_conv_axis(1, c->tmpA[o], c->tmpB[o], dst.nx, dst.ny, dst.nz, t, nullptr, nullptr, nullptr, st);
-	launch_conv_axis(2, c->tmpB[o], dst.d, dst.nx, dst.ny, dst.nz, t, prev, dog, dogmax, st);
+	launch_conv_axis(0, src, c->tmpA[o], dst.nx, dst.ny, dst.nz, t, nullptr, nullptr, nullptr, st, c->nonfinite);
+	launch_conv_axis(1, c->tmpA[o], c->tmpB[o], dst.nx, dst.ny, dst.nz, t, nullptr, nullptr, nullptr, st, c->nonfinite);
+	launch_conv_axis(2, c->tmpB[o], dst.d, dst.nx, dst.ny, dst.nz, t, prev, dog, dogmax, st, c->nonfinite);
 	return false;
 }
 

@@ -103,6 +103,7 @@ struct sift3d_ctx {
 	sift3d_refined *d_refined = nullptr;
 	unsigned refined_cap = 0;
 
+	bool nonfinite = false;  // the input volume holds a NaN or Inf (k_absmax's flag, read once in sift3d_create): every level by k_conv_axis's `exact` form
 	bool use_fused = true;  // SIFT3D_HOOK_SEPARABLE forces the generic three-pass kernels (parity cross-check)
 	int n_regrow = 0, n_desc_redo = 0;  // sift3d_debug_counters: list regrows / second descriptor passes of the last run
 

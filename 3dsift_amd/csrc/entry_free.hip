@@ -15,6 +15,13 @@
 
 using namespace s3d;
 
+// NaN or Inf in caller-held data: the passes then keep the reference's 0 * src[p - d + 1] term (k_conv_axis, `exact`)
+static bool host_nonfinite(const float *a, size_t n) {
+	for (size_t i = 0; i < n; i++)
+		if (!(fabsf(a[i]) <= FLT_MAX)) return true;
+	return false;
+}
+
 extern "C" int sift3d_gaussian_smooth(const float *src, int nx, int ny, int nz, float sigma, float *dst, int device) {
 	if (!src || !dst || nx <= 0 || ny <= 0 || nz <= 0) return SIFT3D_ERR_ARG;
 	int rc = set_device(device);
@@ -26,9 +33,10 @@ extern "C" int sift3d_gaussian_smooth(const float *src, int nx, int ny, int nz, 
 	S3D_HIP(hipMalloc(&d, sizeof(float) * n * 3));
 	hipError_t e = hipMemcpy(d, src, sizeof(float) * n, hipMemcpyHostToDevice);
 	if (e == hipSuccess) {
-		launch_conv_axis(0, d, d + n, nx, ny, nz, t, nullptr, nullptr, nullptr, nullptr);
-		launch_conv_axis(1, d + n, d + 2 * n, nx, ny, nz, t, nullptr, nullptr, nullptr, nullptr);
-		launch_conv_axis(2, d + 2 * n, d, nx, ny, nz, t, nullptr, nullptr, nullptr, nullptr);
+		const bool exact = host_nonfinite(src, n);
+		launch_conv_axis(0, d, d + n, nx, ny, nz, t, nullptr, nullptr, nullptr, nullptr, exact);
+		launch_conv_axis(1, d + n, d + 2 * n, nx, ny, nz, t, nullptr, nullptr, nullptr, nullptr, exact);
+		launch_conv_axis(2, d + 2 * n, d, nx, ny, nz, t, nullptr, nullptr, nullptr, nullptr, exact);
 		e = hipDeviceSynchronize();
 	}
 	if (e == hipSuccess) e = hipMemcpy(dst, d, sizeof(float) * n, hipMemcpyDeviceToHost);
@@ -53,7 +61,7 @@ extern "C" int sift3d_conv_axis(const float *src, int nx, int ny, int nz, int di
 	S3D_HIP(hipMalloc(&d, sizeof(float) * n * 2));
 	hipError_t e = hipMemcpy(d, src, sizeof(float) * n, hipMemcpyHostToDevice);
 	if (e == hipSuccess) {
-		launch_conv_axis(dim, d, d + n, nx, ny, nz, t, nullptr, nullptr, nullptr, nullptr);
+		launch_conv_axis(dim, d, d + n, nx, ny, nz, t, nullptr, nullptr, nullptr, nullptr, host_nonfinite(src, n));
 		e = hipDeviceSynchronize();
 	}
 	if (e == hipSuccess) e = hipMemcpy(dst, d + n, sizeof(float) * n, hipMemcpyDeviceToHost);

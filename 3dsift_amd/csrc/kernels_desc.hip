@@ -246,7 +246,13 @@ __device__ __forceinline__ float accumulate_voxel(bool valid, float bx, float by
 	float b0 = 0.f, b1 = 0.f, b2 = 0.f;
 	int o0, o1, o2;
 	const int f = face_lookup(valid, rx, ry, rz, s_fidx, s_sym, b0, b1, b2, o0, o1, o2);
-	if (!valid || f < 0) return 0.0f;
+	// A NaN / Inf gradient (volumes with non-finite voxels) is `valid` (every comparison with NaN is false).  In the reference such a
+	// sample passes every rejection of the face test the same way (Src/cSIFT3D.cc:1542-1573) and puts NaN into the float histogram.  An
+	// integer histogram cannot hold one (the conversion gives 0 and the row would look like any other), so the sample poisons the
+	// window's gradient MASS instead -- this function's return value: sqrt(g2) below, g2 * 0 here (+0 for every finite gradient) -- and
+	// normalise_store turns a window whose mass is not finite into the reference's row.
+	if (!valid) return 0.0f;
+	if (f < 0) return g2 * 0.0f;
 	const float mag = __fsqrt_rn(g2);
 	const float fx = bx - floorf(bx), fy = by - floorf(by), fz = bz - floorf(bz);
 	const int ix = (int)bx, iy = (int)by, iz = (int)bz;  // truncation toward zero, like the reference: 0..3
@@ -404,6 +410,7 @@ __device__ __forceinline__ float first_pass_unit(const DevKp &kp, const WinLut &
 // lattice points in its sphere than 2^18 (the default parameters' largest: 2.1e5) must therefore use a share of the range larger by
 // that ratio, at most 1/4 -- the average contribution stays what it is for the default windows at 1/64.
 __device__ __forceinline__ bool unit_fails(float mass, float fix_scale, float provable, int nin) {
+	if (!(mass <= FLT_MAX)) return false;  // a poisoned window (accumulate_voxel): its row does not depend on the histogram, no second pass
 	const bool overflow = !(mass * fix_scale + 1048576.0f < 2147483648.0f);
 	const float nsphere = 4.18879f * (float)nin * __fsqrt_rn((float)nin);  // lattice points within radius sqrt(nin)
 	const float share = fminf(fmaxf(nsphere * (1.0f / 262144.0f), 1.0f) * (1.0f / 64.0f), 0.25f);
@@ -412,8 +419,13 @@ __device__ __forceinline__ bool unit_fails(float mass, float fix_scale, float pr
 }
 // normalise -> clamp -> normalise (Src/cSIFT3D.cc:1350-1358, 1639-1656) of the 768 values the first 256 threads of a workgroup hold
 // three each (elements te, te + 256, te + 512), and the store of the descriptor row.  Every thread of the workgroup calls it (barriers).
-__device__ __forceinline__ void normalise_store(float v0, float v1, float v2, int te, int lane, int wid, float *red /*[>= 4]*/, float *out) {
+// mass: the window's gradient mass; NaN when a sample of the window had a non-finite gradient (accumulate_voxel).  The reference's float
+// histogram then holds a NaN, its first normalisation makes the whole row NaN, and its truncation `d < thresh ? d : thresh` replaces
+// every NaN by the threshold: the row ends as the CONSTANT row.  The same arithmetic runs here on a row of NaN (block-uniform; one
+// comparison for every other window).
+__device__ __forceinline__ void normalise_store(float v0, float v1, float v2, int te, int lane, int wid, float *red /*[>= 4]*/, float *out, float mass) {
 	const float trunc_thresh = (float)(0.2 * 128 / kDesc);
+	if (!(mass <= FLT_MAX)) v0 = v1 = v2 = __builtin_nanf("");
 	for (int pass = 0; pass < 2; pass++) {
 		float s = v0 * v0 + v1 * v1 + v2 * v2;
 #pragma unroll
@@ -577,6 +589,7 @@ __global__ void __launch_bounds__(NT) S3D_DESC_ATTR k_describe(const DevKp *__re
 		const gfloat_p centre = Ld + (size_t)cxi + (size_t)sy * (size_t)cyi + (size_t)sz * (size_t)(czi - L.zoff);  // always valid
 
 		bool finished = false;
+		float win_mass = 0.0f;  // the finished window's gradient mass (NaN: poisoned, see normalise_store)
 		for (int attempt = 0;; attempt++) {  // block-uniform; a second pass only when the first unit was too fine
 		float msum = 0.0f;  // this lane's share of the gradient mass
 		__syncthreads();  // previous keypoint / pass finished with hist / s_lut
@@ -933,6 +946,7 @@ __global__ void __launch_bounds__(NT) S3D_DESC_ATTR k_describe(const DevKp *__re
 		const float mass = mass_sum * 1.001f;
 		if (attempt == 1 || !unit_fails(mass, fix_scale, lut.fix_scale, lut.nin)) {
 			finished = true;
+			win_mass = mass;
 			break;
 		}
 		if (S > 1) {
@@ -984,7 +998,7 @@ __global__ void __launch_bounds__(NT) S3D_DESC_ATTR k_describe(const DevKp *__re
 			__syncthreads();
 			if (te < 256) { v0 = vbuf[te]; v1 = vbuf[te + 256]; v2 = vbuf[te + 512]; }
 		}
-		normalise_store(v0, v1, v2, te, lane, wid, red, d_desc + (size_t)slot * kDesc);
+		normalise_store(v0, v1, v2, te, lane, wid, red, d_desc + (size_t)slot * kDesc, win_mass);
 
 	}
 }
@@ -1082,7 +1096,7 @@ __global__ void __launch_bounds__(256) k_describe_finish(const DevKp *__restrict
 			a0 += (long long)h[tid]; a1 += (long long)h[tid + 256]; a2 += (long long)h[tid + 512];
 		}
 		const float v0 = (float)((double)a0 * fix_inv), v1 = (float)((double)a1 * fix_inv), v2 = (float)((double)a2 * fix_inv);
-		normalise_store(v0, v1, v2, tid, lane, wid, red, d_desc + (size_t)recs[k].slot * kDesc);
+		normalise_store(v0, v1, v2, tid, lane, wid, red, d_desc + (size_t)recs[k].slot * kDesc, m);
 		__syncthreads();  // red[] is reused by the next record
 	}
 }

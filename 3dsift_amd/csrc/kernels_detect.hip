@@ -165,6 +165,12 @@ __global__ void __launch_bounds__(kThreads) k_mark(DetectLevels L, int nx, int n
 			const float *__restrict__ pl = cur + sz * (size_t)z + (size_t)seg0 * 64;
 			// one word: v against the peak threshold and against its four in-plane neighbours (up / down rows, left / right voxels)
 			auto word = [&](float v, float u, float d, float xl, float xr, int wseg, unsigned idrow) {
+				// fmaxf / fminf DROP a NaN neighbour where the reference's chain `v > n_k` is false for it: a different predicate on volumes
+				// with non-finite voxels, and an unobservable one.  If an in-plane neighbour q of voxel p is NaN in DoG level i, Gaussian level
+				// i or i + 1 is NaN at q; every level is a blur of the one below with half width >= 1 whose taps at p read q (p is interior,
+				// |p - q| = 1), so Gaussian level i + 2 is NaN at p, and so is DoG level i + 1 there: n7 is NaN (stored, formed from the two
+				// Gaussian levels, or evaluated by the lazy kernels from level i + 1) and `v > n7` / `v < n7` reject the voxel in evaluate().
+				// tests/test_gpu_input_classes.py (nan_*): the extrema of NaN volumes equal the oracle's.
 				const float hi = fmaxf(fmaxf(u, d), fmaxf(xl, xr)), lo = fminf(fminf(u, d), fminf(xl, xr));
 				const bool gmax = v > hi;
 				const bool c = fabsf(v) > thr && (gmax || v < lo) && !((S3D_DETDIAG & 2) && v != 12345.678f);  // |v| > thr == (v > thr || v < -thr)

@@ -8,6 +8,8 @@
 //   * interior term = src[p-d]; boundary term = (1-frac)*src[lo] + frac*src[hi] with the mirror /
 //     "2*dim_end - c - 0.1f" coordinate rule of Src/cSIFT3D.cc:722-788 evaluated in fp32
 //   * DoG = (cur - prev) * (-1)  (Src/cSIFT3D.cc:875)
+#include <float.h>
+
 #include <algorithm>
 
 #include "sift3d_internal.h"
@@ -100,8 +102,11 @@ void launch_max_merge(const MaxMerge &a, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------
 // data_scale (Src/cUtil.cc:536-564): global max|v|, then v /= max
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_absmax(const float *__restrict__ src, size_t n, unsigned *dst) {
+// nonfinite (optional): set to 1 when a voxel is NaN or +-Inf.  The maximum cannot tell (NaN never wins it); the host reads the word
+// once per volume and sends such a volume down the kernels that keep the reference's 0 * src[p - d + 1] term (k_conv_axis, `exact`).
+__global__ void __launch_bounds__(256) k_absmax(const float *__restrict__ src, size_t n, unsigned *dst, unsigned *nonfinite) {
 	float m = 0.0f;
+	bool nf = false;
 	// scalar head up to the first 16-byte boundary (a z-slab's owned planes start at plane * nx * ny floats: any dword alignment),
 	// float4 body, scalar tail
 	const size_t mis = ((size_t)src >> 2) & 3;
@@ -111,12 +116,14 @@ __global__ void __launch_bounds__(256) k_absmax(const float *__restrict__ src, s
 	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
 		float4 v = s4[i];
 		m = absmax_step(m, v.x); m = absmax_step(m, v.y); m = absmax_step(m, v.z); m = absmax_step(m, v.w);
+		nf = nf || !(fabsf(v.x) <= FLT_MAX) || !(fabsf(v.y) <= FLT_MAX) || !(fabsf(v.z) <= FLT_MAX) || !(fabsf(v.w) <= FLT_MAX);
 	}
 	if (blockIdx.x == 0) {
-		if (threadIdx.x < head) m = absmax_step(m, src[threadIdx.x]);
+		if (threadIdx.x < head) { m = absmax_step(m, src[threadIdx.x]); nf |= !(fabsf(src[threadIdx.x]) <= FLT_MAX); }
 		const size_t tail0 = head + n4 * 4;
-		if (threadIdx.x < n - tail0) m = absmax_step(m, src[tail0 + threadIdx.x]);
+		if (threadIdx.x < n - tail0) { m = absmax_step(m, src[tail0 + threadIdx.x]); nf |= !(fabsf(src[tail0 + threadIdx.x]) <= FLT_MAX); }
 	}
+	if (nonfinite != nullptr && nf) *nonfinite = 1u;
 	block_max_to_global(m, dst);
 }
 
@@ -142,9 +149,10 @@ static int grid_for(size_t n, int block, int per_thread = 1) {
 	return (int)b;
 }
 
-void launch_absmax(const float *src, size_t n, unsigned *d_max_bits, hipStream_t st) {
+void launch_absmax(const float *src, size_t n, unsigned *d_max_bits, hipStream_t st, unsigned *d_nonfinite) {
 	hipMemsetAsync(d_max_bits, 0, sizeof(unsigned), st);
-	hipLaunchKernelGGL(k_absmax, dim3(grid_for(n, 256, 4)), dim3(256), 0, st, src, n, d_max_bits);
+	if (d_nonfinite) hipMemsetAsync(d_nonfinite, 0, sizeof(unsigned), st);
+	hipLaunchKernelGGL(k_absmax, dim3(grid_for(n, 256, 4)), dim3(256), 0, st, src, n, d_max_bits, d_nonfinite);
 }
 
 // Sub (Src/cSIFT3D.cc:849-882) for a DoG level the pipeline did not materialise (checking accessor only): dog = (hi - lo) * (-1)
@@ -180,7 +188,7 @@ __device__ __forceinline__ float boundary_term(const float *__restrict__ line, s
 template <int AXIS, bool DOG>
 __global__ void __launch_bounds__(256) k_conv_axis(const float *__restrict__ src, float *__restrict__ dst, int nx, int ny,
                                                    int nz, Taps t, const float *__restrict__ prev,
-                                                   float *__restrict__ dog, unsigned *dogmax) {
+                                                   float *__restrict__ dog, unsigned *dogmax, bool exact) {
 	const size_t total = (size_t)nx * ny * nz;
 	const int hw = t.hw;
 	float m = 0.0f;
@@ -196,7 +204,16 @@ __global__ void __launch_bounds__(256) k_conv_axis(const float *__restrict__ src
 		const float *line = src + (i - (size_t)p * stride);
 		float acc = 0.0f;
 		if (p >= hw && p <= n - 2 - hw) {
-			for (int d = -hw; d <= hw; d++) acc = acc + t.w[d + hw] * line[(size_t)(p - d) * stride];
+			// The reference's interior term is tap * ((1 - frac) * src[lo] + frac * src[lo + 1]) with frac == 0 (Src/cSIFT3D.cc:701-708).
+			// On finite data 1 * a + 0 * b == a bit for bit (and an accumulator that starts at +0 never becomes -0), so the second voxel
+			// is not read; a NaN or Inf there makes the reference's term NaN -- a non-finite voxel spreads ONE VOXEL FURTHER towards the
+			// low end of every axis than the taps reach.  `exact` (kernel-uniform; volumes whose input holds a non-finite voxel) keeps the
+			// reference's form: p - d + 1 <= p + hw + 1 <= n - 1.
+			if (exact) {
+				for (int d = -hw; d <= hw; d++) acc = acc + t.w[d + hw] * (1.0f * line[(size_t)(p - d) * stride] + 0.0f * line[(size_t)(p - d + 1) * stride]);
+			} else {
+				for (int d = -hw; d <= hw; d++) acc = acc + t.w[d + hw] * line[(size_t)(p - d) * stride];
+			}
 		} else {
 			for (int d = -hw; d <= hw; d++) acc = acc + t.w[d + hw] * boundary_term(line, stride, p, d, n);
 		}
@@ -211,13 +228,13 @@ __global__ void __launch_bounds__(256) k_conv_axis(const float *__restrict__ src
 }
 
 void launch_conv_axis(int axis, const float *src, float *dst, int nx, int ny, int nz, const Taps &t, const float *prev,
-                      float *dog, unsigned *d_dogmax, hipStream_t st) {
+                      float *dog, unsigned *d_dogmax, hipStream_t st, bool exact) {
 	const size_t total = (size_t)nx * ny * nz;
 	dim3 grid((unsigned)((total + 255) / 256 > 65535u * 64u ? 65535u * 64u : (total + 255) / 256)), block(256);
-	if (axis == 0) hipLaunchKernelGGL((k_conv_axis<0, false>), grid, block, 0, st, src, dst, nx, ny, nz, t, nullptr, nullptr, nullptr);
-	else if (axis == 1) hipLaunchKernelGGL((k_conv_axis<1, false>), grid, block, 0, st, src, dst, nx, ny, nz, t, nullptr, nullptr, nullptr);
-	else if (dog) hipLaunchKernelGGL((k_conv_axis<2, true>), grid, block, 0, st, src, dst, nx, ny, nz, t, prev, dog, d_dogmax);
-	else hipLaunchKernelGGL((k_conv_axis<2, false>), grid, block, 0, st, src, dst, nx, ny, nz, t, nullptr, nullptr, nullptr);
+	if (axis == 0) hipLaunchKernelGGL((k_conv_axis<0, false>), grid, block, 0, st, src, dst, nx, ny, nz, t, nullptr, nullptr, nullptr, exact);
+	else if (axis == 1) hipLaunchKernelGGL((k_conv_axis<1, false>), grid, block, 0, st, src, dst, nx, ny, nz, t, nullptr, nullptr, nullptr, exact);
+	else if (dog) hipLaunchKernelGGL((k_conv_axis<2, true>), grid, block, 0, st, src, dst, nx, ny, nz, t, prev, dog, d_dogmax, exact);
+	else hipLaunchKernelGGL((k_conv_axis<2, false>), grid, block, 0, st, src, dst, nx, ny, nz, t, nullptr, nullptr, nullptr, exact);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -120,13 +120,15 @@ struct FaceSym {
 };
 
 // ---- kernels_pyramid.hip -------------------------------------------------------------------
-void launch_absmax(const float *src, size_t n, unsigned *d_max_bits, hipStream_t st);
+// d_nonfinite (optional): set to 1 when a voxel is NaN or +-Inf (cleared first)
+void launch_absmax(const float *src, size_t n, unsigned *d_max_bits, hipStream_t st, unsigned *d_nonfinite = nullptr);
 void launch_scale_by_max(float *data, size_t n, const unsigned *d_max_bits, hipStream_t st);
 void launch_dog_from_gss(const float *hi, const float *lo, float *dog, size_t n, hipStream_t st);  // dog = (hi - lo) * (-1)
 // separable pass along AXIS (0 x, 1 y, 2 z); for AXIS==2 optionally also emits
-// dog = -(dst - prev) and accumulates max|dog| (bits) into d_dogmax.
+// dog = -(dst - prev) and accumulates max|dog| (bits) into d_dogmax.  exact: the interior term keeps the reference's
+// 0 * src[p - d + 1] (data with NaN / Inf; bit-identical and slower on finite data).
 void launch_conv_axis(int axis, const float *src, float *dst, int nx, int ny, int nz, const Taps &t,
-                      const float *prev, float *dog, unsigned *d_dogmax, hipStream_t st);
+                      const float *prev, float *dog, unsigned *d_dogmax, hipStream_t st, bool exact = false);
 // fused single-pass level kernel (kernels_march.hip): descending z-march with scatter accumulators; false => not applicable (half
 // width without an instantiation, planes smaller than a tile): the caller takes the separable kernels above
 // level 0 of the next octave, written by the march kernel together with the seed level (DownSample_3D fused into the producer)

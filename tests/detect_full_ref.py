@@ -15,9 +15,14 @@ def _shift(a, dz, dy, dx):
     return a[1 + dz:nz - 1 + dz, 1 + dy:ny - 1 + dy, 1 + dx:nx - 1 + dx]
 
 
+def level_absmax(cur):
+    """max|level| by the reference's comparison `fabs(v) > max ? fabs(v) : max` (Src/cUtil.cc:548): a NaN never wins, an all-NaN level gives 0"""
+    return np.float32(np.fmax.reduce(np.abs(np.asarray(cur, np.float32)).ravel(), initial=np.float32(0.0)))
+
+
 def level_threshold(cur, peak_thresh):
     """peak_thresh * max|level|: the fp32 product the detection kernels form"""
-    return np.float32(peak_thresh) * np.float32(np.abs(cur).max())
+    return np.float32(peak_thresh) * level_absmax(cur)
 
 
 def extrema_mask(prev, cur, nxt, peak_thresh, neighbours):
@@ -137,7 +142,7 @@ def refined_table(dogs, rows, peak_thresh, neighbours, opts):
         o, lv, x, y, z = (int(v) for v in r)
         D = dogs[o]
         ok, d, contrast, Hs = quad_fit(D[lv - 1], D[lv], D[lv + 1], x, y, z)
-        if ok and fit_accepts(d, contrast, Hs, np.abs(D[lv]).max(), **opts):
+        if ok and fit_accepts(d, contrast, Hs, level_absmax(D[lv]), **opts):
             keep.append(r)
     return np.array(keep, np.int64).reshape(-1, 5)
 

@@ -101,3 +101,59 @@ def test_matcher_matches_reference(orc, synth, g11):
             assert keys
             for k in keys:
                 assert np.array_equal(g11[pre + k], o[k]), (mode, thr, k)
+
+
+# ---- the value classes of tests/input_classes.py on the reference itself, where oracle/_ref/libref3dsift.so was built -------------
+import input_classes as ic  # noqa: E402
+import oracle_lib as ol  # noqa: E402
+from hipcheck import nan_equal_bits  # noqa: E402
+
+needs_ref = pytest.mark.skipif(not ol.available("ref"), reason="oracle/_ref/libref3dsift.so is built only where the reference tree exists")
+
+
+@needs_ref
+@pytest.mark.parametrize("name", ["mixed", "masked", "steps", "negdom", "hot3e38", "nan_slab", "nan_voxel", "nan_block", "nan_corner", "pos_inf", "neg_inf"])
+def test_input_classes_match_the_reference(orc, name):
+    """One subnormal class with keypoints (mixed) and one without (hot3e38), the tie-heavy ones, a signed one and EVERY non-finite class
+    through the untouched reference and the restatement: every level (NaN positions as a mask, everything else by bits; the shell of the
+    last level of an octave of <= 9 voxels is cropped as in g11), extrema, keypoint records and descriptors bit for bit.
+
+    The reference survives NaN and Inf input and its result does not depend on the thread count (run here on 1 and 7 threads).  Two
+    things it does there, both restated:
+      * its interior convolution term is tap * (1 * src[p - d] + 0 * src[p - d + 1]) (Src/cSIFT3D.cc:701-708): a non-finite voxel
+        spreads one voxel further towards the low end of every axis than the taps reach.  The restatement used tap * src[p - d],
+        which is the same bits on finite data only, and disagreed on nan_voxel / nan_block / nan_corner / the Inf classes (91 voxels
+        of level 0 on nan_voxel, 275 instead of 312 extrema) until it took the reference's form for volumes that hold a non-finite voxel.
+      * a descriptor window with a NaN sample ends as the CONSTANT row, never a NaN row: the truncation at Src/cSIFT3D.cc:1355
+        replaces NaN by the threshold."""
+    vol = ic.make(name)
+    ref = ol.load("ref")
+    b = orc.extractor(vol).run(5)
+    eb = b.extrema()
+    kb, db_ = b.keypoints()
+    try:
+        for threads in (1, 7):
+            ref.set_threads(threads)
+            a = ref.extractor(vol).run(5)
+            assert a.num_octaves == b.num_octaves
+            assert nan_equal_bits(a.input(), b.input()) == 0
+            for o in range(a.num_octaves):
+                for kind, n, ga, gb in (("gss", 6, a.gss, b.gss), ("dog", 5, a.dog, b.dog)):
+                    for i in range(n):
+                        x, y = ga(o, i), gb(o, i)
+                        if min(x.shape) <= 9 and i == n - 1:
+                            x, y = x[1:-1, 1:-1, 1:-1], y[1:-1, 1:-1, 1:-1]
+                        assert nan_equal_bits(x, y) == 0, (kind, o, i, threads)
+            ea = a.extrema()
+            assert len(ea) == len(eb)
+            for f in ("x", "y", "z", "scale", "octave", "level"):
+                assert np.array_equal(ea[f], eb[f]), f
+            ka, da_ = a.keypoints()
+            assert len(ka) == len(kb)
+            for f in ("x", "y", "z", "scale", "octave", "level", "rx", "ry", "rz", "win", "eigvalue", "Rotation", "str_tensor"):
+                assert np.array_equal(bits(ka[f]) if ka[f].dtype == np.float32 else ka[f], bits(kb[f]) if kb[f].dtype == np.float32 else kb[f]), f
+            assert np.array_equal(bits(da_), bits(db_))
+            if name in ic.NAN:
+                assert (da_ == da_[:, :1]).all(axis=1).any() and not np.isnan(da_).any()
+    finally:
+        ref.set_threads(0)
