@@ -5,7 +5,7 @@
 //                   the 12 x 12 fp64 Cholesky of H in LDS (a column per step, the trailing update spread over the workgroup) and
 //                   H^-1 by 12 column solves; a record per POI (IcgnState) for the second launch
 //   k_icgn_iterate  every iteration inside the launch: one pass over the subset per iteration gathers 15 sums at the current warp
-//                   (sum T', sum T'^2, sum R'T' and the 12 sums SD^T T', with T' = T(W) - Rm and R' = R - Rm), reduced in a fixed
+//                   (sum T', sum T'^2, sum R'T' and the 12 sums SD^T T', with T' = T(W) - Tc and R' = R - Rm; Tc: T's voxel under the subset centre), reduced in a fixed
 //                   order (xor butterfly in the wave, waves in index order); every thread then forms the same step from the sums
 //                   (fp64, redundantly: no broadcast and one barrier per pass), composes the warp, tests convergence and the 8 corners.
 //                   The pass after the last update gives zncc at the returned p.
@@ -22,7 +22,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kPrepSums = 86;  // dR^2, sum R', 12 sum SD, 12 sum SD R', 60 H pieces
-constexpr int kIterSums = 15;  // sum T', sum T'^2, 12 sum SD T', sum R'T'
+constexpr int kIterSums = 15;  // sum T', sum T'^2, 12 sum SD T', sum R'T' (T' = T - Tc)
 constexpr int kRun = -1;       // IcgnState::status: go on to the iteration
 
 struct IcgnState {
@@ -279,9 +279,14 @@ __global__ __launch_bounds__(kThreads) void k_icgn_prepare(IcgnVol R, IcgnVol T,
 
 // ---- iterate ---------------------------------------------------------------------------------------------------------------------
 
-// one pass over the subset at the warp p: the 15 sums, reduced (every thread returns the same values)
+// one pass over the subset at the warp p: the 15 sums, reduced (every thread returns the same values).  T is shifted by Tc, the voxel of T
+// at the base tap of the subset's centre (any constant serves: ZNSSD does not change when T is shifted), and the taps are shifted
+// before they are weighted: a constant T gives T' = 0 exactly, T scaled by a power of two scales T' exactly, and an offset common to
+// the taps leaves the interpolation's rounding.  Tc is one voxel: an outlier there (a hot voxel |Tc - Tm| >> dT) makes every T' large
+// and costs the fp32 sums that many ulps, as a T far brighter than R did under the shift by Rm; a mean of T would need a pass of its
+// own.  Returns Tc - (float)Rm, which turns the sums into those of T - Rm.
 template <bool CUBIC>
-__device__ inline void subset_pass(const IcgnVol &R, const IcgnVol &T, const int q[3], int r, float rmf, const double p[12],
+__device__ inline double subset_pass(const IcgnVol &R, const IcgnVol &T, const int q[3], int r, float rmf, const double p[12],
                                    double (*red)[kIterSums], double sums[kIterSums]) {
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	const int D = 2 * r + 1, N = D * D * D;
@@ -303,6 +308,7 @@ __device__ inline void subset_pass(const IcgnVol &R, const IcgnVol &T, const int
 	const size_t tsy = (size_t)T.nx, tsz = (size_t)T.nx * T.ny;
 	const float *Rq = R.d + vidx(R, q[0], q[1], q[2]);
 	const int sy = R.nx, sz = R.nx * R.ny;
+	const float tc = T.d[vidx(T, min(max(ci[0], lo), hx), min(max(ci[1], lo), hy), min(max(ci[2], lo), hz))];
 	float acc[13];
 #pragma unroll
 	for (int k = 0; k < 13; k++) acc[k] = 0.f;
@@ -316,20 +322,23 @@ __device__ inline void subset_pass(const IcgnVol &R, const IcgnVol &T, const int
 #pragma unroll
 		for (int a = 0; a < 3; a++) o[a] = cf[a] + ((F[3 * a] * fx + F[3 * a + 1] * fy) + F[3 * a + 2] * fz);
 		const float flx = floorf(o[0]), fly = floorf(o[1]), flz = floorf(o[2]);
-		const float tx = o[0] - flx, ty = o[1] - fly, tz = o[2] - flz;
-		// the clamp only guards memory: the corner test keeps every tap inside T up to fp32 rounding
-		const int gx = min(max(ci[0] + (int)flx, lo), hx), gy = min(max(ci[1] + (int)fly, lo), hy), gz = min(max(ci[2] + (int)flz, lo), hz);
+		// the corner test keeps every tap inside T in fp64; fp32 rounding (cf = 1.0f for a fraction within 2^-25 of 1, cf + F d a
+		// rounding below or onto the next integer) can still put the base tap one voxel outside.  The clamp moves it back and the
+		// fraction takes the difference, so the position is kept (t = 1 or t = -eps at the edge; + 0.f elsewhere: same bits)
+		const int ux = ci[0] + (int)flx, uy = ci[1] + (int)fly, uz = ci[2] + (int)flz;
+		const int gx = min(max(ux, lo), hx), gy = min(max(uy, lo), hy), gz = min(max(uz, lo), hz);
+		const float tx = (o[0] - flx) + (float)(ux - gx), ty = (o[1] - fly) + (float)(uy - gy), tz = (o[2] - flz) + (float)(uz - gz);
 		float tv;
 		if (CUBIC) {
 			float w[3][4];
 			const float t3[3] = {tx, ty, tz};
 #pragma unroll
 			for (int a = 0; a < 3; a++) {
-				const float t = t3[a], t2 = t * t, tc = t2 * t;
-				w[a][0] = 0.5f * ((2.f * t2 - tc) - t);
-				w[a][1] = 0.5f * ((3.f * tc - 5.f * t2) + 2.f);
-				w[a][2] = 0.5f * ((4.f * t2 - 3.f * tc) + t);
-				w[a][3] = 0.5f * (tc - t2);
+				const float t = t3[a], t2 = t * t, tq = t2 * t;
+				w[a][0] = 0.5f * ((2.f * t2 - tq) - t);
+				w[a][1] = 0.5f * ((3.f * tq - 5.f * t2) + 2.f);
+				w[a][2] = 0.5f * ((4.f * t2 - 3.f * tq) + t);
+				w[a][3] = 0.5f * (tq - t2);
 			}
 			const float *b = T.d + (((size_t)(gz - 1) * T.ny + (gy - 1)) * T.nx + (gx - 1));
 			tv = 0.f;
@@ -338,7 +347,7 @@ __device__ inline void subset_pass(const IcgnVol &R, const IcgnVol &T, const int
 				float zv = 0.f;
 #pragma unroll
 				for (int j = 0; j < 4; j++) {
-					const f4u v = *reinterpret_cast<const f4u *>(b + (k * tsz + j * tsy));
+					const f4u v = *reinterpret_cast<const f4u *>(b + (k * tsz + j * tsy)) - tc;
 					const float row = fmaf(w[0][3], v.w, fmaf(w[0][2], v.z, fmaf(w[0][1], v.y, w[0][0] * v.x)));
 					zv = fmaf(w[1][j], row, zv);
 				}
@@ -346,8 +355,8 @@ __device__ inline void subset_pass(const IcgnVol &R, const IcgnVol &T, const int
 			}
 		} else {
 			const float *b = T.d + (((size_t)gz * T.ny + gy) * T.nx + gx);
-			const f2u a00 = *reinterpret_cast<const f2u *>(b), a01 = *reinterpret_cast<const f2u *>(b + tsy);
-			const f2u a10 = *reinterpret_cast<const f2u *>(b + tsz), a11 = *reinterpret_cast<const f2u *>(b + tsz + tsy);
+			const f2u a00 = *reinterpret_cast<const f2u *>(b) - tc, a01 = *reinterpret_cast<const f2u *>(b + tsy) - tc;
+			const f2u a10 = *reinterpret_cast<const f2u *>(b + tsz) - tc, a11 = *reinterpret_cast<const f2u *>(b + tsz + tsy) - tc;
 			const float r00 = fmaf(tx, a00.y - a00.x, a00.x), r01 = fmaf(tx, a01.y - a01.x, a01.x);
 			const float r10 = fmaf(tx, a10.y - a10.x, a10.x), r11 = fmaf(tx, a11.y - a11.x, a11.x);
 			const float z0 = fmaf(ty, r01 - r00, r00), z1 = fmaf(ty, r11 - r10, r10);
@@ -355,7 +364,7 @@ __device__ inline void subset_pass(const IcgnVol &R, const IcgnVol &T, const int
 		}
 		const float *c = Rq + (dz * sz + dy * sy + dx);
 		const float g[3] = {0.5f * (c[1] - c[-1]), 0.5f * (c[sy] - c[-sy]), 0.5f * (c[sz] - c[-sz])};
-		const float tp = tv - rmf, rp = c[0] - rmf;
+		const float tp = tv, rp = c[0] - rmf;
 		sT += (double)tp;
 		sTT = fma((double)tp, (double)tp, sTT);
 		acc[12] = fmaf(rp, tp, acc[12]);
@@ -382,6 +391,7 @@ __device__ inline void subset_pass(const IcgnVol &R, const IcgnVol &T, const int
 	__syncthreads();
 #pragma unroll
 	for (int k = 0; k < kIterSums; k++) sums[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+	return (double)tc - (double)rmf;
 }
 
 template <bool CUBIC>
@@ -406,11 +416,12 @@ __global__ __launch_bounds__(kThreads) void k_icgn_iterate(IcgnVol R, IcgnVol T,
 	bool done = false;
 	for (int pass = 0;; pass++) {
 		double s[kIterSums];
-		subset_pass<CUBIC>(R, T, q, r, rmf, p, red[pass & 1], s);
+		const double sh = subset_pass<CUBIC>(R, T, q, r, rmf, p, red[pass & 1], s);
 		// s: 0 sum T', 1 sum T'^2, 2..13 sum SD T', 14 sum R'T'
 		const double tm = s[0] / N;
 		const double dt2 = s[1] - s[0] * tm;
-		const bool flat = !(dt2 > 1e-10 * s[1]);  // dT = 0 to rounding
+		const double ttm = (s[1] + 2.0 * sh * s[0]) + (N * sh) * sh;  // sum (T - Rm)^2 from the sums of T' = T - Tc
+		const bool flat = !(dt2 > 1e-10 * ttm);  // dT = 0 to rounding
 		const double dt = flat ? 0.0 : sqrt(dt2);
 		const double zncc = flat ? 0.0 : (s[14] - tm * sr) / (dr * dt);
 		if (done) {

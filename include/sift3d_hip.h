@@ -505,8 +505,11 @@ int sift3d_fit_affine_local(const float *pairs6, int n, const float *points3, in
  *     6 a non-finite dp or a singular M(dp) (the last p);  4 dT = 0 during the iteration, to rounding: dT^2 <= 1e-10 sum (T - Rm)^2
  *       (the last p);
  *     1 max_iterations reached without convergence (the last p);  0 converged (the final p).
- *   Precision: per-voxel interpolation in fp32; the sums over the subset are formed with T shifted by Rm (ZNSSD does not change when T
- *   is shifted) and reduced in a fixed order with no float atomics: two calls return the same bits.
+ *   Precision: per-voxel interpolation in fp32 (the fraction, the weights, every product and sum; a position whose fp32 form rounds
+ *   onto the next integer at T's edge is read with fraction 1 from the last admissible base tap: the domain is the fp64 test's); the
+ *   sums over the subset are formed with T shifted by Tc, the voxel of T under the subset's centre (ZNSSD does not change when T is
+ *   shifted), and the taps are shifted before they are weighted: a constant T has dT = 0 exactly, and scaling T by a power of two
+ *   returns the same bits.  The sums are reduced in a fixed order with no float atomics: two calls return the same bits.
  * SIFT3D_ERR_ARG (checked before any device call): m < 0, a dimension < 1, an option outside its range or a non-zero reserved word,
  * NULL ref / tar / out, NULL points3 with m > 0; m = 0 succeeds.  o may be NULL (defaults).  on_device != 0: ref, tar, points3 and
  * init12 are device pointers on `device`; out is host memory, filled by one copy at the end.  *seconds (may be NULL): device time

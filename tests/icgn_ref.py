@@ -12,20 +12,35 @@ def keys_weights(t):
     return np.stack([(-t3 + 2 * t2 - t) / 2, (3 * t3 - 5 * t2 + 2) / 2, (-3 * t3 + 4 * t2 + t) / 2, (t3 - t2) / 2], -1)
 
 
-def interp(T, pos, cubic=True):
-    """T (nz, ny, nx) at positions (n, 3) (x, y, z) whose taps lie inside T"""
+def interp(T, pos, cubic=True, f32=False):
+    """T (nz, ny, nx) at positions (n, 3) (x, y, z) whose taps lie inside T: the taps are weighted and summed along x, then y, then z,
+    each sum in tap order.  f32: the header's "per-voxel interpolation in fp32" -- the fraction, the weights, every product and every
+    sum rounded to float32 (same weights, same order, not fused); the result is returned as float64"""
     fl = np.floor(pos)
-    t = pos - fl
+    dt = np.float32 if f32 else np.float64
+    t = (pos - fl).astype(dt)
     i = fl.astype(np.int64)
     if cubic:
-        off, w = np.arange(-1, 3), keys_weights(t)
+        off, w = (-1, 0, 1, 2), keys_weights(t)
     else:
-        off, w = np.arange(0, 2), np.stack([1 - t, t], -1)
-    ix, iy, iz = (i[:, a, None] + off for a in range(3))
-    v = T[iz[:, :, None, None], iy[:, None, :, None], ix[:, None, None, :]].astype(np.float64)  # (n, z, y, x)
-    v = (v * w[:, 0, None, None, :]).sum(-1)
-    v = (v * w[:, 1, None, :]).sum(-1)
-    return (v * w[:, 2]).sum(-1)
+        off, w = (0, 1), np.stack([1 - t, t], -1)
+    nz, ny, nx = T.shape
+    flat = np.ascontiguousarray(T).reshape(-1)
+    base = (i[:, 2] * ny + i[:, 1]) * nx + i[:, 0]
+    out = None
+    for kz, oz in enumerate(off):
+        vz = None
+        for ky, oy in enumerate(off):
+            row = base + (oz * ny + oy) * nx
+            vy = None
+            for kx, ox in enumerate(off):
+                term = flat[row + ox].astype(dt) * w[:, 0, kx]
+                vy = term if vy is None else vy + term
+            term = vy * w[:, 1, ky]
+            vz = term if vz is None else vz + term
+        term = vz * w[:, 2, kz]
+        out = term if out is None else out + term
+    return out.astype(np.float64)
 
 
 def offsets(r):
@@ -67,14 +82,35 @@ def in_domain(shape, p, q, r, cubic):
     return bool(np.all(f - lo >= 0) and np.all(f + hi <= n - 1))
 
 
-def refine(R, T, q, init=None, subset_radius=16, max_iterations=20, tolerance=1e-3, interpolation=0):
-    """one POI: dict(p, zncc, last_step, iterations, status) as sift3d_icgn_result"""
+def positive_definite(H):
+    """the contract's test of H: a column Cholesky (the order of k_icgn_prepare) that stops at the first pivot that is <= 0 or NaN.
+    np.linalg.cholesky does not state it: it returns a NaN factor for a NaN entry and accepts an infinite pivot's NaN remainder."""
+    A = np.array(H, np.float64)
+    n = len(A)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for k in range(n):
+            d = A[k, k]
+            if not d > 0:
+                return False
+            A[k, k] = np.sqrt(d)
+            A[k + 1:, k] = A[k + 1:, k] / A[k, k]
+            for j in range(k + 1, n):
+                A[j:, j] = A[j:, j] - A[j:, k] * A[j, k]
+    return True
+
+
+def refine(R, T, q, init=None, subset_radius=16, max_iterations=20, tolerance=1e-3, interpolation=0, f32=False):
+    """one POI: dict(p, zncc, last_step, iterations, status) as sift3d_icgn_result, and steps (||dp||_r of every computed step).
+    f32: interp's float32 form"""
     r, cubic = subset_radius, interpolation == 0
     q = np.asarray(q, np.int64)
     p = np.zeros(12) if init is None else np.array(init, np.float64)
 
+    steps = []  # ||dp||_r of every computed step, in order
+
     def res(p, zncc, last, it, status):
-        return dict(p=np.array(p, np.float64), zncc=float(zncc), last_step=float(last), iterations=int(it), status=int(status))
+        return dict(p=np.array(p, np.float64), zncc=float(zncc), last_step=float(last), iterations=int(it), status=int(status),
+                    steps=tuple(steps))
 
     if not np.all(np.isfinite(p)):
         return res(p, 0, 0, 0, 5)
@@ -96,17 +132,16 @@ def refine(R, T, q, init=None, subset_radius=16, max_iterations=20, tolerance=1e
     SD = np.concatenate([gc[:, None] * v for gc in g], 1)
     if not dR > 0:
         return res(p, 0, 0, 0, 4)
-    H = SD.T @ SD
-    try:
-        np.linalg.cholesky(H)
-    except np.linalg.LinAlgError:
+    with np.errstate(invalid="ignore", over="ignore"):
+        H = SD.T @ SD
+    if not positive_definite(H):
         return res(p, 0, 0, 0, 4)
     if not in_domain(T.shape, p, q, r, cubic):
         return res(p, 0, 0, 0, 3)
     N = float(len(d))
     it, last, done, status = 0, 0.0, False, None
     while True:
-        Tp = interp(T, warp(p, q, d), cubic) - Rm  # ZNSSD does not change when T is shifted
+        Tp = interp(T, warp(p, q, d), cubic, f32) - Rm  # ZNSSD does not change when T is shifted
         sT = Tp.sum()
         sTT = np.sum(Tp * Tp)
         tm = sT / N
@@ -123,6 +158,7 @@ def refine(R, T, q, init=None, subset_radius=16, max_iterations=20, tolerance=1e
         gd = dp.reshape(3, 4)[:, 1:]
         with np.errstate(invalid="ignore", over="ignore"):
             last = float(np.sqrt(dp[0] ** 2 + dp[4] ** 2 + dp[8] ** 2 + r * r * np.sum(gd * gd)))
+        steps.append(last)
         if not np.all(np.isfinite(dp)):
             return res(p, zncc, last, it, 6)
         det = np.linalg.det(F_of(dp))
@@ -145,7 +181,7 @@ def icgn(R, T, points, init=None, **opts):
     rows = [refine(R, T, q, None if init is None else init[i], **opts) for i, q in enumerate(pts)]
     p = np.array([w["p"] for w in rows]).reshape(-1, 12)
     return {"p": p, "displacement": p[:, [0, 4, 8]], "gradient": p.reshape(-1, 3, 4)[:, :, 1:],
-            **{k: np.array([w[k] for w in rows]) for k in ("zncc", "last_step", "iterations", "status")}}
+            **{k: np.array([w[k] for w in rows]) for k in ("zncc", "last_step", "iterations", "status")}, "steps": [w["steps"] for w in rows]}
 
 
 def init_from_fits(A, status, points):
