@@ -42,6 +42,8 @@ SYMBOLS = [
     "sift3d_default_ransac_options", "sift3d_fit_affine", "sift3d_fit_affine_local",
     # IC-GN displacement refinement (digital volume correlation)
     "sift3d_default_icgn_options", "sift3d_icgn_init_from_fits", "sift3d_icgn",
+    # ZNCC integer search: the initial guess of IC-GN where no local fit exists
+    "sift3d_default_search_options", "sift3d_zncc_search", "sift3d_icgn_init_from_search",
     "sift3d_device_count", "sift3d_error_string", "sift3d_last_error",
     # multi-GPU sharding (z-slabs of octave 0 + seeded replicated tail)
     "sift3d_slab_min_halo", "sift3d_slab_arena_floats", "sift3d_slab_create", "sift3d_slab_buffer", "sift3d_slab_upload",
@@ -120,6 +122,19 @@ ICGN_DTYPE = np.dtype([("p", "<f8", (12,)), ("zncc", "<f8"), ("last_step", "<f8"
 assert ICGN_DTYPE.itemsize == 128
 
 
+class SearchOptions(C.Structure):
+    """sift3d_search_options (include/sift3d_hip.h)"""
+    _fields_ = [("subset_radius", C.c_int), ("search_radius", C.c_int), ("reserved", C.c_int * 6)]
+
+
+assert C.sizeof(SearchOptions) == 32
+
+# sift3d_search_result: d = (du, dv, dw), status, zncc at d, the best score away from d, candidates scored
+SEARCH_DTYPE = np.dtype([("d", "<i4", (3,)), ("status", "<i4"), ("zncc", "<f8"), ("zncc_second", "<f8"), ("candidates", "<i4"),
+                         ("reserved", "<i4", (3,))])
+assert SEARCH_DTYPE.itemsize == 48
+
+
 class SlabDesc(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("z0", C.c_int), ("z1", C.c_int), ("halo", C.c_int),
                 ("noct_total", C.c_int), ("octave", C.c_int)]
@@ -192,6 +207,11 @@ def lib():
         L.sift3d_icgn_init_from_fits.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.sift3d_icgn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                   C.POINTER(IcgnOptions), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+        L.sift3d_default_search_options.argtypes = [C.POINTER(SearchOptions)]
+        L.sift3d_default_search_options.restype = None
+        L.sift3d_zncc_search.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.POINTER(SearchOptions), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+        L.sift3d_icgn_init_from_search.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _sz = C.POINTER(C.c_size_t)
         L.sift3d_slab_min_halo.argtypes = [C.POINTER(Params), _ip]
         L.sift3d_slab_arena_floats.argtypes = [C.POINTER(SlabDesc), C.POINTER(Params), _sz]
@@ -482,6 +502,87 @@ def icgn(ref, tar, points, init=None, device=0, **opts):
     G = p.reshape(-1, 3, 4)[:, :, 1:].copy()
     return {"p": p, "displacement": p[:, [0, 4, 8]].copy(), "gradient": G, "zncc": out["zncc"].copy(), "last_step": out["last_step"].copy(),
             "iterations": out["iterations"].copy(), "status": out["status"].copy(), "seconds": sec.value}
+
+
+SEARCH_OPTIONS = ("subset_radius", "search_radius")
+
+
+def default_search_options():
+    """sift3d_default_search_options as a dict (needs no GPU)"""
+    o = SearchOptions()
+    lib().sift3d_default_search_options(C.byref(o))
+    return {k: getattr(o, k) for k in SEARCH_OPTIONS}
+
+
+def zncc_search(ref, tar, points, guess=None, device=0, **opts):
+    """sift3d_zncc_search: the integer displacement of highest ZNCC at each point ((m, 3) int32 x, y, z of ref) within search_radius of
+    guess ((m, 3) int32 or None: zero).  ref / tar: (nz, ny, nx) float32 numpy arrays or contiguous float32 device tensors, both of
+    the same kind.  Options: subset_radius, search_radius.  Returns d (m, 3) int32, zncc, zncc_second, candidates, status (m,) and
+    the device seconds."""
+    o = SearchOptions()
+    lib().sift3d_default_search_options(C.byref(o))
+    for k, v in opts.items():
+        if k not in SEARCH_OPTIONS:
+            raise TypeError(f"unknown search option {k!r}")
+        setattr(o, k, v)
+    dev = [hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) for a in (ref, tar)]
+    if dev[0] != dev[1]:
+        raise ValueError("ref and tar must both be numpy arrays or both device tensors")
+    vols, keep = [], []
+    if dev[0]:
+        import torch
+
+        for a, name in ((ref, "ref"), (tar, "tar")):
+            if a.dtype != torch.float32 or not a.is_contiguous() or a.dim() != 3:
+                raise ValueError(f"{name}: a contiguous float32 (nz, ny, nx) device tensor is needed")
+            vols.append((C.c_void_p(a.data_ptr()), a.shape))
+        q = torch.as_tensor(points, dtype=torch.int32, device=ref.device).reshape(-1, 3).contiguous()
+        m = q.shape[0]
+        gs = None if guess is None else torch.as_tensor(guess, dtype=torch.int32, device=ref.device).reshape(-1, 3).contiguous()
+        qp = C.c_void_p(q.data_ptr())
+        gp = None if gs is None else C.c_void_p(gs.data_ptr())
+    else:
+        for a, name in ((ref, "ref"), (tar, "tar")):
+            h = np.ascontiguousarray(a, np.float32)
+            if h.ndim != 3:
+                raise ValueError(f"{name}: a (nz, ny, nx) volume is needed")
+            keep.append(h)
+            vols.append((h.ctypes.data_as(C.c_void_p), h.shape))
+        q = np.ascontiguousarray(points, np.int32).reshape(-1, 3)
+        m = len(q)
+        gs = None if guess is None else np.ascontiguousarray(guess, np.int32).reshape(-1, 3)
+        qp = q.ctypes.data_as(C.c_void_p)
+        gp = None if gs is None else gs.ctypes.data_as(C.c_void_p)
+    keep += [q, gs]
+    if gs is not None and gs.shape[0] != m:
+        raise ValueError("guess: one (gx, gy, gz) per point")
+    (rp, (rz, ry, rx)), (tp, (tz, ty, tx)) = vols
+    out = np.zeros(max(m, 1), SEARCH_DTYPE)
+    sec = C.c_double(0)
+    _check(lib().sift3d_zncc_search(rp, int(rx), int(ry), int(rz), tp, int(tx), int(ty), int(tz), qp, m, gp, C.byref(o), int(dev[0]),
+                                    int(device), out.ctypes.data_as(C.c_void_p), C.byref(sec)))
+    out = out[:m]
+    return {"d": out["d"].copy(), "zncc": out["zncc"].copy(), "zncc_second": out["zncc_second"].copy(),
+            "candidates": out["candidates"].copy(), "status": out["status"].copy(), "seconds": sec.value}
+
+
+def icgn_init_from_search(res, init=None, only_missing=True):
+    """sift3d_icgn_init_from_search: (m, 12) float64 initial parameters for icgn from the dict zncc_search returns.  Rows of init
+    (None: all NaN) whose search has status 0 become (du, 0, 0, 0, dv, 0, 0, 0, dw, 0, 0, 0) -- with only_missing only the rows that
+    hold a non-finite value; every other row is returned as given."""
+    d = np.ascontiguousarray(res["d"], np.int32).reshape(-1, 3)
+    m = len(d)
+    rec = np.zeros(max(m, 1), SEARCH_DTYPE)
+    rec["d"][:m] = d
+    rec["status"][:m] = np.asarray(res["status"])
+    out = np.full((max(m, 1), 12), np.nan)
+    if init is not None:
+        ini = np.asarray(init, np.float64).reshape(-1, 12)
+        if len(ini) != m:
+            raise ValueError("init: one row of 12 per search result")
+        out[:m] = ini
+    _check(lib().sift3d_icgn_init_from_search(rec.ctypes.data_as(C.c_void_p), m, int(bool(only_missing)), out.ctypes.data_as(C.c_void_p)))
+    return out[:m].copy()
 
 
 def device_count():

@@ -337,6 +337,13 @@ size_t icgn_state_bytes();  // per-POI scratch record of the prepare kernel
 void launch_icgn(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_init, int r, int max_it, double tol, int cubic, void *d_state,
                  sift3d_icgn_result *d_out, hipStream_t st);
 
+// ---- kernels_search.hip: ZNCC integer search (sift3d_zncc_search, include/sift3d_hip.h) -----------------------------------------
+int search_groups(int m);                  // workgroups of the launch: each walks its POIs in turn
+size_t search_score_bytes(int m, int s);   // score scratch of the launch (a table of (2s+1)^3 doubles per workgroup)
+// d_guess: m int triples or null (zero); d_scores: search_score_bytes(m, s); d_out: m records
+void launch_zncc_search(IcgnVol R, IcgnVol T, const int *d_pts, int m, const int *d_guess, int r, int s, double *d_scores,
+                        sift3d_search_result *d_out, hipStream_t st);
+
 // code-object preload of the translation units whose kernels would otherwise be loaded by the first KpSiftAlgorithm of a process
 void preload_march_kernels();
 void preload_small_kernels();

@@ -1,6 +1,6 @@
-// cRegistration.h -- RANSAC affine fits of matched keypoints and IC-GN displacement refinement (no reference counterpart): the steps
-// after enhancedMatch, on the GPU.
-// Over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_icgn (include/sift3d_hip.h, which states the numerical contracts).  Both functions take
+// cRegistration.h -- RANSAC affine fits of matched keypoints, ZNCC integer search and IC-GN displacement refinement (no reference
+// counterpart): the steps after enhancedMatch, on the GPU.
+// Over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_zncc_search / sift3d_icgn (include/sift3d_hip.h, which states the numerical contracts).  Both functions take
 // exactly the two std::vector<Cvec> that muBruteMatcher::enhancedMatch fills (refMatch[i] <-> tarMatch[i]).
 #ifndef S3D_HOST_CREGISTRATION_H
 #define S3D_HOST_CREGISTRATION_H
@@ -65,11 +65,36 @@ struct SIFT_LIBRARY_API IcgnResult {
 	void Gradient(double G[9]) const;
 };
 
+struct SIFT_LIBRARY_API SearchOptions {
+	int subset_radius = 8;  // r: the subset is (2r+1)^3 voxels, 2..16
+	int search_radius = 8;  // s: candidates are guess + [-s, s]^3, 1..16
+};
+
+// the integer displacement of highest ZNCC at one point of interest (include/sift3d_hip.h); status 0 found, 2 subset outside ref,
+// 3 no candidate scored (d = the guess), 4 flat subset, -1 the call failed (message on stderr, like EstimateAffine)
+struct SIFT_LIBRARY_API SearchResult {
+	int d[3] = {0, 0, 0};
+	int status = -1;
+	double zncc = 0, zncc_second = -2.0;  // at d; the best score at Chebyshev distance > 1 from d (-2: none)
+	int candidates = 0;                   // candidates scored
+	double seconds = 0;                   // device time of the call
+
+	Cvec Displacement() const;
+};
+
+// exhaustive integer search of the displacement from ref to tar at integral points of ref, around the guesses (integral, one per
+// point) or around zero: the initial guess of RefineDisplacements where no local fit exists
+SIFT_LIBRARY_API std::vector<SearchResult> SearchDisplacements(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
+                                                               const std::vector<Cvec> &points, const std::vector<Cvec> *guesses = nullptr,
+                                                               const SearchOptions &o = SearchOptions());
+
 // IC-GN refinement of the displacement from ref (nx x ny x nz, fp32, x fastest) to tar (tnx x tny x tnz) at integral points of ref,
-// starting from the local affine fits (one per point, e.g. EstimateLocalAffine at the same points) or from zero
+// starting from the local affine fits (one per point, e.g. EstimateLocalAffine at the same points) or from zero; fallback (one per
+// point, e.g. SearchDisplacements at the same points) gives the start of a point whose fit has status != 0
 SIFT_LIBRARY_API std::vector<IcgnResult> RefineDisplacements(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
                                                              const std::vector<Cvec> &points, const std::vector<AffineFit> *init = nullptr,
-                                                             const IcgnOptions &opts = IcgnOptions());
+                                                             const IcgnOptions &opts = IcgnOptions(),
+                                                             const std::vector<SearchResult> *fallback = nullptr);
 
 }  // namespace CPUSIFT
 #endif

@@ -1,5 +1,5 @@
-// cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine / RefineDisplacements over sift3d_fit_affine / sift3d_fit_affine_local /
-// sift3d_icgn (include/sift3d_hip.h).
+// cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine / SearchDisplacements / RefineDisplacements over sift3d_fit_affine /
+// sift3d_fit_affine_local / sift3d_zncc_search / sift3d_icgn (include/sift3d_hip.h).
 #include "../Include/cRegistration.h"
 
 #include <cmath>
@@ -39,6 +39,22 @@ std::vector<float> pairs6(const std::vector<Cvec> &ref, const std::vector<Cvec> 
 		p[6 * i + 3] = tar[i].x; p[6 * i + 4] = tar[i].y; p[6 * i + 5] = tar[i].z;
 	}
 	return p;
+}
+// points with integral coordinates -> int triples; false (message on stderr) when one is not integral
+bool int_triples(const char *who, const char *what, const std::vector<Cvec> &points, std::vector<int> &q) {
+	const size_t m = points.size();
+	q.assign(3 * (m ? m : 1), 0);
+	for (size_t i = 0; i < m; i++) {
+		const float c[3] = {points[i].x, points[i].y, points[i].z};
+		for (int a = 0; a < 3; a++) {
+			if (!(std::floor(c[a]) == c[a]) || std::fabs(c[a]) > 2e9f) {
+				fprintf(stderr, "[3dsift_amd] %s: %s %zu is not an integral voxel\n", who, what, i);
+				return false;
+			}
+			q[3 * i + a] = (int)c[a];
+		}
+	}
+	return true;
 }
 }  // namespace
 
@@ -100,23 +116,55 @@ void IcgnResult::Gradient(double G[9]) const {
 		for (int j = 0; j < 3; j++) G[3 * i + j] = p[4 * i + 1 + j];
 }
 
+Cvec SearchResult::Displacement() const { return Cvec((float)d[0], (float)d[1], (float)d[2]); }
+
+std::vector<SearchResult> SearchDisplacements(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
+                                              const std::vector<Cvec> &points, const std::vector<Cvec> *guesses, const SearchOptions &opts) {
+	const size_t m = points.size();
+	std::vector<SearchResult> res(m);
+	std::vector<int> q, g;
+	if (!int_triples("SearchDisplacements", "point", points, q)) return res;
+	if (guesses && guesses->size() != m) {
+		fprintf(stderr, "[3dsift_amd] SearchDisplacements: %zu guesses for %zu points\n", guesses->size(), m);
+		return res;
+	}
+	if (guesses && !int_triples("SearchDisplacements", "guess", *guesses, g)) return res;
+	sift3d_search_options o;
+	sift3d_default_search_options(&o);
+	o.subset_radius = opts.subset_radius;
+	o.search_radius = opts.search_radius;
+	std::vector<sift3d_search_result> r(m ? m : 1);
+	double sec = 0;
+	const int rc = sift3d_zncc_search(ref, nx, ny, nz, tar, tnx, tny, tnz, q.data(), (int)m, guesses ? g.data() : nullptr, &o, 0, GetDevice(), r.data(),
+	                                  &sec);
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] SearchDisplacements: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return res;
+	}
+	for (size_t i = 0; i < m; i++) {
+		memcpy(res[i].d, r[i].d, sizeof(res[i].d));
+		res[i].status = r[i].status;
+		res[i].zncc = r[i].zncc;
+		res[i].zncc_second = r[i].zncc_second;
+		res[i].candidates = r[i].candidates;
+		res[i].seconds = sec;
+	}
+	return res;
+}
+
 std::vector<IcgnResult> RefineDisplacements(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
-                                            const std::vector<Cvec> &points, const std::vector<AffineFit> *init, const IcgnOptions &opts) {
+                                            const std::vector<Cvec> &points, const std::vector<AffineFit> *init, const IcgnOptions &opts,
+                                            const std::vector<SearchResult> *fallback) {
 	const size_t m = points.size();
 	std::vector<IcgnResult> res(m);
-	std::vector<int> q(3 * (m ? m : 1));
-	for (size_t i = 0; i < m; i++) {
-		const float c[3] = {points[i].x, points[i].y, points[i].z};
-		for (int a = 0; a < 3; a++) {
-			if (!(std::floor(c[a]) == c[a]) || std::fabs(c[a]) > 2e9f) {
-				fprintf(stderr, "[3dsift_amd] RefineDisplacements: point %zu is not an integral voxel\n", i);
-				return res;
-			}
-			q[3 * i + a] = (int)c[a];
-		}
-	}
+	std::vector<int> q;
+	if (!int_triples("RefineDisplacements", "point", points, q)) return res;
 	if (init && init->size() != m) {
 		fprintf(stderr, "[3dsift_amd] RefineDisplacements: %zu initial fits for %zu points\n", init->size(), m);
+		return res;
+	}
+	if (fallback && fallback->size() != m) {
+		fprintf(stderr, "[3dsift_amd] RefineDisplacements: %zu fallback results for %zu points\n", fallback->size(), m);
 		return res;
 	}
 	std::vector<double> p0;
@@ -129,6 +177,15 @@ std::vector<IcgnResult> RefineDisplacements(const float *ref, int nx, int ny, in
 		}
 		p0.assign(12 * (m ? m : 1), 0.0);
 		sift3d_icgn_init_from_fits(f.data(), q.data(), (int)m, p0.data());
+		if (fallback) {  // the NaN rows of the failed fits take the search's displacement
+			std::vector<sift3d_search_result> sr(m ? m : 1);
+			memset(sr.data(), 0, sizeof(sift3d_search_result) * sr.size());
+			for (size_t i = 0; i < m; i++) {
+				memcpy(sr[i].d, (*fallback)[i].d, sizeof(sr[i].d));
+				sr[i].status = (*fallback)[i].status;
+			}
+			sift3d_icgn_init_from_search(sr.data(), (int)m, 1, p0.data());
+		}
 	}
 	sift3d_icgn_options o;
 	sift3d_default_icgn_options(&o);

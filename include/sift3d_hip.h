@@ -549,6 +549,68 @@ int sift3d_icgn_init_from_fits(const sift3d_affine_fit *fits, const int *points3
 int sift3d_icgn(const float *ref, int rnx, int rny, int rnz, const float *tar, int tnx, int tny, int tnz, const int *points3, int m,
                 const double *init12, const sift3d_icgn_options *o, int on_device, int device, sift3d_icgn_result *out, double *seconds);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * ZNCC integer search: the zero-order initial guess of IC-GN where no local affine fit exists (no reference counterpart: the
+ * exhaustive integer-voxel search of DIC / DVC codes).  The reference subset of a POI is slid over a window of the target and the
+ * integer displacement with the highest zero-normalised cross-correlation is returned.  It uses no neighbouring POI.
+ * Numerical contract (a tolerance contract like IC-GN's, not bit for bit; tests/zncc_search_ref.py restates it in NumPy fp64):
+ *   Volumes: fp32, [z][y][x], as for sift3d_icgn; R and T may differ in size.  A POI q is an integer voxel (x, y, z) of R.
+ *   Subset: q + [-r, r]^3, N = (2r+1)^3 voxels; Rm = mean of R over it; dR = sqrt(sum (R - Rm)^2).
+ *   Candidates: c = g + e with e in [-s, s]^3, g the POI's guess (zero without guess3).  c is admissible when q + c - r >= 0 and
+ *     q + c + r <= n - 1 on every axis of T; a guess component of magnitude above 2^24 makes every candidate inadmissible.  The test
+ *     is made in 64-bit arithmetic: no int overflows, whatever g holds.
+ *   Score of an admissible candidate: zncc(c) = sum (R - Rm)(T(x + c) - Tm) / (dR dT), Tm and dT = sqrt(sum (T - Tm)^2) the mean
+ *     and the deviation of T over the shifted subset.  A candidate with dT = 0 to rounding -- IC-GN's rule, dT^2 <= 1e-10 sum (T - Rm)^2
+ *     -- is skipped, not scored.  A non-finite sum skips the candidate too.
+ *   Result: the scored candidate with the highest score; among candidates whose scores are equal in the kernel's own arithmetic the
+ *     lowest index (ez, ey, ex), ex fastest, wins.  zncc_second: the best score among the scored candidates at Chebyshev distance
+ *     > 1 from d (-2.0: none).  candidates: how many were scored.
+ *   Status per POI (results of a successful call, not errors), checked in this order:
+ *     2 subset outside R;  4 dR = 0 (or not finite);  3 no candidate scored -- these return d = g, zncc 0, zncc_second -2.0, candidates 0;
+ *     0 otherwise: the best scored candidate.  A POI with status 2 reads no voxel of R; no voxel outside R or T is ever read.
+ *   Precision: the sums of a candidate are formed on T - Tc, Tc = the voxel of T nearest to q + g (ZNCC does not change when T is
+ *     shifted): a T constant over the search region has dT = 0 exactly and no candidate is scored.  Products and the sums along x are
+ *     fp32 ((R - (float)Rm) and (T - Tc) rounded once), the sums over rows, planes and slabs fp64, reduced in a fixed order with no
+ *     float atomics: two calls return the same bytes, and a POI's result does not depend on the other POIs of the call.
+ * SIFT3D_ERR_ARG (checked before any device call): m < 0, a dimension < 1, subset_radius outside 2..16, search_radius outside 1..16,
+ * a non-zero reserved word, NULL ref / tar / out, NULL points3 with m > 0; m = 0 succeeds.  SIFT3D_ERR_NO_DEVICE after that check when
+ * no GPU is visible: there is no CPU fallback.  o may be NULL (defaults).  on_device != 0: ref, tar, points3 and guess3 are device
+ * pointers on `device`, ordered behind the legacy default stream; out is host memory, filled by one copy at the end.  *seconds (may
+ * be NULL): device time of the call (HIP events; the uploads of host inputs excluded).
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct sift3d_search_options {
+	int subset_radius;     /* r, 2..16, default 8 */
+	int search_radius;     /* s, 1..16, default 8 */
+	int reserved[6];       /* must be 0 */
+} sift3d_search_options;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_search_options) == 32, "sift3d_search_options must be 32 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_search_options, search_radius) == 4 && offsetof(sift3d_search_options, reserved) == 8,
+                     "sift3d_search_options field offsets");
+
+typedef struct sift3d_search_result {
+	int d[3];              /* best integer displacement (du, dv, dw) = guess + e */
+	int status;            /* the table above */
+	double zncc;           /* at d */
+	double zncc_second;    /* best score among the scored candidates at Chebyshev distance > 1 from d; -2.0 if there is none */
+	int candidates;        /* candidates scored */
+	int reserved[3];       /* 0 */
+} sift3d_search_result;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_search_result) == 48, "sift3d_search_result must be 48 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_search_result, status) == 12 && offsetof(sift3d_search_result, zncc) == 16 &&
+                     offsetof(sift3d_search_result, zncc_second) == 24 && offsetof(sift3d_search_result, candidates) == 32 &&
+                     offsetof(sift3d_search_result, reserved) == 36, "sift3d_search_result field offsets");
+
+/* the defaults above; needs no GPU */
+void sift3d_default_search_options(sift3d_search_options *o);
+/* m POIs (x, y, z int triples) of ref searched in tar; guess3: m int triples (gx, gy, gz) or NULL (zero); out: m records */
+int sift3d_zncc_search(const float *ref, int rnx, int rny, int rnz, const float *tar, int tnx, int tny, int tnz, const int *points3, int m,
+                       const int *guess3, const sift3d_search_options *o, int on_device, int device, sift3d_search_result *out,
+                       double *seconds);
+/* host only: fills rows of init12 (m * 12) from the search results with status 0 as (du, 0, 0, 0, dv, 0, 0, 0, dw, 0, 0, 0);
+ * only_missing != 0: only rows that hold a non-finite value are touched.  Rows whose search failed stay as they are.
+ * SIFT3D_ERR_ARG: m < 0, or a NULL pointer with m > 0. */
+int sift3d_icgn_init_from_search(const sift3d_search_result *res, int m, int only_missing, double *init12);
+
 /* Test hooks, rare-path counters and the unit-level debug entry points live in include/sift3d_hip_test.h: this header is the
  * product boundary only. */
 const char *sift3d_error_string(int code);
