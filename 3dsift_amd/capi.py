@@ -44,6 +44,8 @@ SYMBOLS = [
     "sift3d_default_icgn_options", "sift3d_icgn_init_from_fits", "sift3d_icgn",
     # ZNCC integer search: the initial guess of IC-GN where no local fit exists
     "sift3d_default_search_options", "sift3d_zncc_search", "sift3d_icgn_init_from_search",
+    # strain fields from the refined displacements
+    "sift3d_default_strain_options", "sift3d_strain_input_from_icgn", "sift3d_strain",
     "sift3d_device_count", "sift3d_error_string", "sift3d_last_error",
     # multi-GPU sharding (z-slabs of octave 0 + seeded replicated tail)
     "sift3d_slab_min_halo", "sift3d_slab_arena_floats", "sift3d_slab_create", "sift3d_slab_buffer", "sift3d_slab_upload",
@@ -135,6 +137,20 @@ SEARCH_DTYPE = np.dtype([("d", "<i4", (3,)), ("status", "<i4"), ("zncc", "<f8"),
 assert SEARCH_DTYPE.itemsize == 48
 
 
+class StrainOptions(C.Structure):
+    """sift3d_strain_options (include/sift3d_hip.h)"""
+    _fields_ = [("radius", C.c_int), ("min_neighbours", C.c_int), ("measure", C.c_int), ("reserved", C.c_int * 5)]
+
+
+assert C.sizeof(StrainOptions) == 32
+
+# sift3d_strain_result: the fitted displacement, gradient (rows u v w, columns x y z), E (xx yy zz xy yz zx), its eigenvalues
+# (descending), the equivalent strain, the fit's residual, the neighbour count and the status
+STRAIN_DTYPE = np.dtype([("disp", "<f8", (3,)), ("G", "<f8", (9,)), ("E", "<f8", (6,)), ("principal", "<f8", (3,)), ("equivalent", "<f8"),
+                         ("rms", "<f8"), ("neighbours", "<i4"), ("status", "<i4")])
+assert STRAIN_DTYPE.itemsize == 192
+
+
 class SlabDesc(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("z0", C.c_int), ("z1", C.c_int), ("halo", C.c_int),
                 ("noct_total", C.c_int), ("octave", C.c_int)]
@@ -212,6 +228,11 @@ def lib():
         L.sift3d_zncc_search.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                          C.c_void_p, C.POINTER(SearchOptions), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
         L.sift3d_icgn_init_from_search.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.sift3d_default_strain_options.argtypes = [C.POINTER(StrainOptions)]
+        L.sift3d_default_strain_options.restype = None
+        L.sift3d_strain_input_from_icgn.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
+        L.sift3d_strain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(StrainOptions), C.c_int, C.c_int, C.c_void_p,
+                                    C.POINTER(C.c_double)]
         _sz = C.POINTER(C.c_size_t)
         L.sift3d_slab_min_halo.argtypes = [C.POINTER(Params), _ip]
         L.sift3d_slab_arena_floats.argtypes = [C.POINTER(SlabDesc), C.POINTER(Params), _sz]
@@ -583,6 +604,76 @@ def icgn_init_from_search(res, init=None, only_missing=True):
         out[:m] = ini
     _check(lib().sift3d_icgn_init_from_search(rec.ctypes.data_as(C.c_void_p), m, int(bool(only_missing)), out.ctypes.data_as(C.c_void_p)))
     return out[:m].copy()
+
+
+STRAIN_OPTIONS = ("radius", "min_neighbours", "measure")
+
+
+def default_strain_options():
+    """sift3d_default_strain_options as a dict (needs no GPU)"""
+    o = StrainOptions()
+    lib().sift3d_default_strain_options(C.byref(o))
+    return {k: getattr(o, k) for k in STRAIN_OPTIONS}
+
+
+def strain_input_from_icgn(res, zncc_min=0.0, accept_unconverged=False):
+    """sift3d_strain_input_from_icgn: the displacements (m, 3) float64 and the validity bytes (m,) uint8 that strain takes, from the
+    dict icgn returns (p, zncc, status): valid where IC-GN converged (or ran out of iterations, with accept_unconverged), zncc >=
+    zncc_min and the displacement is finite.  Needs no GPU."""
+    p = np.asarray(res["p"], np.float64).reshape(-1, 12)
+    m = len(p)
+    rec = np.zeros(max(m, 1), ICGN_DTYPE)
+    rec["p"][:m] = p
+    rec["zncc"][:m] = np.asarray(res["zncc"])
+    rec["status"][:m] = np.asarray(res["status"])
+    disp = np.zeros((max(m, 1), 3), np.float64)
+    valid = np.zeros(max(m, 1), np.uint8)
+    _check(lib().sift3d_strain_input_from_icgn(rec.ctypes.data_as(C.c_void_p), m, float(zncc_min), int(bool(accept_unconverged)),
+                                               disp.ctypes.data_as(C.c_void_p), valid.ctypes.data_as(C.c_void_p)))
+    return disp[:m].copy(), valid[:m].copy()
+
+
+def strain(points, disp, valid=None, device=0, **opts):
+    """sift3d_strain: a plane fitted to the displacements ((m, 3) float64 u, v, w) of the POIs ((m, 3) int32 x, y, z) within `radius`
+    voxels (Chebyshev) of each POI, and the strain of the fitted gradient.  valid: (m,) bytes or None (all valid).  points / disp /
+    valid: numpy arrays or contiguous device tensors, all of the same kind.  Options: radius, min_neighbours, measure (0
+    Green-Lagrange, 1 infinitesimal).  Returns disp (m, 3), G (m, 3, 3) (rows u, v, w; columns x, y, z), E (m, 6) (xx yy zz xy yz zx),
+    principal (m, 3), equivalent, rms, neighbours, status (m,) and the device seconds."""
+    o = StrainOptions()
+    lib().sift3d_default_strain_options(C.byref(o))
+    for k, v in opts.items():
+        if k not in STRAIN_OPTIONS:
+            raise TypeError(f"unknown strain option {k!r}")
+        setattr(o, k, v)
+    given = [a for a in (points, disp, valid) if a is not None]
+    dev = [hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) for a in given]
+    if any(dev) != all(dev):
+        raise ValueError("points, disp and valid must all be numpy arrays or all device tensors")
+    if dev[0]:
+        import torch
+
+        q = torch.as_tensor(points, dtype=torch.int32, device=points.device).reshape(-1, 3).contiguous()
+        u = torch.as_tensor(disp, dtype=torch.float64, device=points.device).reshape(-1, 3).contiguous()
+        ok = None if valid is None else torch.as_tensor(valid, device=points.device).ne(0).to(torch.uint8).reshape(-1).contiguous()
+        m = q.shape[0]
+        qp, up = C.c_void_p(q.data_ptr()), C.c_void_p(u.data_ptr())
+        vp = None if ok is None else C.c_void_p(ok.data_ptr())
+    else:
+        q = np.ascontiguousarray(points, np.int32).reshape(-1, 3)
+        u = np.ascontiguousarray(disp, np.float64).reshape(-1, 3)
+        ok = None if valid is None else np.ascontiguousarray(np.asarray(valid) != 0, np.uint8).reshape(-1)
+        m = len(q)
+        qp, up = q.ctypes.data_as(C.c_void_p), u.ctypes.data_as(C.c_void_p)
+        vp = None if ok is None else ok.ctypes.data_as(C.c_void_p)
+    if u.shape[0] != m or (ok is not None and ok.shape[0] != m):
+        raise ValueError("disp, valid: one row per point")
+    out = np.zeros(max(m, 1), STRAIN_DTYPE)
+    sec = C.c_double(0)
+    _check(lib().sift3d_strain(qp, up, vp, m, C.byref(o), int(dev[0]), int(device), out.ctypes.data_as(C.c_void_p), C.byref(sec)))
+    out = out[:m]
+    return {"disp": out["disp"].copy(), "G": out["G"].reshape(-1, 3, 3).copy(), "E": out["E"].copy(), "principal": out["principal"].copy(),
+            "equivalent": out["equivalent"].copy(), "rms": out["rms"].copy(), "neighbours": out["neighbours"].copy(),
+            "status": out["status"].copy(), "seconds": sec.value}
 
 
 def device_count():

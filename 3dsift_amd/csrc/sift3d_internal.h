@@ -344,6 +344,25 @@ size_t search_score_bytes(int m, int s);   // score scratch of the launch (a tab
 void launch_zncc_search(IcgnVol R, IcgnVol T, const int *d_pts, int m, const int *d_guess, int r, int s, double *d_scores,
                         sift3d_search_result *d_out, hipStream_t st);
 
+// ---- kernels_strain.hip: strain fields from the POIs' displacements (sift3d_strain, include/sift3d_hip.h) ------------------------
+// the cell grid over the bounding box of the contributing POIs: cell (cx, cy, cz) = (q - origin) / side per axis, cx fastest
+struct StrainGrid {
+	int x0, y0, z0, side, nx, ny, nz;
+};
+// the contributing POIs in cell order, a cell's POIs in ascending index
+struct StrainSorted {
+	int *x, *y, *z, *idx;
+	double *u, *v, *w;
+};
+size_t strain_scan_tiles(size_t n);  // entries of the scan's tile scratch for n scanned values
+// d_cell: m ints (1 contributes, -1 does not); d_box: 6 ints preset to 0x7f7f7f7f -> min x, y, z and min -x, -y, -z of the contributing POIs
+void launch_strain_mark(const int *d_pts, const double *d_disp, const unsigned char *d_valid, int m, int *d_cell, int *d_box, hipStream_t st);
+// d_cnt (zeroed), d_start: cells + 1 ints; d_tiles: strain_scan_tiles(cells + 1) ints; d_slots: m ints; fills d_start and S
+hipError_t launch_strain_bin(const int *d_pts, const double *d_disp, int m, StrainGrid g, int *d_cell, int *d_cnt, int *d_start, int *d_tiles,
+                             int *d_slots, StrainSorted S, hipStream_t st);
+void launch_strain_fit(const int *d_pts, const double *d_disp, int m, StrainGrid g, const int *d_start, StrainSorted S, int radius, int min_nb,
+                       int measure, sift3d_strain_result *d_out, hipStream_t st);
+
 // code-object preload of the translation units whose kernels would otherwise be loaded by the first KpSiftAlgorithm of a process
 void preload_march_kernels();
 void preload_small_kernels();

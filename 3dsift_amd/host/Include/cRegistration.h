@@ -1,6 +1,6 @@
-// cRegistration.h -- RANSAC affine fits of matched keypoints, ZNCC integer search and IC-GN displacement refinement (no reference
-// counterpart): the steps after enhancedMatch, on the GPU.
-// Over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_zncc_search / sift3d_icgn (include/sift3d_hip.h, which states the numerical contracts).  Both functions take
+// cRegistration.h -- RANSAC affine fits of matched keypoints, ZNCC integer search, IC-GN displacement refinement and strain fields (no
+// reference counterpart): the steps after enhancedMatch, on the GPU.
+// Over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_zncc_search / sift3d_icgn / sift3d_strain (include/sift3d_hip.h, which states the numerical contracts).  Both functions take
 // exactly the two std::vector<Cvec> that muBruteMatcher::enhancedMatch fills (refMatch[i] <-> tarMatch[i]).
 #ifndef S3D_HOST_CREGISTRATION_H
 #define S3D_HOST_CREGISTRATION_H
@@ -95,6 +95,32 @@ SIFT_LIBRARY_API std::vector<IcgnResult> RefineDisplacements(const float *ref, i
                                                              const std::vector<Cvec> &points, const std::vector<AffineFit> *init = nullptr,
                                                              const IcgnOptions &opts = IcgnOptions(),
                                                              const std::vector<SearchResult> *fallback = nullptr);
+
+struct SIFT_LIBRARY_API StrainOptions {
+	int radius = 16;          // window half width in voxels (Chebyshev), 1..4096
+	int min_neighbours = 10;  // 4..1048576
+	int measure = 0;          // 0 Green-Lagrange, 1 infinitesimal
+};
+
+// the plane fitted to the displacements of the points within `radius` of one point of interest and its strain (include/sift3d_hip.h);
+// status 0 fitted, 1 fewer than min_neighbours neighbours, 2 coordinate out of range, 4 degenerate window (coplanar neighbours),
+// -1 the call failed (message on stderr, like EstimateAffine)
+struct SIFT_LIBRARY_API StrainResult {
+	double disp[3] = {0, 0, 0};                    // fitted displacement at the point
+	double G[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};     // fitted gradient, row-major: rows u, v, w; columns x, y, z
+	double E[6] = {0, 0, 0, 0, 0, 0};              // xx yy zz xy yz zx
+	double principal[3] = {0, 0, 0};               // eigenvalues of E, descending
+	double equivalent = 0, rms = 0;
+	int neighbours = 0;
+	int status = -1;
+	double seconds = 0;  // device time of the call
+};
+
+// strain at every point from the displacements RefineDisplacements returned at the same points: a point is a neighbour where IC-GN
+// converged (or ran out of iterations, with accept_unconverged) with zncc >= zncc_min; the others are filled from their neighbours
+SIFT_LIBRARY_API std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp,
+                                                          const StrainOptions &o = StrainOptions(), double zncc_min = 0,
+                                                          bool accept_unconverged = false);
 
 }  // namespace CPUSIFT
 #endif

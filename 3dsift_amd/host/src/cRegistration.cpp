@@ -1,5 +1,5 @@
-// cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine / SearchDisplacements / RefineDisplacements over sift3d_fit_affine /
-// sift3d_fit_affine_local / sift3d_zncc_search / sift3d_icgn (include/sift3d_hip.h).
+// cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine / SearchDisplacements / RefineDisplacements / ComputeStrains over
+// sift3d_fit_affine / sift3d_fit_affine_local / sift3d_zncc_search / sift3d_icgn / sift3d_strain (include/sift3d_hip.h).
 #include "../Include/cRegistration.h"
 
 #include <cmath>
@@ -205,6 +205,52 @@ std::vector<IcgnResult> RefineDisplacements(const float *ref, int nx, int ny, in
 		res[i].zncc = r[i].zncc;
 		res[i].last_step = r[i].last_step;
 		res[i].iterations = r[i].iterations;
+		res[i].status = r[i].status;
+		res[i].seconds = sec;
+	}
+	return res;
+}
+
+std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const StrainOptions &opts, double zncc_min,
+                                         bool accept_unconverged) {
+	const size_t m = points.size();
+	std::vector<StrainResult> res(m);
+	std::vector<int> q;
+	if (!int_triples("ComputeStrains", "point", points, q)) return res;
+	if (disp.size() != m) {
+		fprintf(stderr, "[3dsift_amd] ComputeStrains: %zu displacements for %zu points\n", disp.size(), m);
+		return res;
+	}
+	std::vector<sift3d_icgn_result> ic(m ? m : 1);
+	memset(ic.data(), 0, sizeof(sift3d_icgn_result) * ic.size());
+	for (size_t i = 0; i < m; i++) {
+		memcpy(ic[i].p, disp[i].p, sizeof(ic[i].p));
+		ic[i].zncc = disp[i].zncc;
+		ic[i].status = disp[i].status;
+	}
+	std::vector<double> u(3 * (m ? m : 1));
+	std::vector<unsigned char> valid(m ? m : 1);
+	sift3d_strain_options o;
+	sift3d_default_strain_options(&o);
+	o.radius = opts.radius;
+	o.min_neighbours = opts.min_neighbours;
+	o.measure = opts.measure;
+	std::vector<sift3d_strain_result> r(m ? m : 1);
+	double sec = 0;
+	int rc = sift3d_strain_input_from_icgn(ic.data(), (int)m, zncc_min, accept_unconverged ? 1 : 0, u.data(), valid.data());
+	if (rc == SIFT3D_OK) rc = sift3d_strain(q.data(), u.data(), valid.data(), (int)m, &o, 0, GetDevice(), r.data(), &sec);
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] ComputeStrains: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return res;
+	}
+	for (size_t i = 0; i < m; i++) {
+		memcpy(res[i].disp, r[i].disp, sizeof(res[i].disp));
+		memcpy(res[i].G, r[i].G, sizeof(res[i].G));
+		memcpy(res[i].E, r[i].E, sizeof(res[i].E));
+		memcpy(res[i].principal, r[i].principal, sizeof(res[i].principal));
+		res[i].equivalent = r[i].equivalent;
+		res[i].rms = r[i].rms;
+		res[i].neighbours = r[i].neighbours;
 		res[i].status = r[i].status;
 		res[i].seconds = sec;
 	}

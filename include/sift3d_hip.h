@@ -611,6 +611,74 @@ int sift3d_zncc_search(const float *ref, int rnx, int rny, int rnz, const float 
  * SIFT3D_ERR_ARG: m < 0, or a NULL pointer with m > 0. */
 int sift3d_icgn_init_from_search(const sift3d_search_result *res, int m, int only_missing, double *init12);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Strain fields from the refined displacements (no reference counterpart: the pointwise least-squares window of DIC / DVC codes).
+ * A plane is fitted to the displacements of the POIs around each POI and the strain is formed from the fitted gradient.
+ * Numerical contract (a tolerance contract like IC-GN's and the search's, not bit for bit; tests/strain_ref.py restates it in NumPy
+ * fp64):
+ *   Inputs: points3, m integer voxels (x, y, z) -- the array given to sift3d_icgn; disp3, m rows (u, v, w) in fp64; valid, m bytes
+ *     (NULL: every POI is valid).  A POI contributes as a neighbour only if its byte is non-zero, its three displacements are finite
+ *     and every coordinate has magnitude <= 2^24.  Duplicate points are allowed and each one counts.
+ *   Neighbours of POI i: the contributing POIs j with |x_j - x_i| <= radius, |y_j - y_i| <= radius and |z_j - z_i| <= radius, in integer
+ *     arithmetic: membership is exact.  POI i is its own neighbour if it contributes.  A POI that does not contribute still gets a
+ *     result from its neighbours (this fills holes), except that a POI with a coordinate of magnitude above 2^24 gets status 2, no fit.
+ *   Fit: d_j = q_j - q_i, n the neighbour count, u0 the displacement of the neighbour with the lowest index; every sum of
+ *     displacements is formed on u - u0, so a constant field gives G = 0, E = 0, rms = 0 and disp = the constant, exactly.
+ *     S1 = sum d, S2 = sum d d^T (sums of integers: exact), U_c = sum (u_c - u0_c), P_ca = sum (u_c - u0_c) d_a, all fp64.
+ *     C_ab = S2_ab - S1_a S1_b / n;  B_ca = P_ca - S1_a U_c / n;  C = L L^T (3 x 3 Cholesky);  row c of G = C^-1 B_c;
+ *     disp_c = u0_c + U_c / n - G_c . S1 / n;
+ *     rms = sqrt(sum_j sum_c (u_c(j) - disp_c - G_c . d_j)^2 / (3 n)), from a second pass over the neighbours (not from squared sums).
+ *   Strain: measure 0 Green-Lagrange E = (G + G^T + G^T G) / 2; measure 1 infinitesimal E = (G + G^T) / 2.  principal: the eigenvalues
+ *     of E, descending (cyclic Jacobi, fp64).  equivalent = sqrt(2/3 dev(E) : dev(E)), the shear terms counted twice.
+ *   Status per POI (results of a successful call, not errors), checked in this order:
+ *     2 a coordinate out of range (neighbours 0);  1 n < min_neighbours;  4 degenerate window: a Cholesky pivot (c00, c11 - l10^2,
+ *     c22 - l20^2 - l21^2) is <= 1e-9 x the largest diagonal entry of C, or NaN -- coplanar and collinear neighbours land here;
+ *     0 otherwise.  A non-zero status zeroes every double and reports n.
+ *   Determinism: no float atomics; the neighbours are visited in an order the input alone fixes (cells of a uniform grid, a cell's
+ *     POIs in ascending index) and every fp64 sum is reduced in a fixed order: two calls on the same input return the same bytes.
+ * SIFT3D_ERR_ARG (checked before any device call): m < 0, radius outside 1..4096, min_neighbours outside 4..1048576, measure outside
+ * 0..1, a non-zero reserved word, NULL out, NULL points3 or disp3 with m > 0; m = 0 succeeds.  SIFT3D_ERR_NO_DEVICE after that check
+ * when no GPU is visible: there is no CPU fallback.  o may be NULL (defaults).  on_device != 0: points3, disp3 and valid are device
+ * pointers on `device`, ordered behind the legacy default stream; out is host memory, filled by one copy at the end.  *seconds (may
+ * be NULL): device time of the call (HIP events; the uploads of host inputs excluded).
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct sift3d_strain_options {
+	int radius;            /* window half width in voxels (Chebyshev), 1..4096, default 16 */
+	int min_neighbours;    /* 4..1048576, default 10 */
+	int measure;           /* 0 Green-Lagrange (default), 1 infinitesimal */
+	int reserved[5];       /* must be 0 */
+} sift3d_strain_options;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_strain_options) == 32, "sift3d_strain_options must be 32 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_strain_options, min_neighbours) == 4 && offsetof(sift3d_strain_options, measure) == 8 &&
+                     offsetof(sift3d_strain_options, reserved) == 12, "sift3d_strain_options field offsets");
+
+typedef struct sift3d_strain_result {
+	double disp[3];        /* fitted displacement at the POI (the plane's constant term) */
+	double G[9];           /* fitted displacement gradient, row-major: rows u v w, columns x y z */
+	double E[6];           /* xx yy zz xy yz zx of the chosen measure */
+	double principal[3];   /* eigenvalues of E, descending */
+	double equivalent;     /* sqrt(2/3 dev(E):dev(E)) */
+	double rms;            /* residual of the fit */
+	int neighbours;        /* n */
+	int status;            /* the table above */
+} sift3d_strain_result;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_strain_result) == 192, "sift3d_strain_result must be 192 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_strain_result, G) == 24 && offsetof(sift3d_strain_result, E) == 96 &&
+                     offsetof(sift3d_strain_result, principal) == 144 && offsetof(sift3d_strain_result, equivalent) == 168 &&
+                     offsetof(sift3d_strain_result, rms) == 176 && offsetof(sift3d_strain_result, neighbours) == 184 &&
+                     offsetof(sift3d_strain_result, status) == 188, "sift3d_strain_result field offsets");
+
+/* the defaults above; needs no GPU */
+void sift3d_default_strain_options(sift3d_strain_options *o);
+/* host only, no GPU: row i of disp3 = (p[0], p[4], p[8]) of res[i]; valid[i] = 1 iff (status is 0, or status is 1 and
+ * accept_unconverged != 0), zncc >= zncc_min and the three values are finite.  SIFT3D_ERR_ARG: m < 0, a non-finite zncc_min, or a
+ * NULL pointer with m > 0. */
+int sift3d_strain_input_from_icgn(const sift3d_icgn_result *res, int m, double zncc_min, int accept_unconverged, double *disp3,
+                                  unsigned char *valid);
+/* m POIs (x, y, z int triples), their displacements (m * 3) and validity bytes (m, or NULL); out: m records */
+int sift3d_strain(const int *points3, const double *disp3, const unsigned char *valid, int m, const sift3d_strain_options *o, int on_device,
+                  int device, sift3d_strain_result *out, double *seconds);
+
 /* Test hooks, rare-path counters and the unit-level debug entry points live in include/sift3d_hip_test.h: this header is the
  * product boundary only. */
 const char *sift3d_error_string(int code);
