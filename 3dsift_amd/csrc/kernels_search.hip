@@ -2,7 +2,8 @@
 // No reference counterpart.  One workgroup of 256 threads per point of interest (POI); a launch has at most kMaxGroups workgroups and
 // each walks its POIs in turn, so the score table (one double per candidate, needed for zncc_second) is a scratch per workgroup.
 //   checks     status 2, then Rm and dR over the subset (fp64, two passes over R), status 4, then the admissible range of e per axis in
-//              64-bit arithmetic (status 3 when it is empty on an axis) and Tc, the voxel of T nearest to q + g
+//              64-bit arithmetic (status 3 when it is empty on an axis) and Tc, the level the sums are centred on: the voxel nearest
+//              to the mean of T over the subset at q + g clamped into T (fp64, two passes over it), so that no one voxel sets it
 //   chunks     the candidates are taken in chunks of `ec` planes of ez (at most kThreads * kK candidates); slot f = tid + kThreads k of a
 //              chunk is candidate (ezl, ey, ex) = (f / E^2, f / E % E, f % E): consecutive lanes own candidates consecutive in ex, so a
 //              wave reads consecutive LDS words of T and one word of R (a broadcast).  A thread owns kK candidates and their 3 sums
@@ -134,15 +135,52 @@ __global__ __launch_bounds__(kThreads) void k_zncc_search(IcgnVol R, IcgnVol T, 
 			if (tid == 0) write_result(o, g[0], g[1], g[2], 3, 0.0, -2.0, 0);
 			continue;
 		}
+		// Tc: over the subset of T at q + g clamped into T (the admissible candidate nearest to e = 0), the finite voxel nearest to the
+		// fp64 mean of the finite voxels, the lowest index among equals; 0 when no voxel is finite
 		float tc;
 		{
 			long long c[3];
 #pragma unroll
 			for (int ax = 0; ax < 3; ax++) {
 				c[ax] = (long long)q[ax] + (long long)g[ax];
-				c[ax] = c[ax] < 0 ? 0 : (c[ax] > tn[ax] - 1 ? tn[ax] - 1 : c[ax]);
+				c[ax] = c[ax] < r ? r : (c[ax] > tn[ax] - 1 - r ? tn[ax] - 1 - r : c[ax]);  // tn >= D: a candidate is admissible
 			}
-			tc = T.d[((size_t)c[2] * T.ny + (size_t)c[1]) * T.nx + (size_t)c[0]];
+			const float *Tq = T.d + (((size_t)(c[2] - r) * T.ny + (size_t)(c[1] - r)) * T.nx + (size_t)(c[0] - r));
+			const size_t tsy = (size_t)T.nx, tsz = (size_t)T.nx * T.ny;
+			a = 0.0;
+			b = 0.0;
+			for (int i = tid; i < N; i += kThreads) {
+				const int dz = i / DD, rem = i - dz * DD, dy = rem / D, dx = rem - dy * D;
+				const float v = Tq[dz * tsz + dy * tsy + dx];
+				if (isfinite(v)) { a += (double)v; b += 1.0; }
+			}
+			block_sum2(a, b, red);
+			const double tmean = a / b;
+			double nd = INFINITY;
+			int ni = 0x7fffffff;
+			for (int i = tid; i < N; i += kThreads) {
+				const int dz = i / DD, rem = i - dz * DD, dy = rem / D, dx = rem - dy * D;
+				const float v = Tq[dz * tsz + dy * tsy + dx];
+				const double dv = fabs((double)v - tmean);
+				if (isfinite(v) && dv < nd) { nd = dv; ni = i; }
+			}
+			for (int sft = 32; sft > 0; sft >>= 1) {
+				const double od = __shfl_xor(nd, sft);
+				const int oi = __shfl_xor(ni, sft);
+				if (od < nd || (od == nd && oi < ni)) { nd = od; ni = oi; }
+			}
+			if (lane == 0) { red[wv][0] = nd; redi[wv][0] = ni; }
+			__syncthreads();
+			nd = red[0][0];
+			ni = redi[0][0];
+			for (int w = 1; w < kWaves; w++)
+				if (red[w][0] < nd || (red[w][0] == nd && redi[w][0] < ni)) { nd = red[w][0]; ni = redi[w][0]; }
+			__syncthreads();
+			tc = 0.f;
+			if (ni != 0x7fffffff) {
+				const int dz = ni / DD, rem = ni - dz * DD, dy = rem / D, dx = rem - dy * D;
+				tc = Tq[dz * tsz + dy * tsy + dx];
+			}
 		}
 		const double sh = (double)tc - (double)rmf, Nd = (double)N;
 		double best = kUnscored;

@@ -561,17 +561,23 @@ int sift3d_icgn(const float *ref, int rnx, int rny, int rnz, const float *tar, i
  *     is made in 64-bit arithmetic: no int overflows, whatever g holds.
  *   Score of an admissible candidate: zncc(c) = sum (R - Rm)(T(x + c) - Tm) / (dR dT), Tm and dT = sqrt(sum (T - Tm)^2) the mean
  *     and the deviation of T over the shifted subset.  A candidate with dT = 0 to rounding -- IC-GN's rule, dT^2 <= 1e-10 sum (T - Rm)^2
- *     -- is skipped, not scored.  A non-finite sum skips the candidate too.
+ *     -- is skipped, not scored.  A non-finite sum skips the candidate too; the sums meant are the float32 and fp64 sums of the
+ *     Precision paragraph, so a candidate whose float32 products overflow (voxels of T - Tc beyond about 1.8e19) is skipped, and a
+ *     NaN or Inf voxel of T silences exactly the candidates whose subset holds it.
  *   Result: the scored candidate with the highest score; among candidates whose scores are equal in the kernel's own arithmetic the
  *     lowest index (ez, ey, ex), ex fastest, wins.  zncc_second: the best score among the scored candidates at Chebyshev distance
  *     > 1 from d (-2.0: none).  candidates: how many were scored.
  *   Status per POI (results of a successful call, not errors), checked in this order:
  *     2 subset outside R;  4 dR = 0 (or not finite);  3 no candidate scored -- these return d = g, zncc 0, zncc_second -2.0, candidates 0;
  *     0 otherwise: the best scored candidate.  A POI with status 2 reads no voxel of R; no voxel outside R or T is ever read.
- *   Precision: the sums of a candidate are formed on T - Tc, Tc = the voxel of T nearest to q + g (ZNCC does not change when T is
- *     shifted): a T constant over the search region has dT = 0 exactly and no candidate is scored.  Products and the sums along x are
- *     fp32 ((R - (float)Rm) and (T - Tc) rounded once), the sums over rows, planes and slabs fp64, reduced in a fixed order with no
- *     float atomics: two calls return the same bytes, and a POI's result does not depend on the other POIs of the call.
+ *   Precision: the sums of a candidate are formed on T - Tc (ZNCC does not change when T is shifted).  Tc is a voxel of T: over the
+ *     subset of T at q + g clamped to [r, n - 1 - r] on every axis (the subset of the admissible candidate nearest to e = 0), the
+ *     finite voxel nearest to the fp64 mean of the finite voxels, the lowest index (dz, dy, dx) among equals, and 0 when no voxel is
+ *     finite.  It lies within one standard deviation of that subset's mean, so no single voxel -- a dead or hot detector voxel at
+ *     q + g -- sets the level, T - Tc is exact on integer-valued data, and a T constant over the search region has dT = 0 exactly
+ *     and no candidate is scored.  A NaN or Inf at q + g therefore only skips the candidates that see it.  Products and the sums
+ *     along x are fp32 ((R - (float)Rm) and (T - Tc) rounded once), the sums over rows, planes and slabs fp64, reduced in a fixed
+ *     order with no float atomics: two calls return the same bytes, and a POI's result does not depend on the other POIs of the call.
  * SIFT3D_ERR_ARG (checked before any device call): m < 0, a dimension < 1, subset_radius outside 2..16, search_radius outside 1..16,
  * a non-zero reserved word, NULL ref / tar / out, NULL points3 with m > 0; m = 0 succeeds.  SIFT3D_ERR_NO_DEVICE after that check when
  * no GPU is visible: there is no CPU fallback.  o may be NULL (defaults).  on_device != 0: ref, tar, points3 and guess3 are device

@@ -4,7 +4,7 @@ and T, flat subsets and targets, reproducibility and independence of the POIs, a
 
 The zncc bar: e = the largest |zncc(float32 restatement) - zncc(fp64 restatement)| over every scored candidate of the parity inputs,
 computed on the CPU (zncc_search_ref.parity_error; tests/test_search_cpu.py prints it), and the bar is max(4 e, 1e-6).  Measured:
-e = 1.53e-06, bar = 6.1e-06.  The parity inputs' best score beats every other by at least 0.05 (tests/test_search_cpu.py checks it),
+e = 2.50e-07, bar = 1.0e-06.  The parity inputs' best score beats every other by at least 0.05 (tests/test_search_cpu.py checks it),
 which is why d is compared exactly and no POI is excluded."""
 import importlib
 

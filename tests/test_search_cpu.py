@@ -1,7 +1,8 @@
 """CPU tests of the ZNCC integer search's boundary (sift3d_zncc_search, sift3d_icgn_init_from_search, include/sift3d_hip.h): the
 header compiles as C and C++ with its layout guards, the library exports the entry points, the defaults need no GPU, bad arguments
 are refused before any device call, the init from search results is exact, the CPU restatement (tests/zncc_search_ref.py) recovers
-known shifts and gives every status, the inputs of the GPU parity test have the margin that lets it compare d exactly, and the C++
+known shifts and gives every status, the inputs of the GPU parity test and of tests/test_gpu_search_plans.py (every launch plan, the long call, the
+invariance pair, the voxel classes) have the margin that lets them compare d exactly and a float32 error e under the cap, and the C++
 shell's SearchDisplacements and RefineDisplacements with a fallback link."""
 import ctypes as C
 import importlib
@@ -216,6 +217,143 @@ def test_parity_bar():
     print(f"e = {e:.3e}, bar = {ref.parity_bar():.3e}")
     assert 0.0 < e < 1e-4  # a float32 evaluation of a score in [-1, 1] over at most 33^3 voxels
     assert ref.parity_bar() >= 1e-6
+
+
+def margin(tab):
+    v = np.sort(tab[np.isfinite(tab)])[::-1]
+    return v[0] - v[1] if len(v) > 1 else 1.0
+
+
+def check_margins(a, b, truth):
+    """the best score beats every other by at least 0.05 in fp64 (a) and in float32 (b), and both choose the truth"""
+    ok = a["status"] == 0
+    assert np.array_equal(a["status"], b["status"]) and np.array_equal(a["d"], b["d"]) and np.array_equal(a["candidates"], b["candidates"])
+    assert (a["d"][ok] == truth).all(), a["d"]
+    for res in (a, b):
+        for i in np.flatnonzero(ok):
+            assert margin(res["tables"][i]) >= 0.05, (i, margin(res["tables"][i]))
+
+
+def test_search_plan_regimes():
+    """the restated search_plan enters the regimes that tests/test_gpu_search_plans.py is there for"""
+    plan = {p: ref.search_plan(*p) for p in ref.PAIRS}
+    assert len(plan) == 240
+    assert [plan[p] for p in ((2, 1), (4, 2), (5, 3), (5, 7), (8, 8), (16, 16))] == [(3, 5), (5, 9), (7, 11), (5, 11), (4, 9), (1, 3)]
+    assert sorted(p for p, (ec, zs) in plan.items() if zs == 1) == [(13, 5), (14, 5), (15, 4), (15, 5), (15, 6), (16, 4), (16, 5), (16, 6)]
+    free = lambda s: min(max(1280 // (2 * s + 1) ** 2, 1), 2 * s + 1)  # noqa: E731  ec before the LDS bound lowers it
+    assert sorted(p for p, (ec, zs) in plan.items() if ec < free(p[1])) == [(15, 5), (16, 4), (16, 5)]
+    full = [p for p, (ec, zs) in plan.items() if ec == 2 * p[1] + 1 and (2 * p[0] + 1) % zs]
+    assert len(full) == 28 and (8, 3) in full and (16, 2) in full
+    assert sorted(p for p, (ec, zs) in plan.items() if ec == 1 and zs == 2 * p[0] + 1) == [(r, s) for r in (2, 3, 4) for s in (13, 14, 15, 16)]
+    assert sum(1 for (r, s), (ec, zs) in plan.items() if (2 * s + 1) % ec and (2 * r + 1) % zs) == 63
+    for (r, s), (ec, zs) in plan.items():
+        D, E = 2 * r + 1, 2 * s + 1
+        assert 1 <= ec <= E and 1 <= zs <= D and (ec * E * E <= 1280 or ec == 1)
+        assert (zs + ec - 1) * (D + 2 * s) ** 2 + zs * D * D <= ref.LDS_FLOATS
+
+
+@pytest.mark.parametrize("r", range(2, 17))
+def test_plan_inputs_have_margin(r):
+    """every input of test_every_plan: the geometry of its three POIs and the margin that lets the GPU test compare d exactly"""
+    for s in range(1, 17):
+        R, T, q = ref.plan_case(r, s)
+        assert R.shape == T.shape == ref.PLAN_SHAPE and len(set(R.shape)) == 3
+        E, (ec, _) = 2 * s + 1, ref.search_plan(r, s)
+        rng = [[ref.admissible(q[i][ax], 0, r, s, n) for ax, n in enumerate(R.shape[::-1])] for i in range(3)]
+        assert all(lo == 0 and hi == E - 1 for lo, hi in rng[0])
+        (xl, xh), _, (zl, zh) = rng[1]
+        assert zl > 0 and zh == E - 1 and xl == 0 and xh < E - 1 and (ec == 1 or (zh - zl + 1) % ec)
+        _, (yl, yh), (zl, zh) = rng[2]
+        assert zl == 0 and zh < E - 1 and yl > 0 and yh == E - 1
+        a, b = ref.plan_reference(r, s), ref.plan_reference(r, s, True)
+        assert (a["status"] == 0).all() and a["candidates"][0] == E ** 3 and (a["candidates"][1:] < E ** 3).all()
+        check_margins(a, b, ref.PLAN_D)
+
+
+def test_long_inputs_have_margin():
+    R, T, q, g, kinds = ref.long_case()
+    M = ref.MAX_GROUPS
+    assert len(q) == 2 * M + 37 and all(kinds[i] != kinds[i + M] for i in range(M + 37))
+    assert any(kinds[j] == "full" and kinds[j + M] == "clipped" for j in range(M))
+    a, b = ref.long_reference(), ref.long_reference(True)
+    want = {"full": 0, "clipped": 0, "st2": 2, "st4": 4, "st3": 3}
+    assert [int(v) for v in a["status"]] == [want[k] for k in kinds]
+    cand = a["candidates"]
+    assert all(cand[i] == 125 for i, k in enumerate(kinds) if k == "full") and all(27 <= cand[i] <= 80 for i, k in enumerate(kinds) if k == "clipped")
+    check_margins(a, b, ref.LONG_D)
+
+
+def test_plan_bar():
+    e = ref.plan_error()
+    print(f"plans and long call: e = {e:.3e}, bar = {ref.plan_bar():.3e}")
+    assert 0.0 < e < 1e-4
+
+
+def test_invariance_inputs_have_margin():
+    R, T, q = ref.invariance_case()
+    assert np.array_equal(R, np.round(R)) and np.array_equal(T, np.round(T)) and 0 < min(R.min(), T.min()) and max(R.max(), T.max()) < 2 ** 12
+    for off in (False, True):
+        a, b = ref.invariance_reference(off), ref.invariance_reference(off, True)
+        assert (a["status"] == 0).all() and len(set(a["candidates"])) > 2
+        check_margins(a, b, ref.INV_D)
+    e = ref.invariance_error()
+    print(f"invariance pair: e = {e:.3e}, bar = {ref.invariance_bar():.3e}")
+    assert 0.0 < e < 1e-4
+    base = ref.invariance_reference()
+    for add in ref.INV_T_OFFSETS:  # the restatement itself: an integer added to T changes no scored set and no d
+        got = ref.search(R, T + np.float32(add), q, subset_radius=ref.INV_R, search_radius=ref.INV_S)
+        assert np.array_equal(got["candidates"], base["candidates"]) and np.array_equal(got["d"], base["d"])
+        assert np.abs(got["zncc"] - base["zncc"]).max() < 1e-12
+
+
+@pytest.mark.parametrize("name", ref.CLASSES)
+def test_class_inputs(name):
+    """the voxel classes of tests/test_gpu_search_plans.py: what each is named for, e under the cap, and the margins"""
+    R, T, q = ref.class_case(name)
+    r, s = ref.CLASS_R, ref.CLASS_S
+    a, b = ref.class_reference(name), ref.class_reference(name, True)
+    e, same = ref.class_error(name)
+    print(f"class {name}: e = {e:.3e}, bar = {ref.class_bar(name):.3e}")
+    assert e < 1e-4
+    full = np.array([(2 * s + 1) ** 3] * 6)
+    if name == "huge":
+        assert (a["status"] == 0).all() and (b["status"] == 3).all() and not b["candidates"].any()
+        return
+    assert same
+    if name in ("nan_subset", "inf_subset"):
+        assert (a["status"] == 4).all() and (b["status"] == 4).all()
+        return
+    assert (a["status"] == 0).all()
+    check_margins(a, b, ref.CLASS_D)
+    assert np.abs(b["zncc"]).max() <= 1.0 + ref.class_bar(name) and np.abs(b["zncc_second"]).max() <= 1.0 + ref.class_bar(name)
+    if name in ("nan_corner", "inf_corner"):
+        assert np.array_equal(a["candidates"][:6], full - 1) and all(np.isnan(t[0, 0, 0]) for t in a["tables"][:6])
+    elif name == "nan_tc":  # the candidates whose subset holds q + g are skipped, the others scored
+        assert np.array_equal(a["candidates"][:6], full - (2 * r + 1) ** 3)
+        assert all(np.isnan(t[s - r:s + r + 1, s - r:s + r + 1, s - r:s + r + 1]).all() for t in a["tables"])
+    else:
+        assert np.array_equal(a["candidates"][:6], full)
+    assert a["candidates"][6] < full[0]  # the last POI's window hangs over T's high x face
+    if name.startswith("outlier"):
+        v = 0.0 if name.startswith("outlier0") else 65535.0
+        assert all(T[z, y, x] == v for x, y, z in q) and (T == v).sum() == len(q) and abs(np.median(T) - 30000) < 300
+        assert max(abs(c) for c in ref.CLASS_D) > r  # the subset of the best candidate does not hold the outlier
+        for i in range(len(q)):
+            for j in range(len(q)):
+                assert i == j or np.abs(q[i] - q[j]).max() > r + s  # no POI's outlier lies in another's window
+
+
+def test_centre_resists_one_voxel():
+    """the level the sums are centred on: a voxel of T within the subset's spread, whatever the voxel at q + g holds"""
+    R, T, q = ref.class_case("outlier0")
+    for x, y, z in q:
+        tc = ref.centre(T, (x, y, z), ref.CLASS_R)
+        assert 29900 < tc < 30400 and (T == tc).any()
+    flat = np.full((9, 9, 9), 3e7, np.float32)
+    assert ref.centre(flat, (4, 4, 4), 3) == np.float32(3e7) and ref.centre(flat, (-50, 100, 4), 3) == np.float32(3e7)
+    flat[4, 4, 4] = np.nan
+    assert ref.centre(flat, (4, 4, 4), 3) == np.float32(3e7)
+    assert ref.centre(np.full((9, 9, 9), np.nan, np.float32), (4, 4, 4), 3) == 0.0
 
 
 SHELL = r"""
