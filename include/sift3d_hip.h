@@ -429,7 +429,11 @@ int sift3d_get_refined(sift3d_handle h, sift3d_refined *out);
  *     every accepted round.  Sums run in a fixed order of the implementation: two calls give the same bits (checked to tolerance).
  *   Local neighbours of q: fp32 d2_i = (dx dx + dy dy) + dz dz, dx = r_x - q_x; the candidates are the k smallest (d2_i, i) in
  *     lexicographic order among the pairs with d2_i <= radius * radius (fp32; radius <= 0: no limit; a NaN d2_i never qualifies),
- *     listed in that order; 4 <= k <= 64; fewer than 4 candidates: status 1.
+ *     listed in that order; 4 <= k <= 64; fewer than 4 candidates: status 1.  A d2_i that overflows to +inf qualifies when there is no
+ *     limit (behind every finite one, in index order) and never under a finite radius * radius.
+ *   Non-finite values: the expressions above are IEEE operations, so a NaN or an infinity in a pair goes where they carry it (a NaN
+ *     in a sampled reference position: degenerate; in a target: a NaN transform that counts no inlier; min_det = 0 accepts det = 0 and
+ *     divides by it).  Where A or hyp holds a NaN its position is part of the contract, its sign and payload are unspecified.
  * Results: A = the final transform; hyp = the best hypothesis's minimal-sample transform (bit exact); inliers / rms (sqrt of the mean
  * d2, fp32) over the final inlier set, which the mask holds.  Status 1 / 2 leave A, hyp zero, best_hypothesis -1 and the mask empty:
  * they are results of a successful call, not errors.  SIFT3D_ERR_ARG (checked before any device call): n < 0, m < 0, k outside

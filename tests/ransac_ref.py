@@ -43,24 +43,25 @@ def draws(seed, p, H, c):
     return idx
 
 
-def _inv3(M, min_det):
-    """cofactor inverse of (..., 3, 3); returns (inv, ok)"""
+def _inv3(M, min_det, with_det=False):
+    """cofactor inverse of (..., 3, 3); returns (inv, ok), with_det: (inv, ok, det)"""
     C = np.empty_like(M)
     for r in range(3):
         r1, r2 = [x for x in range(3) if x != r]
         for c in range(3):
             c1, c2 = [x for x in range(3) if x != c]
-            v = M[..., r1, c1] * M[..., r2, c2] - M[..., r1, c2] * M[..., r2, c1]
+            with np.errstate(invalid="ignore", over="ignore"):
+                v = M[..., r1, c1] * M[..., r2, c2] - M[..., r1, c2] * M[..., r2, c1]
             C[..., r, c] = -v if (r + c) & 1 else v
-    det = (M[..., 0, 0] * C[..., 0, 0] + M[..., 0, 1] * C[..., 0, 1]) + M[..., 0, 2] * C[..., 0, 2]
-    with np.errstate(invalid="ignore"):
+    with np.errstate(invalid="ignore", over="ignore"):
+        det = (M[..., 0, 0] * C[..., 0, 0] + M[..., 0, 1] * C[..., 0, 1]) + M[..., 0, 2] * C[..., 0, 2]
         ok = np.abs(det) >= min_det
     inv = np.empty_like(M)
     with np.errstate(divide="ignore", invalid="ignore"):
         for i in range(3):
             for j in range(3):
                 inv[..., i, j] = C[..., j, i] / det
-    return inv, ok
+    return (inv, ok, det) if with_det else (inv, ok)
 
 
 def _affine(N, inv, p0, t0):
@@ -77,9 +78,10 @@ def minimal_solve(P, T, min_det):
     """P, T: (H, 4, 3) float64 -> (A (H, 12), ok (H,))"""
     M = np.empty(P.shape[:-2] + (3, 3))
     N = np.empty_like(M)
-    for k in range(1, 4):
-        M[..., :, k - 1] = P[..., k, :] - P[..., 0, :]
-        N[..., :, k - 1] = T[..., k, :] - T[..., 0, :]
+    with np.errstate(invalid="ignore"):
+        for k in range(1, 4):
+            M[..., :, k - 1] = P[..., k, :] - P[..., 0, :]
+            N[..., :, k - 1] = T[..., k, :] - T[..., 0, :]
     inv, ok = _inv3(M, float(min_det))
     with np.errstate(invalid="ignore", over="ignore"):
         A = _affine(N, inv, P[..., 0, :], T[..., 0, :])
@@ -99,8 +101,28 @@ def tau2_of(tau):
     return float(np.float32(tau)) * float(np.float32(tau))
 
 
-def fit(pairs, p=0, iterations=4096, inlier_thresh=3.0, seed=1, refine=1, min_det=1.0, chunk=1 << 22):
-    """the fit of one problem whose candidates are the rows of pairs (c, 6) float32, in order"""
+def hypotheses(pairs, p=0, iterations=4096, inlier_thresh=3.0, seed=1, min_det=1.0, chunk=1 << 22):
+    """every hypothesis of one problem (c >= 4 candidates): draws (H, 4), transforms (H, 12), counts (H,), -1 where degenerate"""
+    pairs = np.asarray(pairs, np.float32).reshape(-1, 6)
+    c = len(pairs)
+    r = pairs[:, :3].astype(np.float64)
+    t = pairs[:, 3:].astype(np.float64)
+    idx = draws(seed, p, iterations, c)
+    A, ok = minimal_solve(r[idx], t[idx], float(np.float32(min_det)))
+    tau2 = tau2_of(inlier_thresh)
+    counts = np.zeros(iterations, np.int64)
+    step = max(1, chunk // c)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for h0 in range(0, iterations, step):
+            counts[h0:h0 + step] = (resid2(A[h0:h0 + step], r, t) <= tau2).sum(1)
+    counts[~ok] = -1
+    return idx, A, counts
+
+
+def fit(pairs, p=0, iterations=4096, inlier_thresh=3.0, seed=1, refine=1, min_det=1.0, chunk=1 << 22, trace=None):
+    """the fit of one problem whose candidates are the rows of pairs (c, 6) float32, in order; trace (a list) receives one
+    dict(round, d2, det) per scoring of the refit: the candidates' d2 under the round's transform and the det Cov that followed
+    (None where no covariance was formed)"""
     pairs = np.asarray(pairs, np.float32).reshape(-1, 6)
     c = len(pairs)
     out = dict(status=1, candidates=c, best_hypothesis=-1, best_count=0, inliers=0, hyp=np.zeros(12), A=np.zeros(12), mask=np.zeros(c, bool),
@@ -111,14 +133,7 @@ def fit(pairs, p=0, iterations=4096, inlier_thresh=3.0, seed=1, refine=1, min_de
     tau2 = tau2_of(inlier_thresh)
     r = pairs[:, :3].astype(np.float64)
     t = pairs[:, 3:].astype(np.float64)
-    idx = draws(seed, p, iterations, c)
-    A, ok = minimal_solve(r[idx], t[idx], md)
-    counts = np.zeros(iterations, np.int64)
-    step = max(1, chunk // c)
-    with np.errstate(invalid="ignore", over="ignore"):
-        for h0 in range(0, iterations, step):
-            counts[h0:h0 + step] = (resid2(A[h0:h0 + step], r, t) <= tau2).sum(1)
-    counts[~ok] = -1
+    idx, A, counts = hypotheses(pairs, p, iterations, inlier_thresh, seed, min_det, chunk)
     if counts.max() < 0:
         out["status"] = 2
         return out
@@ -131,12 +146,16 @@ def fit(pairs, p=0, iterations=4096, inlier_thresh=3.0, seed=1, refine=1, min_de
             d2 = resid2(cur, r, t)
         mask = d2 <= tau2
         cnt = int(mask.sum())
+        if trace is not None:
+            trace.append(dict(round=rnd, d2=d2, det=None))
         if rnd == refine or cnt < 4:
             break
         rb, tb = r[mask].mean(0), t[mask].mean(0)
         dr, dt = r[mask] - rb, t[mask] - tb
         Cov, S = dr.T @ dr, dt.T @ dr
-        inv, ok1 = _inv3(Cov, md)
+        inv, ok1, det = _inv3(Cov, md, with_det=True)
+        if trace is not None:
+            trace[-1]["det"] = float(det)
         if not ok1:
             out["status"] = 3
             break
@@ -145,18 +164,29 @@ def fit(pairs, p=0, iterations=4096, inlier_thresh=3.0, seed=1, refine=1, min_de
     return out
 
 
+def distances(pairs, q):
+    """fp32 d2_i of the contract (NaN and +inf included)"""
+    pairs = np.asarray(pairs, np.float32).reshape(-1, 6)
+    q = np.asarray(q, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        dx = pairs[:, 0] - q[0]
+        dy = pairs[:, 1] - q[1]
+        dz = pairs[:, 2] - q[2]
+        return (dx * dx + dy * dy) + dz * dz
+
+
+def radius2(radius):
+    return np.float32(radius) * np.float32(radius)
+
+
 def neighbours(pairs, q, k, radius=0.0):
     """candidate list of query q: the k smallest (d2, i), float32 d2, among the pairs within radius (radius <= 0: all)"""
     pairs = np.asarray(pairs, np.float32).reshape(-1, 6)
     q = np.asarray(q, np.float32)
-    dx = pairs[:, 0] - q[0]
-    dy = pairs[:, 1] - q[1]
-    dz = pairs[:, 2] - q[2]
-    d2 = (dx * dx + dy * dy) + dz * dz
+    d2 = distances(pairs, q)
     keep = ~np.isnan(d2)
     if radius > 0:
-        rr = np.float32(radius) * np.float32(radius)
-        keep &= d2 <= rr
+        keep &= d2 <= radius2(radius)
     i = np.nonzero(keep)[0]
     order = np.lexsort((i, d2[i]))
     return i[order[:k]]
