@@ -750,6 +750,7 @@ static int run_enqueue(sift3d_ctx *c, int upto, bool part_orient) {
 		// ---- Detect_KeyPoints (Src/cSIFT3D.cc:362-425) ----
 		if (upto >= 3) {
 			if (two && !early) { S3D_HIP(hipEventRecord(c->ev_det_fork, st)); S3D_HIP(hipStreamWaitEvent(sb, c->ev_det_fork, 0)); }
+			bool join2 = false;  // the octaves >= 2 ran on a stream of their own
 			if (two) {
 				// late r04: the masks of the octaves >= 2 (twelve launches of a few microseconds at 512^3) on a THIRD stream beside octave
 				// 1's: they used to queue behind octave 1's candidate pass (0.35 ms beside octave 0's masks) and ended the stage 0.13 ms
@@ -768,15 +769,22 @@ static int run_enqueue(sift3d_ctx *c, int upto, bool part_orient) {
 					launch_detect_mark(DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), c->p.peak_thresh, o + c->octave_base, c->det_o[(size_t)o], o == 1 ? sb : sc, lt, dop);
 				}
 				S3D_HIP(hipEventRecord(c->ev_det_join, sb));
-				if (sc != sb) { S3D_HIP(hipEventRecord(c->ev_det_join2, sc)); S3D_HIP(hipStreamWaitEvent(sb, c->ev_det_join2, 0)); S3D_HIP(hipEventRecord(c->ev_det_join, sb)); }
+				join2 = sc != sb;
+				if (join2) S3D_HIP(hipEventRecord(c->ev_det_join2, sc));  // (the main stream waits for both itself: one hop across queues each, not two in a row)
 			}
-			std::vector<DetectEmitItem> rest;  // two streams: the octaves behind the first one are emitted by one scan + one emit launch
+			// two streams: one scan + one emit launch for the octaves' ordered compaction -- r07: octave 0 included (it had a scan and an emit
+			// launch of its own in front of the others'); only a volume of more than eight octaves (k_emit_multi's table) keeps them apart
+			const bool all = two && c->noct <= 8;
+			std::vector<DetectEmitItem> rest;
 			for (int o = 0; o < c->noct; o++) {
 				const Level &C = c->dog[(size_t)o * c->nd + 1];
 				const DetectBufs &b = (two && o > 0) ? c->det_o[(size_t)o] : c->det;
 				if (!(two && o > 0) && !(early && o == 0)) launch_detect_mark(DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), c->p.peak_thresh, o + c->octave_base, b, st, lt, dop);
-				if (two && o == 1) S3D_HIP(hipStreamWaitEvent(st, c->ev_det_join, 0));
-				if (two && o > 0 && c->noct - 1 <= 8) rest.push_back(DetectEmitItem{&DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), o + c->octave_base, &b});
+				if (two && o == 1) {
+					S3D_HIP(hipStreamWaitEvent(st, c->ev_det_join, 0));
+					if (join2) S3D_HIP(hipStreamWaitEvent(st, c->ev_det_join2, 0));
+				}
+				if (two && (o > 0 || all) && c->noct - 1 <= 8) rest.push_back(DetectEmitItem{&DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), o + c->octave_base, &b});
 				else launch_detect_emit(DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), o + c->octave_base, b, c->d_ext, c->ext_cap, st);
 			}
 			if (!rest.empty()) launch_detect_emit_multi(rest.data(), (int)rest.size(), c->d_ext, c->ext_cap, c->d_total, st);

@@ -730,14 +730,19 @@ void launch_detect_mark(const DetectLevels &L, int nlevels, int nx, int ny, cons
 		// (next to a border, other half widths): one workgroup each
 		// (the wave form keeps its 23 piece offsets as 32-bit byte offsets from the block's first sample: 17 planes must span < 4 GB)
 		const bool wave_form = lazy_taps->hw == 8 && !hook(SIFT3D_HOOK_LAZY_GENERIC) && (size_t)nx * (size_t)ny * 17u * sizeof(float) < ((size_t)1 << 32);
+		// r07: the grids are sized to the octave -- at most one workgroup (k_lazy_wave: one wave) per workgroup of k_mark, i.e. per kRows rows
+		// of a keypoint level.  Both kernels stride over the parked list with gridDim (k_lazy_next compacts entry blockIdx + tid * gridDim),
+		// so the grid is a launch parameter; the octaves of 128^3 and above keep the full grids, and the 64^3 ... 8^3 octaves of a 512^3
+		// volume, which park a few dozen voxels or none, no longer launch 768 + 1536 workgroups that read the count and leave.
+		auto grid = [&](unsigned full, unsigned per_wg) { return dim3(std::max(1u, std::min(full, (nblocks + per_wg - 1) / per_wg))); };
 		if (wave_form)
-			hipLaunchKernelGGL(k_lazy_wave, dim3(256 * 3), dim3(64 * kLwWaves), 0, st, L, *lazy_taps, nx, ny, zr, nyb, b.prov, b.prov_count, b.prov_cap,
+			hipLaunchKernelGGL(k_lazy_wave, grid(256 * 3, kLwWaves), dim3(64 * kLwWaves), 0, st, L, *lazy_taps, nx, ny, zr, nyb, b.prov, b.prov_count, b.prov_cap,
 			                   b.masks, b.block_counts);
 		if (2 * lazy_taps->hw + 1 <= 17)
-			hipLaunchKernelGGL(k_lazy_next<17>, dim3(wave_form ? 1536 : 1024), dim3(256), 0, st, L, *lazy_taps, nx, ny, zr, nyb, b.prov, b.prov_count, b.prov_cap,
+			hipLaunchKernelGGL(k_lazy_next<17>, grid(wave_form ? 1536 : 1024, 1), dim3(256), 0, st, L, *lazy_taps, nx, ny, zr, nyb, b.prov, b.prov_count, b.prov_cap,
 			                   b.masks, b.block_counts, wave_form ? 1 : 0);
 		else
-			hipLaunchKernelGGL(k_lazy_next<25>, dim3(512), dim3(256), 0, st, L, *lazy_taps, nx, ny, zr, nyb, b.prov, b.prov_count, b.prov_cap,
+			hipLaunchKernelGGL(k_lazy_next<25>, grid(512, 1), dim3(256), 0, st, L, *lazy_taps, nx, ny, zr, nyb, b.prov, b.prov_count, b.prov_cap,
 			                   b.masks, b.block_counts, 0);
 	}
 }
