@@ -249,7 +249,10 @@ __global__ void __launch_bounds__(256, 2) k_scores_top4(const float *__restrict_
 #pragma unroll 4
 			for (int jj = 0; jj < ncol; jj++) {
 				const float sv = srow_p[jj];
-				if (sv > bs[TOPK - 1] || bj[TOPK - 1] < 0) topk_bubble(bs, bj, sv, cbase + jj);
+				// an empty last slot holds -FLT_MAX: every finite score passes, a NaN score never enters (like the mask of
+				// k_scores_topk2).  Admitted into an empty slot it froze the list -- nothing is > NaN -- and the later columns of
+				// this lane's half were lost without the guard noticing; the reference never chooses such a column either.
+				if (sv > bs[TOPK - 1]) topk_bubble(bs, bj, sv, cbase + jj);
 			}
 		}
 	}

@@ -155,7 +155,13 @@ int sift3d_describe_keypoint(const float *level, int nx, int ny, int nz, float u
  * on_device != 0: the four input pointers are device pointers on `device`.
  * Outputs (host, any may be NULL): gIdx/sIdx/gDist/sDist sized n = getGlodenIdx / getSilverIdx /
  * getGlodenDistSquare / getSilverDistSquare (Include/cMatcher.h:69-73); pairs6: up to n rows of
- * (ref rx,ry,rz, tar rx,ry,rz) in ascending ref index (toCvec, Src/cMatcher.cc:99-112). */
+ * (ref rx,ry,rz, tar rx,ry,rz) in ascending ref index (toCvec, Src/cMatcher.cc:99-112).
+ * Descriptor values: any finite floats are accepted (signed, all-zero rows, exact duplicates, any scaling), the result is the
+ * reference's bit for bit.  Its scan is a strict '>' from FLT_MIN (Src/cMatcher.cc:52-77), so a column whose dot product is
+ * <= FLT_MIN or NaN is never chosen, and a row with no other column returns index -1 and d = 2 - 2 * FLT_MIN (2.0f) in that place.
+ * +-inf / NaN components follow the reference's arithmetic (fp32 product, fp64 sum: inf * 0 and inf - inf are NaN; a +inf score wins,
+ * d = -inf, ties keep the lower column).  Outside the contract: magnitudes at which an fp32 product a[k] * b[k] or the fp32 squared
+ * norm of a row overflows. */
 int sift3d_match(const float *ref_desc, const float *ref_xyz, int n, const float *tar_desc,
                  const float *tar_xyz, int m, double thresHold, int mode, int on_device, int device,
                  int *gIdx, int *sIdx, float *gDist, float *sDist, float *pairs6, int *npairs,

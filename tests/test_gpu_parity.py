@@ -672,8 +672,10 @@ def test_free_functions_downsample_and_sub(capi, orc):
 def test_matcher_awkward_sizes(capi, orc):
     """The score kernel deals HALF tiles (128 rows x 64 columns) to a fixed number of workgroups and the merge kernel recomputes which
     slots were written (r03): sizes around the tile edges -- one row, one column, 63 / 65 / 127 / 129 columns, more row blocks than
-    column tiles and the other way round, a set large enough that a workgroup's share crosses row blocks -- all outputs against the
-    oracle's matcher (Src/cMatcher.cc:146-228)."""
+    column tiles and the other way round, a set of several row blocks and column tiles -- all outputs against the oracle's matcher
+    (Src/cMatcher.cc:146-228).  No size here makes a workgroup's share cross a row block: up to 51 row blocks the shares end on every
+    row-block border.  tests/test_gpu_match_edges.py has the sizes that cross (tests/test_match_cpu.py proves which regime each
+    size reaches)."""
     rng = np.random.Generator(np.random.PCG64(23))
 
     def descs(n):
