@@ -369,37 +369,100 @@ def _options_dict(o):
             "edge_ratio": o.edge_ratio}
 
 
-def default_ransac_options():
-    """sift3d_default_ransac_options as a dict (needs no GPU)"""
-    o = RansacOptions()
-    lib().sift3d_default_ransac_options(C.byref(o))
-    return {"iterations": o.iterations, "inlier_thresh": o.inlier_thresh, "seed": o.seed, "refine": o.refine, "min_det": o.min_det}
-
-
-def _ransac_options(opts):
-    o = RansacOptions()
-    lib().sift3d_default_ransac_options(C.byref(o))
+def _options(cls, default_fn_name, names, what, opts):
+    """the options struct `cls` filled with the library's defaults (needs no GPU) and then with opts, whose keys must be in names"""
+    o = cls()
+    getattr(lib(), default_fn_name)(C.byref(o))
     for k, v in opts.items():
-        if k not in ("iterations", "inlier_thresh", "seed", "refine", "min_det"):
-            raise TypeError(f"unknown RANSAC option {k!r}")
+        if k not in names:
+            raise TypeError(f"unknown {what} option {k!r}")
         setattr(o, k, v)
     return o
 
 
+RANSAC_OPTIONS = ("iterations", "inlier_thresh", "seed", "refine", "min_det")
+
+
+def default_ransac_options():
+    """sift3d_default_ransac_options as a dict (needs no GPU)"""
+    o = _ransac_options({})
+    return {k: getattr(o, k) for k in RANSAC_OPTIONS}
+
+
+def _ransac_options(opts):
+    return _options(RansacOptions, "sift3d_default_ransac_options", RANSAC_OPTIONS, "RANSAC", opts)
+
+
+def _is_dev(a):
+    """a device tensor (the entry points take it as it lies: it must be contiguous)"""
+    return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)
+
+
+def _p(a):
+    """the pointer to a host array, which the caller keeps alive"""
+    return C.c_void_p(a.ctypes.data)
+
+
+def _table(a, dtype, width, like):
+    """(pointer or None, rows, keep-alive) of an optional (m, width) table (width 0: (m,)) as contiguous `dtype` (a numpy type): a numpy
+    array when `like` is a host array, a tensor on like.device otherwise"""
+    if a is None:
+        return None, 0, None
+    shape = (-1, width) if width else (-1,)
+    if _is_dev(like):
+        import torch
+
+        t = torch.as_tensor(a, dtype=getattr(torch, np.dtype(dtype).name), device=like.device).reshape(shape).contiguous()
+        return C.c_void_p(t.data_ptr()), t.shape[0], t
+    h = np.ascontiguousarray(a, dtype).reshape(shape)
+    return _p(h), len(h), h
+
+
 def _rows(a, width, name):
     """(pointer, rows, keep-alive, on_device) of an (n, width) float32 numpy array or a contiguous float32 device tensor"""
-    if hasattr(a, "data_ptr") and getattr(a, "is_cuda", False):
+    if _is_dev(a):
         if str(a.dtype) != "torch.float32" or not a.is_contiguous() or (a.numel() and a.shape[-1] != width):
             raise ValueError(f"{name}: a contiguous float32 (n, {width}) device tensor is needed")
         return C.c_void_p(a.data_ptr()), a.numel() // width, a, 1
     h = np.ascontiguousarray(a, np.float32).reshape(-1, width)
-    return h.ctypes.data_as(C.c_void_p), len(h), h, 0
+    return _p(h), len(h), h, 0
 
 
-def _fit_dict(f):
-    return {"A": f["A"].reshape(f.shape + (3, 4)).copy(), "hyp": f["hyp"].reshape(f.shape + (3, 4)).copy(), "status": f["status"].copy(),
-            "candidates": f["candidates"].copy(), "best_hypothesis": f["best_hypothesis"].copy(), "best_count": f["best_count"].copy(),
-            "inliers": f["inliers"].copy(), "rms": f["rms"].copy()}
+def _volume(a, name, on_dev):
+    if on_dev:
+        if str(a.dtype) != "torch.float32" or not a.is_contiguous() or a.dim() != 3:
+            raise ValueError(f"{name}: a contiguous float32 (nz, ny, nx) device tensor is needed")
+        return C.c_void_p(a.data_ptr()), a
+    h = np.ascontiguousarray(a, np.float32)
+    if h.ndim != 3:
+        raise ValueError(f"{name}: a (nz, ny, nx) volume is needed")
+    return _p(h), h
+
+
+def _volume_pair(ref, tar):
+    """((ref pointer, tar pointer), ((nx, ny, nz) of ref, of tar), on_device, keep-alives) of two (nz, ny, nx) float32 volumes"""
+    on_dev = _is_dev(ref)
+    if on_dev != _is_dev(tar):
+        raise ValueError("ref and tar must both be numpy arrays or both device tensors")
+    (rp, r), (tp, t) = _volume(ref, "ref", on_dev), _volume(tar, "tar", on_dev)
+    return (rp, tp), (r.shape[::-1], t.shape[::-1]), int(on_dev), (r, t)
+
+
+def _fields(rec, m, names):
+    """copies of the named fields of the first m records (m None: of the one record of a 0-d array)"""
+    if m is not None:
+        rec = rec[:m]
+    return {k: rec[k].copy() for k in names}
+
+
+FIT_FIELDS = ("A", "hyp", "status", "candidates", "best_hypothesis", "best_count", "inliers", "rms")
+
+
+def _fit_dict(f, m):
+    d = _fields(f, m, FIT_FIELDS)
+    for k in ("A", "hyp"):
+        d[k] = d[k].reshape(d[k].shape[:-1] + (3, 4))
+    return d
 
 
 def fit_affine(pairs, device=0, **opts):
@@ -411,9 +474,8 @@ def fit_affine(pairs, device=0, **opts):
     out = np.zeros((), FIT_DTYPE)
     mask = np.zeros(max(n, 1), np.uint8)
     sec = C.c_double(0)
-    _check(lib().sift3d_fit_affine(pp, n, C.byref(o), on_dev, int(device), out.ctypes.data_as(C.c_void_p), mask.ctypes.data_as(C.c_void_p),
-                                   C.byref(sec)))
-    d = {k: (v if k in ("A", "hyp") else v.item()) for k, v in _fit_dict(out).items()}
+    _check(lib().sift3d_fit_affine(pp, n, C.byref(o), on_dev, int(device), _p(out), _p(mask), C.byref(sec)))
+    d = {k: (v if k in ("A", "hyp") else v.item()) for k, v in _fit_dict(out, None).items()}
     d["mask"] = mask[:n].astype(bool)
     d["seconds"] = sec.value
     return d
@@ -431,9 +493,8 @@ def fit_affine_local(pairs, points, k=32, radius=0.0, device=0, **opts):
     out = np.zeros(max(m, 1), FIT_DTYPE)
     nb = np.zeros((max(m, 1), max(int(k), 1)), np.int32)
     sec = C.c_double(0)
-    _check(lib().sift3d_fit_affine_local(pp, n, qp, m, int(k), float(radius), C.byref(o), dev_p, int(device), out.ctypes.data_as(C.c_void_p),
-                                         nb.ctypes.data_as(C.c_void_p), C.byref(sec)))
-    d = _fit_dict(out[:m])
+    _check(lib().sift3d_fit_affine_local(pp, n, qp, m, int(k), float(radius), C.byref(o), dev_p, int(device), _p(out), _p(nb), C.byref(sec)))
+    d = _fit_dict(out, m)
     d["neighbours"] = nb[:m].copy()
     d["seconds"] = sec.value
     return d
@@ -444,19 +505,12 @@ ICGN_OPTIONS = ("subset_radius", "max_iterations", "tolerance", "interpolation")
 
 def default_icgn_options():
     """sift3d_default_icgn_options as a dict (needs no GPU)"""
-    o = IcgnOptions()
-    lib().sift3d_default_icgn_options(C.byref(o))
+    o = _icgn_options({})
     return {k: getattr(o, k) for k in ICGN_OPTIONS}
 
 
 def _icgn_options(opts):
-    o = IcgnOptions()
-    lib().sift3d_default_icgn_options(C.byref(o))
-    for k, v in opts.items():
-        if k not in ICGN_OPTIONS:
-            raise TypeError(f"unknown IC-GN option {k!r}")
-        setattr(o, k, v)
-    return o
+    return _options(IcgnOptions, "sift3d_default_icgn_options", ICGN_OPTIONS, "IC-GN", opts)
 
 
 def icgn_init_from_fits(fits, points):
@@ -470,7 +524,7 @@ def icgn_init_from_fits(fits, points):
     if len(q) != len(A):
         raise ValueError("one point per fit")
     out = np.zeros((max(len(A), 1), 12), np.float64)
-    _check(lib().sift3d_icgn_init_from_fits(f.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p), len(A), out.ctypes.data_as(C.c_void_p)))
+    _check(lib().sift3d_icgn_init_from_fits(_p(f), _p(q), len(A), _p(out)))
     return out[:len(A)].copy()
 
 
@@ -481,48 +535,19 @@ def icgn(ref, tar, points, init=None, device=0, **opts):
     (m, 3) = (u, v, w), gradient (m, 3, 3) (rows u, v, w; columns x, y, z), zncc, last_step, iterations, status (m,) and the device
     seconds."""
     o = _icgn_options(opts)
-    dev = [hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) for a in (ref, tar)]
-    if dev[0] != dev[1]:
-        raise ValueError("ref and tar must both be numpy arrays or both device tensors")
-    vols, keep = [], []
-    if dev[0]:
-        import torch
-
-        for a, name in ((ref, "ref"), (tar, "tar")):
-            if a.dtype != torch.float32 or not a.is_contiguous() or a.dim() != 3:
-                raise ValueError(f"{name}: a contiguous float32 (nz, ny, nx) device tensor is needed")
-            vols.append((C.c_void_p(a.data_ptr()), a.shape))
-        q = torch.as_tensor(points, dtype=torch.int32, device=ref.device).reshape(-1, 3).contiguous()
-        m = q.shape[0]
-        ini = None if init is None else torch.as_tensor(init, dtype=torch.float64, device=ref.device).reshape(-1, 12).contiguous()
-        keep += [q, ini]
-        qp = C.c_void_p(q.data_ptr())
-        ip = None if ini is None else C.c_void_p(ini.data_ptr())
-    else:
-        for a, name in ((ref, "ref"), (tar, "tar")):
-            h = np.ascontiguousarray(a, np.float32)
-            if h.ndim != 3:
-                raise ValueError(f"{name}: a (nz, ny, nx) volume is needed")
-            keep.append(h)
-            vols.append((h.ctypes.data_as(C.c_void_p), h.shape))
-        q = np.ascontiguousarray(points, np.int32).reshape(-1, 3)
-        m = len(q)
-        ini = None if init is None else np.ascontiguousarray(init, np.float64).reshape(-1, 12)
-        keep += [q, ini]
-        qp = q.ctypes.data_as(C.c_void_p)
-        ip = None if ini is None else ini.ctypes.data_as(C.c_void_p)
-    if ini is not None and ini.shape[0] != m:
+    (rp, tp), (rdim, tdim), on_dev, keep = _volume_pair(ref, tar)
+    qp, m, q = _table(points, np.int32, 3, ref)
+    ip, mi, ini = _table(init, np.float64, 12, ref)
+    if ini is not None and mi != m:
         raise ValueError("init: one row of 12 per point")
-    (rp, (rz, ry, rx)), (tp, (tz, ty, tx)) = vols
     out = np.zeros(max(m, 1), ICGN_DTYPE)
     sec = C.c_double(0)
-    _check(lib().sift3d_icgn(rp, int(rx), int(ry), int(rz), tp, int(tx), int(ty), int(tz), qp, m, ip, C.byref(o), int(dev[0]), int(device),
-                             out.ctypes.data_as(C.c_void_p), C.byref(sec)))
-    out = out[:m]
-    p = out["p"].copy()
-    G = p.reshape(-1, 3, 4)[:, :, 1:].copy()
-    return {"p": p, "displacement": p[:, [0, 4, 8]].copy(), "gradient": G, "zncc": out["zncc"].copy(), "last_step": out["last_step"].copy(),
-            "iterations": out["iterations"].copy(), "status": out["status"].copy(), "seconds": sec.value}
+    _check(lib().sift3d_icgn(rp, *rdim, tp, *tdim, qp, m, ip, C.byref(o), on_dev, int(device), _p(out), C.byref(sec)))
+    d = _fields(out, m, ("p", "zncc", "last_step", "iterations", "status"))
+    d["displacement"] = d["p"][:, [0, 4, 8]].copy()
+    d["gradient"] = d["p"].reshape(-1, 3, 4)[:, :, 1:].copy()
+    d["seconds"] = sec.value
+    return d
 
 
 SEARCH_OPTIONS = ("subset_radius", "search_radius")
@@ -530,8 +555,7 @@ SEARCH_OPTIONS = ("subset_radius", "search_radius")
 
 def default_search_options():
     """sift3d_default_search_options as a dict (needs no GPU)"""
-    o = SearchOptions()
-    lib().sift3d_default_search_options(C.byref(o))
+    o = _options(SearchOptions, "sift3d_default_search_options", SEARCH_OPTIONS, "search", {})
     return {k: getattr(o, k) for k in SEARCH_OPTIONS}
 
 
@@ -540,51 +564,18 @@ def zncc_search(ref, tar, points, guess=None, device=0, **opts):
     guess ((m, 3) int32 or None: zero).  ref / tar: (nz, ny, nx) float32 numpy arrays or contiguous float32 device tensors, both of
     the same kind.  Options: subset_radius, search_radius.  Returns d (m, 3) int32, zncc, zncc_second, candidates, status (m,) and
     the device seconds."""
-    o = SearchOptions()
-    lib().sift3d_default_search_options(C.byref(o))
-    for k, v in opts.items():
-        if k not in SEARCH_OPTIONS:
-            raise TypeError(f"unknown search option {k!r}")
-        setattr(o, k, v)
-    dev = [hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) for a in (ref, tar)]
-    if dev[0] != dev[1]:
-        raise ValueError("ref and tar must both be numpy arrays or both device tensors")
-    vols, keep = [], []
-    if dev[0]:
-        import torch
-
-        for a, name in ((ref, "ref"), (tar, "tar")):
-            if a.dtype != torch.float32 or not a.is_contiguous() or a.dim() != 3:
-                raise ValueError(f"{name}: a contiguous float32 (nz, ny, nx) device tensor is needed")
-            vols.append((C.c_void_p(a.data_ptr()), a.shape))
-        q = torch.as_tensor(points, dtype=torch.int32, device=ref.device).reshape(-1, 3).contiguous()
-        m = q.shape[0]
-        gs = None if guess is None else torch.as_tensor(guess, dtype=torch.int32, device=ref.device).reshape(-1, 3).contiguous()
-        qp = C.c_void_p(q.data_ptr())
-        gp = None if gs is None else C.c_void_p(gs.data_ptr())
-    else:
-        for a, name in ((ref, "ref"), (tar, "tar")):
-            h = np.ascontiguousarray(a, np.float32)
-            if h.ndim != 3:
-                raise ValueError(f"{name}: a (nz, ny, nx) volume is needed")
-            keep.append(h)
-            vols.append((h.ctypes.data_as(C.c_void_p), h.shape))
-        q = np.ascontiguousarray(points, np.int32).reshape(-1, 3)
-        m = len(q)
-        gs = None if guess is None else np.ascontiguousarray(guess, np.int32).reshape(-1, 3)
-        qp = q.ctypes.data_as(C.c_void_p)
-        gp = None if gs is None else gs.ctypes.data_as(C.c_void_p)
-    keep += [q, gs]
-    if gs is not None and gs.shape[0] != m:
+    o = _options(SearchOptions, "sift3d_default_search_options", SEARCH_OPTIONS, "search", opts)
+    (rp, tp), (rdim, tdim), on_dev, keep = _volume_pair(ref, tar)
+    qp, m, q = _table(points, np.int32, 3, ref)
+    gp, mg, gs = _table(guess, np.int32, 3, ref)
+    if gs is not None and mg != m:
         raise ValueError("guess: one (gx, gy, gz) per point")
-    (rp, (rz, ry, rx)), (tp, (tz, ty, tx)) = vols
     out = np.zeros(max(m, 1), SEARCH_DTYPE)
     sec = C.c_double(0)
-    _check(lib().sift3d_zncc_search(rp, int(rx), int(ry), int(rz), tp, int(tx), int(ty), int(tz), qp, m, gp, C.byref(o), int(dev[0]),
-                                    int(device), out.ctypes.data_as(C.c_void_p), C.byref(sec)))
-    out = out[:m]
-    return {"d": out["d"].copy(), "zncc": out["zncc"].copy(), "zncc_second": out["zncc_second"].copy(),
-            "candidates": out["candidates"].copy(), "status": out["status"].copy(), "seconds": sec.value}
+    _check(lib().sift3d_zncc_search(rp, *rdim, tp, *tdim, qp, m, gp, C.byref(o), on_dev, int(device), _p(out), C.byref(sec)))
+    d = _fields(out, m, ("d", "zncc", "zncc_second", "candidates", "status"))
+    d["seconds"] = sec.value
+    return d
 
 
 def icgn_init_from_search(res, init=None, only_missing=True):
@@ -602,7 +593,7 @@ def icgn_init_from_search(res, init=None, only_missing=True):
         if len(ini) != m:
             raise ValueError("init: one row of 12 per search result")
         out[:m] = ini
-    _check(lib().sift3d_icgn_init_from_search(rec.ctypes.data_as(C.c_void_p), m, int(bool(only_missing)), out.ctypes.data_as(C.c_void_p)))
+    _check(lib().sift3d_icgn_init_from_search(_p(rec), m, int(bool(only_missing)), _p(out)))
     return out[:m].copy()
 
 
@@ -611,8 +602,7 @@ STRAIN_OPTIONS = ("radius", "min_neighbours", "measure")
 
 def default_strain_options():
     """sift3d_default_strain_options as a dict (needs no GPU)"""
-    o = StrainOptions()
-    lib().sift3d_default_strain_options(C.byref(o))
+    o = _options(StrainOptions, "sift3d_default_strain_options", STRAIN_OPTIONS, "strain", {})
     return {k: getattr(o, k) for k in STRAIN_OPTIONS}
 
 
@@ -628,8 +618,7 @@ def strain_input_from_icgn(res, zncc_min=0.0, accept_unconverged=False):
     rec["status"][:m] = np.asarray(res["status"])
     disp = np.zeros((max(m, 1), 3), np.float64)
     valid = np.zeros(max(m, 1), np.uint8)
-    _check(lib().sift3d_strain_input_from_icgn(rec.ctypes.data_as(C.c_void_p), m, float(zncc_min), int(bool(accept_unconverged)),
-                                               disp.ctypes.data_as(C.c_void_p), valid.ctypes.data_as(C.c_void_p)))
+    _check(lib().sift3d_strain_input_from_icgn(_p(rec), m, float(zncc_min), int(bool(accept_unconverged)), _p(disp), _p(valid)))
     return disp[:m].copy(), valid[:m].copy()
 
 
@@ -639,41 +628,23 @@ def strain(points, disp, valid=None, device=0, **opts):
     valid: numpy arrays or contiguous device tensors, all of the same kind.  Options: radius, min_neighbours, measure (0
     Green-Lagrange, 1 infinitesimal).  Returns disp (m, 3), G (m, 3, 3) (rows u, v, w; columns x, y, z), E (m, 6) (xx yy zz xy yz zx),
     principal (m, 3), equivalent, rms, neighbours, status (m,) and the device seconds."""
-    o = StrainOptions()
-    lib().sift3d_default_strain_options(C.byref(o))
-    for k, v in opts.items():
-        if k not in STRAIN_OPTIONS:
-            raise TypeError(f"unknown strain option {k!r}")
-        setattr(o, k, v)
-    given = [a for a in (points, disp, valid) if a is not None]
-    dev = [hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) for a in given]
+    o = _options(StrainOptions, "sift3d_default_strain_options", STRAIN_OPTIONS, "strain", opts)
+    dev = [_is_dev(a) for a in (points, disp, valid) if a is not None]
     if any(dev) != all(dev):
         raise ValueError("points, disp and valid must all be numpy arrays or all device tensors")
-    if dev[0]:
-        import torch
-
-        q = torch.as_tensor(points, dtype=torch.int32, device=points.device).reshape(-1, 3).contiguous()
-        u = torch.as_tensor(disp, dtype=torch.float64, device=points.device).reshape(-1, 3).contiguous()
-        ok = None if valid is None else torch.as_tensor(valid, device=points.device).ne(0).to(torch.uint8).reshape(-1).contiguous()
-        m = q.shape[0]
-        qp, up = C.c_void_p(q.data_ptr()), C.c_void_p(u.data_ptr())
-        vp = None if ok is None else C.c_void_p(ok.data_ptr())
-    else:
-        q = np.ascontiguousarray(points, np.int32).reshape(-1, 3)
-        u = np.ascontiguousarray(disp, np.float64).reshape(-1, 3)
-        ok = None if valid is None else np.ascontiguousarray(np.asarray(valid) != 0, np.uint8).reshape(-1)
-        m = len(q)
-        qp, up = q.ctypes.data_as(C.c_void_p), u.ctypes.data_as(C.c_void_p)
-        vp = None if ok is None else ok.ctypes.data_as(C.c_void_p)
-    if u.shape[0] != m or (ok is not None and ok.shape[0] != m):
+    qp, m, q = _table(points, np.int32, 3, points)
+    up, mu, u = _table(disp, np.float64, 3, points)
+    ok = None if valid is None else (valid.ne(0) if dev[0] else np.asarray(valid) != 0)
+    vp, mv, ok = _table(ok, np.uint8, 0, points)
+    if mu != m or (ok is not None and mv != m):
         raise ValueError("disp, valid: one row per point")
     out = np.zeros(max(m, 1), STRAIN_DTYPE)
     sec = C.c_double(0)
-    _check(lib().sift3d_strain(qp, up, vp, m, C.byref(o), int(dev[0]), int(device), out.ctypes.data_as(C.c_void_p), C.byref(sec)))
-    out = out[:m]
-    return {"disp": out["disp"].copy(), "G": out["G"].reshape(-1, 3, 3).copy(), "E": out["E"].copy(), "principal": out["principal"].copy(),
-            "equivalent": out["equivalent"].copy(), "rms": out["rms"].copy(), "neighbours": out["neighbours"].copy(),
-            "status": out["status"].copy(), "seconds": sec.value}
+    _check(lib().sift3d_strain(qp, up, vp, m, C.byref(o), int(dev[0]), int(device), _p(out), C.byref(sec)))
+    d = _fields(out, m, ("disp", "G", "E", "principal", "equivalent", "rms", "neighbours", "status"))
+    d["G"] = d["G"].reshape(-1, 3, 3)
+    d["seconds"] = sec.value
+    return d
 
 
 def device_count():

@@ -1,38 +1,17 @@
 // entry_strain.hip -- C-ABI of the strain fields (include/sift3d_hip.h: sift3d_strain, sift3d_strain_input_from_icgn,
-// sift3d_default_strain_options).  No reference counterpart.  Conventions of entry_search.hip: per-device state created on first use (a
-// non-blocking stream and timing events), one call at a time per device, device time from HIP events (input uploads excluded, the
-// result copy included), arguments checked before any device call.  The temporaries depend on the input (the cell grid on the POIs'
-// bounding box), so they are allocated and freed inside the call.
-#include "sift3d_internal.h"
+// sift3d_default_strain_options).  No reference counterpart.  Call state, scratch layout, timing and the order of the checks: DESIGN
+// 4.10 (call_state.h).  The temporaries depend on the input (the cell grid on the POIs' bounding box), so they are allocated and freed
+// inside the call, and the state's grow-only blocks stay empty.
+#include "call_state.h"
 
 #include <math.h>
 #include <string.h>
 
-#include <mutex>
-
 using namespace s3d;
 
 namespace {
-struct StrainDevState {
-	std::mutex mu;
-	bool ready = false;
-	hipStream_t stream = nullptr;
-	hipEvent_t e0 = nullptr, e1 = nullptr, e_in = nullptr;
-};
-constexpr int kMaxDev = 64;
 constexpr long long kMaxCells = 1 << 24;
-StrainDevState g_strain[kMaxDev];
-
-int ensure(StrainDevState &S) {
-	if (S.ready) return SIFT3D_OK;
-	if (!S.stream) S3D_HIP(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
-	if (!S.e0) S3D_HIP(hipEventCreate(&S.e0));
-	if (!S.e1) S3D_HIP(hipEventCreate(&S.e1));
-	if (!S.e_in) S3D_HIP(hipEventCreateWithFlags(&S.e_in, hipEventDisableTiming));
-	S.ready = true;
-	return SIFT3D_OK;
-}
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+CallState g_strain[kMaxDev];
 
 // the temporaries of one call: freed when the call returns, however it returns
 struct Temps {
@@ -100,8 +79,6 @@ extern "C" int sift3d_strain_input_from_icgn(const sift3d_icgn_result *res, int 
 	return SIFT3D_OK;
 }
 
-#define SCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); (void)hipStreamSynchronize(st); return SIFT3D_ERR_HIP; } } while (0)
-
 extern "C" int sift3d_strain(const int *points3, const double *disp3, const unsigned char *valid, int m, const sift3d_strain_options *o,
                              int on_device, int device, sift3d_strain_result *out, double *seconds) {
 	int radius, min_nb, measure;
@@ -110,40 +87,36 @@ extern "C" int sift3d_strain(const int *points3, const double *disp3, const unsi
 		return SIFT3D_ERR_ARG;
 	}
 	if (seconds) *seconds = 0;
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_last_error("no HIP device visible: no CPU fallback"); return SIFT3D_ERR_NO_DEVICE; }
-	if (device < 0 || device >= ndev || device >= kMaxDev) { set_last_error("bad device index"); return SIFT3D_ERR_ARG; }
-	S3D_HIP(hipSetDevice(device));
-	if (m == 0) return SIFT3D_OK;
-	StrainDevState &D = g_strain[device];
-	std::lock_guard<std::mutex> lock(D.mu);
-	int rc = ensure(D);
+	int rc = pick_device(device);
 	if (rc) return rc;
+	if (m == 0) return SIFT3D_OK;
+	CallState &D = g_strain[device];
+	std::lock_guard<std::mutex> lock(D.mu);
+	if ((rc = D.ensure(0, 0))) return rc;
 	hipStream_t st = D.stream;
 	Temps T;
 	// block a: [results | box | cell of a POI | slots | sorted x y z idx | sorted u v w | (host inputs) points | disp | valid]
 	const size_t M = (size_t)m, wi = al256(sizeof(int) * M), wd = al256(sizeof(double) * M), res_bytes = sizeof(sift3d_strain_result) * M;
-	const size_t o_box = al256(res_bytes), o_cell = o_box + 256, o_slots = o_cell + wi, o_si = o_slots + wi, o_sd = o_si + 4 * wi;
-	const size_t o_pts = o_sd + 3 * wd, o_disp = o_pts + (on_device ? 0 : al256(sizeof(int) * 3 * M));
-	const size_t o_valid = o_disp + (on_device ? 0 : al256(sizeof(double) * 3 * M));
-	const size_t a_bytes = o_valid + (on_device || !valid ? 0 : al256(M));
-	S3D_HIP(hipMalloc(&T.a, a_bytes));
+	Layout L;
+	L.take(res_bytes);
+	const size_t o_box = L.take(sizeof(int) * 6), o_cell = L.take(wi), o_slots = L.take(wi), o_si = L.take(4 * wi), o_sd = L.take(3 * wd);
+	const size_t o_pts = L.take(on_device ? 0 : sizeof(int) * 3 * M), o_disp = L.take(on_device ? 0 : sizeof(double) * 3 * M);
+	const size_t o_valid = L.take(on_device || !valid ? 0 : M);
+	S3D_HIP(hipMalloc(&T.a, L.end));
 	char *A = T.a;
 	const int *d_pts = points3;
 	const double *d_disp = disp3;
 	const unsigned char *d_valid = valid;
 	if (on_device) {
-		// device inputs: work the caller queued on the legacy default stream is ordered in front (as in sift3d_icgn)
-		SCHK(hipEventRecord(D.e_in, nullptr));
-		SCHK(hipStreamWaitEvent(st, D.e_in, 0));
+		if ((rc = D.after_legacy_stream())) return rc;
 	} else {
 		d_pts = reinterpret_cast<int *>(A + o_pts);
 		d_disp = reinterpret_cast<double *>(A + o_disp);
-		SCHK(hipMemcpyAsync(A + o_pts, points3, sizeof(int) * 3 * M, hipMemcpyHostToDevice, st));
-		SCHK(hipMemcpyAsync(A + o_disp, disp3, sizeof(double) * 3 * M, hipMemcpyHostToDevice, st));
+		S3D_HIP_ST(st, hipMemcpyAsync(A + o_pts, points3, sizeof(int) * 3 * M, hipMemcpyHostToDevice, st));
+		S3D_HIP_ST(st, hipMemcpyAsync(A + o_disp, disp3, sizeof(double) * 3 * M, hipMemcpyHostToDevice, st));
 		if (valid) {
 			d_valid = reinterpret_cast<unsigned char *>(A + o_valid);
-			SCHK(hipMemcpyAsync(A + o_valid, valid, M, hipMemcpyHostToDevice, st));
+			S3D_HIP_ST(st, hipMemcpyAsync(A + o_valid, valid, M, hipMemcpyHostToDevice, st));
 		}
 	}
 	int *d_box = reinterpret_cast<int *>(A + o_box), *d_cell = reinterpret_cast<int *>(A + o_cell), *d_slots = reinterpret_cast<int *>(A + o_slots);
@@ -151,28 +124,23 @@ extern "C" int sift3d_strain(const int *points3, const double *disp3, const unsi
 	S.x = reinterpret_cast<int *>(A + o_si); S.y = reinterpret_cast<int *>(A + o_si + wi); S.z = reinterpret_cast<int *>(A + o_si + 2 * wi);
 	S.idx = reinterpret_cast<int *>(A + o_si + 3 * wi);
 	S.u = reinterpret_cast<double *>(A + o_sd); S.v = reinterpret_cast<double *>(A + o_sd + wd); S.w = reinterpret_cast<double *>(A + o_sd + 2 * wd);
-	SCHK(hipEventRecord(D.e0, st));
-	SCHK(hipMemsetAsync(d_box, 0x7f, sizeof(int) * 6, st));
+	S3D_HIP_ST(st, hipEventRecord(D.e0, st));
+	S3D_HIP_ST(st, hipMemsetAsync(d_box, 0x7f, sizeof(int) * 6, st));
 	launch_strain_mark(d_pts, d_disp, d_valid, m, d_cell, d_box, st);
-	SCHK(hipGetLastError());
+	S3D_HIP_ST(st, hipGetLastError());
 	int box[6];
-	SCHK(hipMemcpyAsync(box, d_box, sizeof(box), hipMemcpyDeviceToHost, st));
-	SCHK(hipStreamSynchronize(st));
+	S3D_HIP_ST(st, hipMemcpyAsync(box, d_box, sizeof(box), hipMemcpyDeviceToHost, st));
+	S3D_HIP_ST(st, hipStreamSynchronize(st));
 	const StrainGrid g = choose_grid(box, radius);
 	// block b: [counts per cell (then the scatter's fill marks) | cell starts | the scan's tile sums]
 	const size_t cells = (size_t)g.nx * g.ny * g.nz, wc = al256(sizeof(int) * (cells + 1));
 	S3D_HIP(hipMalloc(&T.b, 2 * wc + sizeof(int) * strain_scan_tiles(cells + 1)));
 	int *d_cnt = reinterpret_cast<int *>(T.b), *d_start = reinterpret_cast<int *>(T.b + wc), *d_tiles = reinterpret_cast<int *>(T.b + 2 * wc);
-	SCHK(hipMemsetAsync(d_cnt, 0, sizeof(int) * (cells + 1), st));
-	SCHK(launch_strain_bin(d_pts, d_disp, m, g, d_cell, d_cnt, d_start, d_tiles, d_slots, S, st));
+	S3D_HIP_ST(st, hipMemsetAsync(d_cnt, 0, sizeof(int) * (cells + 1), st));
+	S3D_HIP_ST(st, launch_strain_bin(d_pts, d_disp, m, g, d_cell, d_cnt, d_start, d_tiles, d_slots, S, st));
 	launch_strain_fit(d_pts, d_disp, m, g, d_start, S, radius, min_nb, measure, reinterpret_cast<sift3d_strain_result *>(A), st);
-	SCHK(hipGetLastError());
-	SCHK(hipMemcpyAsync(out, A, res_bytes, hipMemcpyDeviceToHost, st));
-	SCHK(hipEventRecord(D.e1, st));
-	SCHK(hipEventSynchronize(D.e1));
-	float ms = 0;
-	SCHK(hipEventElapsedTime(&ms, D.e0, D.e1));
-	if (seconds) *seconds = (double)ms * 1e-3;
-	return SIFT3D_OK;
+	S3D_HIP_ST(st, hipGetLastError());
+	S3D_HIP_ST(st, hipMemcpyAsync(out, A, res_bytes, hipMemcpyDeviceToHost, st));
+	S3D_HIP_ST(st, hipEventRecord(D.e1, st));
+	return D.finish(seconds);
 }
-#undef SCHK

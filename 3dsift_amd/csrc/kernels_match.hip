@@ -715,60 +715,19 @@ static void ratio_filter(std::vector<int> &gi, const std::vector<float> &gd, con
 	}
 }
 
-// Per-device matcher state, created on first use and reused by every later call (r03: a call used to do 3-5 hipMalloc / hipFree and
-// ran on the null stream): a grow-only device scratch, a pinned host block for the results, the matcher's own non-blocking stream
-// and its timing events.  One call at a time per device (the mutex is held for the whole call).
+// Per-device matcher state (call_state.h; r03: a call used to do 3-5 hipMalloc / hipFree and ran on the null stream).  d holds
+// everything but the descriptor matrices, h the results of a pass (+ the coordinates of device-resident inputs).
 #include <chrono>
-#include <mutex>
+
+#include "call_state.h"
 
 namespace {
-struct MatchState {
-	std::mutex mu;
-	bool ready = false;
-	hipStream_t stream = nullptr;
-	hipEvent_t e0 = nullptr, e1 = nullptr, e_in = nullptr;
-	char *d_scratch = nullptr; size_t d_bytes = 0;   // device: everything but the descriptor matrices
-	float *d_ab = nullptr; size_t ab_floats = 0;     // device copies of host-resident descriptor matrices
-	char *h_pin = nullptr; size_t h_bytes = 0;       // pinned host: results of a pass (+ the coordinates of device-resident inputs)
-	int last_redo = 0;
+struct MatchState : CallState {
+	DevBlock ab;  // device copies of host-resident descriptor matrices
 };
-constexpr int kMaxDev = 64;
 MatchState g_match[kMaxDev];
 thread_local double t_match_dev = 0.0, t_match_wall = 0.0;
 thread_local int t_match_redo_rows = 0;  // rows re-scored exactly by the calling thread's last call (sift3d_debug_counters)
-
-int ensure(MatchState &S, size_t d_bytes, size_t ab_floats, size_t h_bytes) {
-	if (!S.ready) {  // (a failed creation leaves the objects made so far in place: the next call goes on from there)
-		if (!S.stream) S3D_HIP(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
-		if (!S.e0) S3D_HIP(hipEventCreate(&S.e0));
-		if (!S.e1) S3D_HIP(hipEventCreate(&S.e1));
-		if (!S.e_in) S3D_HIP(hipEventCreateWithFlags(&S.e_in, hipEventDisableTiming));
-		S.ready = true;
-	}
-	auto grow = [](size_t want) { return want + want / 4 + 4096; };  // head room: sets of similar size do not reallocate
-	if (d_bytes > S.d_bytes) {
-		S3D_HIP(hipStreamSynchronize(S.stream));
-		if (S.d_scratch) (void)hipFree(S.d_scratch);
-		S.d_scratch = nullptr; S.d_bytes = 0;
-		S3D_HIP(hipMalloc(&S.d_scratch, grow(d_bytes)));
-		S.d_bytes = grow(d_bytes);
-	}
-	if (ab_floats > S.ab_floats) {
-		S3D_HIP(hipStreamSynchronize(S.stream));
-		if (S.d_ab) (void)hipFree(S.d_ab);
-		S.d_ab = nullptr; S.ab_floats = 0;
-		S3D_HIP(hipMalloc(&S.d_ab, sizeof(float) * grow(ab_floats)));
-		S.ab_floats = grow(ab_floats);
-	}
-	if (h_bytes > S.h_bytes) {
-		if (S.h_pin) (void)hipHostFree(S.h_pin);
-		S.h_pin = nullptr; S.h_bytes = 0;
-		S3D_HIP(hipHostMalloc(&S.h_pin, grow(h_bytes), hipHostMallocDefault));
-		S.h_bytes = grow(h_bytes);
-	}
-	return SIFT3D_OK;
-}
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 }  // namespace
 
 namespace s3d { int match_redo_rows() { return t_match_redo_rows; } }
@@ -780,14 +739,12 @@ namespace s3d {
 void preload_match_kernels() { hipFuncAttributes a; (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_scores_topk2)); }
 }
 extern "C" int sift3d_match_warmup(int device) {
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_last_error("no HIP device visible: no CPU fallback"); return SIFT3D_ERR_NO_DEVICE; }
-	if (device < 0 || device >= ndev || device >= kMaxDev) return SIFT3D_ERR_ARG;
-	S3D_HIP(hipSetDevice(device));
+	int rc = pick_device(device);
+	if (rc) return rc;
 	s3d::preload_match_kernels();
 	MatchState &S = g_match[device];
 	std::lock_guard<std::mutex> lock(S.mu);
-	return ensure(S, 0, 0, 0);  // (stream and events; the scratch is sized by the first call)
+	return S.ensure(0, 0);  // (stream and events; the scratch is sized by the first call)
 }
 
 extern "C" int sift3d_match_times(double *device_seconds, double *wall_seconds) {
@@ -804,10 +761,8 @@ extern "C" int sift3d_match(const float *ref_desc, const float *ref_xyz, int n, 
 		set_last_error("sift3d_match: bad argument");
 		return SIFT3D_ERR_ARG;
 	}
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_last_error("no HIP device visible: no CPU fallback"); return SIFT3D_ERR_NO_DEVICE; }
-	if (device < 0 || device >= ndev || device >= kMaxDev) return SIFT3D_ERR_ARG;
-	S3D_HIP(hipSetDevice(device));
+	int rc = pick_device(device);
+	if (rc) return rc;
 	if (npairs) *npairs = 0;
 	if (seconds) *seconds = 0;
 	t_match_dev = t_match_wall = 0.0;
@@ -816,50 +771,47 @@ extern "C" int sift3d_match(const float *ref_desc, const float *ref_xyz, int n, 
 	std::lock_guard<std::mutex> lock(S.mu);
 	const size_t nn = (size_t)std::max(n, 1), mm = (size_t)std::max(m, 1), big = std::max(nn, mm);
 	// device scratch layout (256-B aligned pieces): results [gd | sd | gi | si] of a pass (ONE D2H copy), then the working arrays
-	const size_t o_res = 0, res_bytes = al256(4 * 4 * big);
-	const size_t o_cand = o_res + res_bytes, o_rows = o_cand + al256(4 * (size_t)TOPK * big), o_redo = o_rows + al256(4 * big);
-	const size_t o_s4 = o_redo + al256(4 * (big + 1)), o_an2 = o_s4 + al256(4 * big), o_bn2 = o_an2 + al256(4 * nn);
-	const size_t o_nmax = o_bn2 + al256(4 * mm), o_part = o_nmax + 256, d_bytes = o_part + al256(sizeof(Cand) * TOPK * kMaxSplits * big);
-	const size_t h_res = 0, h_xyz = res_bytes + 256, h_bytes = h_xyz + (on_device ? 4 * 3 * (nn + mm) : 0);
-	int rc = ensure(S, d_bytes, on_device ? 0 : (size_t)kDesc * (nn + mm), h_bytes);
-	if (rc) return rc;
+	// pinned host: [results | redo count | coordinates (device inputs)]
+	Layout L, H;
+	const size_t o_res = L.take(4 * 4 * big), o_cand = L.take(4 * (size_t)TOPK * big), o_rows = L.take(4 * big), o_redo = L.take(4 * (big + 1));
+	const size_t o_s4 = L.take(4 * big), o_an2 = L.take(4 * nn), o_bn2 = L.take(4 * mm), o_nmax = L.take(2 * sizeof(unsigned));
+	const size_t o_part = L.take(sizeof(Cand) * TOPK * kMaxSplits * big);
+	const size_t h_res = H.take(4 * 4 * big), h_redo_at = H.take(sizeof(int)), h_xyz = H.take(on_device ? 4 * 3 * (nn + mm) : 0);
+	if ((rc = S.ensure(L.end, H.end))) return rc;
 	hipStream_t st = S.stream;
+	if (!on_device && (rc = S.ab.reserve(sizeof(float) * kDesc * (nn + mm), st))) return rc;
 
 	std::vector<float> gd(n, 0.f), sd(n, 0.f), gd2(m, 0.f), sd2(m, 0.f);
 	std::vector<int> gi(n, -1), si(n, -1), gi2(m, -1), si2(m, -1);
 	const float *rx = ref_xyz, *tx = tar_xyz;
 	int redo_rows = 0;
-#define MCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); (void)hipStreamSynchronize(st); return SIFT3D_ERR_HIP; } } while (0)
 	float *d_a, *d_b;
 	if (on_device) {
-		// device-resident inputs: work the caller queued on the legacy default stream (torch's default stream is that one) is
-		// ordered in front of the matcher; inputs produced on other streams must be complete when the call is made (sift3d_run is)
-		MCHK(hipEventRecord(S.e_in, nullptr));
-		MCHK(hipStreamWaitEvent(st, S.e_in, 0));
+		if ((rc = S.after_legacy_stream())) return rc;
 		d_a = const_cast<float *>(ref_desc); d_b = const_cast<float *>(tar_desc);
-		float *hx = reinterpret_cast<float *>(S.h_pin + h_xyz), *hy = hx + 3 * nn;
-		if (n) MCHK(hipMemcpyAsync(hx, ref_xyz, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, st));
-		if (m) MCHK(hipMemcpyAsync(hy, tar_xyz, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, st));
+		float *hx = reinterpret_cast<float *>(S.h.p + h_xyz), *hy = hx + 3 * nn;
+		if (n) S3D_HIP_ST(st, hipMemcpyAsync(hx, ref_xyz, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, st));
+		if (m) S3D_HIP_ST(st, hipMemcpyAsync(hy, tar_xyz, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, st));
 		rx = hx; tx = hy;  // read after the first synchronisation below
 	} else {
-		d_a = S.d_ab; d_b = S.d_ab + (size_t)kDesc * nn;
-		if (n) MCHK(hipMemcpyAsync(d_a, ref_desc, sizeof(float) * kDesc * n, hipMemcpyHostToDevice, st));
-		if (m) MCHK(hipMemcpyAsync(d_b, tar_desc, sizeof(float) * kDesc * m, hipMemcpyHostToDevice, st));
+		d_a = reinterpret_cast<float *>(S.ab.p); d_b = d_a + (size_t)kDesc * nn;
+		if (n) S3D_HIP_ST(st, hipMemcpyAsync(d_a, ref_desc, sizeof(float) * kDesc * n, hipMemcpyHostToDevice, st));
+		if (m) S3D_HIP_ST(st, hipMemcpyAsync(d_b, tar_desc, sizeof(float) * kDesc * m, hipMemcpyHostToDevice, st));
 	}
 	{
-		char *D = S.d_scratch;
+		char *D = S.d.p;
 		float *d_gd = reinterpret_cast<float *>(D + o_res), *d_sd = d_gd + big;
 		int *d_gi = reinterpret_cast<int *>(d_sd + big), *d_si = d_gi + big;
 		int *d_cand = reinterpret_cast<int *>(D + o_cand), *d_rows = reinterpret_cast<int *>(D + o_rows), *d_redo = reinterpret_cast<int *>(D + o_redo);
 		float *d_s4 = reinterpret_cast<float *>(D + o_s4), *d_an2 = reinterpret_cast<float *>(D + o_an2), *d_bn2 = reinterpret_cast<float *>(D + o_bn2);
 		unsigned *d_nmax = reinterpret_cast<unsigned *>(D + o_nmax);
 		void *d_part = D + o_part;
-		float *h_gd = reinterpret_cast<float *>(S.h_pin + h_res), *h_sd = h_gd + big;
+		float *h_gd = reinterpret_cast<float *>(S.h.p + h_res), *h_sd = h_gd + big;
 		int *h_gi = reinterpret_cast<int *>(h_sd + big), *h_si = h_gi + big;
-		int *h_redo = reinterpret_cast<int *>(S.h_pin + res_bytes);
+		int *h_redo = reinterpret_cast<int *>(S.h.p + h_redo_at);
 
-		MCHK(hipEventRecord(S.e0, st));
-		MCHK(hipMemsetAsync(d_nmax, 0, 2 * sizeof(unsigned), st));
+		S3D_HIP_ST(st, hipEventRecord(S.e0, st));
+		S3D_HIP_ST(st, hipMemsetAsync(d_nmax, 0, 2 * sizeof(unsigned), st));
 		if (n + m > 0) hipLaunchKernelGGL(k_row_norm2, dim3((n + 15) / 16 + (m + 15) / 16), dim3(256), 0, st, d_a, n, d_an2, d_b, m, d_bn2, d_nmax);
 		// matrices of 4 GB and more take the register-staged form (SIFT3D_HOOK_MATCH_NODMA forces it on any size, for the tests)
 		const bool small = !hook(SIFT3D_HOOK_MATCH_NODMA) && (size_t)std::max(n, m) * KD * sizeof(float) < ((size_t)1 << 32);
@@ -868,16 +820,16 @@ extern "C" int sift3d_match(const float *ref_desc, const float *ref_xyz, int n, 
 		// ---- ref -> tar ----
 		if (n > 0 && m > 0) {
 			match_rows_device(d_a, nullptr, n, d_b, m, d_cand, d_part, d_gd, d_sd, d_gi, d_si, g_fwd, st);
-			MCHK(hipMemcpyAsync(h_gd, d_gd, 4 * 4 * big, hipMemcpyDeviceToHost, st));
-			MCHK(hipMemcpyAsync(h_redo, d_redo, sizeof(int), hipMemcpyDeviceToHost, st));
-			MCHK(hipEventRecord(S.e1, st));  // device time ends with the last device operation of the call (recorded again behind a reverse pass)
-			MCHK(hipStreamSynchronize(st));
+			S3D_HIP_ST(st, hipMemcpyAsync(h_gd, d_gd, 4 * 4 * big, hipMemcpyDeviceToHost, st));
+			S3D_HIP_ST(st, hipMemcpyAsync(h_redo, d_redo, sizeof(int), hipMemcpyDeviceToHost, st));
+			S3D_HIP_ST(st, hipEventRecord(S.e1, st));  // device time ends with the last device operation of the call (recorded again behind a reverse pass)
+			S3D_HIP_ST(st, hipStreamSynchronize(st));
 			memcpy(gd.data(), h_gd, sizeof(float) * n); memcpy(sd.data(), h_sd, sizeof(float) * n);
 			memcpy(gi.data(), h_gi, sizeof(int) * n); memcpy(si.data(), h_si, sizeof(int) * n);
 			redo_rows += h_redo[0];
 		} else {
-			MCHK(hipEventRecord(S.e1, st));
-			MCHK(hipStreamSynchronize(st));
+			S3D_HIP_ST(st, hipEventRecord(S.e1, st));
+			S3D_HIP_ST(st, hipStreamSynchronize(st));
 			// no targets: every dot loop is empty -> d = 2 - 2*FLT_MIN, idx -1
 			for (int i = 0; i < n; i++) { gd[i] = sd[i] = (float)(2 - 2 * (double)FLT_MIN); }
 		}
@@ -891,12 +843,12 @@ extern "C" int sift3d_match(const float *ref_desc, const float *ref_xyz, int n, 
 			for (int j = 0; j < m; j++) { cnt[j] = cnt[j] > mask_thres ? 1 : 0; if (cnt[j]) rows.push_back(j); }  // toMask :122-131
 			// ---- tar -> ref over the masked targets only (masked-out rows keep gIdx2 = -1) ----
 			if (!rows.empty() && n > 0) {
-				MCHK(hipMemcpyAsync(d_rows, rows.data(), sizeof(int) * rows.size(), hipMemcpyHostToDevice, st));
+				S3D_HIP_ST(st, hipMemcpyAsync(d_rows, rows.data(), sizeof(int) * rows.size(), hipMemcpyHostToDevice, st));
 				match_rows_device(d_b, d_rows, (int)rows.size(), d_a, n, d_cand, d_part, d_gd, d_sd, d_gi, d_si, g_rev, st);
-				MCHK(hipMemcpyAsync(h_gd, d_gd, 4 * 4 * big, hipMemcpyDeviceToHost, st));
-				MCHK(hipMemcpyAsync(h_redo, d_redo, sizeof(int), hipMemcpyDeviceToHost, st));
-				MCHK(hipEventRecord(S.e1, st));
-				MCHK(hipStreamSynchronize(st));
+				S3D_HIP_ST(st, hipMemcpyAsync(h_gd, d_gd, 4 * 4 * big, hipMemcpyDeviceToHost, st));
+				S3D_HIP_ST(st, hipMemcpyAsync(h_redo, d_redo, sizeof(int), hipMemcpyDeviceToHost, st));
+				S3D_HIP_ST(st, hipEventRecord(S.e1, st));
+				S3D_HIP_ST(st, hipStreamSynchronize(st));
 				for (int j : rows) { gd2[j] = h_gd[j]; sd2[j] = h_sd[j]; gi2[j] = h_gi[j]; si2[j] = h_si[j]; }
 				redo_rows += h_redo[0];
 			}
@@ -907,10 +859,7 @@ extern "C" int sift3d_match(const float *ref_desc, const float *ref_xyz, int n, 
 				if (gi2[j] != i) gi[i] *= -1;
 			}
 		}
-		MCHK(hipEventSynchronize(S.e1));
-		float ms = 0;
-		hipEventElapsedTime(&ms, S.e0, S.e1);
-		t_match_dev = (double)ms * 1e-3;
+		if ((rc = S.finish(&t_match_dev))) return rc;
 		if (seconds) *seconds = t_match_dev;
 
 		int np = 0;
@@ -930,7 +879,6 @@ extern "C" int sift3d_match(const float *ref_desc, const float *ref_xyz, int n, 
 			if (sDist) sDist[i] = sd[i];
 		}
 	}
-#undef MCHK
 	t_match_redo_rows = redo_rows;
 	t_match_wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
 	return SIFT3D_OK;

@@ -13,6 +13,7 @@
 #include <thread>
 #include <vector>
 
+#include "call_state.h"  // kMaxDev
 #include "sift3d_internal.h"
 
 namespace s3d {
@@ -34,7 +35,6 @@ struct Pool {
 	hipEvent_t ev[kBufs] = {};
 	hipEvent_t ev2[kBufs * kSub] = {};  // one per piece of the device -> host direction
 };
-constexpr int kMaxDev = 64;
 Pool g_pools[kMaxDev];
 Pool &pool_of(int device) { return g_pools[(device >= 0 && device < kMaxDev) ? device : 0]; }
 
