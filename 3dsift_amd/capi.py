@@ -42,6 +42,8 @@ SYMBOLS = [
     "sift3d_default_ransac_options", "sift3d_fit_affine", "sift3d_fit_affine_local",
     # IC-GN displacement refinement (digital volume correlation)
     "sift3d_default_icgn_options", "sift3d_icgn_init_from_fits", "sift3d_icgn",
+    # cubic B-spline interpolation of the target: the prefilter and the IC-GN mode on its coefficients
+    "sift3d_bspline_prefilter", "sift3d_icgn_bspline",
     # ZNCC integer search: the initial guess of IC-GN where no local fit exists
     "sift3d_default_search_options", "sift3d_zncc_search", "sift3d_icgn_init_from_search",
     # strain fields from the refined displacements
@@ -223,6 +225,9 @@ def lib():
         L.sift3d_icgn_init_from_fits.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.sift3d_icgn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                   C.POINTER(IcgnOptions), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+        L.sift3d_bspline_prefilter.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
+        L.sift3d_icgn_bspline.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.POINTER(IcgnOptions), C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
         L.sift3d_default_search_options.argtypes = [C.POINTER(SearchOptions)]
         L.sift3d_default_search_options.restype = None
         L.sift3d_zncc_search.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -534,6 +539,11 @@ def icgn(ref, tar, points, init=None, device=0, **opts):
     Options: subset_radius, max_iterations, tolerance, interpolation (0 tricubic, 1 trilinear).  Returns p (m, 12), displacement
     (m, 3) = (u, v, w), gradient (m, 3, 3) (rows u, v, w; columns x, y, z), zncc, last_step, iterations, status (m,) and the device
     seconds."""
+    return _icgn(ref, tar, points, init, device, opts, None)
+
+
+def _icgn(ref, tar, points, init, device, opts, coefficients):
+    """icgn (coefficients None) and icgn_bspline (coefficients False / True)"""
     o = _icgn_options(opts)
     (rp, tp), (rdim, tdim), on_dev, keep = _volume_pair(ref, tar)
     qp, m, q = _table(points, np.int32, 3, ref)
@@ -542,12 +552,41 @@ def icgn(ref, tar, points, init=None, device=0, **opts):
         raise ValueError("init: one row of 12 per point")
     out = np.zeros(max(m, 1), ICGN_DTYPE)
     sec = C.c_double(0)
-    _check(lib().sift3d_icgn(rp, *rdim, tp, *tdim, qp, m, ip, C.byref(o), on_dev, int(device), _p(out), C.byref(sec)))
+    if coefficients is None:
+        _check(lib().sift3d_icgn(rp, *rdim, tp, *tdim, qp, m, ip, C.byref(o), on_dev, int(device), _p(out), C.byref(sec)))
+    else:
+        _check(lib().sift3d_icgn_bspline(rp, *rdim, tp, *tdim, qp, m, ip, C.byref(o), int(bool(coefficients)), on_dev, int(device), _p(out),
+                                         C.byref(sec)))
     d = _fields(out, m, ("p", "zncc", "last_step", "iterations", "status"))
     d["displacement"] = d["p"][:, [0, 4, 8]].copy()
     d["gradient"] = d["p"].reshape(-1, 3, 4)[:, :, 1:].copy()
     d["seconds"] = sec.value
     return d
+
+
+def bspline_prefilter(vol, device=0, with_seconds=False):
+    """sift3d_bspline_prefilter: the cubic B-spline coefficients (mirror boundary) of vol, an (nz, ny, nx) float32 numpy array or a
+    contiguous float32 device tensor; returns an array / a tensor of the same kind (with_seconds: and the device seconds)"""
+    on_dev = _is_dev(vol)
+    vp, v = _volume(vol, "vol", on_dev)
+    if on_dev:
+        import torch
+
+        out = torch.empty_like(v)
+        op = C.c_void_p(out.data_ptr())
+    else:
+        out = np.empty_like(v)
+        op = _p(out)
+    sec = C.c_double(0)
+    _check(lib().sift3d_bspline_prefilter(vp, *v.shape[::-1], op, int(on_dev), int(device), C.byref(sec)))
+    return (out, sec.value) if with_seconds else out
+
+
+def icgn_bspline(ref, tar, points, init=None, coefficients=False, device=0, **opts):
+    """sift3d_icgn_bspline: icgn with the target interpolated by cubic B-splines.  coefficients False: tar is the volume, prefiltered
+    inside the call; True: tar is bspline_prefilter's output.  Options: subset_radius, max_iterations, tolerance (interpolation must
+    stay 0).  Returns what icgn returns."""
+    return _icgn(ref, tar, points, init, device, opts, bool(coefficients))
 
 
 SEARCH_OPTIONS = ("subset_radius", "search_radius")

@@ -12,6 +12,8 @@
 // SD is recomputed per voxel from R (6 cached loads; a 12-float table per voxel does not fit in LDS at r = 16).  Per-voxel arithmetic is
 // fp32 (positions relative to floor(q + u), so the fraction keeps its bits); per-thread sums are fp32 except sum T' and sum T'^2
 // (fp64: the variance is their difference); the reduction is fp64.  No float atomics: two calls give the same bits.
+// sift3d_icgn_bspline runs the same two launches with the cubic B-spline weights on the prefiltered T (kernels_bspline.hip): the
+// third instantiation of k_icgn_iterate.
 #include "sift3d_internal.h"
 
 #include <math.h>
@@ -24,6 +26,8 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kPrepSums = 86;  // dR^2, sum R', 12 sum SD, 12 sum SD R', 60 H pieces
 constexpr int kIterSums = 15;  // sum T', sum T'^2, 12 sum SD T', sum R'T' (T' = T - Tc)
 constexpr int kRun = -1;       // IcgnState::status: go on to the iteration
+// how T is interpolated: the values of launch_icgn's `kind` (sift3d_internal.h)
+constexpr int kKeys = 0, kLinear = 1, kBspline = 2;
 
 struct IcgnState {
 	double hinv[144];  // H^-1, row-major
@@ -285,9 +289,10 @@ __global__ __launch_bounds__(kThreads) void k_icgn_prepare(IcgnVol R, IcgnVol T,
 // the taps leaves the interpolation's rounding.  Tc is one voxel: an outlier there (a hot voxel |Tc - Tm| >> dT) makes every T' large
 // and costs the fp32 sums that many ulps, as a T far brighter than R did under the shift by Rm; a mean of T would need a pass of its
 // own.  Returns Tc - (float)Rm, which turns the sums into those of T - Rm.
-template <bool CUBIC>
+template <int KIND>
 __device__ inline double subset_pass(const IcgnVol &R, const IcgnVol &T, const int q[3], int r, float rmf, const double p[12],
                                    double (*red)[kIterSums], double sums[kIterSums]) {
+	constexpr bool CUBIC = KIND != kLinear;  // 64 taps
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	const int D = 2 * r + 1, N = D * D * D;
 	const SubsetWalk W(r);
@@ -335,10 +340,18 @@ __device__ inline double subset_pass(const IcgnVol &R, const IcgnVol &T, const i
 #pragma unroll
 			for (int a = 0; a < 3; a++) {
 				const float t = t3[a], t2 = t * t, tq = t2 * t;
-				w[a][0] = 0.5f * ((2.f * t2 - tq) - t);
-				w[a][1] = 0.5f * ((3.f * tq - 5.f * t2) + 2.f);
-				w[a][2] = 0.5f * ((4.f * t2 - 3.f * tq) + t);
-				w[a][3] = 0.5f * (tq - t2);
+				if (KIND == kBspline) {  // T holds the coefficients
+					const float u = 1.f - t, sixth = 1.f / 6.f;
+					w[a][0] = sixth * ((u * u) * u);
+					w[a][1] = sixth * ((3.f * tq - 6.f * t2) + 4.f);
+					w[a][2] = sixth * (((3.f * t2 - 3.f * tq) + 3.f * t) + 1.f);
+					w[a][3] = sixth * tq;
+				} else {
+					w[a][0] = 0.5f * ((2.f * t2 - tq) - t);
+					w[a][1] = 0.5f * ((3.f * tq - 5.f * t2) + 2.f);
+					w[a][2] = 0.5f * ((4.f * t2 - 3.f * tq) + t);
+					w[a][3] = 0.5f * (tq - t2);
+				}
 			}
 			const float *b = T.d + (((size_t)(gz - 1) * T.ny + (gy - 1)) * T.nx + (gx - 1));
 			tv = 0.f;
@@ -394,7 +407,7 @@ __device__ inline double subset_pass(const IcgnVol &R, const IcgnVol &T, const i
 	return (double)tc - (double)rmf;
 }
 
-template <bool CUBIC>
+template <int KIND>
 __global__ __launch_bounds__(kThreads) void k_icgn_iterate(IcgnVol R, IcgnVol T, const int *__restrict__ pts, const double *__restrict__ init,
                                                           int r, int max_it, double tol, const IcgnState *__restrict__ state,
                                                           sift3d_icgn_result *__restrict__ out) {
@@ -416,7 +429,7 @@ __global__ __launch_bounds__(kThreads) void k_icgn_iterate(IcgnVol R, IcgnVol T,
 	bool done = false;
 	for (int pass = 0;; pass++) {
 		double s[kIterSums];
-		const double sh = subset_pass<CUBIC>(R, T, q, r, rmf, p, red[pass & 1], s);
+		const double sh = subset_pass<KIND>(R, T, q, r, rmf, p, red[pass & 1], s);
 		// s: 0 sum T', 1 sum T'^2, 2..13 sum SD T', 14 sum R'T'
 		const double tm = s[0] / N;
 		const double dt2 = s[1] - s[0] * tm;
@@ -484,7 +497,7 @@ __global__ __launch_bounds__(kThreads) void k_icgn_iterate(IcgnVol R, IcgnVol T,
 			for (int c = 0; c < 3; c++)
 				pn[4 * a + 1 + c] = ((Fp[3 * a] * inv[c] + Fp[3 * a + 1] * inv[3 + c]) + Fp[3 * a + 2] * inv[6 + c]) - (a == c ? 1.0 : 0.0);
 		}
-		if (!in_domain(pn, q, r, T, CUBIC)) {
+		if (!in_domain(pn, q, r, T, KIND != kLinear)) {
 			if (threadIdx.x == 0) write_result(out + poi, p, zncc, last, it, 3);
 			return;
 		}
@@ -505,14 +518,16 @@ __global__ __launch_bounds__(kThreads) void k_icgn_iterate(IcgnVol R, IcgnVol T,
 
 size_t icgn_state_bytes() { return sizeof(IcgnState); }
 
-void launch_icgn(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_init, int r, int max_it, double tol, int cubic, void *d_state,
+void launch_icgn(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_init, int r, int max_it, double tol, int kind, void *d_state,
                  sift3d_icgn_result *d_out, hipStream_t st) {
 	IcgnState *S = static_cast<IcgnState *>(d_state);
-	hipLaunchKernelGGL(k_icgn_prepare, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, cubic, S, d_out);
-	if (cubic)
-		hipLaunchKernelGGL(k_icgn_iterate<true>, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out);
+	hipLaunchKernelGGL(k_icgn_prepare, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, kind != kLinear, S, d_out);
+	if (kind == kKeys)
+		hipLaunchKernelGGL(k_icgn_iterate<kKeys>, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out);
+	else if (kind == kLinear)
+		hipLaunchKernelGGL(k_icgn_iterate<kLinear>, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out);
 	else
-		hipLaunchKernelGGL(k_icgn_iterate<false>, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out);
+		hipLaunchKernelGGL(k_icgn_iterate<kBspline>, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out);
 }
 
 }  // namespace s3d

@@ -333,9 +333,15 @@ struct IcgnVol {
 	int nx, ny, nz;
 };
 size_t icgn_state_bytes();  // per-POI scratch record of the prepare kernel
-// d_init: m * 12 doubles or null (zero); d_state: m * icgn_state_bytes(); d_out: m records
-void launch_icgn(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_init, int r, int max_it, double tol, int cubic, void *d_state,
+// d_init: m * 12 doubles or null (zero); d_state: m * icgn_state_bytes(); d_out: m records; kind: how T is interpolated, 0 tricubic
+// Keys, 1 trilinear, 2 cubic B-spline (T then holds the prefilter's coefficients)
+void launch_icgn(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_init, int r, int max_it, double tol, int kind, void *d_state,
                  sift3d_icgn_result *d_out, hipStream_t st);
+
+// ---- kernels_bspline.hip: cubic B-spline prefilter (sift3d_bspline_prefilter, include/sift3d_hip.h) ------------------------------
+bool bspline_prefilter_fits(int nx, int ny, int nz);  // ny * nz below 2^31 and at most 2^24 - 1 workgroups per pass
+// d_dst: the coefficients of d_src; d_tmp: a volume of the same size, overwritten (the y pass's output); d_dst != d_src
+void launch_bspline_prefilter(const float *d_src, int nx, int ny, int nz, float *d_dst, float *d_tmp, hipStream_t st);
 
 // ---- kernels_search.hip: ZNCC integer search (sift3d_zncc_search, include/sift3d_hip.h) -----------------------------------------
 int search_groups(int m);                  // workgroups of the launch: each walks its POIs in turn

@@ -47,7 +47,7 @@ struct SIFT_LIBRARY_API IcgnOptions {
 	int subset_radius = 16;   // r: the subset is (2r+1)^3 voxels, 2..32
 	int max_iterations = 20;  // 1..100
 	float tolerance = 1e-3f;  // on ||dp||_r; 0 runs max_iterations updates
-	int interpolation = 0;    // 0 tricubic Keys (Catmull-Rom), 1 trilinear
+	int interpolation = 0;    // 0 tricubic Keys (Catmull-Rom), 1 trilinear, 2 cubic B-spline on the prefiltered target
 };
 
 // the refined first-order shape function at one point of interest: p = (u, ux, uy, uz, v, vx, vy, vz, w, wx, wy, wz) (include/sift3d_hip.h);
@@ -88,13 +88,25 @@ SIFT_LIBRARY_API std::vector<SearchResult> SearchDisplacements(const float *ref,
                                                                const std::vector<Cvec> &points, const std::vector<Cvec> *guesses = nullptr,
                                                                const SearchOptions &o = SearchOptions());
 
+// the cubic B-spline coefficients (mirror boundary) of vol (nx x ny x nz, fp32, x fastest) into coefficients, host memory of the same
+// size and not vol itself: what RefineDisplacements takes as tar with interpolation 2 and tar_is_coefficients, so a target refined
+// against more than once is prefiltered once.  false: the call failed (message on stderr).  seconds (may be null): device time
+SIFT_LIBRARY_API bool PrefilterBSpline(const float *vol, int nx, int ny, int nz, float *coefficients, double *seconds = nullptr);
+
 // IC-GN refinement of the displacement from ref (nx x ny x nz, fp32, x fastest) to tar (tnx x tny x tnz) at integral points of ref,
 // starting from the local affine fits (one per point, e.g. EstimateLocalAffine at the same points) or from zero; fallback (one per
-// point, e.g. SearchDisplacements at the same points) gives the start of a point whose fit has status != 0
+// point, e.g. SearchDisplacements at the same points) gives the start of a point whose fit has status != 0.  opts.interpolation 2
+// interpolates tar by cubic B-splines: tar is prefiltered inside the call, or, with tar_is_coefficients, already holds
+// PrefilterBSpline's output, through the second overload (the flag has no meaning for the interpolations 0 and 1).  The first
+// overload is the function as it was: programs linked against an earlier libsift3d.so still resolve it
 SIFT_LIBRARY_API std::vector<IcgnResult> RefineDisplacements(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
                                                              const std::vector<Cvec> &points, const std::vector<AffineFit> *init = nullptr,
                                                              const IcgnOptions &opts = IcgnOptions(),
                                                              const std::vector<SearchResult> *fallback = nullptr);
+SIFT_LIBRARY_API std::vector<IcgnResult> RefineDisplacements(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
+                                                             const std::vector<Cvec> &points, const std::vector<AffineFit> *init,
+                                                             const IcgnOptions &opts, const std::vector<SearchResult> *fallback,
+                                                             bool tar_is_coefficients);
 
 struct SIFT_LIBRARY_API StrainOptions {
 	int radius = 16;          // window half width in voxels (Chebyshev), 1..4096

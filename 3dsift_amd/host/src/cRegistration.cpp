@@ -1,5 +1,6 @@
 // cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine / SearchDisplacements / RefineDisplacements / ComputeStrains over
-// sift3d_fit_affine / sift3d_fit_affine_local / sift3d_zncc_search / sift3d_icgn / sift3d_strain (include/sift3d_hip.h).
+// sift3d_fit_affine / sift3d_fit_affine_local / sift3d_zncc_search / sift3d_icgn / sift3d_icgn_bspline / sift3d_strain, and
+// CPUSIFT::PrefilterBSpline over sift3d_bspline_prefilter (include/sift3d_hip.h).
 #include "../Include/cRegistration.h"
 
 #include <cmath>
@@ -116,6 +117,12 @@ void IcgnResult::Gradient(double G[9]) const {
 		for (int j = 0; j < 3; j++) G[3 * i + j] = p[4 * i + 1 + j];
 }
 
+bool PrefilterBSpline(const float *vol, int nx, int ny, int nz, float *coefficients, double *seconds) {
+	const int rc = sift3d_bspline_prefilter(vol, nx, ny, nz, coefficients, 0, GetDevice(), seconds);
+	if (rc != SIFT3D_OK) fprintf(stderr, "[3dsift_amd] PrefilterBSpline: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+	return rc == SIFT3D_OK;
+}
+
 Cvec SearchResult::Displacement() const { return Cvec((float)d[0], (float)d[1], (float)d[2]); }
 
 std::vector<SearchResult> SearchDisplacements(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
@@ -155,6 +162,12 @@ std::vector<SearchResult> SearchDisplacements(const float *ref, int nx, int ny, 
 std::vector<IcgnResult> RefineDisplacements(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
                                             const std::vector<Cvec> &points, const std::vector<AffineFit> *init, const IcgnOptions &opts,
                                             const std::vector<SearchResult> *fallback) {
+	return RefineDisplacements(ref, nx, ny, nz, tar, tnx, tny, tnz, points, init, opts, fallback, false);
+}
+
+std::vector<IcgnResult> RefineDisplacements(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
+                                            const std::vector<Cvec> &points, const std::vector<AffineFit> *init, const IcgnOptions &opts,
+                                            const std::vector<SearchResult> *fallback, bool tar_is_coefficients) {
 	const size_t m = points.size();
 	std::vector<IcgnResult> res(m);
 	std::vector<int> q;
@@ -192,10 +205,14 @@ std::vector<IcgnResult> RefineDisplacements(const float *ref, int nx, int ny, in
 	o.subset_radius = opts.subset_radius;
 	o.max_iterations = opts.max_iterations;
 	o.tolerance = opts.tolerance;
-	o.interpolation = opts.interpolation;
+	const bool bspline = opts.interpolation == 2;  // the C entry of its own: sift3d_icgn's option stays 0 / 1
+	o.interpolation = bspline ? 0 : opts.interpolation;
 	std::vector<sift3d_icgn_result> r(m ? m : 1);
 	double sec = 0;
-	const int rc = sift3d_icgn(ref, nx, ny, nz, tar, tnx, tny, tnz, q.data(), (int)m, init ? p0.data() : nullptr, &o, 0, GetDevice(), r.data(), &sec);
+	const double *p0p = init ? p0.data() : nullptr;
+	const int rc = bspline ? sift3d_icgn_bspline(ref, nx, ny, nz, tar, tnx, tny, tnz, q.data(), (int)m, p0p, &o, tar_is_coefficients ? 1 : 0, 0,
+	                                             GetDevice(), r.data(), &sec)
+	                       : sift3d_icgn(ref, nx, ny, nz, tar, tnx, tny, tnz, q.data(), (int)m, p0p, &o, 0, GetDevice(), r.data(), &sec);
 	if (rc != SIFT3D_OK) {
 		fprintf(stderr, "[3dsift_amd] RefineDisplacements: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
 		return res;

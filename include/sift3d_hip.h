@@ -560,6 +560,48 @@ int sift3d_icgn(const float *ref, int rnx, int rny, int rnz, const float *tar, i
                 const double *init12, const sift3d_icgn_options *o, int on_device, int device, sift3d_icgn_result *out, double *seconds);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Cubic B-spline interpolation of the target (no reference counterpart: the interpolation DVC codes use, because the bias of the
+ * Keys kernel limits IC-GN's accuracy).  A prefilter turns a volume into its B-spline coefficients; sift3d_icgn_bspline is
+ * sift3d_icgn with the B-spline weights applied to them.
+ * Numerical contract of the prefilter (a tolerance contract; tests/bspline_ref.py restates it in NumPy): dst receives the cubic
+ * B-spline coefficients of src (fp32, [z][y][x]) with a mirror (whole-sample symmetric) boundary -- scipy.ndimage.spline_filter(
+ * order=3, mode="mirror") to fp32 accuracy -- as a truncated, differenced FIR, not the recursion:
+ *   z1 = sqrt(3) - 2, K = 16;  h_k = z1^k / (1 + 2 sum_{j=1..K} z1^j) for k = 1..K, formed in fp64 and rounded to fp32 (the 2K + 1
+ *     weights sum to 1; the central one is implied).
+ *   Per axis, x then y then z, every intermediate volume stored as fp32:
+ *     c[i] = s[i] + sum_{k=K..1} h_k * ((s[m(i - k)] - s[i]) + (s[m(i + k)] - s[i])),
+ *     m the mirror index map of period 2n - 2 (m(-j) = j, m(n - 1 + j) = n - 1 - j, folded repeatedly when n <= K; m = 0 when n = 1).
+ *   Products and sums are fp32, not fused, the sum over k accumulated from k = K down to 1 and added to s[i] last.  No float
+ *     atomics and a fixed order: two calls return the same bytes.
+ *   Consequences: a constant volume returns itself bit for bit; an axis of length 1 is the identity (on finite values); a single
+ *     non-finite voxel in the interior makes exactly the (2K+1)^3 cube around it non-finite and nothing outside that cube changes;
+ *     the truncated tail (|z1|^17 = 1.9e-10) is below fp32 resolution: the fp64 form of this formula differs from the exact filter
+ *     by at most 2.8e-8 max|src| (measured on noise).
+ * SIFT3D_ERR_ARG (checked before any device call): NULL src / dst, dst == src, a dimension < 1, or a volume too large for a pass:
+ * ny * nz >= 2^31, or more than 2^24 - 1 tiles of 64 x 64 voxels in a pass (about 6.8e10 voxels).  SIFT3D_ERR_NO_DEVICE after that
+ * check when no GPU is visible: there is no CPU fallback.  on_device != 0: src and dst are device pointers on `device`, ordered
+ * behind the legacy default stream; otherwise both are host memory.  Only dst == src is checked: volumes that overlap in part
+ * give undefined results.  The call keeps one more volume of src's size on the device (three for host volumes).  *seconds (may be NULL):
+ * device time of the call (HIP events; the upload of a host input excluded).
+ *
+ * sift3d_icgn_bspline: the contract of sift3d_icgn -- the gradient of R, H, the update, the status table, the cubic domain rule
+ * (taps floor - 1 .. floor + 2) -- with one difference: T(x) is the tensor product of the cubic B-spline weights
+ *     w-1 = (1 - t)^3 / 6, w0 = (3t^3 - 6t^2 + 4) / 6, w1 = (-3t^3 + 3t^2 + 3t + 1) / 6, w2 = t^3 / 6
+ * applied to the coefficients of T.  tar_is_coefficients 0: tar is the volume and the call prefilters it into its own scratch (it
+ * then holds up to two more volumes of T's size on the device, and *seconds includes the prefilter); 1: tar already holds
+ * sift3d_bspline_prefilter's output (prefilter once, refine often).  The centring carries over: Tc is the coefficient at the base
+ * tap of the subset's centre and the taps are shifted before they are weighted; a constant T has constant coefficients exactly, so
+ * a constant T still has dT = 0 exactly, and scaling T by a power of two still returns the same bits.  A non-finite voxel of T
+ * reaches the POIs whose warped subset comes within K + 2 voxels of it (Chebyshev) and no other.
+ * SIFT3D_ERR_ARG: as sift3d_icgn, and o->interpolation != 0 (the option has no meaning here; 1 is refused) or tar_is_coefficients
+ * outside 0..1.  sift3d_icgn itself is unchanged: it refuses interpolation = 2.
+ * ------------------------------------------------------------------------------------------------------------ */
+int sift3d_bspline_prefilter(const float *src, int nx, int ny, int nz, float *dst, int on_device, int device, double *seconds);
+int sift3d_icgn_bspline(const float *ref, int rnx, int rny, int rnz, const float *tar, int tnx, int tny, int tnz, const int *points3, int m,
+                        const double *init12, const sift3d_icgn_options *o, int tar_is_coefficients, int on_device, int device,
+                        sift3d_icgn_result *out, double *seconds);
+
+/* ------------------------------------------------------------------------------------------------------------
  * ZNCC integer search: the zero-order initial guess of IC-GN where no local affine fit exists (no reference counterpart: the
  * exhaustive integer-voxel search of DIC / DVC codes).  The reference subset of a POI is slid over a window of the target and the
  * integer displacement with the highest zero-normalised cross-correlation is returned.  It uses no neighbouring POI.
