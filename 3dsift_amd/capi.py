@@ -44,6 +44,8 @@ SYMBOLS = [
     "sift3d_default_icgn_options", "sift3d_icgn_init_from_fits", "sift3d_icgn",
     # cubic B-spline interpolation of the target: the prefilter and the IC-GN mode on its coefficients
     "sift3d_bspline_prefilter", "sift3d_icgn_bspline",
+    # second-order (30-parameter) IC-GN
+    "sift3d_icgn2_init_from_icgn", "sift3d_icgn2", "sift3d_strain_input_from_icgn2",
     # ZNCC integer search: the initial guess of IC-GN where no local fit exists
     "sift3d_default_search_options", "sift3d_zncc_search", "sift3d_icgn_init_from_search",
     # strain fields from the refined displacements
@@ -124,6 +126,10 @@ assert C.sizeof(IcgnOptions) == 32
 ICGN_DTYPE = np.dtype([("p", "<f8", (12,)), ("zncc", "<f8"), ("last_step", "<f8"), ("iterations", "<i4"), ("status", "<i4"),
                        ("reserved", "<i4", (2,))])
 assert ICGN_DTYPE.itemsize == 128
+# sift3d_icgn2_result: p = (c, cx, cy, cz, cxx, cyy, czz, cxy, cxz, cyz) of u, then v, then w
+ICGN2_DTYPE = np.dtype([("p", "<f8", (30,)), ("zncc", "<f8"), ("last_step", "<f8"), ("iterations", "<i4"), ("status", "<i4"),
+                        ("reserved", "<i4", (2,))])
+assert ICGN2_DTYPE.itemsize == 272
 
 
 class SearchOptions(C.Structure):
@@ -232,6 +238,10 @@ def lib():
         L.sift3d_default_search_options.restype = None
         L.sift3d_zncc_search.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                          C.c_void_p, C.POINTER(SearchOptions), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+        L.sift3d_icgn2_init_from_icgn.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.sift3d_icgn2.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                   C.POINTER(IcgnOptions), C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+        L.sift3d_strain_input_from_icgn2.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
         L.sift3d_icgn_init_from_search.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.sift3d_default_strain_options.argtypes = [C.POINTER(StrainOptions)]
         L.sift3d_default_strain_options.restype = None
@@ -589,6 +599,43 @@ def icgn_bspline(ref, tar, points, init=None, coefficients=False, device=0, **op
     return _icgn(ref, tar, points, init, device, opts, bool(coefficients))
 
 
+def icgn2_init_from_icgn(res):
+    """sift3d_icgn2_init_from_icgn: (m, 30) float64 initial parameters for icgn2 from the dict icgn / icgn_bspline returns (p,
+    status): a row with status 0 or 1 gives its 12 parameters and zero second derivatives, any other status a NaN row.  Needs no GPU."""
+    p = np.asarray(res["p"], np.float64).reshape(-1, 12)
+    m = len(p)
+    rec = np.zeros(max(m, 1), ICGN_DTYPE)
+    rec["p"][:m] = p
+    rec["status"][:m] = np.asarray(res["status"])
+    out = np.zeros((max(m, 1), 30), np.float64)
+    _check(lib().sift3d_icgn2_init_from_icgn(_p(rec), m, _p(out)))
+    return out[:m].copy()
+
+
+def icgn2(ref, tar, points, init=None, coefficients=False, device=0, **opts):
+    """sift3d_icgn2: second-order IC-GN at each point ((m, 3) int32 x, y, z of ref) from ref to tar.  ref / tar as for icgn; init:
+    (m, 30) float64 (icgn2_init_from_icgn) or None (zero).  Options: subset_radius, max_iterations, tolerance, interpolation (0
+    tricubic Keys, 1 trilinear, 2 cubic B-spline; coefficients True: tar is bspline_prefilter's output, interpolation 2 only).
+    Returns p (m, 30), displacement (m, 3), gradient (m, 3, 3) (rows u, v, w; columns x, y, z), second (m, 3, 6) (columns xx, yy, zz,
+    xy, xz, yz), zncc, last_step, iterations, status (m,) and the device seconds."""
+    o = _icgn_options(opts)
+    (rp, tp), (rdim, tdim), on_dev, keep = _volume_pair(ref, tar)
+    qp, m, q = _table(points, np.int32, 3, ref)
+    ip, mi, ini = _table(init, np.float64, 30, ref)
+    if ini is not None and mi != m:
+        raise ValueError("init: one row of 30 per point")
+    out = np.zeros(max(m, 1), ICGN2_DTYPE)
+    sec = C.c_double(0)
+    _check(lib().sift3d_icgn2(rp, *rdim, tp, *tdim, qp, m, ip, C.byref(o), int(bool(coefficients)), on_dev, int(device), _p(out), C.byref(sec)))
+    d = _fields(out, m, ("p", "zncc", "last_step", "iterations", "status"))
+    e = d["p"].reshape(-1, 3, 10)
+    d["displacement"] = e[:, :, 0].copy()
+    d["gradient"] = e[:, :, 1:4].copy()
+    d["second"] = e[:, :, 4:].copy()
+    d["seconds"] = sec.value
+    return d
+
+
 SEARCH_OPTIONS = ("subset_radius", "search_radius")
 
 
@@ -658,6 +705,20 @@ def strain_input_from_icgn(res, zncc_min=0.0, accept_unconverged=False):
     disp = np.zeros((max(m, 1), 3), np.float64)
     valid = np.zeros(max(m, 1), np.uint8)
     _check(lib().sift3d_strain_input_from_icgn(_p(rec), m, float(zncc_min), int(bool(accept_unconverged)), _p(disp), _p(valid)))
+    return disp[:m].copy(), valid[:m].copy()
+
+
+def strain_input_from_icgn2(res, zncc_min=0.0, accept_unconverged=False):
+    """sift3d_strain_input_from_icgn2: strain_input_from_icgn for the dict icgn2 returns.  Needs no GPU."""
+    p = np.asarray(res["p"], np.float64).reshape(-1, 30)
+    m = len(p)
+    rec = np.zeros(max(m, 1), ICGN2_DTYPE)
+    rec["p"][:m] = p
+    rec["zncc"][:m] = np.asarray(res["zncc"])
+    rec["status"][:m] = np.asarray(res["status"])
+    disp = np.zeros((max(m, 1), 3), np.float64)
+    valid = np.zeros(max(m, 1), np.uint8)
+    _check(lib().sift3d_strain_input_from_icgn2(_p(rec), m, float(zncc_min), int(bool(accept_unconverged)), _p(disp), _p(valid)))
     return disp[:m].copy(), valid[:m].copy()
 
 

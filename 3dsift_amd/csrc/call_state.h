@@ -39,6 +39,8 @@ struct CallState {
 
 int pick_device(int device);  // checks the index, makes the device current
 
+CallState &icgn_call_state(int device);  // entry_icgn.hip: the IC-GN family's state, which sift3d_icgn2 shares (device checked by pick_device)
+
 // a HIP call of an entry that has work on stream st: the stream is drained before the error is returned
 #define S3D_HIP_ST(st, call)                                                                            \
 	do {                                                                                                \

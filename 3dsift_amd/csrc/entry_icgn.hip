@@ -27,6 +27,9 @@ bool take_options(const sift3d_icgn_options *o, int &r, int &max_it, double &tol
 }
 }  // namespace
 
+// the family's state, shared with the second-order entry (entry_icgn2.hip): DESIGN 4.10
+CallState &s3d::icgn_call_state(int device) { return g_icgn[device]; }
+
 extern "C" void sift3d_default_icgn_options(sift3d_icgn_options *o) {
 	if (!o) return;
 	memset(o, 0, sizeof(*o));

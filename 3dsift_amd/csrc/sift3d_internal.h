@@ -338,6 +338,12 @@ size_t icgn_state_bytes();  // per-POI scratch record of the prepare kernel
 void launch_icgn(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_init, int r, int max_it, double tol, int kind, void *d_state,
                  sift3d_icgn_result *d_out, hipStream_t st);
 
+// ---- kernels_icgn2.hip: second-order IC-GN (sift3d_icgn2, include/sift3d_hip.h) --------------------------------------------------
+size_t icgn2_state_bytes();  // per-POI scratch record of the prepare kernel
+// as launch_icgn, with m * 30 doubles in d_init and m * icgn2_state_bytes() in d_state
+void launch_icgn2(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_init, int r, int max_it, double tol, int kind, void *d_state,
+                  sift3d_icgn2_result *d_out, hipStream_t st);
+
 // ---- kernels_bspline.hip: cubic B-spline prefilter (sift3d_bspline_prefilter, include/sift3d_hip.h) ------------------------------
 bool bspline_prefilter_fits(int nx, int ny, int nz);  // ny * nz below 2^31 and at most 2^24 - 1 workgroups per pass
 // d_dst: the coefficients of d_src; d_tmp: a volume of the same size, overwritten (the y pass's output); d_dst != d_src

@@ -108,6 +108,31 @@ SIFT_LIBRARY_API std::vector<IcgnResult> RefineDisplacements(const float *ref, i
                                                              const IcgnOptions &opts, const std::vector<SearchResult> *fallback,
                                                              bool tar_is_coefficients);
 
+// the refined second-order shape function at one point of interest: p = (c, cx, cy, cz, cxx, cyy, czz, cxy, cxz, cyz) of u, then v, then w
+// -- the displacement and its first and second derivatives at the point (include/sift3d_hip.h); status as IcgnResult's
+struct SIFT_LIBRARY_API Icgn2Result {
+	double p[30] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+	double zncc = 0, last_step = 0;
+	int iterations = 0;
+	int status = -1;
+	double seconds = 0;  // device time of the call
+
+	// (u, v, w), the displacement gradient (row-major 3x3: rows u, v, w; columns x, y, z) and the second derivatives (row-major 3x6:
+	// rows u, v, w; columns xx, yy, zz, xy, xz, yz)
+	Cvec Displacement() const;
+	void Gradient(double G[9]) const;
+	void SecondDerivatives(double S[18]) const;
+};
+
+// second-order IC-GN at integral points of ref, started from the first-order results at the same points (RefineDisplacements): a point
+// whose first-order status is 0 or 1 starts from its 12 parameters with zero second derivatives, any other point returns status 5.
+// Removes the bias of the first-order fit where the displacement gradient varies across the subset.  opts.interpolation 0, 1 or 2;
+// tar_is_coefficients as for RefineDisplacements (interpolation 2 only)
+SIFT_LIBRARY_API std::vector<Icgn2Result> RefineDisplacementsSecondOrder(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny,
+                                                                         int tnz, const std::vector<Cvec> &points,
+                                                                         const std::vector<IcgnResult> &first,
+                                                                         const IcgnOptions &opts = IcgnOptions(), bool tar_is_coefficients = false);
+
 struct SIFT_LIBRARY_API StrainOptions {
 	int radius = 16;          // window half width in voxels (Chebyshev), 1..4096
 	int min_neighbours = 10;  // 4..1048576
@@ -131,6 +156,10 @@ struct SIFT_LIBRARY_API StrainResult {
 // strain at every point from the displacements RefineDisplacements returned at the same points: a point is a neighbour where IC-GN
 // converged (or ran out of iterations, with accept_unconverged) with zncc >= zncc_min; the others are filled from their neighbours
 SIFT_LIBRARY_API std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp,
+                                                          const StrainOptions &o = StrainOptions(), double zncc_min = 0,
+                                                          bool accept_unconverged = false);
+// the same from the second-order results of RefineDisplacementsSecondOrder
+SIFT_LIBRARY_API std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp,
                                                           const StrainOptions &o = StrainOptions(), double zncc_min = 0,
                                                           bool accept_unconverged = false);
 

@@ -228,6 +228,36 @@ std::vector<IcgnResult> RefineDisplacements(const float *ref, int nx, int ny, in
 	return res;
 }
 
+// the strain call behind both ComputeStrains overloads: rc is what the input conversion returned
+static std::vector<StrainResult> strains_of(const std::vector<int> &q, size_t m, int rc, const std::vector<double> &u,
+                                            const std::vector<unsigned char> &valid, const StrainOptions &opts) {
+	std::vector<StrainResult> res(m);
+	sift3d_strain_options o;
+	sift3d_default_strain_options(&o);
+	o.radius = opts.radius;
+	o.min_neighbours = opts.min_neighbours;
+	o.measure = opts.measure;
+	std::vector<sift3d_strain_result> r(m ? m : 1);
+	double sec = 0;
+	if (rc == SIFT3D_OK) rc = sift3d_strain(q.data(), u.data(), valid.data(), (int)m, &o, 0, GetDevice(), r.data(), &sec);
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] ComputeStrains: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return res;
+	}
+	for (size_t i = 0; i < m; i++) {
+		memcpy(res[i].disp, r[i].disp, sizeof(res[i].disp));
+		memcpy(res[i].G, r[i].G, sizeof(res[i].G));
+		memcpy(res[i].E, r[i].E, sizeof(res[i].E));
+		memcpy(res[i].principal, r[i].principal, sizeof(res[i].principal));
+		res[i].equivalent = r[i].equivalent;
+		res[i].rms = r[i].rms;
+		res[i].neighbours = r[i].neighbours;
+		res[i].status = r[i].status;
+		res[i].seconds = sec;
+	}
+	return res;
+}
+
 std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const StrainOptions &opts, double zncc_min,
                                          bool accept_unconverged) {
 	const size_t m = points.size();
@@ -247,31 +277,84 @@ std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const 
 	}
 	std::vector<double> u(3 * (m ? m : 1));
 	std::vector<unsigned char> valid(m ? m : 1);
-	sift3d_strain_options o;
-	sift3d_default_strain_options(&o);
-	o.radius = opts.radius;
-	o.min_neighbours = opts.min_neighbours;
-	o.measure = opts.measure;
-	std::vector<sift3d_strain_result> r(m ? m : 1);
+	const int rc = sift3d_strain_input_from_icgn(ic.data(), (int)m, zncc_min, accept_unconverged ? 1 : 0, u.data(), valid.data());
+	return strains_of(q, m, rc, u, valid, opts);
+}
+
+Cvec Icgn2Result::Displacement() const { return Cvec((float)p[0], (float)p[10], (float)p[20]); }
+void Icgn2Result::Gradient(double G[9]) const {
+	for (int i = 0; i < 3; i++)
+		for (int j = 0; j < 3; j++) G[3 * i + j] = p[10 * i + 1 + j];
+}
+void Icgn2Result::SecondDerivatives(double S[18]) const {
+	for (int i = 0; i < 3; i++)
+		for (int j = 0; j < 6; j++) S[6 * i + j] = p[10 * i + 4 + j];
+}
+
+std::vector<Icgn2Result> RefineDisplacementsSecondOrder(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
+                                                        const std::vector<Cvec> &points, const std::vector<IcgnResult> &first,
+                                                        const IcgnOptions &opts, bool tar_is_coefficients) {
+	const size_t m = points.size();
+	std::vector<Icgn2Result> res(m);
+	std::vector<int> q;
+	if (!int_triples("RefineDisplacementsSecondOrder", "point", points, q)) return res;
+	if (first.size() != m) {
+		fprintf(stderr, "[3dsift_amd] RefineDisplacementsSecondOrder: %zu first-order results for %zu points\n", first.size(), m);
+		return res;
+	}
+	std::vector<sift3d_icgn_result> f(m ? m : 1);
+	memset(f.data(), 0, sizeof(sift3d_icgn_result) * f.size());
+	for (size_t i = 0; i < m; i++) {
+		memcpy(f[i].p, first[i].p, sizeof(f[i].p));
+		f[i].status = first[i].status;
+	}
+	std::vector<double> p0(30 * (m ? m : 1), 0.0);
+	sift3d_icgn2_init_from_icgn(f.data(), (int)m, p0.data());
+	sift3d_icgn_options o;
+	sift3d_default_icgn_options(&o);
+	o.subset_radius = opts.subset_radius;
+	o.max_iterations = opts.max_iterations;
+	o.tolerance = opts.tolerance;
+	o.interpolation = opts.interpolation;
+	std::vector<sift3d_icgn2_result> r(m ? m : 1);
 	double sec = 0;
-	int rc = sift3d_strain_input_from_icgn(ic.data(), (int)m, zncc_min, accept_unconverged ? 1 : 0, u.data(), valid.data());
-	if (rc == SIFT3D_OK) rc = sift3d_strain(q.data(), u.data(), valid.data(), (int)m, &o, 0, GetDevice(), r.data(), &sec);
+	const int rc = sift3d_icgn2(ref, nx, ny, nz, tar, tnx, tny, tnz, q.data(), (int)m, p0.data(), &o, tar_is_coefficients ? 1 : 0, 0, GetDevice(),
+	                            r.data(), &sec);
 	if (rc != SIFT3D_OK) {
-		fprintf(stderr, "[3dsift_amd] ComputeStrains: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		fprintf(stderr, "[3dsift_amd] RefineDisplacementsSecondOrder: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
 		return res;
 	}
 	for (size_t i = 0; i < m; i++) {
-		memcpy(res[i].disp, r[i].disp, sizeof(res[i].disp));
-		memcpy(res[i].G, r[i].G, sizeof(res[i].G));
-		memcpy(res[i].E, r[i].E, sizeof(res[i].E));
-		memcpy(res[i].principal, r[i].principal, sizeof(res[i].principal));
-		res[i].equivalent = r[i].equivalent;
-		res[i].rms = r[i].rms;
-		res[i].neighbours = r[i].neighbours;
+		memcpy(res[i].p, r[i].p, sizeof(res[i].p));
+		res[i].zncc = r[i].zncc;
+		res[i].last_step = r[i].last_step;
+		res[i].iterations = r[i].iterations;
 		res[i].status = r[i].status;
 		res[i].seconds = sec;
 	}
 	return res;
+}
+
+std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp, const StrainOptions &opts,
+                                         double zncc_min, bool accept_unconverged) {
+	const size_t m = points.size();
+	std::vector<int> q;
+	if (!int_triples("ComputeStrains", "point", points, q)) return std::vector<StrainResult>(m);
+	if (disp.size() != m) {
+		fprintf(stderr, "[3dsift_amd] ComputeStrains: %zu displacements for %zu points\n", disp.size(), m);
+		return std::vector<StrainResult>(m);
+	}
+	std::vector<sift3d_icgn2_result> ic(m ? m : 1);
+	memset(ic.data(), 0, sizeof(sift3d_icgn2_result) * ic.size());
+	for (size_t i = 0; i < m; i++) {
+		memcpy(ic[i].p, disp[i].p, sizeof(ic[i].p));
+		ic[i].zncc = disp[i].zncc;
+		ic[i].status = disp[i].status;
+	}
+	std::vector<double> u(3 * (m ? m : 1));
+	std::vector<unsigned char> valid(m ? m : 1);
+	const int rc = sift3d_strain_input_from_icgn2(ic.data(), (int)m, zncc_min, accept_unconverged ? 1 : 0, u.data(), valid.data());
+	return strains_of(q, m, rc, u, valid, opts);
 }
 
 }  // namespace CPUSIFT

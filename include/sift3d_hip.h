@@ -602,6 +602,61 @@ int sift3d_icgn_bspline(const float *ref, int rnx, int rny, int rnz, const float
                         sift3d_icgn_result *out, double *seconds);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Second-order IC-GN (no reference counterpart: the 30-parameter shape function of DVC codes, for subsets across which the
+ * displacement gradient varies -- bending, indentation, the neighbourhood of cracks and inclusions -- where the first-order fit is
+ * biased by about kappa r (r + 1) / 6 for a second derivative kappa).  Intended use: sift3d_icgn, sift3d_icgn2_init_from_icgn,
+ * sift3d_icgn2.  Numerical contract (a tolerance contract; tests/icgn2_ref.py restates it in NumPy fp64).  Everything not named here
+ * is the contract of sift3d_icgn / sift3d_icgn_bspline word for word: the volumes and POIs, the fp32 central-difference gradient of
+ * R, Rm and dR, the three interpolations and their tap domains, the centring by Tc with the shift applied before the weights, the
+ * fp32 per-voxel arithmetic and the clamp at T's edge, zncc, no float atomics and two calls returning the same bytes.
+ *   Parameters: p[30], ten per component in the order u, v, w: (c, cx, cy, cz, cxx, cyy, czz, cxy, cxz, cyz) -- the displacement and
+ *     its first and second derivatives at q.  The subset offset d maps, per axis a, to
+ *       q_a + d_a + c + cx dx + cy dy + cz dz + 1/2 cxx dx^2 + 1/2 cyy dy^2 + 1/2 czz dz^2 + cxy dx dy + cxz dx dz + cyz dy dz.
+ *   Steepest-descent row: SD = (Rx xi', Ry xi', Rz xi') with xi'(d) = (1, dx, dy, dz, 1/2 dx^2, 1/2 dy^2, 1/2 dz^2, dx dy, dx dz, dy dz);
+ *     H = sum SD^T SD is 30 x 30, formed in fp64; status 4 by the same column Cholesky, with 30 pivots (a pivot <= 0 or NaN).
+ *   Step: dp = -H^-1 sum SD^T [(R - Rm) - (dR/dT)(T(W) - Tm)], fp64.
+ *   Update: with xi(d) = (1, dx, dy, dz, dx^2, dy^2, dz^2, dx dy, dx dz, dy dz), M(p) is the 10 x 10 matrix with
+ *     xi(W(d) - q) ~ M(p) xi(d): row 0 is e_0; rows 1..3 are the coefficient vectors of the three position polynomials (e_{1+a} plus
+ *     the parameters, the squares carrying their 1/2); rows 4..9 are the products of rows (x,x), (y,y), (z,z), (x,y), (x,z), (y,z) as
+ *     polynomials in d with every term of degree 3 or 4 dropped.  M(p) <- M(p) . M(dp)^-1 in fp64; the new p is read from rows 1..3.
+ *     Status 6: a non-finite dp, or a singular M(dp): an LU pivot (partial pivoting by rows, the first entry of largest magnitude)
+ *     that is 0 or not finite.
+ *   Stopping norm: ||dp||_r = sqrt(sum over a of [dc^2 + r^2 (dcx^2 + dcy^2 + dcz^2) + r^4 (dcxx^2 / 4 + dcyy^2 / 4 + dczz^2 / 4 +
+ *     dcxy^2 + dcxz^2 + dcyz^2)]): each term's displacement at the subset's edge.
+ *   Domain: the warped subset is not the affine image of a box, so the rule is conservative and closed-form.  Per axis a,
+ *     B_a = r^2 (|cxx| / 2 + |cyy| / 2 + |czz| / 2 + |cxy| + |cxz| + |cyz|) of that component.  With the 8 corners of the affine part
+ *     (p with its second-order terms set to zero), p is in the domain when floor(min corner_a - B_a) - lo >= 0 and
+ *     floor(max corner_a + B_a) + hi <= n_a - 1 on every axis, (lo, hi) = (1, 2) for the cubic interpolations and (0, 1) for the
+ *     trilinear one; fp64, a NaN is outside.  With zero second-order terms this is sift3d_icgn's rule.
+ *   Status table and its order: sift3d_icgn's (5, 2, 4, 3, 6, 4, 1, 0).
+ *   Precision: the position of a voxel is floor(q + c) + d, integers, plus the fp32 sum frac(q + c) + (F - I) d + the quadratic part;
+ *     the sample T' is fp32 as in sift3d_icgn; the products SD^T T' (Rx, Ry, Rz times T' times xi') and their sums are fp64.
+ * o->interpolation: 0 Keys, 1 trilinear, 2 cubic B-spline; tar_is_coefficients has the meaning and the checks of
+ * sift3d_icgn_bspline and must be 0 unless interpolation is 2.  SIFT3D_ERR_ARG (before any device call): as sift3d_icgn with these
+ * rules; m = 0 succeeds.  The call keeps 4224 bytes of scratch per POI on the device.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct sift3d_icgn2_result {
+	double p[30];          /* (c cx cy cz cxx cyy czz cxy cxz cyz) of u, then v, then w */
+	double zncc;
+	double last_step;      /* ||dp||_r of the last computed step (0: none) */
+	int iterations;        /* updates applied */
+	int status;            /* sift3d_icgn's table */
+	int reserved[2];
+} sift3d_icgn2_result;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_icgn2_result) == 272, "sift3d_icgn2_result must be 272 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_icgn2_result, zncc) == 240 && offsetof(sift3d_icgn2_result, last_step) == 248 &&
+                     offsetof(sift3d_icgn2_result, iterations) == 256 && offsetof(sift3d_icgn2_result, status) == 260 &&
+                     offsetof(sift3d_icgn2_result, reserved) == 264, "sift3d_icgn2_result field offsets");
+
+/* host only: m rows of 30 initial parameters from m first-order results; a row with status 0 or 1 gives its 12 parameters and zero
+ * second derivatives, any other status a NaN row (POI status 5).  SIFT3D_ERR_ARG: m < 0, or a NULL pointer with m > 0. */
+int sift3d_icgn2_init_from_icgn(const sift3d_icgn_result *res, int m, double *init30);
+/* m POIs (x, y, z int triples) refined between ref and tar; init30: m*30 or NULL (zero) */
+int sift3d_icgn2(const float *ref, int rnx, int rny, int rnz, const float *tar, int tnx, int tny, int tnz, const int *points3, int m,
+                 const double *init30, const sift3d_icgn_options *o, int tar_is_coefficients, int on_device, int device,
+                 sift3d_icgn2_result *out, double *seconds);
+
+/* ------------------------------------------------------------------------------------------------------------
  * ZNCC integer search: the zero-order initial guess of IC-GN where no local affine fit exists (no reference counterpart: the
  * exhaustive integer-voxel search of DIC / DVC codes).  The reference subset of a POI is slid over a window of the target and the
  * integer displacement with the highest zero-normalised cross-correlation is returned.  It uses no neighbouring POI.
@@ -733,6 +788,9 @@ void sift3d_default_strain_options(sift3d_strain_options *o);
  * NULL pointer with m > 0. */
 int sift3d_strain_input_from_icgn(const sift3d_icgn_result *res, int m, double zncc_min, int accept_unconverged, double *disp3,
                                   unsigned char *valid);
+/* the same from second-order results: row i of disp3 = (p[0], p[10], p[20]) of res[i] */
+int sift3d_strain_input_from_icgn2(const sift3d_icgn2_result *res, int m, double zncc_min, int accept_unconverged, double *disp3,
+                                   unsigned char *valid);
 /* m POIs (x, y, z int triples), their displacements (m * 3) and validity bytes (m, or NULL); out: m records */
 int sift3d_strain(const int *points3, const double *disp3, const unsigned char *valid, int m, const sift3d_strain_options *o, int on_device,
                   int device, sift3d_strain_result *out, double *seconds);

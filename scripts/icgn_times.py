@@ -9,8 +9,11 @@ rocprofv3 --kernel-trace --stats (scripts/README.md) and divide the evaluations 
 roofline for the 6 volume transfers of its three passes, and of the 512_step16_r10 call), and in every case sift3d_icgn_bspline on
 the prefiltered target (tar_is_coefficients = 1) timed in the same loop as the Keys call, the two alternating; the output then goes to
 profiles/icgn_bspline_times.json.
+--second-order adds the second-order leg: in every case sift3d_icgn2 (Keys) started from the first-order result
+(sift3d_icgn2_init_from_icgn), timed in the same loop as the first-order call, the two alternating; its device time, mean iterations,
+voxel evaluations per second and the ratio of that rate to the first-order call's in the same run go to profiles/icgn2_times.json.
 
-    python scripts/icgn_times.py [--steps 20] [--warmup 3] [--bspline] [--out profiles/icgn_times.json]
+    python scripts/icgn_times.py [--steps 20] [--warmup 3] [--bspline | --second-order] [--out profiles/icgn_times.json]
 """
 import argparse
 import importlib
@@ -38,9 +41,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--bspline", action="store_true", help="add the B-spline prefilter and sift3d_icgn_bspline, alternating with the Keys calls")
+    ap.add_argument("--second-order", action="store_true", help="add sift3d_icgn2 from the first-order result, alternating with the first-order calls")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "icgn_bspline_times.json" if a.bspline else "icgn_times.json")
+    if a.bspline and a.second_order:
+        raise SystemExit("--bspline and --second-order are separate legs")
+    a.out = a.out or os.path.join(ROOT, "profiles", "icgn_bspline_times.json" if a.bspline else "icgn2_times.json" if a.second_order else "icgn_times.json")
     capi = importlib.import_module("3dsift_amd.capi")
     synth = importlib.import_module("3dsift_amd.synth")
     if capi.device_count() < 1:
@@ -73,7 +79,11 @@ def main():
         dq = torch.from_numpy(q).cuda()
         for _ in range(a.warmup):
             res = capi.icgn(R, T, dq, subset_radius=r)
-        dev, wall, bdev = [], [], []
+        dev, wall, bdev, sdev = [], [], [], []
+        if a.second_order:
+            init2 = torch.from_numpy(capi.icgn2_init_from_icgn(res)).cuda()
+            for _ in range(a.warmup):
+                capi.icgn2(R, T, dq, init=init2, subset_radius=r)
         if a.bspline:
             for _ in range(a.warmup):
                 capi.icgn_bspline(R, coef, dq, coefficients=True, subset_radius=r)
@@ -85,6 +95,9 @@ def main():
             if a.bspline:  # the same loop, the two alternating
                 bres = capi.icgn_bspline(R, coef, dq, coefficients=True, subset_radius=r)
                 bdev.append(bres["seconds"])
+            if a.second_order:  # the same loop, the two alternating
+                sres = capi.icgn2(R, T, dq, init=init2, subset_radius=r)
+                sdev.append(sres["seconds"])
         st, it = res["status"], res["iterations"]
         passes = np.where((st <= 1) | (res["last_step"] > 0), it + 1, 0)
         evals = int(passes.sum()) * (2 * r + 1) ** 3
@@ -107,6 +120,18 @@ def main():
                                     "max_disp_error_converged": round(float(np.abs(bres["displacement"][bok] - np.array(SHIFT)).max()), 6)
                                     if bok.any() else None,
                                     "prefilter_share_of_keys_call": round(out[f"prefilter_{n}"]["device_ms"] / out[name]["device_ms"], 4)}
+        if a.second_order:
+            sst, sit = sres["status"], sres["iterations"]
+            sev = int(np.where((sst <= 1) | (sres["last_step"] > 0), sit + 1, 0).sum()) * (2 * r + 1) ** 3
+            sok = sst == 0
+            smed = float(np.median(sdev))
+            out[name]["second_order"] = {"converged": int(sok.sum()), "status_counts": np.bincount(sst + 1, minlength=8)[1:].tolist(),
+                                         "mean_iterations": round(float(sit.mean()), 3), "voxel_evaluations": sev,
+                                         "device_ms": round(smed * 1e3, 4), "device_ms_min": round(float(np.min(sdev)) * 1e3, 4),
+                                         "evals_per_s_call": float(f"{sev / smed:.4g}"),
+                                         "rate_vs_first_order": round(sev / smed / (evals / med), 4),
+                                         "max_disp_error_converged": round(float(np.abs(sres["displacement"][sok] - np.array(SHIFT)).max()), 6)
+                                         if sok.any() else None}
         print(json.dumps({name: out[name]}), flush=True)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
