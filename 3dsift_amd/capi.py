@@ -549,27 +549,29 @@ def icgn(ref, tar, points, init=None, device=0, **opts):
     Options: subset_radius, max_iterations, tolerance, interpolation (0 tricubic, 1 trilinear).  Returns p (m, 12), displacement
     (m, 3) = (u, v, w), gradient (m, 3, 3) (rows u, v, w; columns x, y, z), zncc, last_step, iterations, status (m,) and the device
     seconds."""
-    return _icgn(ref, tar, points, init, device, opts, None)
+    return _icgn(1, "sift3d_icgn", ref, tar, points, init, device, opts, None)
 
 
-def _icgn(ref, tar, points, init, device, opts, coefficients):
-    """icgn (coefficients None) and icgn_bspline (coefficients False / True)"""
+def _icgn(order, entry, ref, tar, points, init, device, opts, coefficients):
+    """the call behind icgn, icgn_bspline (order 1) and icgn2 (order 2); entry: the exported function's name; coefficients None: the
+    entry has no tar_is_coefficients argument"""
+    width, dtype = {1: (12, ICGN_DTYPE), 2: (30, ICGN2_DTYPE)}[order]
     o = _icgn_options(opts)
     (rp, tp), (rdim, tdim), on_dev, keep = _volume_pair(ref, tar)
     qp, m, q = _table(points, np.int32, 3, ref)
-    ip, mi, ini = _table(init, np.float64, 12, ref)
+    ip, mi, ini = _table(init, np.float64, width, ref)
     if ini is not None and mi != m:
-        raise ValueError("init: one row of 12 per point")
-    out = np.zeros(max(m, 1), ICGN_DTYPE)
+        raise ValueError(f"init: one row of {width} per point")
+    out = np.zeros(max(m, 1), dtype)
     sec = C.c_double(0)
-    if coefficients is None:
-        _check(lib().sift3d_icgn(rp, *rdim, tp, *tdim, qp, m, ip, C.byref(o), on_dev, int(device), _p(out), C.byref(sec)))
-    else:
-        _check(lib().sift3d_icgn_bspline(rp, *rdim, tp, *tdim, qp, m, ip, C.byref(o), int(bool(coefficients)), on_dev, int(device), _p(out),
-                                         C.byref(sec)))
+    coef = () if coefficients is None else (int(bool(coefficients)),)
+    _check(getattr(lib(), entry)(rp, *rdim, tp, *tdim, qp, m, ip, C.byref(o), *coef, on_dev, int(device), _p(out), C.byref(sec)))
     d = _fields(out, m, ("p", "zncc", "last_step", "iterations", "status"))
-    d["displacement"] = d["p"][:, [0, 4, 8]].copy()
-    d["gradient"] = d["p"].reshape(-1, 3, 4)[:, :, 1:].copy()
+    e = d["p"].reshape(-1, 3, width // 3)
+    d["displacement"] = e[:, :, 0].copy()
+    d["gradient"] = e[:, :, 1:4].copy()
+    if order == 2:
+        d["second"] = e[:, :, 4:].copy()
     d["seconds"] = sec.value
     return d
 
@@ -596,7 +598,7 @@ def icgn_bspline(ref, tar, points, init=None, coefficients=False, device=0, **op
     """sift3d_icgn_bspline: icgn with the target interpolated by cubic B-splines.  coefficients False: tar is the volume, prefiltered
     inside the call; True: tar is bspline_prefilter's output.  Options: subset_radius, max_iterations, tolerance (interpolation must
     stay 0).  Returns what icgn returns."""
-    return _icgn(ref, tar, points, init, device, opts, bool(coefficients))
+    return _icgn(1, "sift3d_icgn_bspline", ref, tar, points, init, device, opts, bool(coefficients))
 
 
 def icgn2_init_from_icgn(res):
@@ -618,22 +620,7 @@ def icgn2(ref, tar, points, init=None, coefficients=False, device=0, **opts):
     tricubic Keys, 1 trilinear, 2 cubic B-spline; coefficients True: tar is bspline_prefilter's output, interpolation 2 only).
     Returns p (m, 30), displacement (m, 3), gradient (m, 3, 3) (rows u, v, w; columns x, y, z), second (m, 3, 6) (columns xx, yy, zz,
     xy, xz, yz), zncc, last_step, iterations, status (m,) and the device seconds."""
-    o = _icgn_options(opts)
-    (rp, tp), (rdim, tdim), on_dev, keep = _volume_pair(ref, tar)
-    qp, m, q = _table(points, np.int32, 3, ref)
-    ip, mi, ini = _table(init, np.float64, 30, ref)
-    if ini is not None and mi != m:
-        raise ValueError("init: one row of 30 per point")
-    out = np.zeros(max(m, 1), ICGN2_DTYPE)
-    sec = C.c_double(0)
-    _check(lib().sift3d_icgn2(rp, *rdim, tp, *tdim, qp, m, ip, C.byref(o), int(bool(coefficients)), on_dev, int(device), _p(out), C.byref(sec)))
-    d = _fields(out, m, ("p", "zncc", "last_step", "iterations", "status"))
-    e = d["p"].reshape(-1, 3, 10)
-    d["displacement"] = e[:, :, 0].copy()
-    d["gradient"] = e[:, :, 1:4].copy()
-    d["second"] = e[:, :, 4:].copy()
-    d["seconds"] = sec.value
-    return d
+    return _icgn(2, "sift3d_icgn2", ref, tar, points, init, device, opts, bool(coefficients))
 
 
 SEARCH_OPTIONS = ("subset_radius", "search_radius")

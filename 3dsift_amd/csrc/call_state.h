@@ -1,6 +1,7 @@
 // call_state.h -- what the one-shot entry points share (sift3d_match, sift3d_fit_affine[_local], sift3d_icgn[_bspline],
-// sift3d_zncc_search, sift3d_strain, sift3d_bspline_prefilter): the per-device call state, its grow-only blocks, the scratch layout,
-// the device pick and the stream-aware check macro.  Every family keeps an array of states of its own (its own stream and mutex per device).
+// sift3d_icgn2, sift3d_zncc_search, sift3d_strain, sift3d_bspline_prefilter): the per-device call state, its grow-only blocks, the
+// scratch layout, the staging of a volume pair, the device pick and the stream-aware check macro.  Every family keeps an array of
+// states of its own (its own stream and mutex per device).
 #pragma once
 #include <mutex>
 
@@ -34,12 +35,13 @@ struct CallState {
 	PinBlock h;
 	int ensure(size_t d_bytes, size_t h_bytes);  // stream and events on first use; d and h hold at least that much
 	int after_legacy_stream();                   // device inputs: the call runs behind the legacy default stream
+	// a volume pair's inputs (scratch_layout.h, PairPlan) -> where the kernels read them: device inputs stay where they are and the call
+	// runs behind the legacy default stream; host inputs are uploaded to their pieces of d, in the plan's order (opt may be null)
+	int stage_pair(const PairPlan &P, bool on_device, const float *&ref, const float *&tar, const int *&pts, const void *&opt);
 	int finish(double *seconds);                 // waits for e1; *seconds (may be NULL) = e0 -> e1
 };
 
 int pick_device(int device);  // checks the index, makes the device current
-
-CallState &icgn_call_state(int device);  // entry_icgn.hip: the IC-GN family's state, which sift3d_icgn2 shares (device checked by pick_device)
 
 // a HIP call of an entry that has work on stream st: the stream is drained before the error is returned
 #define S3D_HIP_ST(st, call)                                                                            \

@@ -44,6 +44,19 @@ int CallState::after_legacy_stream() {
 	return SIFT3D_OK;
 }
 
+int CallState::stage_pair(const PairPlan &P, bool on_device, const float *&ref, const float *&tar, const int *&pts, const void *&opt) {
+	if (on_device) return after_legacy_stream();
+	S3D_HIP_ST(stream, hipMemcpyAsync(d.p + P.o_ref, ref, P.b_ref, hipMemcpyHostToDevice, stream));
+	S3D_HIP_ST(stream, hipMemcpyAsync(d.p + P.o_tar, tar, P.b_tar, hipMemcpyHostToDevice, stream));
+	S3D_HIP_ST(stream, hipMemcpyAsync(d.p + P.o_pts, pts, P.b_pts, hipMemcpyHostToDevice, stream));
+	if (opt) S3D_HIP_ST(stream, hipMemcpyAsync(d.p + P.o_opt, opt, P.b_opt, hipMemcpyHostToDevice, stream));
+	ref = reinterpret_cast<const float *>(d.p + P.o_ref);
+	tar = reinterpret_cast<const float *>(d.p + P.o_tar);
+	pts = reinterpret_cast<const int *>(d.p + P.o_pts);
+	if (opt) opt = d.p + P.o_opt;
+	return SIFT3D_OK;
+}
+
 int CallState::finish(double *seconds) {
 	S3D_HIP_ST(stream, hipEventSynchronize(e1));
 	float ms = 0;

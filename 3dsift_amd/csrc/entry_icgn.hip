@@ -1,7 +1,11 @@
-// entry_icgn.hip -- C-ABI of the IC-GN displacement refinement (include/sift3d_hip.h: sift3d_icgn, sift3d_icgn_bspline,
-// sift3d_icgn_init_from_fits, sift3d_default_icgn_options).  No reference counterpart.  Call state, scratch layout, timing and the order of the checks: DESIGN 4.10
-// (call_state.h).
+// entry_icgn.hip -- C-ABI of the IC-GN displacement refinement of both orders (include/sift3d_hip.h: sift3d_icgn, sift3d_icgn_bspline,
+// sift3d_icgn2, sift3d_icgn_init_from_fits, sift3d_icgn2_init_from_icgn, sift3d_strain_input_from_icgn2, sift3d_default_icgn_options).
+// No reference counterpart.  Call state, scratch layout, timing and the order of the checks: DESIGN 4.10 (call_state.h).  The three
+// calls run through one shell on one state per device: the two orders are used one after the other in one chain, so a second mutex
+// would never be contended, the grown scratch block is reused, and the process creates no further stream.  The host-only logic lives
+// in icgn_host.h.
 #include "call_state.h"
+#include "icgn_host.h"
 
 #include <math.h>
 #include <string.h>
@@ -10,33 +14,10 @@ using namespace s3d;
 
 namespace {
 CallState g_icgn[kMaxDev];
-
-// options (NULL: defaults) -> checked values; kind: launch_icgn's (the interpolation option as it is)
-bool take_options(const sift3d_icgn_options *o, int &r, int &max_it, double &tol, int &kind) {
-	sift3d_icgn_options d;
-	sift3d_default_icgn_options(&d);
-	if (!o) o = &d;
-	if (o->subset_radius < 2 || o->subset_radius > 32 || o->max_iterations < 1 || o->max_iterations > 100) return false;
-	if (!std::isfinite(o->tolerance) || o->tolerance < 0.f || (o->interpolation != 0 && o->interpolation != 1)) return false;
-	if (o->reserved[0] || o->reserved[1] || o->reserved[2] || o->reserved[3]) return false;
-	r = o->subset_radius;
-	max_it = o->max_iterations;
-	tol = o->tolerance;
-	kind = o->interpolation;
-	return true;
-}
 }  // namespace
 
-// the family's state, shared with the second-order entry (entry_icgn2.hip): DESIGN 4.10
-CallState &s3d::icgn_call_state(int device) { return g_icgn[device]; }
-
 extern "C" void sift3d_default_icgn_options(sift3d_icgn_options *o) {
-	if (!o) return;
-	memset(o, 0, sizeof(*o));
-	o->subset_radius = 16;
-	o->max_iterations = 20;
-	o->tolerance = 1e-3f;
-	o->interpolation = 0;
+	if (o) *o = icgn_default_options();
 }
 
 extern "C" int sift3d_icgn_init_from_fits(const sift3d_affine_fit *fits, const int *points3, int m, double *init12) {
@@ -57,71 +38,83 @@ extern "C" int sift3d_icgn_init_from_fits(const sift3d_affine_fit *fits, const i
 	return SIFT3D_OK;
 }
 
+extern "C" int sift3d_icgn2_init_from_icgn(const sift3d_icgn_result *res, int m, double *init30) {
+	if (m < 0 || (m > 0 && (!res || !init30))) {
+		set_last_error("sift3d_icgn2_init_from_icgn: bad argument");
+		return SIFT3D_ERR_ARG;
+	}
+	for (int i = 0; i < m; i++) icgn2_init_row(res[i], init30 + 30 * (size_t)i);
+	return SIFT3D_OK;
+}
+
+extern "C" int sift3d_strain_input_from_icgn2(const sift3d_icgn2_result *res, int m, double zncc_min, int accept_unconverged, double *disp3,
+                                              unsigned char *valid) {
+	if (m < 0 || !std::isfinite(zncc_min) || (m > 0 && (!res || !disp3 || !valid))) {
+		set_last_error("sift3d_strain_input_from_icgn2: bad argument");
+		return SIFT3D_ERR_ARG;
+	}
+	for (int i = 0; i < m; i++) valid[i] = icgn2_strain_row(res[i], zncc_min, accept_unconverged, disp3 + 3 * (size_t)i);
+	return SIFT3D_OK;
+}
+
 namespace {
-// the call behind sift3d_icgn (bspline 0) and sift3d_icgn_bspline (bspline 1: kind 2, T read as coefficients; coef 0: they are made
-// here, in the call's scratch)
-int run_icgn(const char *who, const float *ref, int rnx, int rny, int rnz, const float *tar, int tnx, int tny, int tnz, const int *points3, int m,
-             const double *init12, const sift3d_icgn_options *o, int bspline, int coef, int on_device, int device, sift3d_icgn_result *out,
-             double *seconds) {
+// what the shell needs to know of an order: its result record, parameter count, state record and launch function
+struct FirstOrder {
+	typedef sift3d_icgn_result Result;
+	static constexpr int kParameters = 12;
+	static size_t state_bytes() { return icgn_state_bytes(); }
+	static constexpr auto launch = launch_icgn;
+};
+struct SecondOrder {
+	typedef sift3d_icgn2_result Result;
+	static constexpr int kParameters = 30;
+	static size_t state_bytes() { return icgn2_state_bytes(); }
+	static constexpr auto launch = launch_icgn2;
+};
+
+// the call behind sift3d_icgn, sift3d_icgn_bspline and sift3d_icgn2 (max_interpolation, bspline: icgn_args_ok's, which states each
+// call's rules).  B-spline coefficients the caller did not bring (coef 0) are made here, in the call's scratch.
+template <class Order>
+int run_icgn(const char *who, int max_interpolation, bool bspline, const float *ref, int rnx, int rny, int rnz, const float *tar, int tnx, int tny,
+             int tnz, const int *points3, int m, const double *init, const sift3d_icgn_options *o, int coef, int on_device, int device,
+             typename Order::Result *out, double *seconds) {
 	int r, max_it, kind;
 	double tol;
-	if (m < 0 || rnx < 1 || rny < 1 || rnz < 1 || tnx < 1 || tny < 1 || tnz < 1 || !ref || !tar || !out || (m > 0 && !points3) ||
-	    !take_options(o, r, max_it, tol, kind) || (bspline && (kind != 0 || (coef != 0 && coef != 1))) ||
-	    (bspline && !coef && !bspline_prefilter_fits(tnx, tny, tnz))) {
+	if (!icgn_args_ok(ref, rnx, rny, rnz, tar, tnx, tny, tnz, points3, m, o, max_interpolation, bspline, coef, out, r, max_it, tol, kind) ||
+	    (kind == 2 && !coef && !bspline_prefilter_fits(tnx, tny, tnz))) {
 		set_last_error(std::string(who) + ": bad argument");
 		return SIFT3D_ERR_ARG;
 	}
-	if (bspline) kind = 2;
-	const bool filter = bspline && !coef;
+	const bool filter = kind == 2 && !coef;
 	if (seconds) *seconds = 0;
 	int rc = pick_device(device);
 	if (rc) return rc;
 	if (m == 0) return SIFT3D_OK;
 	CallState &S = g_icgn[device];
 	std::lock_guard<std::mutex> lock(S.mu);
-	// device scratch: [results m | state m | (host inputs) ref | tar | points | init | (prefilter) coefficients | the y pass's output];
-	// pinned host: [results]
-	const size_t nr = (size_t)rnx * rny * rnz, nt = (size_t)tnx * tny * tnz, res_bytes = sizeof(sift3d_icgn_result) * (size_t)m;
-	Layout L;
-	L.take(res_bytes);
-	const size_t o_state = L.take(icgn_state_bytes() * (size_t)m), o_ref = L.take(on_device ? 0 : sizeof(float) * nr);
-	const size_t o_tar = L.take(on_device ? 0 : sizeof(float) * nt), o_pts = L.take(on_device ? 0 : sizeof(int) * 3 * (size_t)m);
-	const size_t o_init = L.take(on_device || !init12 ? 0 : sizeof(double) * 12 * (size_t)m);
-	const size_t o_coef = L.take(filter ? sizeof(float) * nt : 0), o_tmp = L.take(filter ? sizeof(float) * nt : 0);
-	if ((rc = S.ensure(L.end, res_bytes))) return rc;
+	const IcgnLayout L = icgn_layout(m, (size_t)rnx * rny * rnz, (size_t)tnx * tny * tnz, on_device != 0, init != nullptr, filter,
+	                                 Order::state_bytes(), sizeof(typename Order::Result), Order::kParameters);
+	if ((rc = S.ensure(L.end, L.res_bytes))) return rc;
 	hipStream_t st = S.stream;
 	char *D = S.d.p, *P = S.h.p;
 	const float *d_ref = ref, *d_tar = tar;
 	const int *d_pts = points3;
-	const double *d_init = init12;
-	if (on_device) {
-		if ((rc = S.after_legacy_stream())) return rc;
-	} else {
-		d_ref = reinterpret_cast<float *>(D + o_ref);
-		d_tar = reinterpret_cast<float *>(D + o_tar);
-		d_pts = reinterpret_cast<int *>(D + o_pts);
-		S3D_HIP_ST(st, hipMemcpyAsync(D + o_ref, ref, sizeof(float) * nr, hipMemcpyHostToDevice, st));
-		S3D_HIP_ST(st, hipMemcpyAsync(D + o_tar, tar, sizeof(float) * nt, hipMemcpyHostToDevice, st));
-		S3D_HIP_ST(st, hipMemcpyAsync(D + o_pts, points3, sizeof(int) * 3 * (size_t)m, hipMemcpyHostToDevice, st));
-		if (init12) {
-			d_init = reinterpret_cast<double *>(D + o_init);
-			S3D_HIP_ST(st, hipMemcpyAsync(D + o_init, init12, sizeof(double) * 12 * (size_t)m, hipMemcpyHostToDevice, st));
-		}
-	}
+	const void *d_init = init;
+	if ((rc = S.stage_pair(L, on_device != 0, d_ref, d_tar, d_pts, d_init))) return rc;
 	S3D_HIP_ST(st, hipEventRecord(S.e0, st));
 	if (filter) {
-		float *d_coef = reinterpret_cast<float *>(D + o_coef);
-		launch_bspline_prefilter(d_tar, tnx, tny, tnz, d_coef, reinterpret_cast<float *>(D + o_tmp), st);
+		float *d_coef = reinterpret_cast<float *>(D + L.o_coef);
+		launch_bspline_prefilter(d_tar, tnx, tny, tnz, d_coef, reinterpret_cast<float *>(D + L.o_tmp), st);
 		S3D_HIP_ST(st, hipGetLastError());
 		d_tar = d_coef;
 	}
-	launch_icgn(IcgnVol{d_ref, rnx, rny, rnz}, IcgnVol{d_tar, tnx, tny, tnz}, d_pts, m, d_init, r, max_it, tol, kind, D + o_state,
-	            reinterpret_cast<sift3d_icgn_result *>(D), st);
+	Order::launch(IcgnVol{d_ref, rnx, rny, rnz}, IcgnVol{d_tar, tnx, tny, tnz}, d_pts, m, static_cast<const double *>(d_init), r, max_it, tol, kind,
+	              D + L.o_state, reinterpret_cast<typename Order::Result *>(D), st);
 	S3D_HIP_ST(st, hipGetLastError());
-	S3D_HIP_ST(st, hipMemcpyAsync(P, D, res_bytes, hipMemcpyDeviceToHost, st));
+	S3D_HIP_ST(st, hipMemcpyAsync(P, D, L.res_bytes, hipMemcpyDeviceToHost, st));
 	S3D_HIP_ST(st, hipEventRecord(S.e1, st));
 	if ((rc = S.finish(seconds))) return rc;
-	memcpy(out, P, res_bytes);
+	memcpy(out, P, L.res_bytes);
 	return SIFT3D_OK;
 }
 }  // namespace
@@ -129,12 +122,20 @@ int run_icgn(const char *who, const float *ref, int rnx, int rny, int rnz, const
 extern "C" int sift3d_icgn(const float *ref, int rnx, int rny, int rnz, const float *tar, int tnx, int tny, int tnz, const int *points3, int m,
                            const double *init12, const sift3d_icgn_options *o, int on_device, int device, sift3d_icgn_result *out,
                            double *seconds) {
-	return run_icgn("sift3d_icgn", ref, rnx, rny, rnz, tar, tnx, tny, tnz, points3, m, init12, o, 0, 0, on_device, device, out, seconds);
+	return run_icgn<FirstOrder>("sift3d_icgn", 1, false, ref, rnx, rny, rnz, tar, tnx, tny, tnz, points3, m, init12, o, 0, on_device, device, out,
+	                            seconds);
 }
 
 extern "C" int sift3d_icgn_bspline(const float *ref, int rnx, int rny, int rnz, const float *tar, int tnx, int tny, int tnz, const int *points3,
                                    int m, const double *init12, const sift3d_icgn_options *o, int tar_is_coefficients, int on_device,
                                    int device, sift3d_icgn_result *out, double *seconds) {
-	return run_icgn("sift3d_icgn_bspline", ref, rnx, rny, rnz, tar, tnx, tny, tnz, points3, m, init12, o, 1, tar_is_coefficients, on_device,
-	                device, out, seconds);
+	return run_icgn<FirstOrder>("sift3d_icgn_bspline", 0, true, ref, rnx, rny, rnz, tar, tnx, tny, tnz, points3, m, init12, o, tar_is_coefficients,
+	                            on_device, device, out, seconds);
+}
+
+extern "C" int sift3d_icgn2(const float *ref, int rnx, int rny, int rnz, const float *tar, int tnx, int tny, int tnz, const int *points3, int m,
+                            const double *init30, const sift3d_icgn_options *o, int tar_is_coefficients, int on_device, int device,
+                            sift3d_icgn2_result *out, double *seconds) {
+	return run_icgn<SecondOrder>("sift3d_icgn2", 2, false, ref, rnx, rny, rnz, tar, tnx, tny, tnz, points3, m, init30, o, tar_is_coefficients,
+	                             on_device, device, out, seconds);
 }

@@ -70,31 +70,19 @@ extern "C" int sift3d_zncc_search(const float *ref, int rnx, int rny, int rnz, c
 	const size_t nr = (size_t)rnx * rny * rnz, nt = (size_t)tnx * tny * tnz, res_bytes = sizeof(sift3d_search_result) * (size_t)m;
 	Layout L;
 	L.take(res_bytes);
-	const size_t o_sc = L.take(search_score_bytes(m, s)), o_ref = L.take(on_device ? 0 : sizeof(float) * nr);
-	const size_t o_tar = L.take(on_device ? 0 : sizeof(float) * nt), o_pts = L.take(on_device ? 0 : sizeof(int) * 3 * (size_t)m);
-	const size_t o_gs = L.take(on_device || !guess3 ? 0 : sizeof(int) * 3 * (size_t)m);
+	const size_t o_sc = L.take(search_score_bytes(m, s));
+	PairPlan in;
+	in.plan(L, on_device != 0, nr, nt, m, guess3 ? sizeof(int) * 3 : 0);
 	if ((rc = S.ensure(L.end, res_bytes))) return rc;
 	hipStream_t st = S.stream;
 	char *D = S.d.p, *P = S.h.p;
 	const float *d_ref = ref, *d_tar = tar;
-	const int *d_pts = points3, *d_gs = guess3;
-	if (on_device) {
-		if ((rc = S.after_legacy_stream())) return rc;
-	} else {
-		d_ref = reinterpret_cast<float *>(D + o_ref);
-		d_tar = reinterpret_cast<float *>(D + o_tar);
-		d_pts = reinterpret_cast<int *>(D + o_pts);
-		S3D_HIP_ST(st, hipMemcpyAsync(D + o_ref, ref, sizeof(float) * nr, hipMemcpyHostToDevice, st));
-		S3D_HIP_ST(st, hipMemcpyAsync(D + o_tar, tar, sizeof(float) * nt, hipMemcpyHostToDevice, st));
-		S3D_HIP_ST(st, hipMemcpyAsync(D + o_pts, points3, sizeof(int) * 3 * (size_t)m, hipMemcpyHostToDevice, st));
-		if (guess3) {
-			d_gs = reinterpret_cast<int *>(D + o_gs);
-			S3D_HIP_ST(st, hipMemcpyAsync(D + o_gs, guess3, sizeof(int) * 3 * (size_t)m, hipMemcpyHostToDevice, st));
-		}
-	}
+	const int *d_pts = points3;
+	const void *d_gs = guess3;
+	if ((rc = S.stage_pair(in, on_device != 0, d_ref, d_tar, d_pts, d_gs))) return rc;
 	S3D_HIP_ST(st, hipEventRecord(S.e0, st));
-	launch_zncc_search(IcgnVol{d_ref, rnx, rny, rnz}, IcgnVol{d_tar, tnx, tny, tnz}, d_pts, m, d_gs, r, s, reinterpret_cast<double *>(D + o_sc),
-	                   reinterpret_cast<sift3d_search_result *>(D), st);
+	launch_zncc_search(IcgnVol{d_ref, rnx, rny, rnz}, IcgnVol{d_tar, tnx, tny, tnz}, d_pts, m, static_cast<const int *>(d_gs), r, s,
+	                   reinterpret_cast<double *>(D + o_sc), reinterpret_cast<sift3d_search_result *>(D), st);
 	S3D_HIP_ST(st, hipGetLastError());
 	S3D_HIP_ST(st, hipMemcpyAsync(P, D, res_bytes, hipMemcpyDeviceToHost, st));
 	S3D_HIP_ST(st, hipEventRecord(S.e1, st));

@@ -1,6 +1,7 @@
 // icgn_subset.h -- what the IC-GN kernels of both orders share (kernels_icgn.hip, kernels_icgn2.hip): the walk over a subset, the
-// fixed-order wave sum and the per-voxel sample of T (the clamp at T's edge, the weights of the three interpolations, the gather).
-// Device code only; every function is inline, so each kernel file compiles its own copy.
+// fixed-order wave sum, the per-voxel sample of T (the clamp at T's edge, the weights of the three interpolations, the gather), the
+// two pieces of the prepare kernels that do not depend on the order (the Rm pass, the LDS Cholesky) and the pick of the iterate
+// kernel by interpolation.  Every function is inline, so each kernel file compiles its own copy.
 #pragma once
 #include "sift3d_internal.h"
 
@@ -104,6 +105,76 @@ __device__ inline float sample_shifted(const IcgnVol &T, const int ci[3], const 
 		tv = fmaf(tz, z1 - z0, z0);
 	}
 	return tv;
+}
+
+// ---- the prepare kernels ---------------------------------------------------------------------------------------------------------
+
+// The two functions below hold barriers and are forced inline: left to the inliner's cost model, one of them became a call in the
+// first-order kernel.  The test of the POI against R's edge stays spelled in both kernels: as a function, in any of a dozen
+// spellings, it cost k_icgn2_prepare two SGPRs.
+
+// Rm: the mean of R over the subset of radius r at q, fp64 in a fixed order through red[][0]; every thread returns the same value.
+// Two barriers: red is free again on return.
+template <int K>
+__device__ __forceinline__ double subset_mean(const IcgnVol &R, const int q[3], int r, double (*red)[K]) {
+	const int D = 2 * r + 1, N = D * D * D;
+	const SubsetWalk W(r);
+	const float *Rq = R.d + vidx(R, q[0], q[1], q[2]);
+	const int sy = R.nx, sz = R.nx * R.ny;
+	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+	double s = 0.0;
+	{
+		int dx, dy, dz;
+		W.start(tid, dx, dy, dz);
+		for (int i = tid; i < N; i += kThreads) {
+			s += (double)Rq[dz * sz + dy * sy + dx];
+			W.next(dx, dy, dz);
+		}
+	}
+	s = wave_sum(s);
+	if (lane == 0) red[wv][0] = s;
+	__syncthreads();
+	const double Rm = (((red[0][0] + red[1][0]) + red[2][0]) + red[3][0]) / (double)N;
+	__syncthreads();
+	return Rm;
+}
+
+// Cholesky H = L L^T in the lower triangle of A (LDS, filled by the caller before the call), a column per step, the trailing update
+// spread over the workgroup.  Returns true (uniform) where a pivot is not positive, or where `bad` (thread 0's word: the caller's own
+// reason to give up) is set.  The flag is read only between the barriers that follow its write.
+template <int N>
+__device__ __forceinline__ bool cholesky_lds(double (*A)[N + 1], int *s_fail, bool bad) {
+	const int tid = threadIdx.x;
+	if (tid == 0) *s_fail = bad;
+	__syncthreads();
+	bool fail = *s_fail;
+	__syncthreads();  // every thread has read the flag before the first pivot may set it
+	for (int k = 0; k < N && !fail; k++) {
+		if (tid == 0) {
+			const double d = A[k][k];
+			if (!(d > 0.0)) *s_fail = 1;
+			A[k][k] = sqrt(d);
+		}
+		__syncthreads();
+		fail = *s_fail;
+		if (fail) break;
+		if (tid > k && tid < N) A[tid][k] = A[tid][k] / A[k][k];
+		__syncthreads();
+		for (int e = tid; e < N * N; e += kThreads) {
+			const int i = e / N, j = e % N;
+			if (j > k && i >= j) A[i][j] = A[i][j] - A[i][k] * A[j][k];
+		}
+		__syncthreads();
+	}
+	return fail;
+}
+
+// ---- the launch functions --------------------------------------------------------------------------------------------------------
+
+// the instantiation of an iterate kernel for launch_icgn's `kind`
+template <class Kernel>
+inline Kernel by_kind(int kind, Kernel keys, Kernel linear, Kernel bspline) {
+	return kind == kKeys ? keys : (kind == kLinear ? linear : bspline);
 }
 
 }  // namespace icgn

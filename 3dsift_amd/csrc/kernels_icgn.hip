@@ -14,20 +14,17 @@
 // (fp64: the variance is their difference); the reduction is fp64.  No float atomics: two calls give the same bits.
 // sift3d_icgn_bspline runs the same two launches with the cubic B-spline weights on the prefiltered T (kernels_bspline.hip): the
 // third instantiation of k_icgn_iterate.
-#include "sift3d_internal.h"
+#include "icgn_subset.h"
 
 #include <math.h>
 
 namespace s3d {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
+using namespace icgn;
+
 constexpr int kPrepSums = 86;  // dR^2, sum R', 12 sum SD, 12 sum SD R', 60 H pieces
 constexpr int kIterSums = 15;  // sum T', sum T'^2, 12 sum SD T', sum R'T' (T' = T - Tc)
-constexpr int kRun = -1;       // IcgnState::status: go on to the iteration
-// how T is interpolated: the values of launch_icgn's `kind` (sift3d_internal.h)
-constexpr int kKeys = 0, kLinear = 1, kBspline = 2;
 
 struct IcgnState {
 	double hinv[144];  // H^-1, row-major
@@ -38,14 +35,6 @@ struct IcgnState {
 	float rm;          // (float)Rm, the shift of T and R in the iterate kernel
 	int status;        // kRun, or the final status the prepare kernel wrote
 };
-
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));  // 4 x-taps of T at dword alignment
-typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
-
-__device__ inline double wave_sum(double x) {
-	for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-	return x;
-}
 
 // the position of the subset offset d under p (fp64, the contract's order): q + F d + (u, v, w)
 __device__ inline void warp_point(const double p[12], const int q[3], double dx, double dy, double dz, double o[3]) {
@@ -73,33 +62,6 @@ __device__ inline bool in_domain(const double p[12], const int q[3], int r, cons
 	}
 	return ok;
 }
-
-// the linear subset index i of offset (dx, dy, dz) advances by kThreads: 256 = sz D^2 + sy D + sx, one carry per axis at most
-struct SubsetWalk {
-	int r, sx, sy, sz;
-	__device__ explicit SubsetWalk(int r_) : r(r_) {
-		const int D = 2 * r + 1;
-		sz = kThreads / (D * D);
-		sy = (kThreads - sz * D * D) / D;
-		sx = kThreads - sz * D * D - sy * D;
-	}
-	__device__ void start(int i, int &dx, int &dy, int &dz) const {
-		const int D = 2 * r + 1;
-		dz = i / (D * D) - r;
-		dy = (i / D) % D - r;
-		dx = i % D - r;
-	}
-	__device__ void next(int &dx, int &dy, int &dz) const {
-		const int D = 2 * r + 1;
-		dx += sx;
-		if (dx > r) { dx -= D; dy++; }
-		dy += sy;
-		if (dy > r) { dy -= D; dz++; }
-		dz += sz;
-	}
-};
-
-__device__ inline size_t vidx(const IcgnVol &V, int x, int y, int z) { return ((size_t)z * V.ny + y) * V.nx + x; }
 
 __device__ inline void write_result(sift3d_icgn_result *o, const double p[12], double zncc, double last, int it, int status) {
 #pragma unroll
@@ -154,21 +116,8 @@ __global__ __launch_bounds__(kThreads) void k_icgn_prepare(IcgnVol R, IcgnVol T,
 	const float *Rq = R.d + vidx(R, q[0], q[1], q[2]);
 	const int sy = R.nx, sz = R.nx * R.ny;
 	// pass 1: Rm
-	double s = 0.0;
-	{
-		int dx, dy, dz;
-		W.start(tid, dx, dy, dz);
-		for (int i = tid; i < N; i += kThreads) {
-			s += (double)Rq[dz * sz + dy * sy + dx];
-			W.next(dx, dy, dz);
-		}
-	}
-	s = wave_sum(s);
-	if (lane == 0) red[wv][0] = s;
-	__syncthreads();
-	const double Rm = (((red[0][0] + red[1][0]) + red[2][0]) + red[3][0]) / (double)N;
+	const double Rm = subset_mean(R, q, r, red);
 	const float rmf = (float)Rm;
-	__syncthreads();
 	// pass 2: the constants
 	double acc[kPrepSums];
 #pragma unroll
@@ -219,29 +168,7 @@ __global__ __launch_bounds__(kThreads) void k_icgn_prepare(IcgnVol R, IcgnVol T,
 		const int i = tid / 12, j = tid % 12;
 		A[i][j] = red[0][26 + h_piece(i, j)];
 	}
-	if (tid == 0) s_fail = !(dr > 0.0);
-	__syncthreads();
-	bool fail = s_fail;
-	__syncthreads();  // every thread has read the flag before the first pivot may set it
-	// Cholesky H = L L^T in A's lower triangle, a column per step; the flag is read only between the barriers that follow its write
-	for (int k = 0; k < 12 && !fail; k++) {
-		if (tid == 0) {
-			const double d = A[k][k];
-			if (!(d > 0.0)) s_fail = 1;
-			A[k][k] = sqrt(d);
-		}
-		__syncthreads();
-		fail = s_fail;
-		if (fail) break;
-		if (tid > k && tid < 12) A[tid][k] = A[tid][k] / A[k][k];
-		__syncthreads();
-		if (tid < 144) {
-			const int i = tid / 12, j = tid % 12;
-			if (j > k && i >= j) A[i][j] = A[i][j] - A[i][k] * A[j][k];
-		}
-		__syncthreads();
-	}
-	if (fail) {
+	if (cholesky_lds<12>(A, &s_fail, !(dr > 0.0))) {
 		if (tid == 0) {
 			S->status = 4;
 			write_result(out + poi, p, 0.0, 0.0, 0, 4);
@@ -326,55 +253,7 @@ __device__ inline double subset_pass(const IcgnVol &R, const IcgnVol &T, const i
 		float o[3];
 #pragma unroll
 		for (int a = 0; a < 3; a++) o[a] = cf[a] + ((F[3 * a] * fx + F[3 * a + 1] * fy) + F[3 * a + 2] * fz);
-		const float flx = floorf(o[0]), fly = floorf(o[1]), flz = floorf(o[2]);
-		// the corner test keeps every tap inside T in fp64; fp32 rounding (cf = 1.0f for a fraction within 2^-25 of 1, cf + F d a
-		// rounding below or onto the next integer) can still put the base tap one voxel outside.  The clamp moves it back and the
-		// fraction takes the difference, so the position is kept (t = 1 or t = -eps at the edge; + 0.f elsewhere: same bits)
-		const int ux = ci[0] + (int)flx, uy = ci[1] + (int)fly, uz = ci[2] + (int)flz;
-		const int gx = min(max(ux, lo), hx), gy = min(max(uy, lo), hy), gz = min(max(uz, lo), hz);
-		const float tx = (o[0] - flx) + (float)(ux - gx), ty = (o[1] - fly) + (float)(uy - gy), tz = (o[2] - flz) + (float)(uz - gz);
-		float tv;
-		if (CUBIC) {
-			float w[3][4];
-			const float t3[3] = {tx, ty, tz};
-#pragma unroll
-			for (int a = 0; a < 3; a++) {
-				const float t = t3[a], t2 = t * t, tq = t2 * t;
-				if (KIND == kBspline) {  // T holds the coefficients
-					const float u = 1.f - t, sixth = 1.f / 6.f;
-					w[a][0] = sixth * ((u * u) * u);
-					w[a][1] = sixth * ((3.f * tq - 6.f * t2) + 4.f);
-					w[a][2] = sixth * (((3.f * t2 - 3.f * tq) + 3.f * t) + 1.f);
-					w[a][3] = sixth * tq;
-				} else {
-					w[a][0] = 0.5f * ((2.f * t2 - tq) - t);
-					w[a][1] = 0.5f * ((3.f * tq - 5.f * t2) + 2.f);
-					w[a][2] = 0.5f * ((4.f * t2 - 3.f * tq) + t);
-					w[a][3] = 0.5f * (tq - t2);
-				}
-			}
-			const float *b = T.d + (((size_t)(gz - 1) * T.ny + (gy - 1)) * T.nx + (gx - 1));
-			tv = 0.f;
-#pragma unroll
-			for (int k = 0; k < 4; k++) {
-				float zv = 0.f;
-#pragma unroll
-				for (int j = 0; j < 4; j++) {
-					const f4u v = *reinterpret_cast<const f4u *>(b + (k * tsz + j * tsy)) - tc;
-					const float row = fmaf(w[0][3], v.w, fmaf(w[0][2], v.z, fmaf(w[0][1], v.y, w[0][0] * v.x)));
-					zv = fmaf(w[1][j], row, zv);
-				}
-				tv = fmaf(w[2][k], zv, tv);
-			}
-		} else {
-			const float *b = T.d + (((size_t)gz * T.ny + gy) * T.nx + gx);
-			const f2u a00 = *reinterpret_cast<const f2u *>(b) - tc, a01 = *reinterpret_cast<const f2u *>(b + tsy) - tc;
-			const f2u a10 = *reinterpret_cast<const f2u *>(b + tsz) - tc, a11 = *reinterpret_cast<const f2u *>(b + tsz + tsy) - tc;
-			const float r00 = fmaf(tx, a00.y - a00.x, a00.x), r01 = fmaf(tx, a01.y - a01.x, a01.x);
-			const float r10 = fmaf(tx, a10.y - a10.x, a10.x), r11 = fmaf(tx, a11.y - a11.x, a11.x);
-			const float z0 = fmaf(ty, r01 - r00, r00), z1 = fmaf(ty, r11 - r10, r10);
-			tv = fmaf(tz, z1 - z0, z0);
-		}
+		const float tv = sample_shifted<KIND>(T, ci, o, tc, lo, hx, hy, hz, tsy, tsz);
 		const float *c = Rq + (dz * sz + dy * sy + dx);
 		const float g[3] = {0.5f * (c[1] - c[-1]), 0.5f * (c[sy] - c[-sy]), 0.5f * (c[sz] - c[-sz])};
 		const float tp = tv, rp = c[0] - rmf;
@@ -522,12 +401,8 @@ void launch_icgn(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_
                  sift3d_icgn_result *d_out, hipStream_t st) {
 	IcgnState *S = static_cast<IcgnState *>(d_state);
 	hipLaunchKernelGGL(k_icgn_prepare, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, kind != kLinear, S, d_out);
-	if (kind == kKeys)
-		hipLaunchKernelGGL(k_icgn_iterate<kKeys>, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out);
-	else if (kind == kLinear)
-		hipLaunchKernelGGL(k_icgn_iterate<kLinear>, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out);
-	else
-		hipLaunchKernelGGL(k_icgn_iterate<kBspline>, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out);
+	hipLaunchKernelGGL(by_kind(kind, k_icgn_iterate<kKeys>, k_icgn_iterate<kLinear>, k_icgn_iterate<kBspline>), dim3(m), dim3(kThreads), 0, st, R, T,
+	                   d_pts, d_init, r, max_it, tol, S, d_out);
 }
 
 }  // namespace s3d

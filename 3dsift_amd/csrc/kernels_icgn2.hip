@@ -117,22 +117,8 @@ __global__ __launch_bounds__(kThreads) void k_icgn2_prepare(IcgnVol R, IcgnVol T
 	const SubsetWalk W(r);
 	const float *Rq = R.d + vidx(R, q[0], q[1], q[2]);
 	const int sy = R.nx, sz = R.nx * R.ny;
-	// Rm
-	double s = 0.0;
-	{
-		int dx, dy, dz;
-		W.start(tid, dx, dy, dz);
-		for (int i = tid; i < N; i += kThreads) {
-			s += (double)Rq[dz * sz + dy * sy + dx];
-			W.next(dx, dy, dz);
-		}
-	}
-	s = wave_sum(s);
-	if (lane == 0) red[wv][0] = s;
-	__syncthreads();
-	const double Rm = (((red[0][0] + red[1][0]) + red[2][0]) + red[3][0]) / (double)N;
+	const double Rm = subset_mean(R, q, r, red);
 	const float rmf = (float)Rm;
-	__syncthreads();
 	// a pass per component a: sum SD and sum SD R' of its ten terms (and, kept from a = 0, dR^2 and sum R')
 #pragma unroll 1
 	for (int a = 0; a < 3; a++) {
@@ -219,29 +205,7 @@ __global__ __launch_bounds__(kThreads) void k_icgn2_prepare(IcgnVol R, IcgnVol T
 		const int pp = a == 0 ? b : (a == 1 ? 2 + b : 5);
 		A[i][j] = hp[pp][mono_index(term_ex(ki) + term_ex(kj), term_ey(ki) + term_ey(kj), term_ez(ki) + term_ez(kj))] * (term_half(ki) * term_half(kj));
 	}
-	if (tid == 0) s_fail = !(dr > 0.0);
-	__syncthreads();
-	bool fail = s_fail;
-	__syncthreads();  // every thread has read the flag before the first pivot may set it
-	// Cholesky H = L L^T in A's lower triangle, a column per step; the flag is read only between the barriers that follow its write
-	for (int k = 0; k < kP && !fail; k++) {
-		if (tid == 0) {
-			const double d = A[k][k];
-			if (!(d > 0.0)) s_fail = 1;
-			A[k][k] = sqrt(d);
-		}
-		__syncthreads();
-		fail = s_fail;
-		if (fail) break;
-		if (tid > k && tid < kP) A[tid][k] = A[tid][k] / A[k][k];
-		__syncthreads();
-		for (int e = tid; e < kP * kP; e += kThreads) {
-			const int i = e / kP, j = e % kP;
-			if (j > k && i >= j) A[i][j] = A[i][j] - A[i][k] * A[j][k];
-		}
-		__syncthreads();
-	}
-	if (fail) {
+	if (cholesky_lds<kP>(A, &s_fail, !(dr > 0.0))) {
 		if (tid == 0) {
 			S->status = 4;
 			write_result(out + poi, p0, 0.0, 0.0, 0, 4);
@@ -606,12 +570,8 @@ void launch_icgn2(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d
                   sift3d_icgn2_result *d_out, hipStream_t st) {
 	Icgn2State *S = static_cast<Icgn2State *>(d_state);
 	hipLaunchKernelGGL(k_icgn2_prepare, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, kind != kLinear, S, d_out);
-	if (kind == kKeys)
-		hipLaunchKernelGGL(k_icgn2_iterate<kKeys>, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out);
-	else if (kind == kLinear)
-		hipLaunchKernelGGL(k_icgn2_iterate<kLinear>, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out);
-	else
-		hipLaunchKernelGGL(k_icgn2_iterate<kBspline>, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out);
+	hipLaunchKernelGGL(by_kind(kind, k_icgn2_iterate<kKeys>, k_icgn2_iterate<kLinear>, k_icgn2_iterate<kBspline>), dim3(m), dim3(kThreads), 0, st, R,
+	                   T, d_pts, d_init, r, max_it, tol, S, d_out);
 }
 
 }  // namespace s3d

@@ -18,4 +18,21 @@ struct Layout {
 	}
 };
 
+// The inputs of a call on a volume pair: ref, tar, m integer points and an optional fourth table of m rows.  Already on the device
+// they take no room; from the host they are pieces of the scratch block, in that order, which CallState::stage_pair (call_state.h)
+// fills.  b_*: the bytes to upload.
+struct PairPlan {
+	size_t o_ref = 0, o_tar = 0, o_pts = 0, o_opt = 0, b_ref = 0, b_tar = 0, b_pts = 0, b_opt = 0;
+	void plan(Layout &L, bool on_device, size_t nr, size_t nt, int m, size_t opt_row_bytes) {  // opt_row_bytes 0: no fourth table
+		b_ref = on_device ? 0 : sizeof(float) * nr;
+		b_tar = on_device ? 0 : sizeof(float) * nt;
+		b_pts = on_device ? 0 : sizeof(int) * 3 * (size_t)m;
+		b_opt = on_device ? 0 : opt_row_bytes * (size_t)m;
+		o_ref = L.take(b_ref);
+		o_tar = L.take(b_tar);
+		o_pts = L.take(b_pts);
+		o_opt = L.take(b_opt);
+	}
+};
+
 }  // namespace s3d

@@ -147,7 +147,7 @@ PROGRAM = r"""
 
 #include <vector>
 
-#include "icgn2_host.h"
+#include "icgn_host.h"
 
 #define CHECK(c) do { if (!(c)) { printf("line %d: %s\n", __LINE__, #c); return 1; } } while (0)
 
@@ -182,36 +182,60 @@ int main() {
 	CHECK(icgn2_strain_row(second[0], 0.96, 0, d) == 0);
 	CHECK(icgn2_strain_row(second[1], 0.9, 0, d) == 0 && icgn2_strain_row(second[1], 0.9, 1, d) == 1);
 	CHECK(icgn2_strain_row(second[2], 0.9, 0, d) == 0 && d[2] == INFINITY);
-	// the layout: pieces in order, aligned, absent pieces take no room
-	for (int m : {1, 7, 30000})
-		for (int dev = 0; dev < 2; dev++)
-			for (int ini = 0; ini < 2; ini++)
-				for (int fil = 0; fil < 2; fil++) {
-					const size_t nr = 64 * 64 * 64, nt = 61 * 64 * 64, sb = 4224;
-					const Icgn2Layout L = icgn2_layout(m, nr, nt, dev, ini, fil, sb);
-					const size_t at[8] = {0, L.o_state, L.o_ref, L.o_tar, L.o_pts, L.o_init, L.o_coef, L.o_tmp};
-					const size_t by[8] = {L.res_bytes, sb * m, dev ? 0 : 4 * nr, dev ? 0 : 4 * nt, dev ? 0 : (size_t)12 * m,
-					                      dev || !ini ? 0 : (size_t)240 * m, fil ? 4 * nt : 0, fil ? 4 * nt : 0};
-					CHECK(L.res_bytes == (size_t)272 * m);
-					size_t end = 0;
-					for (int i = 0; i < 8; i++) {
-						CHECK(at[i] == end && at[i] % 256 == 0);
-						end += al256(by[i]);
+	// the layout: pieces in order, aligned, absent pieces take no room; second order (30 parameters, 272-byte records), then first
+	// order (12 parameters, 128-byte records)
+	for (int order = 2; order >= 1; order--)
+		for (int m : {1, 7, 30000})
+			for (int dev = 0; dev < 2; dev++)
+				for (int ini = 0; ini < 2; ini++)
+					for (int fil = 0; fil < 2; fil++) {
+						const size_t nr = 64 * 64 * 64, nt = 61 * 64 * 64, sb = order == 2 ? 4224 : 1368;
+						const size_t rb = order == 2 ? sizeof(sift3d_icgn2_result) : sizeof(sift3d_icgn_result), np = order == 2 ? 30 : 12;
+						const IcgnLayout L = icgn_layout(m, nr, nt, dev, ini, fil, sb, rb, (int)np);
+						const size_t at[8] = {0, L.o_state, L.o_ref, L.o_tar, L.o_pts, L.o_opt, L.o_coef, L.o_tmp};
+						const size_t by[8] = {L.res_bytes, sb * m, dev ? 0 : 4 * nr, dev ? 0 : 4 * nt, dev ? 0 : (size_t)12 * m,
+						                      dev || !ini ? 0 : (size_t)8 * np * m, fil ? 4 * nt : 0, fil ? 4 * nt : 0};
+						CHECK(L.res_bytes == (size_t)(order == 2 ? 272 : 128) * m);
+						size_t end = 0;
+						for (int i = 0; i < 8; i++) {
+							CHECK(at[i] == end && at[i] % 256 == 0);
+							end += al256(by[i]);
+						}
+						CHECK(L.end == end);
 					}
-					CHECK(L.end == end);
-				}
-	// the argument check
+	// the argument check: sift3d_icgn2 (interpolation 0..2, coefficients only with 2)
 	int r, it, kind;
 	double tol;
 	int x = 0;
 	sift3d_icgn_options o = {10, 5, 0.f, 2, {0, 0, 0, 0}};
-	CHECK(icgn2_args_ok(&x, 1, 1, 1, &x, 1, 1, 1, &x, 1, &o, 1, &x, r, it, tol, kind) && r == 10 && it == 5 && tol == 0 && kind == 2);
-	CHECK(icgn2_args_ok(&x, 1, 1, 1, &x, 1, 1, 1, nullptr, 0, nullptr, 0, &x, r, it, tol, kind) && r == 16 && it == 20 && kind == 0);
-	CHECK(!icgn2_args_ok(&x, 1, 1, 1, &x, 1, 1, 1, nullptr, 1, nullptr, 0, &x, r, it, tol, kind));
-	CHECK(!icgn2_args_ok(&x, 1, 1, 1, &x, 1, 1, 1, &x, 1, nullptr, 1, &x, r, it, tol, kind));
-	CHECK(!icgn2_args_ok(&x, 1, 1, 1, &x, 1, 1, 1, &x, 1, &o, 2, &x, r, it, tol, kind));
+	CHECK(icgn_args_ok(&x, 1, 1, 1, &x, 1, 1, 1, &x, 1, &o, 2, false, 1, &x, r, it, tol, kind) && r == 10 && it == 5 && tol == 0 && kind == 2);
+	CHECK(icgn_args_ok(&x, 1, 1, 1, &x, 1, 1, 1, nullptr, 0, nullptr, 2, false, 0, &x, r, it, tol, kind) && r == 16 && it == 20 && kind == 0);
+	CHECK(!icgn_args_ok(&x, 1, 1, 1, &x, 1, 1, 1, nullptr, 1, nullptr, 2, false, 0, &x, r, it, tol, kind));
+	CHECK(!icgn_args_ok(&x, 1, 1, 1, &x, 1, 1, 1, &x, 1, nullptr, 2, false, 1, &x, r, it, tol, kind));
+	CHECK(!icgn_args_ok(&x, 1, 1, 1, &x, 1, 1, 1, &x, 1, &o, 2, false, 2, &x, r, it, tol, kind));
 	o.interpolation = 3;
-	CHECK(!icgn2_args_ok(&x, 1, 1, 1, &x, 1, 1, 1, &x, 1, &o, 0, &x, r, it, tol, kind));
+	CHECK(!icgn_args_ok(&x, 1, 1, 1, &x, 1, 1, 1, &x, 1, &o, 2, false, 0, &x, r, it, tol, kind));
+	// sift3d_icgn (interpolation 0 or 1, no coefficients)
+	for (int k = -1; k <= 3; k++) {
+		o.interpolation = k;
+		const bool ok = icgn_args_ok(&x, 1, 1, 1, &x, 1, 1, 1, &x, 1, &o, 1, false, 0, &x, r, it, tol, kind);
+		CHECK(ok == (k == 0 || k == 1));
+		if (ok) CHECK(kind == k && r == 10 && it == 5);
+	}
+	CHECK(icgn_args_ok(&x, 1, 1, 1, &x, 1, 1, 1, &x, 1, nullptr, 1, false, 0, &x, r, it, tol, kind) && r == 16 && it == 20 && kind == 0);
+	// sift3d_icgn_bspline (interpolation 0 only, run as kind 2; tar_is_coefficients 0 or 1)
+	for (int k = -1; k <= 3; k++)
+		for (int coef = -1; coef <= 2; coef++) {
+			o.interpolation = k;
+			const bool ok = icgn_args_ok(&x, 1, 1, 1, &x, 1, 1, 1, &x, 1, &o, 0, true, coef, &x, r, it, tol, kind);
+			CHECK(ok == (k == 0 && (coef == 0 || coef == 1)));
+			if (ok) CHECK(kind == 2);
+		}
+	CHECK(icgn_args_ok(&x, 1, 1, 1, &x, 1, 1, 1, &x, 1, nullptr, 0, true, 1, &x, r, it, tol, kind) && kind == 2 && r == 16);
+	// the defaults come from one place
+	const sift3d_icgn_options def = icgn_default_options();
+	CHECK(def.subset_radius == 16 && def.max_iterations == 20 && def.tolerance == 1e-3f && def.interpolation == 0);
+	CHECK(!def.reserved[0] && !def.reserved[1] && !def.reserved[2] && !def.reserved[3]);
 	printf("ok\n");
 	return 0;
 }
