@@ -126,9 +126,10 @@ def solve_rows(f, B):
     return X
 
 
-def compose(p, dp):
-    """the parameters of M(p) M(dp)^-1, or None when M(dp) is singular"""
-    f = lu(M_of(dp))
+def compose(p, dp, f=False):
+    """the parameters of M(p) M(dp)^-1, or None when M(dp) is singular; f: the factors of M(dp) (lu's return) where the caller has them"""
+    if f is False:
+        f = lu(M_of(dp))
     if f is None:
         return None
     M = np.zeros((10, 10))
@@ -159,7 +160,8 @@ def in_domain(shape, p, q, r, cubic):
 
 
 def refine(R, T, q, init=None, subset_radius=16, max_iterations=20, tolerance=1e-3, interpolation=0, f32=False, coefficients_given=False):
-    """one POI: dict(p, zncc, last_step, iterations, status) as sift3d_icgn2_result, and steps.  interpolation 2: T is prefiltered
+    """one POI: dict(p, zncc, last_step, iterations, status) as sift3d_icgn2_result, steps (the norm of every computed step) and perms
+    (the row permutation of the LU of M(dp) for every step that reached it; None: singular).  interpolation 2: T is prefiltered
     (bspline_ref) unless coefficients_given"""
     if interpolation == 2:
         C = bspline_ref.coefficients(T, coefficients_given)
@@ -171,11 +173,11 @@ def refine(R, T, q, init=None, subset_radius=16, max_iterations=20, tolerance=1e
 def _refine(R, T, q, init, r, max_iterations, tolerance, cubic, f32):
     q = np.asarray(q, np.int64)
     p = np.zeros(30) if init is None else np.array(init, np.float64)
-    steps = []
+    steps, perms = [], []
 
     def res(p, zncc, last, it, status):
         return dict(p=np.array(p, np.float64), zncc=float(zncc), last_step=float(last), iterations=int(it), status=int(status),
-                    steps=tuple(steps))
+                    steps=tuple(steps), perms=tuple(perms))
 
     if not np.all(np.isfinite(p)):
         return res(p, 0, 0, 0, 5)
@@ -224,7 +226,9 @@ def _refine(R, T, q, init, r, max_iterations, tolerance, cubic, f32):
         steps.append(last)
         if not np.all(np.isfinite(dp)):
             return res(p, zncc, last, it, 6)
-        pn = compose(p, dp)
+        f = lu(M_of(dp))
+        perms.append(None if f is None else tuple(int(i) for i in f[1]))
+        pn = compose(p, dp, f)
         if pn is None:
             return res(p, zncc, last, it, 6)
         if not in_domain(T.shape, pn, q, r, cubic):
@@ -258,7 +262,8 @@ def icgn2(R, T, points, init=None, interpolation=0, coefficients_given=False, **
     p = np.array([w["p"] for w in out]).reshape(-1, 30)
     e = p.reshape(-1, 3, 10)
     return {"p": p, "displacement": e[:, :, 0].copy(), "gradient": e[:, :, 1:4].copy(), "second": e[:, :, 4:].copy(),
-            **{k: np.array([w[k] for w in out]) for k in ("zncc", "last_step", "iterations", "status")}, "steps": [w["steps"] for w in out]}
+            **{k: np.array([w[k] for w in out]) for k in ("zncc", "last_step", "iterations", "status")}, "steps": [w["steps"] for w in out],
+            "perms": [w["perms"] for w in out]}
 
 
 def init_from_icgn(p12, status):

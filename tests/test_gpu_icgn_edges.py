@@ -91,36 +91,7 @@ def spike_volume():
     return blobs((n, n, n), seed=21)
 
 
-def sentinels(r):
-    """linear subset indices (x fastest) worth a spike: both corners, the last voxel of a thread's first round and the first of its
-    second, the first voxels that k_icgn's walk reaches through a carry into y and into z, two seeded random ones (six at least)"""
-    D = 2 * r + 1
-    N = D ** 3
-    sz = 256 // (D * D)
-    sy = (256 - sz * D * D) // D
-    sx = 256 - sz * D * D - sy * D
-    out = {"first": 0, "last": N - 1}
-    if N > 255:
-        out["i255"] = 255
-    if N > 256:
-        out["i256"] = 256
-        for i in range(256, N):
-            j = i - 256
-            cx = j % D + sx >= D
-            if cx and "ycarry" not in out:
-                out["ycarry"] = i
-            if (j // D) % D + sy + cx >= D and "zcarry" not in out:
-                out["zcarry"] = i
-            if "ycarry" in out and "zcarry" in out:
-                break
-    rng = np.random.default_rng(2000 + r)
-    k = 0
-    while len(out) < 6 or k < 2:
-        i = int(rng.integers(1, N - 1))
-        if i not in out.values():
-            out[f"rand{k}"] = i
-            k += 1
-    return out
+sentinels = ref.sentinels  # one definition for both orders: the walk is shared
 
 
 def spike_amplitude(r):
