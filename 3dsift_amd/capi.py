@@ -1261,6 +1261,13 @@ def describe_keypoint(level, unit, kp, device=0):
     return desc
 
 
+def describe_keypoint_second_passes():
+    """second passes (0 or 1) of this thread's last describe_keypoint: the first fixed-point unit failed and the window was repeated"""
+    a = (C.c_int * 4)()
+    _check(lib().sift3d_debug_counters(None, a))
+    return a[3]
+
+
 class muBruteMatcher:
     """Python mirror of CPUSIFT::muBruteMatcher (Include/cMatcher.h:12-88)."""
 

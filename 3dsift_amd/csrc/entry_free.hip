@@ -85,6 +85,7 @@ struct OneKp {
 };
 std::mutex g_onekp_mu;
 OneKp g_onekp;  // (never destroyed at exit: the HIP runtime may be gone by then)
+thread_local int t_onekp_redo = 0;  // sift3d_debug_counters c[3]
 
 struct Box { int lo[3], n[3]; };  // first voxel of the box in the level, box dimensions
 
@@ -165,6 +166,7 @@ int onekp_check(const float *level, int nx, int ny, int nz, const sift3d_keypoin
 	return SIFT3D_OK;
 }
 }  // namespace
+namespace s3d { int onekp_second_passes() { return t_onekp_redo; } }
 
 // kp in: x, y, z (voxel of the level), scale; out: win, eigvalue, eigvector, Rotation (as Assign_Orientation_Imp leaves it: not
 // transposed), str_tensor (computed from zero: the reference accumulates into what Initialize_Keypoint zeroed).  *code: the reference's
@@ -231,13 +233,17 @@ extern "C" int sift3d_describe_keypoint(const float *level, int nx, int ny, int 
 	launch_slots(c->d_ext, c->d_codes, c->d_total, c->ext_cap, c->d_nkp, c->d_order, c->kp_cap, c->d_slots_part, st);
 	launch_describe(c->d_ext, c->d_total, c->ext_cap, c->d_levels, c->d_luts, c->d_lutpool, c->d_desc, c->kp_cap, 0, 1, c->d_order, c->d_nkp, c->d_nkp + 1, st,
 	                c->desc_lut_lds, &c->dsplit);
+	launch_describe_overflow(c->d_ext, 0u, c->d_levels, c->d_luts, c->d_lutpool, c->d_desc, st);  // (a caller-held level need not be normalised)
 	launch_finalize(c->d_ext, c->d_total, c->ext_cap, 1, c->d_kpout, c->d_xyz, c->kp_cap, st);
 	sift3d_keypoint out;
+	unsigned redone = 0;  // k_describe's count of windows that took the second pass (d_work[1])
+	S3D_HIP(hipMemcpyAsync(&redone, c->d_nkp + 2, sizeof(redone), hipMemcpyDeviceToHost, st));
 	S3D_HIP(hipMemcpyAsync(desc768, c->d_desc, sizeof(float) * kDesc, hipMemcpyDeviceToHost, st));
 	S3D_HIP(hipMemcpyAsync(&out, c->d_kpout, sizeof(out), hipMemcpyDeviceToHost, st));
 	S3D_HIP(hipStreamSynchronize(st));
 	S3D_HIP(hipGetLastError());
 	for (int i = 0; i < 9; i++) kp->Rotation[i] = out.Rotation[i];
+	t_onekp_redo = (int)redone;
 	return SIFT3D_OK;
 }
 

@@ -84,7 +84,7 @@ extern "C" int sift3d_debug_counters(sift3d_handle c, int out[4]) {
 	out[0] = c ? c->n_regrow : 0;
 	out[1] = c ? c->n_desc_redo : 0;
 	out[2] = match_redo_rows();
-	out[3] = 0;
+	out[3] = onekp_second_passes();
 	return SIFT3D_OK;
 }
 

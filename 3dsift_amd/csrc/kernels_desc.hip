@@ -384,6 +384,13 @@ __device__ __forceinline__ float pick_scale_d(float mass, float provable) {
 	const float p2 = __uint_as_float(__float_as_uint(q) & 0xFF800000u);
 	return fminf(fmaxf(p2, provable), 536870912.0f);
 }
+// WinLut::fix_scale, the floor of the unit, is proved (tables.hip) for the pipeline's NORMALISED data only: |g| <= sqrt(3) per voxel, so a
+// window's gradient mass is at most sqrt(3) times the sum of its weights (WinLut::wsum).  A caller-held level (sift3d_describe_keypoint)
+// need not be normalised: a measured mass (x 1.001) above that bound has no floor -- with it the second pass wrapped the 32-bit bins of a
+// level of amplitude 2^20 and above (tests/test_gpu_describe_edges.py::test_amplitude: rows off by 0.03 RMS).  Never taken by the
+// pipeline's windows.  (No ceiling above 2^29 is needed for tiny amplitudes: a voxel that passes the reference's absolute |g|^2 >= 1.19e-6
+// test contributes at least 1.09e-3, 6e5 units of 2^-29.)
+__device__ __forceinline__ float unit_floor(float mass, const WinLut &lut) { return mass <= 1.7321f * 1.002f * lut.wsum ? lut.fix_scale : 0.0f; }
 // ... of the FIRST pass: from an estimate of the gradient mass (rms gradient of the orientation window, from the structure tensor, times
 // the descriptor window's weight sum, with 4x head room) -- a function of the keypoint's record and the level's tables alone, so every
 // GPU that marches a part of the window (PARTIAL) uses the same unit.  dev_flags bits 8..: the hook SIFT3D_HOOK_DESC_MASS_SHIFT (estimate / 2^s)
@@ -423,9 +430,20 @@ __device__ __forceinline__ bool unit_fails(float mass, float fix_scale, float pr
 // histogram then holds a NaN, its first normalisation makes the whole row NaN, and its truncation `d < thresh ? d : thresh` replaces
 // every NaN by the threshold: the row ends as the CONSTANT row.  The same arithmetic runs here on a row of NaN (block-uniform; one
 // comparison for every other window).
+// The reference's row of a histogram that holds a NaN: its first normalisation makes every element NaN, the clamp `d < t ? d : t` makes it
+// t = (float)(0.2 * 128 / 768) = 0x3D088889, the second normalisation divides by norm = (float)((double)sqrtf(s) + DBL_EPSILON) with s =
+// t * t added 768 times one after the other in fp32 (0.8533281, norm 0.9237576): t * (float)(1.0 / (double)norm) = 0.036084503.
+// tests/test_gpu_describe_edges.py holds the poisoned windows to the oracle's row bit for bit.
+constexpr unsigned kConstRow = 0x3D13CD58u;
 __device__ __forceinline__ void normalise_store(float v0, float v1, float v2, int te, int lane, int wid, float *red /*[>= 4]*/, float *out, float mass) {
 	const float trunc_thresh = (float)(0.2 * 128 / kDesc);
-	if (!(mass <= FLT_MAX)) v0 = v1 = v2 = __builtin_nanf("");
+	if (!(mass <= FLT_MAX)) {
+		// block-uniform.  The constant row the reference makes of its all-NaN row (kConstRow; the tree sum and v_sqrt_f32 of the general
+		// path were one float off it)
+		const float cv = __uint_as_float(kConstRow);
+		if (te < 256) { out[te] = cv; out[te + 256] = cv; out[te + 512] = cv; }
+		return;
+	}
 	for (int pass = 0; pass < 2; pass++) {
 		float s = v0 * v0 + v1 * v1 + v2 * v2;
 #pragma unroll
@@ -944,7 +962,7 @@ __global__ void __launch_bounds__(NT) S3D_DESC_ATTR k_describe(const DevKp *__re
 			for (int q = 0; q < S; q++) mass_sum = mass_sum + __hip_atomic_load(&sp.gmass[kpos * 8 + q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // part order: deterministic
 		}
 		const float mass = mass_sum * 1.001f;
-		if (attempt == 1 || !unit_fails(mass, fix_scale, lut.fix_scale, lut.nin)) {
+		if (attempt == 1 || !unit_fails(mass, fix_scale, unit_floor(mass, lut), lut.nin)) {
 			finished = true;
 			win_mass = mass;
 			break;
@@ -958,7 +976,7 @@ __global__ void __launch_bounds__(NT) S3D_DESC_ATTR k_describe(const DevKp *__re
 			S = 1;
 		}
 		if (tid == 0) atomicAdd(d_work + 1, 1u);
-		fix_scale = pick_scale_d(mass, lut.fix_scale);  // exact bound: this pass cannot overflow
+		fix_scale = pick_scale_d(mass, unit_floor(mass, lut));  // exact bound: this pass cannot overflow
 		}
 		if (!finished) continue;  // block-uniform: not this workgroup's keypoint to finish (a split part, or sent to the redo list)
 		int te = tid;  // (opaque, see above)
@@ -1030,6 +1048,112 @@ void launch_face_lookup(const float *d_g3, int n, int route, int *d_face, float 
 	hipLaunchKernelGGL(k_face_lookup, dim3(std::max(1, std::min((n + 255) / 256, 1024))), dim3(256), 0, st, d_g3, n, route, d_face, d_bary3);
 }
 
+// ---- windows whose gradient OVERFLOWS (sift3d_describe_keypoint on a level that is not normalised: a finite voxel of 3e38 beside the
+// window).  The central differences stay finite, |g|^2 = +Inf.  The reference's float histogram then holds +-Inf in the bins such a voxel
+// reaches (NaN where a weight is 0 or both signs meet), its first normalisation (norm = Inf, 1 / norm = 0) turns those bins into NaN and
+// every other bin into 0, the clamp the NaN into the threshold, the second normalisation divides by the root of their count.  k_describe's
+// integer bins cannot hold an Inf: the voxel poisons the window's mass and the row comes out as the constant row (normalise_store).  This
+// kernel, launched by the one-keypoint entry behind launch_describe (the pipeline normalises its volume: |g| <= sqrt(3), no overflow),
+// looks at such a constant row again: one plain pass over the window with the reference's arithmetic marks the bins the overflowing
+// voxels reach; a NaN anywhere leaves the constant row, otherwise the marked bins get the reference's value and the others 0.
+__global__ void __launch_bounds__(256) k_describe_overflow(const DevKp *__restrict__ kps, unsigned k, const LevelRef *__restrict__ levels,
+                                                           const WinLut *__restrict__ luts, const float *__restrict__ lutpool,
+                                                           float *__restrict__ d_desc) {
+	__shared__ unsigned marks[kDesc];
+	__shared__ int s_flag[2];  // a NaN contribution / gradient; an overflowing voxel
+	const int tid = threadIdx.x;
+	const int slot = kps[k].slot;
+	if (slot < 0) return;
+	float *row = d_desc + (size_t)slot * kDesc;
+	const float trunc_thresh = (float)(0.2 * 128 / kDesc);
+	{  // only the constant row is looked at again (block-uniform)
+		const bool same = row[tid] == row[0] && row[tid + 256] == row[0] && row[tid + 512] == row[0] && row[0] > 0.0f;
+		if (!__syncthreads_and(same)) return;
+	}
+	for (int i = tid; i < kDesc; i += 256) marks[i] = 0u;
+	if (tid < 2) s_flag[tid] = 0;
+	__syncthreads();
+	const int cxi = kps[k].x, cyi = kps[k].y, czi = kps[k].z;
+	const int li = kps[k].octave * 8 + kps[k].level;
+	const LevelRef L = levels[li];
+	const WinLut lut = luts[li * 2 + 1];
+	const float R0 = kps[k].rot[0], R1 = kps[k].rot[3], R2 = kps[k].rot[6];
+	const float R3 = kps[k].rot[1], R4 = kps[k].rot[4], R5 = kps[k].rot[7];
+	const float R6 = kps[k].rot[2], R7 = kps[k].rot[5], R8 = kps[k].rot[8];
+	const float sigma = kps[k].scale * 7.071067812f;
+	const float win_radius = 2.0f * sigma;
+	const float desc_hw = (float)((double)win_radius / sqrt(2.0));
+	const float bin_fctr = __fdiv_rn(4.0f, 2.0f * desc_hw);
+	const float u = L.unit;
+	int x0, x1, y0, y1, z0, z1;
+	win_bounds_d((float)cxi, win_radius, u, L.nx, x0, x1);
+	win_bounds_d((float)cyi, win_radius, u, L.ny, y0, y1);
+	win_bounds_d((float)czi, win_radius, u, L.nz, z0, z1);
+	const int wx = x1 - x0 + 1, wy = y1 - y0 + 1, wz = z1 - z0 + 1;
+	const int nvox = (wx > 0 && wy > 0 && wz > 0) ? wx * wy * wz : 0;
+	const size_t sy = (size_t)L.nx, sz = (size_t)L.nx * L.ny;
+	for (int base = 0; base < nvox; base += 256) {  // block-uniform trip count (intersect_scan votes)
+		const int v = base + tid;
+		bool over = false;
+		float vb0 = 0.f, vb1 = 0.f, vb2 = 0.f, rx = 1.f, ry = 0.f, rz = 0.f;
+		if (v < nvox) {
+			const int lz = v / (wx * wy), r2 = v - lz * wx * wy, ly = r2 / wx, lx = r2 - ly * wx;
+			const int x = x0 + lx, y = y0 + ly, z = z0 + lz;
+			const int dx = x - cxi, dy = y - cyi, dz = z - czi;
+			const int n = dx * dx + dy * dy + dz * dz;
+			const float w = n <= lut.nin && n < lut.len ? lutpool[lut.off + n] : -1.0f;  // expf(-0.5 sq / sigma^2) * (0.5 / u), or outside
+			if (!(w < 0.0f)) {
+				const float d0 = (float)dx * u, d1 = (float)dy * u, d2 = (float)dz * u;
+				vb0 = (R0 * d0 + R1 * d1 + R2 * d2 + desc_hw) * bin_fctr - 0.5f;
+				vb1 = (R3 * d0 + R4 * d1 + R5 * d2 + desc_hw) * bin_fctr - 0.5f;
+				vb2 = (R6 * d0 + R7 * d1 + R8 * d2 + desc_hw) * bin_fctr - 0.5f;
+				if (!(vb0 <= -0.5f || vb1 <= -0.5f || vb2 <= -0.5f || vb0 >= 3.5f || vb1 >= 3.5f || vb2 >= 3.5f)) {
+					const float *c = L.d + (size_t)x + sy * (size_t)y + sz * (size_t)(z - L.zoff);
+					const float gx = (c[1] - c[-1]) * w, gy = (c[sy] - *(c - sy)) * w, gz = (c[sz] - *(c - sz)) * w;
+					const float tx = R0 * gx + R1 * gy + R2 * gz, ty = R3 * gx + R4 * gy + R5 * gz, tz = R6 * gx + R7 * gy + R8 * gz;
+					const float g2 = tx * tx + ty * ty + tz * tz;
+					if (!(g2 == g2)) s_flag[0] = 1;            // a NaN gradient: the reference's row is the constant row
+					else if (g2 > FLT_MAX) { over = true; rx = tx; ry = ty; rz = tz; }
+				}
+			}
+		}
+		if (__any(over)) {  // wave-uniform
+			float b[3] = {0.f, 0.f, 0.f};
+			const int f = intersect_scan(rx, ry, rz, b[0], b[1], b[2]);
+			if (over && f >= 0) {
+				s_flag[1] = 1;
+				const float dv0 = vb0 - floorf(vb0), dv1 = vb1 - floorf(vb1), dv2 = vb2 - floorf(vb2);
+				for (int d = 0; d < 8; d++) {
+					const int ddx = d >> 2, ddy = (d >> 1) & 1, ddz = d & 1;
+					const int bx = (int)vb0 + ddx, by = (int)vb1 + ddy, bz = (int)vb2 + ddz;  // truncation, like the reference
+					if (bx < 0 || by < 0 || bz < 0 || bx >= 4 || by >= 4 || bz >= 4) continue;
+					const float wt = (float)((ddx ? (double)dv0 : 1.0 - (double)dv0) * (ddy ? (double)dv1 : 1.0 - (double)dv1) * (ddz ? (double)dv2 : 1.0 - (double)dv2));
+					const float mw = __builtin_inff() * wt;  // mag * w: Inf, or NaN for a weight of 0
+					for (int j = 0; j < 3; j++) {
+						const float cj = mw * b[j];
+						atomicOr(&marks[(bx + by * 4 + bz * 16) * 12 + c_faces[f].idx[j]], !(cj == cj) ? 4u : (cj > 0.0f ? 1u : 2u));
+					}
+				}
+			}
+		}
+	}
+	__syncthreads();
+	bool bad = false;
+	for (int i = tid; i < kDesc; i += 256) { const unsigned m = marks[i]; bad = bad || m == 3u || m >= 4u; }
+	if (__syncthreads_or(bad) || s_flag[0] || !s_flag[1]) return;  // NaN in the reference's histogram, or nothing overflowed: the row stands
+	int total = 0;
+	for (int i = 0; i < kDesc; i++) total += marks[i] != 0u;
+	float n2 = 0.0f;
+	for (int i = 0; i < total; i++) n2 = n2 + trunc_thresh * trunc_thresh;  // the reference's sequential sum over the marked bins (zeros add nothing)
+	const float cn = (float)((double)sqrtf(n2) + DBL_EPSILON);
+	const float cv = trunc_thresh * (float)(1.0 / (double)cn);
+	for (int i = tid; i < kDesc; i += 256) row[i] = marks[i] != 0u ? cv : 0.0f;
+}
+void launch_describe_overflow(const DevKp *kps, unsigned k, const LevelRef *d_levels, const WinLut *d_luts, const float *d_lutpool, float *d_desc,
+                              hipStream_t st) {
+	hipLaunchKernelGGL(k_describe_overflow, dim3(1), dim3(256), 0, st, kps, k, d_levels, d_luts, d_lutpool, d_desc);
+}
+
 void launch_describe(const DevKp *kps, const unsigned *d_count, unsigned cap, const LevelRef *d_levels, const WinLut *d_luts,
                      const float *d_lutpool, float *d_desc, unsigned kp_cap, int part_rank, int part_world, const int *order,
                      const unsigned *d_nkp, unsigned *d_work, hipStream_t st, bool lut_in_lds, const DescSplit *split) {
@@ -1084,8 +1208,8 @@ __global__ void __launch_bounds__(256) k_describe_finish(const DevKp *__restrict
 		float msum = 0.0f;
 		for (int p = 0; p < fp.nparts; p++) msum = msum + fp.mass[p][k];
 		const float m = msum * 1.001f;
-		if (!final_round && unit_fails(m, fix_scale, lut.fix_scale, lut.nin)) {
-			if (tid == 0) { redo[k] = 1; units_next[k] = pick_scale_d(m, lut.fix_scale); atomicAdd(d_counters, 1u); }
+		if (!final_round && unit_fails(m, fix_scale, unit_floor(m, lut), lut.nin)) {
+			if (tid == 0) { redo[k] = 1; units_next[k] = pick_scale_d(m, unit_floor(m, lut)); atomicAdd(d_counters, 1u); }
 			continue;
 		}
 		if (tid == 0 && redo != nullptr) redo[k] = 0;

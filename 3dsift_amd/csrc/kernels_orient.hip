@@ -93,7 +93,19 @@ __device__ __forceinline__ float dot3f(const float *a, const float *b) { return 
 
 // everything after the window sums (Src/cSIFT3D.cc:1000-1137), executed by one lane
 // *near (may be null): set when the extremum is accepted or any test lies within a margin of its threshold -- the fast sums carry
-// a relative error of ~1e-6, the margins are 100x that
+// a relative error of ~1e-6, the margins are 100x that: kRatioMargin on the two eigenvalue ratios, 1e-4 on the corner cosine, 1e-13 on
+// |mean gradient|^2.  These assume eigenvalues of one size.  The tensor's error moves EVERY eigenvalue by ~1e-6 val[2] whatever its own
+// size, so r01 = |val[0] / val[1]| is uncertain by that over |val[1]|: its margin grows by 0.1 val[2] / |val[1]| once val[1] is below a
+// tenth of val[2] (10x the error, like kEigNoise below); and when two eigenvalues lie within kEigNoise val[2] of each other their
+// eigenvectors, and with them the corner cosine and the DistinctEig test, are the rounding's: near.
+// Found on pure ramps (tests/test_gpu_orient_edges.py::test_every_code: a rank-one tensor, val[0] and val[1] are rounding noise of
+// either sign around 1e-8 val[2]; measured gap: the screen's r01 came out above 0.9 where the reference's is 0.06 and 0.07): the screen
+// gave -2 unflagged where the reference's noise passes the ratio test and fails the corner test (-3).  The reference's eigenvalues of the two
+// cases: (-2.4e-10, 3.76e-9, 4.72e-3) and (8.2e-10, 1.109e-8, 1.582e-2), |val[1]| / val[2] = 8.0e-7 and 7.0e-7, val[1] - val[0] = 0.8e-6 and
+// 0.65e-6 of val[2] (the screen's own eigenvalues were not read out).  With them the margin on r01 is 1e-4 * 0.1 / 8e-7 = 12.5 and the
+// pair lies 12x inside kEigNoise; an eigenvalue an order above the sums' error (1e-6 val[2]; measured 1.2e-7 .. 3.9e-7 of sum |term|,
+// tests/test_gpu_orient_edges.py) is what both factors are set to catch.
+constexpr float kRatioMargin = 1.0e-4f, kEigNoise = 1.0e-5f;
 __device__ int finish_orientation(DevKp &kp, const float T6[6], const float w3[3], float max_eig_ratio, float corner_thresh, bool *near = nullptr) {
 	bool nr = false;
 	float T[9] = {T6[0], T6[1], T6[2], T6[1], T6[3], T6[4], T6[2], T6[4], T6[5]};
@@ -129,18 +141,23 @@ __device__ int finish_orientation(DevKp &kp, const float T6[6], const float w3[3
 		kp.eigvector[3 * j] = vec[j][0]; kp.eigvector[3 * j + 1] = vec[j][1]; kp.eigvector[3 * j + 2] = vec[j][2];
 	}
 	const float r01 = fabsf(__fdiv_rn(val[0], val[1])), r12 = fabsf(__fdiv_rn(val[1], val[2]));
-	nr = nr || fabsf(r01 - max_eig_ratio) <= 1e-4f || fabsf(r12 - max_eig_ratio) <= 1e-4f || !(r01 == r01) || !(r12 == r12);
+	const float m01 = kRatioMargin * fmaxf(1.0f, __fdiv_rn(0.1f * fabsf(val[2]), fabsf(val[1])));  // (val[1] = 0: Inf or NaN, near either way)
+	nr = nr || !(fabsf(r01 - max_eig_ratio) > m01) || fabsf(r12 - max_eig_ratio) <= kRatioMargin || !(r01 == r01) || !(r12 == r12);
+	nr = nr || !(val[1] - val[0] > kEigNoise * fabsf(val[2])) || !(val[2] - val[1] > kEigNoise * fabsf(val[2]));
 	if (near) *near = nr;
 	if (r01 > max_eig_ratio || r12 > max_eig_ratio) return -2;
 	if ((double)fabsf(val[0] - val[1]) < DBL_EPSILON || (double)fabsf(val[0] - val[2]) < DBL_EPSILON ||
 	    (double)fabsf(val[2] - val[1]) < DBL_EPSILON)
 		return -2;
 
-	const float d_norm = __fsqrt_rn(dot3f(w3, w3));
+	// sqrtf: correctly rounded, like the reference's.  (__fsqrt_rn is the hardware's v_sqrt_f32 in this toolchain, 1 ulp: the corner cosine
+	// came out one float above the reference's for 3 of 24 keypoints of tests/test_gpu_orient_edges.py::test_thresholds_from_both_sides,
+	// which a corner_thresh planted on that float turns into code 1 against the reference's -3.)
+	const float d_norm = sqrtf(dot3f(w3, w3));
 	float corner = FLT_MAX;
 	for (int i = 2; i > 0; i--) {
 		const float d = dot3f(vec[i], w3);
-		const float q_norm = __fsqrt_rn(dot3f(vec[i], vec[i]));
+		const float q_norm = sqrtf(dot3f(vec[i], vec[i]));
 		const float cos_ang = __fdiv_rn(d, d_norm * q_norm);
 		const float a = fabsf(cos_ang);
 		corner = corner < a ? corner : a;

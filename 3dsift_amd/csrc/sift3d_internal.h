@@ -316,6 +316,9 @@ struct MatchGuard {
 int match_rows_device(const float *d_a, const int *d_row_ids, int nrows, const float *d_b, int m, int *d_cand /*nrows*4*/,
                       void *d_part, float *d_gd, float *d_sd, int *d_gi, int *d_si, const MatchGuard &g, hipStream_t st);
 int match_redo_rows();  // rows the last sift3d_match re-scored exactly (near-tie guard)
+void launch_describe_overflow(const DevKp *kps, unsigned k, const LevelRef *d_levels, const WinLut *d_luts, const float *d_lutpool, float *d_desc,
+                              hipStream_t st);  // one-keypoint entry: a window whose |g|^2 overflows (kernels_desc.hip)
+int onekp_second_passes();  // second descriptor passes of the calling thread's last sift3d_describe_keypoint (entry_free.hip)
 
 // ---- kernels_ransac.hip: RANSAC affine fits (sift3d_fit_affine / sift3d_fit_affine_local, include/sift3d_hip.h) ----------------
 uint32_t ransac_seed(uint32_t seed);  // s = fmix32(seed ^ 0x9E3779B9)

@@ -145,7 +145,11 @@ int sift3d_conv_axis(const float *src, int nx, int ny, int nz, int dim, const fl
  * the box of the level the window reaches.  The keypoint sits on a voxel (integral x, y, z), as every keypoint of the pipeline does;
  * anything else is refused.  orient: in x, y, z, scale; out win, eigvalue, eigvector, Rotation (not transposed), str_tensor and *code =
  * the reference's return value (1 / -1 / -2 / -3).  describe: in x, y, z, scale, Rotation as orientation left it (+ str_tensor: first
- * guess of the fixed-point unit only); out desc768 (normalised) and Rotation TRANSPOSED, like Src/cSIFT3D.cc:1214 leaves it. */
+ * guess of the fixed-point unit only); out desc768 (normalised) and Rotation TRANSPOSED, like Src/cSIFT3D.cc:1214 leaves it.  The level
+ * need not be normalised: any amplitude whose gradients are finite gives the reference's row within the descriptor tolerance, a NaN / Inf
+ * gradient in the window its constant row, and a finite gradient whose square overflows (|g| > 1.8e19) the row the reference's float
+ * histogram ends as (Inf in the bins that voxel reaches: those bins equal, the others 0) -- describe handles that case in a pass of its
+ * own behind the descriptor kernel. */
 int sift3d_orient_keypoint(const float *level, int nx, int ny, int nz, float unit, sift3d_keypoint *kp, float sigma, float max_eig_ratio,
                            float corner_thresh, int device, int *code);
 int sift3d_describe_keypoint(const float *level, int nx, int ny, int nz, float unit, sift3d_keypoint *kp, float *desc768, int device);

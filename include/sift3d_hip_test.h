@@ -40,7 +40,8 @@ enum {
 };
 int sift3d_test_hook(int which, int value);
 /* how often the rare paths ran: c[0] list regrows of the last run, c[1] keypoints whose descriptor took the second pass in
- * the last run, c[2] rows the calling thread's last sift3d_match re-scored exactly (near-tie guard), c[3] reserved */
+ * the last run, c[2] rows the calling thread's last sift3d_match re-scored exactly (near-tie guard), c[3] second passes of the calling thread's last
+ * sift3d_describe_keypoint (0 or 1; h may be NULL) */
 int sift3d_debug_counters(sift3d_handle h, int c[4]);
 /* GB/s (read + write, best of `iters`) of a float4 device-to-device copy of `bytes` bytes on `device`: the measured copy ceiling
  * reported beside the 8 TB/s spec peak */
