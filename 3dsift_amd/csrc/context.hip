@@ -173,6 +173,12 @@ static int octaves_of(int nx, int ny, int nz) {  // Src/cSIFT3D.cc:254-255
 	return std::max(0, (int)log2f((float)mn) - 3 + 1);
 }
 
+float level_scale(const sift3d_params &p, int octave, int s) {
+	const double sigma0 = (double)p.sigma_default * pow(2.0, -1.0 / 3.0);
+	const double scale_factor = pow(2.0, (double)octave + (double)s / (double)p.num_kp_levels);
+	return (float)(scale_factor * sigma0);
+}
+
 void plan_pyramid(sift3d_ctx *c, int noct_total) {
 	c->noct = noct_total >= 0 ? std::max(0, noct_total - c->octave_base) : octaves_of(c->nx, c->ny, c->nz);
 	if (c->slab) c->noct = std::min(c->noct, 1);
@@ -180,7 +186,6 @@ void plan_pyramid(sift3d_ctx *c, int noct_total) {
 	c->nd = c->p.num_kp_levels + 2;
 	c->gss.assign((size_t)c->noct * c->ng, Level());
 	c->dog.assign((size_t)c->noct * c->nd, Level());
-	const double sigma0 = (double)c->p.sigma_default * pow(2.0, -1.0 / 3.0);
 	for (int pyr = 0; pyr < 2; pyr++) {
 		const int interval = pyr ? c->nd : c->ng;
 		std::vector<Level> &P = pyr ? c->dog : c->gss;
@@ -190,8 +195,7 @@ void plan_pyramid(sift3d_ctx *c, int noct_total) {
 			for (int s = 0; s < interval; s++) {
 				Level &L = P[(size_t)o * interval + s];
 				L.nx = nx; L.ny = ny; L.nz = nz; L.unit = u;
-				const double scale_factor = pow(2.0, (double)(o + c->octave_base) + (double)s / (double)c->p.num_kp_levels);
-				L.scale = (float)(scale_factor * sigma0);
+				L.scale = level_scale(c->p, o + c->octave_base, s);
 				if (c->slab) { L.bz = c->own1 - c->own0 + 2 * c->halo; L.zoff = c->own0 - c->halo; }
 			}
 			nx /= 2; ny /= 2; nz /= 2;
@@ -517,6 +521,26 @@ static bool smooth_level(sift3d_ctx *c, int o, const float *src, const Level &ds
 	return false;
 }
 
+// the detection table of the context's octave slot o (a slab context holds one octave: o = 0): DoG levels 1 .. nd-2 (Src/cSIFT3D.cc:376)
+// and, where the run elides them, the Gaussian levels that stand in for DoG[0], DoG[nd-1] and the lazy last Gaussian level
+void fill_detect_levels(const sift3d_ctx *c, int o, DetectLevels &DL) {
+	memset(&DL, 0, sizeof(DL));
+	const Level *G = &c->gss[(size_t)o * c->ng], *D = &c->dog[(size_t)o * c->nd];
+	const int nl = c->nd - 2;
+	for (int i = 1; i <= nl; i++) {
+		DL.cur[i - 1] = D[i].d; DL.prev[i - 1] = D[i - 1].d; DL.next[i - 1] = D[i + 1].d;
+		DL.absmax_bits[i - 1] = c->d_dogmax + (size_t)o * c->nd + i;
+		DL.level_id[i - 1] = i;
+		DL.scale[i - 1] = D[i].scale;
+	}
+	if (c->dog_elide) {
+		DL.prev0_hi = G[1].d; DL.prev0_lo = G[0].d;
+		DL.nextl_hi = G[c->nd].d; DL.nextl_lo = G[c->nd - 1].d;
+		DL.nextl_slot = nl - 1;
+		if (c->g_last_elide) { DL.nextl_hi = nullptr; DL.lazy_src = DL.nextl_lo; }
+	}
+}
+
 // One run = prepare (flags of the run) -> enqueue (the whole pipeline on the handle's streams, up to the asynchronous read-back of the
 // five counters into pinned memory; no host synchronisation) -> finish (synchronise, check the list capacity, fill state and times;
 // on overflow: regrow and enqueue again).  sift3d_run / sift3d_run_stages do all three; sift3d_run_async stops behind the first
@@ -714,24 +738,7 @@ static int run_enqueue(sift3d_ctx *c, int upto, bool part_orient) {
 		dopt.max_offset = c->dopt.max_offset; dopt.contrast_thresh = c->dopt.contrast_thresh; dopt.edge_ratio = c->dopt.edge_ratio;
 		const DetectOpts *dop = c->run_full ? &dopt : nullptr;  // null: the reference rule (k_mark)
 		if (upto >= 3)
-			for (int o = 0; o < c->noct; o++) {
-				DetectLevels &DL = DLs[(size_t)o];
-				memset(&DL, 0, sizeof(DL));
-				for (int i = 1; i <= nl; i++) {
-					DL.cur[i - 1] = c->dog[(size_t)o * c->nd + i].d;
-					DL.prev[i - 1] = c->dog[(size_t)o * c->nd + i - 1].d;
-					DL.next[i - 1] = c->dog[(size_t)o * c->nd + i + 1].d;
-					DL.absmax_bits[i - 1] = c->d_dogmax + (size_t)o * c->nd + i;
-					DL.level_id[i - 1] = i;
-					DL.scale[i - 1] = c->dog[(size_t)o * c->nd + i].scale;
-				}
-				if (c->dog_elide) {
-					DL.prev0_hi = c->gss[(size_t)o * c->ng + 1].d; DL.prev0_lo = c->gss[(size_t)o * c->ng].d;
-					DL.nextl_hi = c->gss[(size_t)o * c->ng + c->nd].d; DL.nextl_lo = c->gss[(size_t)o * c->ng + c->nd - 1].d;
-					DL.nextl_slot = nl - 1;
-					if (c->g_last_elide) { DL.nextl_hi = nullptr; DL.lazy_src = DL.nextl_lo; }
-				}
-			}
+			for (int o = 0; o < c->noct; o++) fill_detect_levels(c, o, DLs[(size_t)o]);
 		hipStream_t sb = two ? c->ostream[1] : st;
 		if (early) {
 			const Level &C0 = c->dog[(size_t)0 * c->nd + 1];

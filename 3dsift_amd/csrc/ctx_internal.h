@@ -140,7 +140,9 @@ bool append_lut(std::vector<float> &pool, WinLut &L, int which, float sigma, flo
 // context.hip
 int set_device(int device);
 int alloc_lists(sift3d_ctx *c, unsigned ext_cap);
+float level_scale(const sift3d_params &p, int octave, int s);  // scale of level s of the ABSOLUTE octave (Src/cUtil.cc:215-225)
 void plan_pyramid(sift3d_ctx *c, int noct_total);
+void fill_detect_levels(const sift3d_ctx *c, int o, DetectLevels &DL);
 int upload_luts(sift3d_ctx *c, const std::vector<WinLut> &luts, std::vector<float> &pool);
 std::vector<WinLut> blank_luts(const sift3d_ctx *c);
 size_t arena_floats_of(const sift3d_ctx *c);

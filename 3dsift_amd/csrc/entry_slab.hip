@@ -19,6 +19,13 @@ using namespace s3d;
 // =============================================================================================================
 // Multi-GPU sharding entry points (include/sift3d_hip.h): seeded tail contexts and z-slab contexts of octave 0
 // =============================================================================================================
+// the head of an entry point that works on a run's results: complete an asynchronous run in flight, require stage >= s, select the device
+static int enter_at_stage(sift3d_ctx *c, int s) {
+	if (c->pending) { int wrc = sift3d_wait(c); if (wrc) return wrc; }
+	if (c->stage < s) return SIFT3D_ERR_STATE;
+	return set_device(c->device);
+}
+
 extern "C" int sift3d_create_seeded(sift3d_handle *out, int nx, int ny, int nz, int octave_base, int noct_total,
                                     const sift3d_params *params, int device) {
 	if (!out || octave_base < 0 || octave_base > 20) { set_last_error("sift3d_create_seeded: bad argument"); return SIFT3D_ERR_ARG; }
@@ -45,28 +52,64 @@ extern "C" int sift3d_set_describe_partition(sift3d_handle c, int rank, int worl
 	return SIFT3D_OK;
 }
 
-// planes a keypoint's descriptor window can reach along z in octave 0 (Src/cSIFT3D.cc:1155-1156, 1276-1290: window
-// [floor(c-r), ceil(c+r)] plus the central-difference neighbours), and never less than the widest Gaussian + 1
-extern "C" int sift3d_slab_min_halo(const sift3d_params *params, int *halo) {
-	if (!halo) return SIFT3D_ERR_ARG;
-	sift3d_params p;
-	if (params) p = *params; else sift3d_default_params(&p);
-	if (p.num_kp_levels < 1 || p.num_kp_levels > 5) return SIFT3D_ERR_ARG;
-	const double sigma0 = (double)p.sigma_default * pow(2.0, -1.0 / 3.0);
-	const float scale = (float)(pow(2.0, (double)p.num_kp_levels / (double)p.num_kp_levels) * sigma0);  // DoG level num_kp_levels, octave 0
-	const float radius = 2.0f * (scale * 7.071067812f);
-	int h = (int)ceilf(radius) + 2;
-	std::vector<float> sig;
-	float base_sigma;
-	level_sigmas(p, sig, base_sigma);
-	for (size_t i = 1; i < sig.size(); i++) {
-		Taps t;
-		if (!build_taps(sig[i], t)) return SIFT3D_ERR_ARG;
-		h = std::max(h, t.hw + 1);
-	}
-	*halo = h;
+// ---- the level schedule and the keypoint windows' reach: what the parameter-only entry points and the slab contexts plan their halos with ----
+// the last Gaussian level is evaluated at parked candidates (k_lazy_next) instead of being built while its kernel fits that kernel's slots
+static bool last_level_lazy(const Taps &last) { return 2 * (2 * last.hw + 1) <= kLazySlots; }
+
+struct SlabSchedule {
+	sift3d_params p;           // the caller's, or the defaults; num_kp_levels validated
+	std::vector<float> sig;    // per Gaussian level of an octave (level_sigmas)
+	float base_sigma = 0;
+	std::vector<Taps> taps;    // taps[i] builds G[i] from G[i-1]; taps[0]: the base blur of the input
+	bool levels_ok = true, base_ok = true;  // build_taps took every level / the base blur (it refuses kernels wider than it supports)
+	bool last_lazy = false;    // last_level_lazy of the last level
+	int ng() const { return (int)sig.size(); }
+};
+static int slab_schedule(const sift3d_params *params, SlabSchedule &s) {
+	if (params) s.p = *params; else sift3d_default_params(&s.p);
+	if (s.p.num_kp_levels < 1 || s.p.num_kp_levels > 5) return SIFT3D_ERR_ARG;
+	level_sigmas(s.p, s.sig, s.base_sigma);
+	s.taps.resize(s.sig.size());
+	for (int i = 1; i < s.ng(); i++) s.levels_ok = build_taps(s.sig[(size_t)i], s.taps[(size_t)i]) && s.levels_ok;
+	s.base_ok = build_taps(s.base_sigma, s.taps[0]);
+	s.last_lazy = s.levels_ok && last_level_lazy(s.taps.back());
 	return SIFT3D_OK;
 }
+
+// planes along z that the windows of a keypoint of this scale reach beyond its own plane, on levels of this unit, without any margin:
+// the descriptor window [floor(c - r), ceil(c + r)] (Src/cSIFT3D.cc:1155-1156, 1276-1290) and the orientation window, a sphere of
+// 3 * 1.5 * scale (Src/cSIFT3D.cc:925-955).  (Not build_luts' (1.5f * scale) * 3.0f: that rounds differently and belongs to the kernels' tables.)
+struct WindowReach { int desc, ori; };
+static WindowReach window_reach(float scale, float unit) {
+	return WindowReach{(int)ceilf(__builtin_fabsf(2.0f * (scale * 7.071067812f)) / unit), (int)floorf(4.5f * scale / unit)};
+}
+// ... of keypoint level i of a context, with the margins the level buffers carry: whole descriptor windows + 2 (the window's own rounding plane
+// and the central difference), or -- r05, partial windows: every rank marches the window planes it OWNS, the halo only carries the orientation
+// window of a keypoint on the slab's face -- the orientation window + 1 (the central difference)
+static int level_window_planes(const sift3d_ctx *c, int i, bool whole_descriptor_windows) {
+	const WindowReach r = window_reach(c->dog[(size_t)i].scale, c->dog[(size_t)i].unit);
+	return whole_descriptor_windows ? r.desc + 2 : r.ori + 1;
+}
+
+// planes per side the level buffers of octave 0 need for the widest keypoint level's windows, and never less than the widest Gaussian + 1
+static int slab_min_window_halo(const SlabSchedule &s, bool whole_descriptor_windows) {
+	const WindowReach r = window_reach(level_scale(s.p, 0, s.p.num_kp_levels), 1.0f);  // DoG level num_kp_levels, octave 0, unit 1
+	// whole: + 2 as in level_window_planes; partial: + 1 for the central difference and + 1 spare plane
+	int h = whole_descriptor_windows ? r.desc + 2 : r.ori + 2;
+	for (int i = 1; i < s.ng(); i++) h = std::max(h, s.taps[(size_t)i].hw + 1);
+	return h;
+}
+static int slab_min_halo_of(const sift3d_params *params, bool whole_descriptor_windows, int *halo) {
+	if (!halo) return SIFT3D_ERR_ARG;
+	SlabSchedule s;
+	int rc = slab_schedule(params, s);
+	if (rc) return rc;
+	if (!s.levels_ok) return SIFT3D_ERR_ARG;
+	*halo = slab_min_window_halo(s, whole_descriptor_windows);
+	return SIFT3D_OK;
+}
+extern "C" int sift3d_slab_min_halo(const sift3d_params *params, int *halo) { return slab_min_halo_of(params, true, halo); }
+extern "C" int sift3d_slab_min_halo_partial(const sift3d_params *params, int *halo) { return slab_min_halo_of(params, false, halo); }
 
 // would the slab contexts take an octave of these GLOBAL dims?  Every level a slab builds goes through the z-march kernel (no separable fallback for
 // slabs): half widths 2 .. 8, planes of one tile or >= 32 + hw, and a column of at least 2 hw + 2 planes (r06: a sharding plan whose deepest octave
@@ -74,21 +117,15 @@ extern "C" int sift3d_slab_min_halo(const sift3d_params *params, int *halo) {
 extern "C" int sift3d_slab_admits(const sift3d_params *params, int nx, int ny, int nz, int first_octave, int *ok) {
 	if (!ok || nx <= 0 || ny <= 0 || nz <= 0) return SIFT3D_ERR_ARG;
 	*ok = 0;
-	sift3d_params p;
-	if (params) p = *params; else sift3d_default_params(&p);
-	if (p.num_kp_levels < 1 || p.num_kp_levels > 5) return SIFT3D_ERR_ARG;
-	std::vector<float> sig;
-	float base_sigma;
-	level_sigmas(p, sig, base_sigma);
-	const int ng = (int)sig.size();
-	Taps t;
-	for (int i = 1; i < ng; i++) {
-		if (!build_taps(sig[(size_t)i], t)) return SIFT3D_OK;
-		// the last Gaussian level is evaluated at parked candidates instead of being built while its kernel fits k_lazy_next (sift3d_slab_level)
-		if (i == ng - 1 && 2 * (2 * t.hw + 1) <= kLazySlots) continue;
-		if (!march_applicable(nx, ny, nz, t)) return SIFT3D_OK;
+	SlabSchedule s;
+	int rc = slab_schedule(params, s);
+	if (rc) return rc;
+	if (!s.levels_ok) return SIFT3D_OK;
+	for (int i = 1; i < s.ng(); i++) {
+		if (i == s.ng() - 1 && s.last_lazy) continue;  // never built
+		if (!march_applicable(nx, ny, nz, s.taps[(size_t)i])) return SIFT3D_OK;
 	}
-	if (first_octave && (!build_taps(base_sigma, t) || !march_applicable(nx, ny, nz, t))) return SIFT3D_OK;  // the base blur of the input
+	if (first_octave && (!s.base_ok || !march_applicable(nx, ny, nz, s.taps[0]))) return SIFT3D_OK;  // the base blur of the input
 	*ok = 1;
 	return SIFT3D_OK;
 }
@@ -97,9 +134,7 @@ extern "C" int sift3d_slab_admits(const sift3d_params *params, int nx, int ny, i
 // only knows its own allocations can reduce / gather them
 extern "C" int sift3d_export_device(sift3d_handle c, float *d_desc_dst, float *d_xyz_dst) {
 	if (!c) return SIFT3D_ERR_ARG;
-	if (c->pending) { int wrc = sift3d_wait(c); if (wrc) return wrc; }  // an asynchronous run in flight is completed first
-	if (c->stage < 5) return SIFT3D_ERR_STATE;
-	int rc = set_device(c->device);
+	int rc = enter_at_stage(c, 5);
 	if (rc) return rc;
 	if (d_desc_dst && c->n_kp) S3D_HIP(hipMemcpyAsync(d_desc_dst, c->d_desc, sizeof(float) * kDesc * (size_t)c->n_kp, hipMemcpyDeviceToDevice, c->stream));
 	if (d_xyz_dst && c->n_kp) S3D_HIP(hipMemcpyAsync(d_xyz_dst, c->d_xyz, sizeof(float) * 3 * (size_t)c->n_kp, hipMemcpyDeviceToDevice, c->stream));
@@ -111,9 +146,7 @@ extern "C" int sift3d_export_device(sift3d_handle c, float *d_desc_dst, float *d
 // partitioned describe), so that sift3d_get_keypoints / sift3d_device_results / sift3d_match see complete rows
 extern "C" int sift3d_import_descriptors_device(sift3d_handle c, const float *d_desc_src) {
 	if (!c || !d_desc_src) return SIFT3D_ERR_ARG;
-	if (c->pending) { int wrc = sift3d_wait(c); if (wrc) return wrc; }  // an asynchronous run in flight is completed first
-	if (c->stage < 5) return SIFT3D_ERR_STATE;
-	int rc = set_device(c->device);
+	int rc = enter_at_stage(c, 5);
 	if (rc) return rc;
 	if (c->n_kp) S3D_HIP(hipMemcpyAsync(c->d_desc, d_desc_src, sizeof(float) * kDesc * (size_t)c->n_kp, hipMemcpyDeviceToDevice, c->stream));
 	S3D_HIP(hipStreamSynchronize(c->stream));
@@ -129,9 +162,7 @@ extern "C" int sift3d_run_partial_orientation(sift3d_handle c) {
 
 extern "C" int sift3d_export_orientation_device(sift3d_handle c, int *d_dst) {
 	if (!c || !d_dst) return SIFT3D_ERR_ARG;
-	if (c->pending) { int wrc = sift3d_wait(c); if (wrc) return wrc; }  // an asynchronous run in flight is completed first
-	if (c->stage < 4) return SIFT3D_ERR_STATE;
-	int rc = set_device(c->device);
+	int rc = enter_at_stage(c, 4);
 	if (rc) return rc;
 	launch_orient_pack(c->d_ext, c->d_total, c->ext_cap, d_dst, c->part_rank, c->part_world, c->stream);
 	S3D_HIP(hipStreamSynchronize(c->stream));
@@ -140,9 +171,7 @@ extern "C" int sift3d_export_orientation_device(sift3d_handle c, int *d_dst) {
 
 extern "C" int sift3d_import_orientation_device(sift3d_handle c, const int *d_src) {
 	if (!c || !d_src) return SIFT3D_ERR_ARG;
-	if (c->pending) { int wrc = sift3d_wait(c); if (wrc) return wrc; }  // an asynchronous run in flight is completed first
-	if (c->stage < 4) return SIFT3D_ERR_STATE;
-	int rc = set_device(c->device);
+	int rc = enter_at_stage(c, 4);
 	if (rc) return rc;
 	launch_orient_unpack(c->d_ext, c->d_codes, c->d_total, c->ext_cap, d_src, c->stream);
 	S3D_HIP(hipStreamSynchronize(c->stream));
@@ -153,9 +182,8 @@ extern "C" int sift3d_import_orientation_device(sift3d_handle c, const int *d_sr
 // handle's share of the descriptors, final records
 extern "C" int sift3d_run_describe(sift3d_handle c) {
 	if (!c) return SIFT3D_ERR_ARG;
-	if (c->pending) { int wrc = sift3d_wait(c); if (wrc) return wrc; }  // an asynchronous run in flight is completed first
-	if (c->stage < 4 || c->slab) return SIFT3D_ERR_STATE;
-	int rc = set_device(c->device);
+	if (c->slab) return SIFT3D_ERR_STATE;  // (a slab context never has an asynchronous run in flight: nothing to complete in front of this)
+	int rc = enter_at_stage(c, 4);
 	if (rc) return rc;
 	hipStream_t st = c->stream;
 	S3D_HIP(hipEventRecord(c->ev[6], st));
@@ -293,15 +321,9 @@ extern "C" int sift3d_slab_halo_planes(sift3d_handle c, int i, int *planes) {
 	// right-boundary lerp of the last planes of the volume, Src/cSIFT3D.cc:751-760)
 	if (i + 1 < c->ng) need = c->taps[i + 1].hw + 1;
 	if (i >= 1 && i <= c->p.num_kp_levels) {
-		// orientation / descriptor windows of the keypoints of level i live on G[i]: the z reach of ITS descriptor window (r03; before:
+		// orientation / descriptor windows of the keypoints of level i live on G[i]: the z reach of ITS windows (r03; before:
 		// the reach of the widest level for all of them: 3 x 38 planes per side instead of 24 + 30 + 38 with the default parameters)
-		const float radius = 2.0f * (c->dog[(size_t)i].scale * 7.071067812f);
-		const int desc_reach = (int)ceilf(__builtin_fabsf(radius) / c->dog[(size_t)i].unit) + 2;
-		// r05, partial descriptor windows: every rank marches the window planes it OWNS (plus one plane either side for the central
-		// difference), so the halo of G[i] only carries the orientation window of a keypoint on the slab's face: sphere of
-		// 3 * 1.5 * scale (Src/cSIFT3D.cc:925-955), i.e. floor(4.5 scale / unit) planes, + 1 for the central difference
-		const int ori_reach = (int)floorf(4.5f * c->dog[(size_t)i].scale / c->dog[(size_t)i].unit) + 1;
-		need = std::max(need, c->desc_partial ? ori_reach : desc_reach);
+		need = std::max(need, level_window_planes(c, i, !c->desc_partial));
 	}
 	*planes = std::min(need, c->halo);
 	return SIFT3D_OK;
@@ -317,11 +339,7 @@ extern "C" int sift3d_slab_halo_planes(sift3d_handle c, int i, int *planes) {
 static void slab_ghost_extents(const sift3d_ctx *c, bool last_lazy, int *g /* [ng] */) {
 	for (int i = c->ng - 1; i >= 0; i--) {
 		int need = 1;  // the z neighbours of the extremum test (every Gaussian level feeds a DoG level)
-		if (i >= 1 && i <= c->p.num_kp_levels) {
-			const float sc = c->dog[(size_t)i].scale, u = c->dog[(size_t)i].unit;
-			const int desc_reach = (int)ceilf(__builtin_fabsf(2.0f * (sc * 7.071067812f)) / u) + 2, ori_reach = (int)floorf(4.5f * sc / u) + 1;
-			need = std::max(need, c->desc_partial ? ori_reach : desc_reach);
-		}
+		if (i >= 1 && i <= c->p.num_kp_levels) need = std::max(need, level_window_planes(c, i, !c->desc_partial));
 		if (i + 1 < c->ng) {
 			const int hw1 = c->taps[i + 1].hw;
 			const bool built = !(last_lazy && i + 1 == c->ng - 1);
@@ -330,9 +348,10 @@ static void slab_ghost_extents(const sift3d_ctx *c, bool last_lazy, int *g /* [n
 		g[i] = need;
 	}
 }
-static bool slab_last_lazy(const sift3d_ctx *c) {  // (the rule of sift3d_slab_level)
-	return !hook(SIFT3D_HOOK_DOG_EAGER) && c->nd >= 3 && !hook(SIFT3D_HOOK_GLAST_EAGER) && 2 * (2 * c->taps[c->ng - 1].hw + 1) <= kLazySlots;
-}
+// this run neither materialises the first and the last DoG level of the octave ...
+static bool slab_dog_elide(const sift3d_ctx *c) { return !hook(SIFT3D_HOOK_DOG_EAGER) && c->nd >= 3; }
+// ... nor builds the last Gaussian level (the context's own taps are the schedule of its parameters)
+static bool slab_last_lazy(const sift3d_ctx *c) { return slab_dog_elide(c) && !hook(SIFT3D_HOOK_GLAST_EAGER) && last_level_lazy(c->taps[c->ng - 1]); }
 extern "C" int sift3d_slab_set_ghost(sift3d_handle c, int on) {
 	if (!c || !c->slab) return SIFT3D_ERR_ARG;
 	if (on) {
@@ -350,23 +369,15 @@ extern "C" int sift3d_slab_set_ghost(sift3d_handle c, int on) {
 // halo planes per side a slab context needs for ghost zones (partial: descriptor windows split along z; else whole windows)
 extern "C" int sift3d_slab_min_halo_ghost(const sift3d_params *params, int partial, int *halo) {
 	if (!halo) return SIFT3D_ERR_ARG;
-	int win = 0;
-	int rc = partial ? sift3d_slab_min_halo_partial(params, &win) : sift3d_slab_min_halo(params, &win);
+	SlabSchedule s;
+	int rc = slab_schedule(params, s);
 	if (rc) return rc;
-	sift3d_params p;
-	if (params) p = *params; else sift3d_default_params(&p);
-	std::vector<float> sig;
-	float base_sigma;
-	level_sigmas(p, sig, base_sigma);
-	const int ng = (int)sig.size();
-	std::vector<int> hw((size_t)ng, 0);
-	Taps t;
-	for (int i = 1; i < ng; i++) { if (!build_taps(sig[(size_t)i], t)) return SIFT3D_ERR_ARG; hw[(size_t)i] = t.hw; }
-	if (!build_taps(base_sigma, t)) return SIFT3D_ERR_ARG;
+	if (!s.levels_ok || !s.base_ok) return SIFT3D_ERR_ARG;
+	const int win = slab_min_window_halo(s, !partial);
 	// (every keypoint level with the widest window's reach, the last level built: an upper bound of slab_ghost_extents)
 	int g = 1;
-	for (int i = ng - 2; i >= 0; i--) g = std::max(i >= 1 && i <= p.num_kp_levels ? win : 1, g + hw[(size_t)i + 1] + 1);
-	*halo = g + t.hw + 1;
+	for (int i = s.ng() - 2; i >= 0; i--) g = std::max(i >= 1 && i <= s.p.num_kp_levels ? win : 1, g + s.taps[(size_t)i + 1].hw + 1);
+	*halo = g + s.taps[0].hw + 1;
 	return SIFT3D_OK;
 }
 
@@ -424,11 +435,10 @@ extern "C" int sift3d_slab_level(sift3d_handle c, int i) {
 	} else {
 		// like the single-volume path, the first and last DoG level of the octave are not materialised (read only as the centre-voxel
 		// neighbour of extremum candidates: no halo, no abs-max)
-		const bool dog_eager = hook(SIFT3D_HOOK_DOG_EAGER) != 0, glast_eager = hook(SIFT3D_HOOK_GLAST_EAGER) != 0;
-		c->dog_elide = !dog_eager && c->nd >= 3;
+		c->dog_elide = slab_dog_elide(c);
 		// ... and the last Gaussian level is not built at all (k_lazy_next evaluates it at the parked extremum candidates; its source
 		// level G[nd-1] holds the hw+1 halo planes the caller exchanged for this level)
-		c->g_last_elide = c->dog_elide && !glast_eager && 2 * (2 * c->taps[c->ng - 1].hw + 1) <= kLazySlots;
+		c->g_last_elide = slab_last_lazy(c);
 		if (c->g_last_elide && i == c->ng - 1) { c->stage = std::max(c->stage, 1); return SIFT3D_OK; }
 		const bool elided = c->dog_elide && (i - 1 == 0 || i - 1 == c->nd - 1);
 		ok = launch_march_level(c->gss[i - 1].d, L.d, elided ? nullptr : c->dog[i - 1].d, elided ? nullptr : c->d_dogmax + (i - 1), L.nx, L.ny,
@@ -470,22 +480,72 @@ extern "C" int sift3d_slab_set_dogmax(sift3d_handle c, const float *max5) {
 	return SIFT3D_OK;
 }
 
-static int slab_count_and_regrow(sift3d_ctx *c, bool &again) {
-	unsigned host_words[3] = {0, 0, 0};
-	S3D_HIP(hipMemcpyAsync(host_words, c->d_total, sizeof(unsigned) * 3, hipMemcpyDeviceToHost, c->stream));
-	S3D_HIP(hipStreamSynchronize(c->stream));
-	S3D_HIP(hipGetLastError());
-	again = false;
-	if (host_words[1] != 0 || host_words[0] > c->ext_cap) {
-		int rc = alloc_lists(c, std::max(host_words[0], c->ext_cap) * 2u);
-		if (rc) return rc;
-		c->n_regrow++;
-		again = true;
-		return SIFT3D_OK;
-	}
-	c->n_ext = host_words[0];
-	c->n_kp = host_words[2];
+// ---- the stage kit: what the blocking entry points (the python driver, 3dsift_amd/slab.py) and the enqueued ones (r06; the native driver,
+// sharded.hip) launch and how both read the counts.  Nothing here synchronises except slab_take_counts.
+// Detect_KeyPoints (Src/cSIFT3D.cc:362-425) of the owned planes
+static int slab_enqueue_detect(sift3d_ctx *c) {
+	S3D_HIP(hipMemsetAsync(c->d_total, 0, sizeof(unsigned) * 3, c->stream));
+	DetectLevels DL;
+	fill_detect_levels(c, 0, DL);
+	const Level &C = c->dog[1];
+	launch_detect_octave(DL, c->nd - 2, C.nx, C.ny, C.zr(c->own0 - C.zoff, c->own1 - C.zoff), c->p.peak_thresh, c->octave_base, c->det,
+	                     c->d_ext, c->ext_cap, c->stream, c->g_last_elide ? &c->taps[c->ng - 1] : nullptr);
 	return SIFT3D_OK;
+}
+// Assign_Orientation (Src/cSIFT3D.cc:427-482) of the slab's extrema and the slots of the accepted ones
+static void slab_enqueue_orient(sift3d_ctx *c) {
+	launch_orient(c->d_ext, c->d_codes, c->d_total, c->ext_cap, c->d_levels, c->d_luts, c->d_lutpool, c->p.max_eig_thres,
+	              c->p.corner_thresh, 0, 1, c->d_order, c->d_nkp + 3, c->stream);
+	launch_slots(c->d_ext, c->d_codes, c->d_total, c->ext_cap, c->d_nkp, c->d_order, c->kp_cap, c->d_slots_part, c->stream);
+}
+// Extract_Description (Src/cSIFT3D.cc:484-502) with WHOLE windows from the slab's own level buffers, and the final records
+static void slab_enqueue_describe(sift3d_ctx *c) {
+	launch_describe(c->d_ext, c->d_total, c->ext_cap, c->d_levels, c->d_luts, c->d_lutpool, c->d_desc, c->kp_cap, 0, 1, c->d_order, c->d_nkp,
+	                c->d_nkp + 1, c->stream, c->desc_lut_lds, &c->dsplit);
+	launch_finalize(c->d_ext, c->d_total, c->ext_cap, 1, c->d_kpout, c->d_xyz, c->kp_cap, c->stream);
+}
+// detection + orientation, and the three counters on their way to pinned memory in front of ev[6]
+static int slab_keypoints_enqueue(sift3d_ctx *c) {
+	int rc = slab_enqueue_detect(c);
+	if (rc) return rc;
+	slab_enqueue_orient(c);
+	S3D_HIP(hipMemcpyAsync(c->h_words, c->d_total, sizeof(unsigned) * 3, hipMemcpyDeviceToHost, c->stream));
+	S3D_HIP(hipEventRecord(c->ev[6], c->stream));
+	return SIFT3D_OK;
+}
+
+// The three counters (extrema, overflow flag, accepted keypoints) behind what has been enqueued: `pinned` waits for the words
+// slab_keypoints_enqueue sent to pinned memory; otherwise they are copied now and the stream is drained.  Lists that held everything: the
+// counts are taken (again = false).  Lists that overflowed: they are regrown -- their contents are gone -- and the caller enqueues again.
+static int slab_take_counts(sift3d_ctx *c, bool pinned, bool &again) {
+	unsigned words[3] = {0, 0, 0};
+	if (pinned) {
+		S3D_HIP(hipEventSynchronize(c->ev[6]));
+		S3D_HIP(hipGetLastError());
+		memcpy(words, c->h_words, sizeof(words));
+	} else {
+		S3D_HIP(hipMemcpyAsync(words, c->d_total, sizeof(words), hipMemcpyDeviceToHost, c->stream));
+		S3D_HIP(hipStreamSynchronize(c->stream));
+		S3D_HIP(hipGetLastError());
+	}
+	const unsigned n_ext = words[0], over = words[1];
+	again = over != 0 || n_ext > c->ext_cap;
+	if (!again) { c->n_ext = n_ext; c->n_kp = words[2]; return SIFT3D_OK; }
+	if (pinned) S3D_HIP(hipStreamSynchronize(c->stream));  // (nothing of this handle may still use the lists that are about to be replaced)
+	int rc = alloc_lists(c, std::max(n_ext, c->ext_cap) * 2u);
+	if (rc) return rc;
+	c->n_regrow++;
+	return SIFT3D_OK;
+}
+// ... where nothing can be enqueued again: the stages behind a detection that fitted its lists never see them overflow (only the detection
+// kernels write the extrema count and the overflow flag), so this is a call out of order on counters of another run
+static int slab_take_counts_final(sift3d_ctx *c, const char *who) {
+	bool again;
+	int rc = slab_take_counts(c, false, again);
+	if (rc) return rc;
+	if (!again) return SIFT3D_OK;
+	set_last_error(std::string(who) + ": the extrema lists overflowed and were regrown -- run sift3d_slab_detect again");
+	return SIFT3D_ERR_CAPACITY;
 }
 
 extern "C" int sift3d_slab_detect(sift3d_handle c) {
@@ -493,28 +553,8 @@ extern "C" int sift3d_slab_detect(sift3d_handle c) {
 	int rc = set_device(c->device);
 	if (rc) return rc;
 	for (int attempt = 0; attempt < 4; attempt++) {
-		S3D_HIP(hipMemsetAsync(c->d_total, 0, sizeof(unsigned) * 3, c->stream));
-		DetectLevels DL;
-		memset(&DL, 0, sizeof(DL));
-		const int nl = c->nd - 2;
-		for (int i = 1; i <= nl; i++) {
-			DL.cur[i - 1] = c->dog[i].d; DL.prev[i - 1] = c->dog[i - 1].d; DL.next[i - 1] = c->dog[i + 1].d;
-			DL.absmax_bits[i - 1] = c->d_dogmax + i;
-			DL.level_id[i - 1] = i;
-			DL.scale[i - 1] = c->dog[i].scale;
-		}
-		if (c->dog_elide) {
-			DL.prev0_hi = c->gss[1].d; DL.prev0_lo = c->gss[0].d;
-			DL.nextl_hi = c->gss[c->nd].d; DL.nextl_lo = c->gss[c->nd - 1].d;
-			DL.nextl_slot = nl - 1;
-			if (c->g_last_elide) { DL.nextl_hi = nullptr; DL.lazy_src = DL.nextl_lo; }
-		}
-		const Level &C = c->dog[1];
-		launch_detect_octave(DL, nl, C.nx, C.ny, C.zr(c->own0 - C.zoff, c->own1 - C.zoff), c->p.peak_thresh, c->octave_base, c->det,
-		                     c->d_ext, c->ext_cap, c->stream, c->g_last_elide ? &c->taps[c->ng - 1] : nullptr);
 		bool again;
-		rc = slab_count_and_regrow(c, again);
-		if (rc) return rc;
+		if ((rc = slab_enqueue_detect(c)) != SIFT3D_OK || (rc = slab_take_counts(c, false, again)) != SIFT3D_OK) return rc;
 		if (!again) { c->stage = 3; c->n_kp = 0; return SIFT3D_OK; }
 	}
 	set_last_error("extrema list kept overflowing");
@@ -525,11 +565,7 @@ extern "C" int sift3d_slab_detect(sift3d_handle c) {
 // orientation windows only
 static int slab_window_halo(const sift3d_ctx *c, bool whole_descriptor_windows) {
 	int need = 0;
-	for (int i = 1; i <= c->p.num_kp_levels; i++) {
-		const float sc = c->dog[(size_t)i].scale, u = c->dog[(size_t)i].unit;
-		const int desc_reach = (int)ceilf(2.0f * (sc * 7.071067812f) / u) + 2, ori_reach = (int)floorf(4.5f * sc / u) + 1;
-		need = std::max(need, whole_descriptor_windows ? desc_reach : ori_reach);
-	}
+	for (int i = 1; i <= c->p.num_kp_levels; i++) need = std::max(need, level_window_planes(c, i, whole_descriptor_windows));
 	return need;
 }
 
@@ -542,16 +578,9 @@ extern "C" int sift3d_slab_describe(sift3d_handle c) {
 	}
 	int rc = set_device(c->device);
 	if (rc) return rc;
-	hipStream_t st = c->stream;
-	launch_orient(c->d_ext, c->d_codes, c->d_total, c->ext_cap, c->d_levels, c->d_luts, c->d_lutpool, c->p.max_eig_thres,
-	              c->p.corner_thresh, 0, 1, c->d_order, c->d_nkp + 3, st);
-	launch_slots(c->d_ext, c->d_codes, c->d_total, c->ext_cap, c->d_nkp, c->d_order, c->kp_cap, c->d_slots_part, st);
-	launch_describe(c->d_ext, c->d_total, c->ext_cap, c->d_levels, c->d_luts, c->d_lutpool, c->d_desc, c->kp_cap, 0, 1, c->d_order, c->d_nkp,
-	                c->d_nkp + 1, st, c->desc_lut_lds, &c->dsplit);
-	launch_finalize(c->d_ext, c->d_total, c->ext_cap, 1, c->d_kpout, c->d_xyz, c->kp_cap, st);
-	bool again;
-	rc = slab_count_and_regrow(c, again);
-	if (rc) return rc;
+	slab_enqueue_orient(c);
+	slab_enqueue_describe(c);
+	if ((rc = slab_take_counts_final(c, "sift3d_slab_describe")) != SIFT3D_OK) return rc;
 	c->stage = 5;
 	return SIFT3D_OK;
 }
@@ -568,26 +597,6 @@ extern "C" int sift3d_slab_set_desc_partial(sift3d_handle c, int on) {
 	return SIFT3D_OK;
 }
 
-extern "C" int sift3d_slab_min_halo_partial(const sift3d_params *params, int *halo) {
-	if (!halo) return SIFT3D_ERR_ARG;
-	sift3d_params p;
-	if (params) p = *params; else sift3d_default_params(&p);
-	if (p.num_kp_levels < 1 || p.num_kp_levels > 5) return SIFT3D_ERR_ARG;
-	const double sigma0 = (double)p.sigma_default * pow(2.0, -1.0 / 3.0);
-	const float scale = (float)(pow(2.0, (double)p.num_kp_levels / (double)p.num_kp_levels) * sigma0);  // DoG level num_kp_levels, octave 0
-	int h = (int)floorf(4.5f * scale) + 2;  // orientation window of the widest keypoint level + the central difference (+ 1 spare)
-	std::vector<float> sig;
-	float base_sigma;
-	level_sigmas(p, sig, base_sigma);
-	for (size_t i = 1; i < sig.size(); i++) {
-		Taps t;
-		if (!build_taps(sig[i], t)) return SIFT3D_ERR_ARG;
-		h = std::max(h, t.hw + 1);
-	}
-	*halo = h;
-	return SIFT3D_OK;
-}
-
 extern "C" int sift3d_slab_record_bytes(int *bytes) {
 	if (!bytes) return SIFT3D_ERR_ARG;
 	*bytes = (int)sizeof(DevKp);
@@ -599,17 +608,32 @@ extern "C" int sift3d_slab_record_bytes(int *bytes) {
 extern "C" int sift3d_slab_desc_reach(sift3d_handle c, int *planes) {
 	if (!c || !c->slab || !planes) return SIFT3D_ERR_ARG;
 	int reach = 0;
-	for (int i = 1; i <= c->p.num_kp_levels; i++) {
-		const float radius = 2.0f * (c->dog[(size_t)i].scale * 7.071067812f);
-		reach = std::max(reach, (int)ceilf(__builtin_fabsf(radius) / c->dog[(size_t)i].unit) + 1);
-	}
+	for (int i = 1; i <= c->p.num_kp_levels; i++)
+		reach = std::max(reach, window_reach(c->dog[(size_t)i].scale, c->dog[(size_t)i].unit).desc + 1);  // + 1: the central difference
 	*planes = reach;
 	return SIFT3D_OK;
 }
 
-// Assign_Orientation (Src/cSIFT3D.cc:427-482) of the slab's extrema; the accepted keypoints are counted (sift3d_num_keypoints)
-extern "C" int sift3d_slab_orient_launch(sift3d_handle c);
-extern "C" int sift3d_slab_orient_count(sift3d_handle c, int *n_kp);
+// Assign_Orientation (Src/cSIFT3D.cc:427-482) of the slab's extrema; the accepted keypoints are counted (sift3d_num_keypoints).  The launch
+// and the read-back are two calls as well: a driver with several ranks in one process (simulated ranks) enqueues every rank's orientation
+// before it waits for the first count
+extern "C" int sift3d_slab_orient_launch(sift3d_handle c) {
+	if (!c || !c->slab || c->stage < 3) return SIFT3D_ERR_STATE;
+	if (c->halo < slab_window_halo(c, false)) { set_last_error("the level buffers' halo is smaller than the orientation windows' reach"); return SIFT3D_ERR_STATE; }
+	int rc = set_device(c->device);
+	if (rc) return rc;
+	slab_enqueue_orient(c);
+	return SIFT3D_OK;
+}
+extern "C" int sift3d_slab_orient_count(sift3d_handle c, int *n_kp) {
+	if (!c || !c->slab || c->stage < 3 || !n_kp) return SIFT3D_ERR_STATE;
+	int rc = set_device(c->device);
+	if (rc) return rc;
+	if ((rc = slab_take_counts_final(c, "sift3d_slab_orient_count")) != SIFT3D_OK) return rc;
+	c->stage = 4;
+	*n_kp = (int)c->n_kp;
+	return SIFT3D_OK;
+}
 extern "C" int sift3d_slab_orient(sift3d_handle c) {
 	int n = 0;
 	const int rc = sift3d_slab_orient_launch(c);
@@ -659,6 +683,23 @@ extern "C" int sift3d_slab_describe_partial(sift3d_handle c, int nlists, const v
 	return SIFT3D_OK;
 }
 
+// The owner's finish of n of its records, the head of both forms below: the argument checks, the count of flagged records cleared, the
+// finish enqueued.  The count lives in a spare word behind the orientation's redo counter (d_total + 6).
+static unsigned *slab_redo_counter(const sift3d_ctx *c) { return c->d_nkp + 4; }
+static int slab_enqueue_finish(sift3d_ctx *c, const void *d_records, int n, int nparts, const int *const *d_hist, const float *const *d_mass,
+                               const float *d_units, bool final_round, int *d_redo, float *d_units_next) {
+	if (!c || !c->slab || n < 0 || nparts < 0 || nparts > kDescSegs || (n > 0 && (!d_records || !d_hist || !d_mass || nparts < 1)))
+		return SIFT3D_ERR_ARG;
+	if (!final_round && n > 0 && (!d_redo || !d_units_next)) return SIFT3D_ERR_ARG;
+	if (c->stage < 4) return SIFT3D_ERR_STATE;
+	int rc = set_device(c->device);
+	if (rc) return rc;
+	S3D_HIP(hipMemsetAsync(slab_redo_counter(c), 0, sizeof(unsigned), c->stream));
+	launch_describe_finish(static_cast<const DevKp *>(d_records), (unsigned)n, c->d_levels, c->d_luts, nparts, d_hist, d_mass, d_units, final_round, c->d_desc,
+	                       d_redo, d_units_next, slab_redo_counter(c), c->stream);
+	return SIFT3D_OK;
+}
+
 // the owner's finish of n of its records (all of them, or the second round's subset): nparts partial results (its own part and its
 // z-neighbours', in ascending rank order: the integer histograms are added, the masses in that order).  Rows go to the descriptor table
 // (sift3d_get_keypoints / sift3d_device_results); records whose unit failed are flagged (d_redo[k] = 1, d_units_next[k]) and counted in
@@ -666,20 +707,13 @@ extern "C" int sift3d_slab_describe_partial(sift3d_handle c, int nlists, const v
 extern "C" int sift3d_slab_describe_finish(sift3d_handle c, const void *d_records, int n, int nparts, const int *const *d_hist,
                                            const float *const *d_mass, const float *d_units, int final_round, int *d_redo, float *d_units_next,
                                            int *n_redo) {
-	if (!c || !c->slab || n < 0 || !n_redo || nparts < 0 || nparts > kDescSegs || (n > 0 && (!d_records || !d_hist || !d_mass || nparts < 1)))
-		return SIFT3D_ERR_ARG;
-	if (!final_round && n > 0 && (!d_redo || !d_units_next)) return SIFT3D_ERR_ARG;
-	if (c->stage < 4) return SIFT3D_ERR_STATE;
-	int rc = set_device(c->device);
+	if (!n_redo) return SIFT3D_ERR_ARG;
+	int rc = slab_enqueue_finish(c, d_records, n, nparts, d_hist, d_mass, d_units, final_round != 0, d_redo, d_units_next);
 	if (rc) return rc;
 	hipStream_t st = c->stream;
-	unsigned *counter = c->d_nkp + 4;  // (d_total + 6: a spare word behind the orientation's redo counter)
-	S3D_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned), st));
-	launch_describe_finish(static_cast<const DevKp *>(d_records), (unsigned)n, c->d_levels, c->d_luts, nparts, d_hist, d_mass, d_units, final_round != 0, c->d_desc,
-	                       d_redo, d_units_next, counter, st);
 	unsigned host = 0;
 	if (!final_round) {  // (a final round flags nothing)
-		S3D_HIP(hipMemcpyAsync(&host, counter, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+		S3D_HIP(hipMemcpyAsync(&host, slab_redo_counter(c), sizeof(unsigned), hipMemcpyDeviceToHost, st));
 		S3D_HIP(hipStreamSynchronize(st));
 		S3D_HIP(hipGetLastError());
 	}
@@ -694,63 +728,9 @@ extern "C" int sift3d_slab_describe_finish(sift3d_handle c, const void *d_record
 	return SIFT3D_OK;
 }
 
-// the launch and the read-back of sift3d_slab_orient as two calls: a driver with several ranks in one process (simulated ranks) enqueues
-// every rank's orientation before it waits for the first count
-extern "C" int sift3d_slab_orient_launch(sift3d_handle c) {
-	if (!c || !c->slab || c->stage < 3) return SIFT3D_ERR_STATE;
-	if (c->halo < slab_window_halo(c, false)) { set_last_error("the level buffers' halo is smaller than the orientation windows' reach"); return SIFT3D_ERR_STATE; }
-	int rc = set_device(c->device);
-	if (rc) return rc;
-	hipStream_t st = c->stream;
-	launch_orient(c->d_ext, c->d_codes, c->d_total, c->ext_cap, c->d_levels, c->d_luts, c->d_lutpool, c->p.max_eig_thres,
-	              c->p.corner_thresh, 0, 1, c->d_order, c->d_nkp + 3, st);
-	launch_slots(c->d_ext, c->d_codes, c->d_total, c->ext_cap, c->d_nkp, c->d_order, c->kp_cap, c->d_slots_part, st);
-	return SIFT3D_OK;
-}
-extern "C" int sift3d_slab_orient_count(sift3d_handle c, int *n_kp) {
-	if (!c || !c->slab || c->stage < 3 || !n_kp) return SIFT3D_ERR_STATE;
-	int rc = set_device(c->device);
-	if (rc) return rc;
-	bool again;
-	rc = slab_count_and_regrow(c, again);
-	if (rc) return rc;
-	c->stage = 4;
-	*n_kp = (int)c->n_kp;
-	return SIFT3D_OK;
-}
-
 // ---- r06: the same stages without a host read-back between them.  A driver enqueues detection + orientation of every sharded octave (and of
 // every simulated rank), then asks for the counts; the GPU works on the later launches while the host learns the earlier counts.  Rare events
 // (a list that overflowed, a record whose fixed-point unit failed) are found when the counts are read and take the blocking forms above.
-static int slab_keypoints_enqueue(sift3d_ctx *c) {
-	hipStream_t st = c->stream;
-	S3D_HIP(hipMemsetAsync(c->d_total, 0, sizeof(unsigned) * 3, st));
-	DetectLevels DL;
-	memset(&DL, 0, sizeof(DL));
-	const int nl = c->nd - 2;
-	for (int i = 1; i <= nl; i++) {
-		DL.cur[i - 1] = c->dog[i].d; DL.prev[i - 1] = c->dog[i - 1].d; DL.next[i - 1] = c->dog[i + 1].d;
-		DL.absmax_bits[i - 1] = c->d_dogmax + i;
-		DL.level_id[i - 1] = i;
-		DL.scale[i - 1] = c->dog[i].scale;
-	}
-	if (c->dog_elide) {
-		DL.prev0_hi = c->gss[1].d; DL.prev0_lo = c->gss[0].d;
-		DL.nextl_hi = c->gss[c->nd].d; DL.nextl_lo = c->gss[c->nd - 1].d;
-		DL.nextl_slot = nl - 1;
-		if (c->g_last_elide) { DL.nextl_hi = nullptr; DL.lazy_src = DL.nextl_lo; }
-	}
-	const Level &C = c->dog[1];
-	launch_detect_octave(DL, nl, C.nx, C.ny, C.zr(c->own0 - C.zoff, c->own1 - C.zoff), c->p.peak_thresh, c->octave_base, c->det,
-	                     c->d_ext, c->ext_cap, st, c->g_last_elide ? &c->taps[c->ng - 1] : nullptr);
-	launch_orient(c->d_ext, c->d_codes, c->d_total, c->ext_cap, c->d_levels, c->d_luts, c->d_lutpool, c->p.max_eig_thres,
-	              c->p.corner_thresh, 0, 1, c->d_order, c->d_nkp + 3, st);
-	launch_slots(c->d_ext, c->d_codes, c->d_total, c->ext_cap, c->d_nkp, c->d_order, c->kp_cap, c->d_slots_part, st);
-	S3D_HIP(hipMemcpyAsync(c->h_words, c->d_total, sizeof(unsigned) * 3, hipMemcpyDeviceToHost, st));
-	S3D_HIP(hipEventRecord(c->ev[6], st));
-	return SIFT3D_OK;
-}
-
 // Detect_KeyPoints + Assign_Orientation (Src/cSIFT3D.cc:362-482) of the slab's owned planes, enqueued; the counts travel to pinned memory behind them
 extern "C" int sift3d_slab_keypoints_launch(sift3d_handle c) {
 	if (!c || !c->slab) return SIFT3D_ERR_ARG;
@@ -767,17 +747,9 @@ extern "C" int sift3d_slab_keypoints_count(sift3d_handle c, int *n_kp) {
 	int rc = set_device(c->device);
 	if (rc) return rc;
 	for (int attempt = 0; attempt < 4; attempt++) {
-		S3D_HIP(hipEventSynchronize(c->ev[6]));
-		S3D_HIP(hipGetLastError());
-		const unsigned n_ext = c->h_words[0], over = c->h_words[1], n_acc = c->h_words[2];
-		if (over == 0 && n_ext <= c->ext_cap) {
-			c->n_ext = n_ext; c->n_kp = n_acc; c->stage = 4;
-			*n_kp = (int)n_acc;
-			return SIFT3D_OK;
-		}
-		S3D_HIP(hipStreamSynchronize(c->stream));  // (nothing of this handle may still use the lists that are about to be replaced)
-		if ((rc = alloc_lists(c, std::max(n_ext, c->ext_cap) * 2u)) != SIFT3D_OK) return rc;
-		c->n_regrow++;
+		bool again;
+		if ((rc = slab_take_counts(c, true, again)) != SIFT3D_OK) return rc;
+		if (!again) { c->stage = 4; *n_kp = (int)c->n_kp; return SIFT3D_OK; }
 		if ((rc = slab_keypoints_enqueue(c)) != SIFT3D_OK) return rc;
 	}
 	set_last_error("extrema list kept overflowing");
@@ -796,10 +768,7 @@ extern "C" int sift3d_slab_describe_launch(sift3d_handle c) {
 	}
 	int rc = set_device(c->device);
 	if (rc) return rc;
-	hipStream_t st = c->stream;
-	launch_describe(c->d_ext, c->d_total, c->ext_cap, c->d_levels, c->d_luts, c->d_lutpool, c->d_desc, c->kp_cap, 0, 1, c->d_order, c->d_nkp,
-	                c->d_nkp + 1, st, c->desc_lut_lds, &c->dsplit);
-	launch_finalize(c->d_ext, c->d_total, c->ext_cap, 1, c->d_kpout, c->d_xyz, c->kp_cap, st);
+	slab_enqueue_describe(c);
 	c->stage = 5;
 	return SIFT3D_OK;
 }
@@ -808,18 +777,11 @@ extern "C" int sift3d_slab_describe_launch(sift3d_handle c) {
 // (to pinned memory) are enqueued; sift3d_slab_describe_finish_count waits for that count.  Nothing flagged (the rule): the results are complete.
 extern "C" int sift3d_slab_describe_finish_launch(sift3d_handle c, const void *d_records, int n, int nparts, const int *const *d_hist,
                                                   const float *const *d_mass, int *d_redo, float *d_units_next) {
-	if (!c || !c->slab || n < 0 || nparts < 0 || nparts > kDescSegs || (n > 0 && (!d_records || !d_hist || !d_mass || nparts < 1 || !d_redo || !d_units_next)))
-		return SIFT3D_ERR_ARG;
-	if (c->stage < 4) return SIFT3D_ERR_STATE;
-	int rc = set_device(c->device);
+	int rc = slab_enqueue_finish(c, d_records, n, nparts, d_hist, d_mass, nullptr, false, d_redo, d_units_next);
 	if (rc) return rc;
 	hipStream_t st = c->stream;
-	unsigned *counter = c->d_nkp + 4;
-	S3D_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned), st));
-	launch_describe_finish(static_cast<const DevKp *>(d_records), (unsigned)n, c->d_levels, c->d_luts, nparts, d_hist, d_mass, nullptr, false, c->d_desc,
-	                       d_redo, d_units_next, counter, st);
 	launch_finalize(c->d_ext, c->d_total, c->ext_cap, 1, c->d_kpout, c->d_xyz, c->kp_cap, st);
-	S3D_HIP(hipMemcpyAsync(c->h_words + 5, counter, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+	S3D_HIP(hipMemcpyAsync(c->h_words + 5, slab_redo_counter(c), sizeof(unsigned), hipMemcpyDeviceToHost, st));
 	S3D_HIP(hipEventRecord(c->ev[7], st));
 	c->n_desc_redo = 0;
 	return SIFT3D_OK;

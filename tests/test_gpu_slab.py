@@ -282,3 +282,78 @@ def test_whole_window_describe_is_refused_on_a_partial_window_halo():
     with pytest.raises(capi.Sift3dError, match="whole descriptor windows"):
         st.ctx.describe()
     ex.close()
+
+
+def _slab_ctx(n, z0, z1, halo, octave=0):
+    """a slab context of octave `octave` of a 64^3 volume (n^3 at that octave) owning planes [z0, z1) -> (context, its arena)"""
+    import torch
+    k = capi.SlabCSIFT3D.arena_floats(n, n, n, z0, z1, halo, 4, octave=octave)
+    arena = torch.zeros(k, dtype=torch.float32, device="cuda")
+    return capi.SlabCSIFT3D(n, n, n, z0, z1, halo, 4, arena.data_ptr(), k, octave=octave), arena
+
+
+def _geometry_readings():
+    """{(octave, halo, partial windows): (halo_planes per level, level_hw per level, desc_reach)} and the ghost-zone admissions
+    {(partial windows, halo - min_halo_ghost): return code of sift3d_slab_set_ghost(1)}"""
+    import ctypes as C
+    L = capi.lib()
+    out, ghost = {}, {}
+    for n, z0, z1, halo, octave in ((64, 16, 48, 38, 0), (64, 16, 48, 13, 0), (32, 8, 24, 38, 1)):
+        ctx, arena = _slab_ctx(n, z0, z1, halo, octave)
+        for partial in (0, 1):
+            ctx.set_desc_partial(partial)
+            ng = ctx.levels + 3
+            out[(octave, halo, partial)] = ([ctx.halo_planes(i) for i in range(ng)], [ctx.level_hw(i) for i in range(ng)], ctx.desc_reach())
+        ctx.close()
+    p = capi._params({})
+    for partial in (0, 1):
+        need = C.c_int(0)
+        assert L.sift3d_slab_min_halo_ghost(C.byref(p), C.c_int(partial), C.byref(need)) == 0
+        for less in (0, 1):
+            ctx, arena = _slab_ctx(64, 16, 48, need.value - less, 0)
+            ctx.set_desc_partial(partial)
+            ghost[(partial, -less)] = L.sift3d_slab_set_ghost(ctx._h, 1)
+            ctx.close()
+    return out, ghost
+
+
+# recorded from the library before the reach rule, the level schedule and the ghost extents were each written once
+GEOMETRY = {(0, 13, 0): ([4, 13, 13, 13, 9, 0], [2, 3, 4, 5, 6, 8], 37),
+            (0, 13, 1): ([4, 8, 10, 12, 9, 0], [2, 3, 4, 5, 6, 8], 37),
+            (0, 38, 0): ([4, 25, 31, 38, 9, 0], [2, 3, 4, 5, 6, 8], 37),
+            (0, 38, 1): ([4, 8, 10, 12, 9, 0], [2, 3, 4, 5, 6, 8], 37),
+            (1, 38, 0): ([4, 25, 31, 38, 9, 0], [2, 3, 4, 5, 6, 8], 37),
+            (1, 38, 1): ([4, 8, 10, 12, 9, 0], [2, 3, 4, 5, 6, 8], 37)}
+GHOST_ADMITTED = {(0, -1): 1, (0, 0): 0, (1, -1): 1, (1, 0): 0}
+
+
+def test_context_bound_geometry_is_what_it_was():
+    """Halo planes per level, half widths and the descriptor reach of slab contexts at octave 0 (whole-window and partial-window halos)
+    and at octave 1, with the descriptor windows whole and split; ghost zones are admitted at sift3d_slab_min_halo_ghost planes and
+    refused at one plane less (1 = SIFT3D_ERR_ARG)."""
+    out, ghost = _geometry_readings()
+    assert out == GEOMETRY
+    assert ghost == GHOST_ADMITTED
+
+
+@pytest.mark.parametrize("partial", [True, False])
+def test_blocking_stages_regrow_their_lists_and_equal_the_single_volume(partial):
+    """The python driver's stage calls (sift3d_slab_detect, _orient_launch / _count, _describe, _describe_finish) with lists that start at
+    48 entries: detection regrows them and runs again, and everything behind it works on the regrown lists.  Bit for bit the single volume."""
+    vol = _volume((64, 64, 64), seed=3)
+    ref = _single(vol)
+    kp_ref, ds_ref = ref.GetKeypoints()
+    assert len(kp_ref) > 48
+    with capi.hook("list_cap", 48):
+        ex = slab.SlabExtractor((64, 64, 64), slab.SimComm(2), sharded_octaves=1, desc_partial=partial)
+        ex.load(volume=vol)
+        ex.KpSiftAlgorithm()
+        kp, ds = ex.GetKeypoints()
+        regrows = sum(st.ctx.debug_counters()["list_regrows"] for w in ex._wl() for st in w.stages)
+    assert regrows >= 1
+    assert len(kp) == len(kp_ref)
+    for f in kp_ref.dtype.names:
+        assert np.array_equal(kp[f], kp_ref[f]), f
+    assert np.array_equal(ds, ds_ref)
+    ex.close()
+    ref.close()
