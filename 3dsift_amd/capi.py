@@ -50,6 +50,9 @@ SYMBOLS = [
     "sift3d_default_search_options", "sift3d_zncc_search", "sift3d_icgn_init_from_search",
     # strain fields from the refined displacements
     "sift3d_default_strain_options", "sift3d_strain_input_from_icgn", "sift3d_strain",
+    # outlier validation of the displacement field (normalised median test)
+    "sift3d_default_validate_options", "sift3d_validate_input_from_icgn", "sift3d_validate_input_from_icgn2", "sift3d_validate_displacements",
+    "sift3d_validate_keep", "sift3d_icgn_init_from_validation", "sift3d_validate_stage_capacity",
     "sift3d_device_count", "sift3d_error_string", "sift3d_last_error",
     # multi-GPU sharding (z-slabs of octave 0 + seeded replicated tail)
     "sift3d_slab_min_halo", "sift3d_slab_arena_floats", "sift3d_slab_create", "sift3d_slab_buffer", "sift3d_slab_upload",
@@ -159,6 +162,21 @@ STRAIN_DTYPE = np.dtype([("disp", "<f8", (3,)), ("G", "<f8", (9,)), ("E", "<f8",
 assert STRAIN_DTYPE.itemsize == 192
 
 
+class ValidateOptions(C.Structure):
+    """sift3d_validate_options (include/sift3d_hip.h)"""
+    _fields_ = [("radius", C.c_int), ("min_neighbours", C.c_int), ("passes", C.c_int), ("reserved0", C.c_int), ("threshold", C.c_double),
+                ("eps", C.c_double), ("reserved", C.c_int * 4)]
+
+
+assert C.sizeof(ValidateOptions) == 48
+
+# sift3d_validate_result: the median and the MAD of the neighbours' estimates, the score against the final set, the neighbour count,
+# the status, the flag and the pass that set it
+VALIDATE_DTYPE = np.dtype([("median", "<f8", (3,)), ("mad", "<f8", (3,)), ("score", "<f8"), ("neighbours", "<i4"), ("status", "<i4"),
+                           ("flagged", "<i4"), ("pass", "<i4")])
+assert VALIDATE_DTYPE.itemsize == 72
+
+
 class SlabDesc(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("z0", C.c_int), ("z1", C.c_int), ("halo", C.c_int),
                 ("noct_total", C.c_int), ("octave", C.c_int)]
@@ -248,6 +266,15 @@ def lib():
         L.sift3d_strain_input_from_icgn.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
         L.sift3d_strain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(StrainOptions), C.c_int, C.c_int, C.c_void_p,
                                     C.POINTER(C.c_double)]
+        L.sift3d_default_validate_options.argtypes = [C.POINTER(ValidateOptions)]
+        L.sift3d_default_validate_options.restype = None
+        L.sift3d_validate_input_from_icgn.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sift3d_validate_input_from_icgn2.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sift3d_validate_displacements.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ValidateOptions), C.c_int,
+                                                    C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+        L.sift3d_validate_keep.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.sift3d_icgn_init_from_validation.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _ip]
+        L.sift3d_validate_stage_capacity.argtypes = [_ip]
         _sz = C.POINTER(C.c_size_t)
         L.sift3d_slab_min_halo.argtypes = [C.POINTER(Params), _ip]
         L.sift3d_slab_arena_floats.argtypes = [C.POINTER(SlabDesc), C.POINTER(Params), _sz]
@@ -732,6 +759,110 @@ def strain(points, disp, valid=None, device=0, **opts):
     d["G"] = d["G"].reshape(-1, 3, 3)
     d["seconds"] = sec.value
     return d
+
+
+VALIDATE_OPTIONS = ("radius", "min_neighbours", "passes", "threshold", "eps")
+VALIDATE_FIELDS = ("median", "mad", "score", "neighbours", "status", "flagged", "pass")
+
+
+def default_validate_options():
+    """sift3d_default_validate_options as a dict (needs no GPU)"""
+    o = _options(ValidateOptions, "sift3d_default_validate_options", VALIDATE_OPTIONS, "validate", {})
+    return {k: getattr(o, k) for k in VALIDATE_OPTIONS}
+
+
+def validate_stage_capacity():
+    """sift3d_validate_stage_capacity (test hook): the neighbour count up to which validate selects its medians in LDS.  Needs no GPU."""
+    n = C.c_int(0)
+    _check(lib().sift3d_validate_stage_capacity(C.byref(n)))
+    return n.value
+
+
+def validate_input_from_icgn(res, zncc_min=0.0, accept_unconverged=False):
+    """sift3d_validate_input_from_icgn / _icgn2 (by the width of res["p"]: 12 or 30): the displacements (m, 3) float64, the gradients
+    (m, 9) float64 and the validity bytes (m,) uint8 that validate takes, from the dict icgn or icgn2 returns.  Needs no GPU."""
+    p = np.asarray(res["p"], np.float64)
+    width = p.shape[-1] if p.ndim == 2 else 12
+    if width not in (12, 30):
+        raise ValueError("p: (m, 12) first-order or (m, 30) second-order parameters")
+    p = p.reshape(-1, width)
+    m = len(p)
+    rec = np.zeros(max(m, 1), ICGN_DTYPE if width == 12 else ICGN2_DTYPE)
+    rec["p"][:m] = p
+    rec["zncc"][:m] = np.asarray(res["zncc"])
+    rec["status"][:m] = np.asarray(res["status"])
+    disp = np.zeros((max(m, 1), 3), np.float64)
+    grad = np.zeros((max(m, 1), 9), np.float64)
+    valid = np.zeros(max(m, 1), np.uint8)
+    fn = lib().sift3d_validate_input_from_icgn if width == 12 else lib().sift3d_validate_input_from_icgn2
+    _check(fn(_p(rec), m, float(zncc_min), int(bool(accept_unconverged)), _p(disp), _p(grad), _p(valid)))
+    return disp[:m].copy(), grad[:m].copy(), valid[:m].copy()
+
+
+def validate(points, disp, grad=None, valid=None, device=0, **opts):
+    """sift3d_validate_displacements: the normalised median test of the displacements ((m, 3) float64 u, v, w) of the POIs ((m, 3) int32
+    x, y, z) against the POIs within `radius` voxels (Chebyshev) of each.  grad: (m, 9) float64 gradients of the POIs (rows u, v, w;
+    columns x, y, z) that carry a neighbour's value to the tested POI, or None; valid: (m,) bytes or None (all valid).  points / disp /
+    grad / valid: numpy arrays or contiguous device tensors, all of the same kind.  Options: radius, min_neighbours, passes,
+    threshold, eps.  Returns median (m, 3), mad (m, 3), score, neighbours, status, flagged, pass (m,), the records themselves as
+    `records` (VALIDATE_DTYPE: what validate_keep and icgn_init_from_validation take) and the device seconds."""
+    o = _options(ValidateOptions, "sift3d_default_validate_options", VALIDATE_OPTIONS, "validate", opts)
+    dev = [_is_dev(a) for a in (points, disp, grad, valid) if a is not None]
+    if any(dev) != all(dev):
+        raise ValueError("points, disp, grad and valid must all be numpy arrays or all device tensors")
+    qp, m, q = _table(points, np.int32, 3, points)
+    up, mu, u = _table(disp, np.float64, 3, points)
+    gp, mg, gr = _table(grad, np.float64, 9, points)
+    ok = None if valid is None else (valid.ne(0) if dev[0] else np.asarray(valid) != 0)
+    vp, mv, ok = _table(ok, np.uint8, 0, points)
+    if mu != m or (gr is not None and mg != m) or (ok is not None and mv != m):
+        raise ValueError("disp, grad, valid: one row per point")
+    out = np.zeros(max(m, 1), VALIDATE_DTYPE)
+    sec = C.c_double(0)
+    _check(lib().sift3d_validate_displacements(qp, up, gp, vp, m, C.byref(o), int(dev[0]), int(device), _p(out), C.byref(sec)))
+    d = _fields(out, m, VALIDATE_FIELDS)
+    d["records"] = out[:m].copy()
+    d["seconds"] = sec.value
+    return d
+
+
+def _validate_records(val):
+    rec = val["records"] if isinstance(val, dict) else val
+    return np.ascontiguousarray(rec, VALIDATE_DTYPE).reshape(-1)
+
+
+def validate_keep(val, valid=None):
+    """sift3d_validate_keep: the bytes (m,) uint8 to hand to strain -- valid (None: all), tested (status 0) and not flagged -- from what
+    validate returns (or its records).  Needs no GPU."""
+    rec = _validate_records(val)
+    m = len(rec)
+    vin = None if valid is None else np.ascontiguousarray(np.asarray(valid) != 0, np.uint8).reshape(-1)
+    if vin is not None and len(vin) != m:
+        raise ValueError("valid: one byte per record")
+    buf = np.zeros(max(m, 1), VALIDATE_DTYPE)
+    buf[:m] = rec
+    out = np.zeros(max(m, 1), np.uint8)
+    _check(lib().sift3d_validate_keep(_p(buf), None if vin is None or m == 0 else _p(vin), m, _p(out)))
+    return out[:m].copy()
+
+
+def icgn_init_from_validation(val, init=None):
+    """sift3d_icgn_init_from_validation: (m, 12) float64 initial parameters for a second icgn run and the number of rows written.  Rows
+    of init (None: all NaN) whose record is flagged with status 0, or has status 3, become (median_u, 0, 0, 0, median_v, 0, 0, 0,
+    median_w, 0, 0, 0); every other row is returned as given.  Needs no GPU."""
+    rec = _validate_records(val)
+    m = len(rec)
+    buf = np.zeros(max(m, 1), VALIDATE_DTYPE)
+    buf[:m] = rec
+    out = np.full((max(m, 1), 12), np.nan)
+    if init is not None:
+        ini = np.asarray(init, np.float64).reshape(-1, 12)
+        if len(ini) != m:
+            raise ValueError("init: one row of 12 per record")
+        out[:m] = ini
+    count = C.c_int(0)
+    _check(lib().sift3d_icgn_init_from_validation(_p(buf), m, _p(out), C.byref(count)))
+    return out[:m].copy(), count.value
 
 
 def device_count():

@@ -1,5 +1,5 @@
 // call_state.h -- what the one-shot entry points share (sift3d_match, sift3d_fit_affine[_local], sift3d_icgn[_bspline],
-// sift3d_icgn2, sift3d_zncc_search, sift3d_strain, sift3d_bspline_prefilter): the per-device call state, its grow-only blocks, the
+// sift3d_icgn2, sift3d_zncc_search, sift3d_strain, sift3d_validate_displacements, sift3d_bspline_prefilter): the per-device call state, its grow-only blocks, the
 // scratch layout, the staging of a volume pair, the device pick and the stream-aware check macro.  Every family keeps an array of
 // states of its own (its own stream and mutex per device).
 #pragma once
@@ -40,6 +40,36 @@ struct CallState {
 	int stage_pair(const PairPlan &P, bool on_device, const float *&ref, const float *&tar, const int *&pts, const void *&opt);
 	int finish(double *seconds);                 // waits for e1; *seconds (may be NULL) = e0 -> e1
 };
+
+// the temporaries of one call whose sizes depend on the input (sift3d_strain, sift3d_validate_displacements): freed when the call
+// returns, however it returns
+struct CallTemps {
+	char *a = nullptr, *b = nullptr;
+	~CallTemps() {
+		if (a) (void)hipFree(a);
+		if (b) (void)hipFree(b);
+	}
+};
+
+// the cell grid of the strain kernels over the box launch_strain_mark left (min x, y, z, min -x, -y, -z; 0x7f7f7f7f where no POI
+// contributes): the side is the radius, enlarged until the grid has at most 2^24 cells.  The extents reach 2^25 + 1, so the products
+// are formed in 64 bits and stepwise.
+inline StrainGrid strain_choose_grid(const int *box, int radius) {
+	constexpr long long kMaxCells = 1 << 24;
+	StrainGrid g = {0, 0, 0, radius, 1, 1, 1};
+	if (box[0] == 0x7f7f7f7f) return g;
+	g.x0 = box[0]; g.y0 = box[1]; g.z0 = box[2];
+	const long long ex = (long long)-box[3] - box[0], ey = (long long)-box[4] - box[1], ez = (long long)-box[5] - box[2];
+	long long side = radius;
+	for (;;) {
+		const long long nx = ex / side + 1, ny = ey / side + 1, nz = ez / side + 1;
+		if (nx * ny <= kMaxCells && nx * ny * nz <= kMaxCells) {
+			g.side = (int)side; g.nx = (int)nx; g.ny = (int)ny; g.nz = (int)nz;
+			return g;
+		}
+		side += (side + 3) / 4;
+	}
+}
 
 int pick_device(int device);  // checks the index, makes the device current
 

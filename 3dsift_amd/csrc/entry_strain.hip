@@ -10,17 +10,7 @@
 using namespace s3d;
 
 namespace {
-constexpr long long kMaxCells = 1 << 24;
 CallState g_strain[kMaxDev];
-
-// the temporaries of one call: freed when the call returns, however it returns
-struct Temps {
-	char *a = nullptr, *b = nullptr;
-	~Temps() {
-		if (a) (void)hipFree(a);
-		if (b) (void)hipFree(b);
-	}
-};
 
 // options (NULL: defaults) -> checked values
 bool take_options(const sift3d_strain_options *o, int &radius, int &min_nb, int &measure) {
@@ -34,24 +24,6 @@ bool take_options(const sift3d_strain_options *o, int &radius, int &min_nb, int 
 	min_nb = o->min_neighbours;
 	measure = o->measure;
 	return true;
-}
-
-// the cell grid over the box (min x, y, z, min -x, -y, -z; 0x7f7f7f7f where no POI contributes): the side is the radius, enlarged
-// until the grid has at most 2^24 cells.  The extents reach 2^25 + 1, so the products are formed in 64 bits and stepwise.
-StrainGrid choose_grid(const int *box, int radius) {
-	StrainGrid g = {0, 0, 0, radius, 1, 1, 1};
-	if (box[0] == 0x7f7f7f7f) return g;
-	g.x0 = box[0]; g.y0 = box[1]; g.z0 = box[2];
-	const long long ex = (long long)-box[3] - box[0], ey = (long long)-box[4] - box[1], ez = (long long)-box[5] - box[2];
-	long long side = radius;
-	for (;;) {
-		const long long nx = ex / side + 1, ny = ey / side + 1, nz = ez / side + 1;
-		if (nx * ny <= kMaxCells && nx * ny * nz <= kMaxCells) {
-			g.side = (int)side; g.nx = (int)nx; g.ny = (int)ny; g.nz = (int)nz;
-			return g;
-		}
-		side += (side + 3) / 4;
-	}
 }
 }  // namespace
 
@@ -94,7 +66,7 @@ extern "C" int sift3d_strain(const int *points3, const double *disp3, const unsi
 	std::lock_guard<std::mutex> lock(D.mu);
 	if ((rc = D.ensure(0, 0))) return rc;
 	hipStream_t st = D.stream;
-	Temps T;
+	CallTemps T;
 	// block a: [results | box | cell of a POI | slots | sorted x y z idx | sorted u v w | (host inputs) points | disp | valid]
 	const size_t M = (size_t)m, wi = al256(sizeof(int) * M), wd = al256(sizeof(double) * M), res_bytes = sizeof(sift3d_strain_result) * M;
 	Layout L;
@@ -131,7 +103,7 @@ extern "C" int sift3d_strain(const int *points3, const double *disp3, const unsi
 	int box[6];
 	S3D_HIP_ST(st, hipMemcpyAsync(box, d_box, sizeof(box), hipMemcpyDeviceToHost, st));
 	S3D_HIP_ST(st, hipStreamSynchronize(st));
-	const StrainGrid g = choose_grid(box, radius);
+	const StrainGrid g = strain_choose_grid(box, radius);
 	// block b: [counts per cell (then the scatter's fill marks) | cell starts | the scan's tile sums]
 	const size_t cells = (size_t)g.nx * g.ny * g.nz, wc = al256(sizeof(int) * (cells + 1));
 	S3D_HIP(hipMalloc(&T.b, 2 * wc + sizeof(int) * strain_scan_tiles(cells + 1)));

@@ -378,6 +378,21 @@ hipError_t launch_strain_bin(const int *d_pts, const double *d_disp, int m, Stra
 void launch_strain_fit(const int *d_pts, const double *d_disp, int m, StrainGrid g, const int *d_start, StrainSorted S, int radius, int min_nb,
                        int measure, sift3d_strain_result *d_out, hipStream_t st);
 
+// ---- kernels_validate.hip: the normalised median test of the displacements (sift3d_validate_displacements, include/sift3d_hip.h) --
+// It runs on the strain kernels' cell grid: launch_strain_mark / launch_strain_bin with d_fold as the valid bytes.
+struct ValidateParams {
+	int radius, min_nb;
+	double threshold, eps;
+};
+int validate_stage_capacity();  // neighbour counts up to this are selected in LDS, larger ones by re-walking the window
+// d_fold[i] = (d_valid null or d_valid[i]) and, with d_grad, nine finite gradients
+void launch_validate_fold(const double *d_grad, const unsigned char *d_valid, int m, unsigned char *d_fold, hipStream_t st);
+// pass > 0: one pass of the test -- reads the flags d_fin, writes d_fout (m bytes each) and the pass number of a new flag into d_pass;
+// pass 0: the report from the final flags d_fin and d_pass into d_out.  d_cell: what launch_strain_bin left (negative: no contributor)
+void launch_validate_test(const int *d_pts, const double *d_disp, const double *d_grad, const int *d_cell, int m, StrainGrid g,
+                          const int *d_start, StrainSorted S, ValidateParams P, int pass, const unsigned char *d_fin, unsigned char *d_fout,
+                          int *d_pass, sift3d_validate_result *d_out, hipStream_t st);
+
 // code-object preload of the translation units whose kernels would otherwise be loaded by the first KpSiftAlgorithm of a process
 void preload_march_kernels();
 void preload_small_kernels();

@@ -1,6 +1,6 @@
-// cRegistration.h -- RANSAC affine fits of matched keypoints, ZNCC integer search, IC-GN displacement refinement and strain fields (no
+// cRegistration.h -- RANSAC affine fits of matched keypoints, ZNCC integer search, IC-GN displacement refinement, validation and strain fields (no
 // reference counterpart): the steps after enhancedMatch, on the GPU.
-// Over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_zncc_search / sift3d_icgn / sift3d_strain (include/sift3d_hip.h, which states the numerical contracts).  Both functions take
+// Over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_zncc_search / sift3d_icgn / sift3d_validate_displacements / sift3d_strain (include/sift3d_hip.h, which states the numerical contracts).  Both functions take
 // exactly the two std::vector<Cvec> that muBruteMatcher::enhancedMatch fills (refMatch[i] <-> tarMatch[i]).
 #ifndef S3D_HOST_CREGISTRATION_H
 #define S3D_HOST_CREGISTRATION_H
@@ -162,6 +162,51 @@ SIFT_LIBRARY_API std::vector<StrainResult> ComputeStrains(const std::vector<Cvec
 SIFT_LIBRARY_API std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp,
                                                           const StrainOptions &o = StrainOptions(), double zncc_min = 0,
                                                           bool accept_unconverged = false);
+
+struct SIFT_LIBRARY_API ValidationOptions {
+	int radius = 16;         // window half width in voxels (Chebyshev), 1..4096
+	int min_neighbours = 6;  // fewest neighbours a tested point may have, 3..1048576
+	int passes = 2;          // 1..8
+	double threshold = 2.0;  // a score above this flags the point
+	double eps = 0.1;        // noise floor in voxels added to the MAD
+};
+
+// the normalised median test of one point's displacement against its neighbours' (include/sift3d_hip.h): status 0 tested, 1 fewer than
+// min_neighbours neighbours, 2 coordinate out of range, 3 the point does not contribute (median and mad are the neighbours': the value
+// that fills the hole), -1 the call failed (message on stderr, like EstimateAffine).  flagged and pass come from the passes and are
+// authoritative, whatever the final score
+struct SIFT_LIBRARY_API ValidationResult {
+	double median[3] = {0, 0, 0}, mad[3] = {0, 0, 0};
+	double score = 0;
+	int neighbours = 0;
+	int status = -1;
+	int flagged = 0, pass = 0;
+	double seconds = 0;  // device time of the call
+};
+
+// outlier test of the displacements RefineDisplacements returned at the same points, between IC-GN and ComputeStrains: a point
+// contributes under ComputeStrains' rule (zncc_min, accept_unconverged); use_gradients carries a neighbour's value to the tested point
+// with the neighbour's own IC-GN gradient, which keeps strongly deforming fields clear of false alarms
+SIFT_LIBRARY_API std::vector<ValidationResult> ValidateDisplacements(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp,
+                                                                     const ValidationOptions &o = ValidationOptions(), double zncc_min = 0,
+                                                                     bool accept_unconverged = false, bool use_gradients = true);
+SIFT_LIBRARY_API std::vector<ValidationResult> ValidateDisplacements(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp,
+                                                                     const ValidationOptions &o = ValidationOptions(), double zncc_min = 0,
+                                                                     bool accept_unconverged = false, bool use_gradients = true);
+// one byte per point: 1 where the point was tested (status 0) and not flagged -- what the ComputeStrains overloads below take as keep
+SIFT_LIBRARY_API std::vector<unsigned char> KeepMask(const std::vector<ValidationResult> &validation);
+// ComputeStrains with a point contributing only where keep is non-zero as well (keep: one byte per point)
+SIFT_LIBRARY_API std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp,
+                                                          const std::vector<unsigned char> &keep, const StrainOptions &o = StrainOptions(),
+                                                          double zncc_min = 0, bool accept_unconverged = false);
+SIFT_LIBRARY_API std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp,
+                                                          const std::vector<unsigned char> &keep, const StrainOptions &o = StrainOptions(),
+                                                          double zncc_min = 0, bool accept_unconverged = false);
+// starts of a second RefineDisplacements (its init) from a first one and its validation: a point that was flagged (status 0), or that
+// did not contribute (status 3), restarts from its neighbours' median, A = [I | median], status 0; a kept point (tested, not flagged)
+// from the affine map of its own result, L = I + G and b with L q + b - q = u, status 0; any other point gets status 1 (no start)
+SIFT_LIBRARY_API std::vector<AffineFit> SeedsFromValidation(const std::vector<Cvec> &points, const std::vector<IcgnResult> &first,
+                                                            const std::vector<ValidationResult> &validation);
 
 }  // namespace CPUSIFT
 #endif

@@ -1,5 +1,6 @@
-// cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine / SearchDisplacements / RefineDisplacements / ComputeStrains over
-// sift3d_fit_affine / sift3d_fit_affine_local / sift3d_zncc_search / sift3d_icgn / sift3d_icgn_bspline / sift3d_strain, and
+// cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine / SearchDisplacements / RefineDisplacements / ValidateDisplacements /
+// ComputeStrains over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_zncc_search / sift3d_icgn / sift3d_icgn_bspline /
+// sift3d_validate_displacements / sift3d_strain, and
 // CPUSIFT::PrefilterBSpline over sift3d_bspline_prefilter (include/sift3d_hip.h).
 #include "../Include/cRegistration.h"
 
@@ -258,8 +259,33 @@ static std::vector<StrainResult> strains_of(const std::vector<int> &q, size_t m,
 	return res;
 }
 
-std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const StrainOptions &opts, double zncc_min,
-                                         bool accept_unconverged) {
+// the C records of m shell results (p, zncc, status; the rest zero)
+template <class CRecord, class Result>
+static std::vector<CRecord> c_records(const std::vector<Result> &disp, size_t m) {
+	std::vector<CRecord> ic(m ? m : 1);
+	memset(ic.data(), 0, sizeof(CRecord) * ic.size());
+	for (size_t i = 0; i < m; i++) {
+		memcpy(ic[i].p, disp[i].p, sizeof(ic[i].p));
+		ic[i].zncc = disp[i].zncc;
+		ic[i].status = disp[i].status;
+	}
+	return ic;
+}
+
+// valid[i] stays set only where keep[i] is (keep null: as it is); false (message on stderr) when keep has the wrong length
+static bool apply_keep(const std::vector<unsigned char> *keep, size_t m, std::vector<unsigned char> &valid) {
+	if (!keep) return true;
+	if (keep->size() != m) {
+		fprintf(stderr, "[3dsift_amd] ComputeStrains: %zu keep bytes for %zu points\n", keep->size(), m);
+		return false;
+	}
+	for (size_t i = 0; i < m; i++) valid[i] = valid[i] && (*keep)[i] ? 1 : 0;
+	return true;
+}
+
+static std::vector<StrainResult> strains_first(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp,
+                                               const std::vector<unsigned char> *keep, const StrainOptions &opts, double zncc_min,
+                                               bool accept_unconverged) {
 	const size_t m = points.size();
 	std::vector<StrainResult> res(m);
 	std::vector<int> q;
@@ -268,17 +294,21 @@ std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const 
 		fprintf(stderr, "[3dsift_amd] ComputeStrains: %zu displacements for %zu points\n", disp.size(), m);
 		return res;
 	}
-	std::vector<sift3d_icgn_result> ic(m ? m : 1);
-	memset(ic.data(), 0, sizeof(sift3d_icgn_result) * ic.size());
-	for (size_t i = 0; i < m; i++) {
-		memcpy(ic[i].p, disp[i].p, sizeof(ic[i].p));
-		ic[i].zncc = disp[i].zncc;
-		ic[i].status = disp[i].status;
-	}
+	const std::vector<sift3d_icgn_result> ic = c_records<sift3d_icgn_result>(disp, m);
 	std::vector<double> u(3 * (m ? m : 1));
 	std::vector<unsigned char> valid(m ? m : 1);
 	const int rc = sift3d_strain_input_from_icgn(ic.data(), (int)m, zncc_min, accept_unconverged ? 1 : 0, u.data(), valid.data());
+	if (!apply_keep(keep, m, valid)) return res;
 	return strains_of(q, m, rc, u, valid, opts);
+}
+
+std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const StrainOptions &opts, double zncc_min,
+                                         bool accept_unconverged) {
+	return strains_first(points, disp, nullptr, opts, zncc_min, accept_unconverged);
+}
+std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const std::vector<unsigned char> &keep,
+                                         const StrainOptions &opts, double zncc_min, bool accept_unconverged) {
+	return strains_first(points, disp, &keep, opts, zncc_min, accept_unconverged);
 }
 
 Cvec Icgn2Result::Displacement() const { return Cvec((float)p[0], (float)p[10], (float)p[20]); }
@@ -335,8 +365,9 @@ std::vector<Icgn2Result> RefineDisplacementsSecondOrder(const float *ref, int nx
 	return res;
 }
 
-std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp, const StrainOptions &opts,
-                                         double zncc_min, bool accept_unconverged) {
+static std::vector<StrainResult> strains_second(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp,
+                                                const std::vector<unsigned char> *keep, const StrainOptions &opts, double zncc_min,
+                                                bool accept_unconverged) {
 	const size_t m = points.size();
 	std::vector<int> q;
 	if (!int_triples("ComputeStrains", "point", points, q)) return std::vector<StrainResult>(m);
@@ -344,17 +375,135 @@ std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const 
 		fprintf(stderr, "[3dsift_amd] ComputeStrains: %zu displacements for %zu points\n", disp.size(), m);
 		return std::vector<StrainResult>(m);
 	}
-	std::vector<sift3d_icgn2_result> ic(m ? m : 1);
-	memset(ic.data(), 0, sizeof(sift3d_icgn2_result) * ic.size());
-	for (size_t i = 0; i < m; i++) {
-		memcpy(ic[i].p, disp[i].p, sizeof(ic[i].p));
-		ic[i].zncc = disp[i].zncc;
-		ic[i].status = disp[i].status;
-	}
+	const std::vector<sift3d_icgn2_result> ic = c_records<sift3d_icgn2_result>(disp, m);
 	std::vector<double> u(3 * (m ? m : 1));
 	std::vector<unsigned char> valid(m ? m : 1);
 	const int rc = sift3d_strain_input_from_icgn2(ic.data(), (int)m, zncc_min, accept_unconverged ? 1 : 0, u.data(), valid.data());
+	if (!apply_keep(keep, m, valid)) return std::vector<StrainResult>(m);
 	return strains_of(q, m, rc, u, valid, opts);
+}
+
+std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp, const StrainOptions &opts,
+                                         double zncc_min, bool accept_unconverged) {
+	return strains_second(points, disp, nullptr, opts, zncc_min, accept_unconverged);
+}
+std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp, const std::vector<unsigned char> &keep,
+                                         const StrainOptions &opts, double zncc_min, bool accept_unconverged) {
+	return strains_second(points, disp, &keep, opts, zncc_min, accept_unconverged);
+}
+
+// the validation call behind both ValidateDisplacements overloads: rc is what the input conversion returned
+static std::vector<ValidationResult> validation_of(const std::vector<int> &q, size_t m, int rc, const std::vector<double> &u,
+                                                   const std::vector<double> &g, bool use_gradients, const std::vector<unsigned char> &valid,
+                                                   const ValidationOptions &opts) {
+	std::vector<ValidationResult> res(m);
+	sift3d_validate_options o;
+	sift3d_default_validate_options(&o);
+	o.radius = opts.radius;
+	o.min_neighbours = opts.min_neighbours;
+	o.passes = opts.passes;
+	o.threshold = opts.threshold;
+	o.eps = opts.eps;
+	std::vector<sift3d_validate_result> r(m ? m : 1);
+	double sec = 0;
+	if (rc == SIFT3D_OK)
+		rc = sift3d_validate_displacements(q.data(), u.data(), use_gradients ? g.data() : nullptr, valid.data(), (int)m, &o, 0, GetDevice(), r.data(),
+		                                   &sec);
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] ValidateDisplacements: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return res;
+	}
+	for (size_t i = 0; i < m; i++) {
+		memcpy(res[i].median, r[i].median, sizeof(res[i].median));
+		memcpy(res[i].mad, r[i].mad, sizeof(res[i].mad));
+		res[i].score = r[i].score;
+		res[i].neighbours = r[i].neighbours;
+		res[i].status = r[i].status;
+		res[i].flagged = r[i].flagged;
+		res[i].pass = r[i].pass;
+		res[i].seconds = sec;
+	}
+	return res;
+}
+
+template <class CRecord, class Result, class Convert>
+static std::vector<ValidationResult> validate_results(const std::vector<Cvec> &points, const std::vector<Result> &disp, const ValidationOptions &opts,
+                                                      double zncc_min, bool accept_unconverged, bool use_gradients, Convert convert) {
+	const size_t m = points.size();
+	std::vector<int> q;
+	if (!int_triples("ValidateDisplacements", "point", points, q)) return std::vector<ValidationResult>(m);
+	if (disp.size() != m) {
+		fprintf(stderr, "[3dsift_amd] ValidateDisplacements: %zu displacements for %zu points\n", disp.size(), m);
+		return std::vector<ValidationResult>(m);
+	}
+	const std::vector<CRecord> ic = c_records<CRecord>(disp, m);
+	std::vector<double> u(3 * (m ? m : 1)), g(9 * (m ? m : 1));
+	std::vector<unsigned char> valid(m ? m : 1);
+	const int rc = convert(ic.data(), (int)m, zncc_min, accept_unconverged ? 1 : 0, u.data(), g.data(), valid.data());
+	return validation_of(q, m, rc, u, g, use_gradients, valid, opts);
+}
+
+std::vector<ValidationResult> ValidateDisplacements(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const ValidationOptions &opts,
+                                                    double zncc_min, bool accept_unconverged, bool use_gradients) {
+	return validate_results<sift3d_icgn_result>(points, disp, opts, zncc_min, accept_unconverged, use_gradients, sift3d_validate_input_from_icgn);
+}
+std::vector<ValidationResult> ValidateDisplacements(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp, const ValidationOptions &opts,
+                                                    double zncc_min, bool accept_unconverged, bool use_gradients) {
+	return validate_results<sift3d_icgn2_result>(points, disp, opts, zncc_min, accept_unconverged, use_gradients, sift3d_validate_input_from_icgn2);
+}
+
+// the C records of the shell's validation results
+static std::vector<sift3d_validate_result> c_validation(const std::vector<ValidationResult> &v) {
+	std::vector<sift3d_validate_result> r(v.size() ? v.size() : 1);
+	memset(r.data(), 0, sizeof(sift3d_validate_result) * r.size());
+	for (size_t i = 0; i < v.size(); i++) {
+		memcpy(r[i].median, v[i].median, sizeof(r[i].median));
+		memcpy(r[i].mad, v[i].mad, sizeof(r[i].mad));
+		r[i].score = v[i].score;
+		r[i].neighbours = v[i].neighbours;
+		r[i].status = v[i].status;
+		r[i].flagged = v[i].flagged;
+		r[i].pass = v[i].pass;
+	}
+	return r;
+}
+
+std::vector<unsigned char> KeepMask(const std::vector<ValidationResult> &validation) {
+	const size_t m = validation.size();
+	std::vector<unsigned char> keep(m ? m : 1);
+	sift3d_validate_keep(c_validation(validation).data(), nullptr, (int)m, keep.data());
+	keep.resize(m);
+	return keep;
+}
+
+std::vector<AffineFit> SeedsFromValidation(const std::vector<Cvec> &points, const std::vector<IcgnResult> &first,
+                                           const std::vector<ValidationResult> &validation) {
+	const size_t m = points.size();
+	std::vector<AffineFit> seeds(m);
+	for (size_t i = 0; i < m; i++) seeds[i].status = 1;
+	if (first.size() != m || validation.size() != m) {
+		fprintf(stderr, "[3dsift_amd] SeedsFromValidation: %zu results and %zu validation records for %zu points\n", first.size(), validation.size(), m);
+		return seeds;
+	}
+	// the rows sift3d_icgn_init_from_validation writes are the reseeded points: every row starts as NaN and a written row is finite
+	std::vector<double> p0(12 * (m ? m : 1), (double)NAN);
+	sift3d_icgn_init_from_validation(c_validation(validation).data(), (int)m, p0.data(), nullptr);
+	for (size_t i = 0; i < m; i++) {
+		const double *p = p0.data() + 12 * i;
+		const bool reseed = std::isfinite(p[0]) && std::isfinite(p[4]) && std::isfinite(p[8]);
+		const bool kept = validation[i].status == 0 && !validation[i].flagged;
+		if (!reseed && !kept) continue;
+		const double q[3] = {points[i].x, points[i].y, points[i].z};
+		for (int c = 0; c < 3; c++) {
+			double L[3], u = reseed ? p[4 * c] : first[i].p[4 * c];
+			for (int a = 0; a < 3; a++) L[a] = (a == c ? 1.0 : 0.0) + (reseed ? 0.0 : first[i].p[4 * c + 1 + a]);
+			// b_c = q_c + u_c - L_c . q
+			for (int a = 0; a < 3; a++) seeds[i].A[4 * c + a] = L[a];
+			seeds[i].A[4 * c + 3] = (q[c] + u) - ((L[0] * q[0] + L[1] * q[1]) + L[2] * q[2]);
+		}
+		seeds[i].status = 0;
+	}
+	return seeds;
 }
 
 }  // namespace CPUSIFT

@@ -799,6 +799,91 @@ int sift3d_strain_input_from_icgn2(const sift3d_icgn2_result *res, int m, double
 int sift3d_strain(const int *points3, const double *disp3, const unsigned char *valid, int m, const sift3d_strain_options *o, int on_device,
                   int device, sift3d_strain_result *out, double *seconds);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Outlier validation of the displacement field: the normalised median test (Westerweel & Scarano 2005) for scattered 3-D POIs (no
+ * reference counterpart).  The step between IC-GN and strain: a POI whose IC-GN converged on the wrong correlation peak has status 0
+ * and a respectable ZNCC, and would spoil the plane fit of every POI within the strain window.  Its vector is compared with the
+ * median of its neighbours' vectors, the difference scaled by their median absolute deviation (MAD) plus a noise floor.
+ * Numerical contract (bit for bit: every step is one correctly rounded fp64 operation and nothing is summed over neighbours;
+ * tests/validate_ref.py restates it in NumPy):
+ *   Inputs: points3, disp3, valid as for sift3d_strain; grad9 (may be NULL): m rows of the POIs' own displacement gradients,
+ *     row-major: rows u v w, columns x y z (IC-GN's p[1..3], p[5..7], p[9..11]).  A POI contributes under sift3d_strain's rule
+ *     (non-zero valid byte, three finite displacements, every |coordinate| <= 2^24) and, with grad9 given, nine finite gradients.
+ *   Neighbours of POI i: the contributing POIs j != i within `radius` of it (integer Chebyshev distance, exact); duplicates count, so
+ *     a duplicate of POI i at another index is its neighbour, POI i itself never is.
+ *   Neighbour j's estimate at POI i: e_c = u_c(j) without grad9; with it e_c = u_c(j) + ((G_c0 dx + G_c1 dy) + G_c2 dz), G row c of
+ *     POI j's gradient and d = q_i - q_j as doubles, in this association and not fused.
+ *   Statistics over a neighbour set N, n = |N|, per component c: median_c the exact order statistic of e_c (n odd: the middle value;
+ *     n even: 0.5 * (lo + hi) of the two middle values); mad_c the same median of |e_c - median_c|;
+ *     score = max_c |u_c(i) - median_c| / (mad_c + eps).  -0 and +0 are one value.  The result depends neither on the order of the
+ *     neighbours nor on the order of the POIs.
+ *   Passes: F_0 is empty.  In pass p = 1..passes every contributing POI i not in F_(p-1) is scored against N = {neighbours not in
+ *     F_(p-1)}; all POIs of a pass read the flags of the pass before.  n >= min_neighbours and score > threshold: i joins F_p with
+ *     pass = p.  Flags are never withdrawn.
+ *   Report: after the last pass every POI gets a record from N built with the final F.  Status, checked in this order:
+ *     2 a coordinate out of range (neighbours 0, the doubles 0);  1 n < min_neighbours (the doubles 0, n reported);  3 the POI does
+ *     not contribute: median and mad are reported, score is 0 and the POI is never flagged -- the value that fills a hole;
+ *     0 the POI was tested: score is its score against the final set.
+ *     flagged and pass come from the passes and are authoritative: the final score of an unflagged POI may end above the threshold
+ *     (its neighbourhood lost members in the last pass) and the POI stays unflagged.  A flagged POI whose final n is below the minimum
+ *     keeps flagged = 1 with status 1.
+ *   Determinism: no float atomics and no reductions in floating point: two calls return the same bytes.
+ * SIFT3D_ERR_ARG (checked before any device call): m < 0, radius outside 1..4096, min_neighbours outside 3..1048576, passes outside
+ * 1..8, a threshold or eps that is not finite and > 0, a non-zero reserved word, NULL out, NULL points3 or disp3 with m > 0; m = 0
+ * succeeds.  SIFT3D_ERR_NO_DEVICE after that check when no GPU is visible: there is no CPU fallback.  o may be NULL (defaults).
+ * on_device != 0: points3, disp3, grad9 and valid are device pointers on `device`, ordered behind the legacy default stream; out is
+ * host memory, filled by one copy at the end.  *seconds (may be NULL): device time of the call (HIP events; uploads excluded).
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct sift3d_validate_options {
+	int radius;            /* window half width in voxels (Chebyshev), 1..4096, default 16 */
+	int min_neighbours;    /* fewest neighbours a tested POI may have, 3..1048576, default 6 */
+	int passes;            /* 1..8, default 2 */
+	int reserved0;         /* must be 0 */
+	double threshold;      /* finite, > 0, default 2.0: a score above it flags the POI */
+	double eps;            /* finite, > 0, default 0.1: noise floor in voxels added to the MAD */
+	int reserved[4];       /* must be 0 */
+} sift3d_validate_options;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_validate_options) == 48, "sift3d_validate_options must be 48 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_validate_options, min_neighbours) == 4 && offsetof(sift3d_validate_options, passes) == 8 &&
+                     offsetof(sift3d_validate_options, reserved0) == 12 && offsetof(sift3d_validate_options, threshold) == 16 &&
+                     offsetof(sift3d_validate_options, eps) == 24 && offsetof(sift3d_validate_options, reserved) == 32,
+                     "sift3d_validate_options field offsets");
+
+typedef struct sift3d_validate_result {
+	double median[3];      /* of the neighbours' estimates at the POI, per component */
+	double mad[3];         /* median absolute deviation of the same */
+	double score;          /* max_c |u_c - median_c| / (mad_c + eps) against the final set; 0 unless status is 0 */
+	int neighbours;        /* n of the final set */
+	int status;            /* the table above */
+	int flagged;           /* 1: an outlier (authoritative, from the passes) */
+	int pass;              /* the pass that flagged it, 0 if none */
+} sift3d_validate_result;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_validate_result) == 72, "sift3d_validate_result must be 72 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_validate_result, mad) == 24 && offsetof(sift3d_validate_result, score) == 48 &&
+                     offsetof(sift3d_validate_result, neighbours) == 56 && offsetof(sift3d_validate_result, status) == 60 &&
+                     offsetof(sift3d_validate_result, flagged) == 64 && offsetof(sift3d_validate_result, pass) == 68,
+                     "sift3d_validate_result field offsets");
+
+/* the defaults above; needs no GPU */
+void sift3d_default_validate_options(sift3d_validate_options *o);
+/* host only, no GPU: sift3d_strain_input_from_icgn (the same disp3 and valid, by the same rule) and row i of grad9 = p[1..3], p[5..7],
+ * p[9..11] of res[i]; grad9 may be NULL (not wanted).  SIFT3D_ERR_ARG as there. */
+int sift3d_validate_input_from_icgn(const sift3d_icgn_result *res, int m, double zncc_min, int accept_unconverged, double *disp3,
+                                    double *grad9, unsigned char *valid);
+/* the same from second-order results: disp3 = (p[0], p[10], p[20]), grad9 = the first derivatives p[1..3], p[11..13], p[21..23] */
+int sift3d_validate_input_from_icgn2(const sift3d_icgn2_result *res, int m, double zncc_min, int accept_unconverged, double *disp3,
+                                     double *grad9, unsigned char *valid);
+/* m POIs (x, y, z int triples), their displacements (m * 3), gradients (m * 9, or NULL) and validity bytes (m, or NULL); out: m records */
+int sift3d_validate_displacements(const int *points3, const double *disp3, const double *grad9, const unsigned char *valid, int m,
+                                  const sift3d_validate_options *o, int on_device, int device, sift3d_validate_result *out, double *seconds);
+/* host only: valid_out[i] = 1 iff (valid_in is NULL or valid_in[i] != 0), val[i].status == 0 and val[i].flagged == 0 -- the bytes to
+ * hand to sift3d_strain.  valid_out may be valid_in.  SIFT3D_ERR_ARG: m < 0, or NULL val / valid_out with m > 0. */
+int sift3d_validate_keep(const sift3d_validate_result *val, const unsigned char *valid_in, int m, unsigned char *valid_out);
+/* host only: the rows of init12 (m * 12) whose record is flagged with status 0, or has status 3, become (median_u, 0, 0, 0, median_v,
+ * 0, 0, 0, median_w, 0, 0, 0): the neighbours' median as the start of a second sift3d_icgn.  Every other row stays as it is.
+ * *count (may be NULL): rows written.  SIFT3D_ERR_ARG: m < 0, or NULL val / init12 with m > 0. */
+int sift3d_icgn_init_from_validation(const sift3d_validate_result *val, int m, double *init12, int *count);
+
 /* Test hooks, rare-path counters and the unit-level debug entry points live in include/sift3d_hip_test.h: this header is the
  * product boundary only. */
 const char *sift3d_error_string(int code);

@@ -65,6 +65,10 @@ int sift3d_test_slab_plan(int nz, int world, int min_planes, double side_w, doub
  * that rank on a node of `world` GPUs, short of what its transfers wait for.  Results are not changed. */
 int sift3d_test_sharded_time_rank(sift3d_sharded_handle h, int rank, double *seconds);
 
+/* sift3d_validate_displacements selects its medians in LDS when a POI has at most *n neighbours and by re-walking the window above
+ * that: the switch point, so that tests can put neighbour counts on both sides of it.  Host only, no GPU. */
+int sift3d_validate_stage_capacity(int *n);
+
 #ifdef __cplusplus
 }
 #endif
