@@ -14,6 +14,14 @@
 // extremum.  Per-voxel terms are bit-identical to the reference; the ORDER of the fp32 additions of this first pass differs
 // (lane-strided + butterfly instead of sequential), which moves the tensor by ~1e-6 relative.
 //
+// What is scalar and what is fetched when.  The wave index goes through readfirstlane, so everything that is the same
+// for the 64 lanes -- the record, LevelRef, WinLut, the window bounds, the plane loop, the number of passes of a plane, the slot
+// rotation -- sits in SGPRs and branches on the scalar unit.  Per WINDOW: the weight table to LDS, the 2 list_R + 2 running starts of
+// the list into one VGPR (lane = plane; v_readlane per plane), the first three tile planes.  Per PLANE, in this order: one
+// s_waitcnt vmcnt(0) (everything it waits for was requested a plane ago), tile plane z + 1 to LDS, the request of tile plane z + 2
+// -- only the 16-byte pieces that touch the sphere dilated by one voxel -- then ceil(cnt / 64) passes, each followed by the load
+// of the same 64-entry slot of plane z + 1 into the register it has just read.  An empty slot issues nothing.
+//
 // r03 -- the window sums of every ACCEPTED keypoint are bit-identical to the reference's.  The descriptor is a discontinuous function
 // of the rotation matrix (a window voxel is in or out of the rotated 4x4x4 cube, Src/cSIFT3D.cc:1299-1303): a last-bit difference
 // of R flips single voxels, and where such a voxel carries a large gradient (small blobs at octave >= 1) one descriptor element
@@ -182,7 +190,7 @@ __device__ int finish_orientation(DevKp &kp, const float T6[6], const float w3[3
 // LDS tiles of the orientation window: the default radius (3 * 1.5 * scale <= 11.43 voxels) gives <= 25 voxels per side,
 // + 2 for the central differences; larger windows (non-default sigma) take the global-load path
 #ifndef S3D_ORI_UN
-#define S3D_ORI_UN 2  /* window voxels per lane and pass */
+#define S3D_ORI_UN 2  /* window voxels per lane and pass of the box scan (the list path runs one slot of 64 entries per pass) */
 #endif
 constexpr int kTileW = 28, kTileH = 27;
 constexpr int kTilePc = ((kTileW / 4) * kTileH + 63) / 64;  // 16-byte pieces of a tile plane per lane (3)
@@ -204,7 +212,11 @@ __global__ void __launch_bounds__(256) k_orient(DevKp *__restrict__ kps, int *__
 	__shared__ __attribute__((aligned(16))) float s_terms[EXACT ? 4 * 9 * kTermPitch : 4];
 	const unsigned count = min(d_count[0], cap);
 	const int lane = threadIdx.x & 63;
-	const unsigned wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+	// the wave-in-block index through readfirstlane: threadIdx.x >> 6 IS the same in every lane of a wave, but only this tells the
+	// compiler -- with it the window's whole state (j, k, the record, LevelRef, WinLut, the bounds, the trip counts, the slot rotation,
+	// the LDS bases) lives in SGPRs and every loop and test on it is a scalar branch, not an exec-mask loop
+	const unsigned wib = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	const unsigned wave = blockIdx.x * (blockDim.x >> 6) + wib;
 	const unsigned nwaves = gridDim.x * (blockDim.x >> 6);
 	// partitioned run: this rank orients the extrema k = j * world + rank (dealt densely to the waves); the others get code 0
 	const unsigned pw = part_world > 1 ? (unsigned)part_world : 1u, pr = part_world > 1 ? (unsigned)part_rank : 0u;
@@ -212,11 +224,12 @@ __global__ void __launch_bounds__(256) k_orient(DevKp *__restrict__ kps, int *__
 		for (unsigned k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x)
 			if (k % pw != pr) { kps[k].code = 0; codes[k] = 0; }
 	const unsigned owned = EXACT ? min(redo_count[0], cap) : (count > pr ? (count - pr + pw - 1) / pw : 0u);
-	float *tb = &s_terms[EXACT ? (threadIdx.x >> 6) * 9 * kTermPitch : 0];
+	float *tb = &s_terms[EXACT ? wib * 9 * kTermPitch : 0];
 	for (unsigned j = wave; j < owned; j += nwaves) {
-		const unsigned k = EXACT ? (unsigned)redo_list[j] : j * pw + pr;
-		const int cxi = kps[k].x, cyi = kps[k].y, czi = kps[k].z;
-		const int li = kps[k].octave * 8 + kps[k].level;
+		// (the record is read from memory this kernel also writes, so its loads are vector loads: one readfirstlane each)
+		const unsigned k = EXACT ? (unsigned)__builtin_amdgcn_readfirstlane(redo_list[j]) : j * pw + pr;
+		const int cxi = __builtin_amdgcn_readfirstlane(kps[k].x), cyi = __builtin_amdgcn_readfirstlane(kps[k].y), czi = __builtin_amdgcn_readfirstlane(kps[k].z);
+		const int li = __builtin_amdgcn_readfirstlane(kps[k].octave * 8 + kps[k].level);
 		const LevelRef L = levels[li];
 		const WinLut lut = luts[li * 2 + 0];
 		const float *__restrict__ wtab = lutpool + lut.off;
@@ -225,6 +238,10 @@ __global__ void __launch_bounds__(256) k_orient(DevKp *__restrict__ kps, int *__
 		win_bounds((float)cxi, lut.radius, u, L.nx, x0, x1);
 		win_bounds((float)cyi, lut.radius, u, L.ny, y0, y1);
 		win_bounds((float)czi, lut.radius, u, L.nz, z0, z1);
+		// (fp32 arithmetic on uniform values runs on the vector unit: the bounds come back to SGPRs here)
+		x0 = __builtin_amdgcn_readfirstlane(x0); x1 = __builtin_amdgcn_readfirstlane(x1);
+		y0 = __builtin_amdgcn_readfirstlane(y0); y1 = __builtin_amdgcn_readfirstlane(y1);
+		z0 = __builtin_amdgcn_readfirstlane(z0); z1 = __builtin_amdgcn_readfirstlane(z1);
 		const int wx = x1 - x0 + 1, wy = y1 - y0 + 1;
 		const int plane = (wx > 0 && wy > 0) ? wx * wy : 0;
 		const float inv_wx = 1.0f / (float)(wx > 0 ? wx : 1);
@@ -287,8 +304,15 @@ __global__ void __launch_bounds__(256) k_orient(DevKp *__restrict__ kps, int *__
 			// ---- LDS path: three consecutive (tw x th) planes of the level live in this wave's LDS slots, so a window
 			// voxel costs one global load (plus border) instead of six; plane z+2 is requested into registers while plane
 			// z is processed and written to its slot one iteration later.  Same voxel -> lane mapping as the global path below.
-			float *tile = &s_tile[(threadIdx.x >> 6) * 3 * kTileW * kTileH];
-			float *wl = &s_wlut[(threadIdx.x >> 6) * kOriLut];   // this wave's copy of the window weights
+			float *tile = &s_tile[wib * 3 * kTileW * kTileH];
+			float *wl = &s_wlut[wib * kOriLut];   // this wave's copy of the window weights
+			// the running starts of the window's list (2 list_R + 2 words, list_R <= 12 wherever the list is used: a central plane of
+			// <= 64 * kEL points), one per lane, requested once per window and ahead of the tile planes: the plane loop takes the
+			// starts of a plane with v_readlane and never waits for memory on their behalf
+			const int LR = lut.list_R;
+			const bool has_list = lut.list_off >= 0 && 2 * LR + 2 <= 64;
+			const unsigned *__restrict__ lst = reinterpret_cast<const unsigned *>(lutpool) + (has_list ? lut.list_off : 0);
+			const int starts = has_list && lane < 2 * LR + 2 ? (int)lst[lane] : 0;
 			for (int i = lane; i < lut.len && i < kOriLut; i += 64) wl[i] = wtab[i];
 			// The tile planes travel as 16-byte pieces (dword-aligned global_load_dwordx4, ds_write_b128): 3 vector-memory
 			// instructions per lane and plane instead of 12 -- their ISSUE is what costs.  The last piece of a row may reach up to
@@ -299,6 +323,8 @@ __global__ void __launch_bounds__(256) k_orient(DevKp *__restrict__ kps, int *__
 			const float inv_npx = 1.0f / (float)npx;
 			int toff[kTilePc];   // per-lane tile offsets of the pieces this lane moves (same for every plane)
 			int goff[kTilePc];
+			int pd2[kTilePc];    // see request() below
+			const int cxt = cxi - x0 + 1, cyt = cyi - y0 + 1;  // the centre's tile column and row
 #pragma unroll
 			for (int i = 0; i < kTilePc; i++) {
 				const int idx = lane + 64 * i;
@@ -307,13 +333,26 @@ __global__ void __launch_bounds__(256) k_orient(DevKp *__restrict__ kps, int *__
 				const bool ok = idx < tnp;
 				toff[i] = ok ? ty * kTileW + 4 * px : -1;
 				goff[i] = ok ? (x0 - 1 + 4 * px) + (int)sy * (y0 - 1 + ty) : (x0 - 1) + (int)sy * (y0 - 1);
+				const int ax = max(max(4 * px - cxt, cxt - (4 * px + 3)) - 1, 0), ay = max(abs(ty - cyt) - 1, 0);
+				pd2[i] = ok ? ax * ax + ay * ay : 0x7fffffff;
 			}
 			const gfloat_p base = Ld - sz * (size_t)L.zoff;
-			f4o pf[kTilePc];
-			auto request = [&](int zp) {  // unconditional, clamped loads (planes z0-1 .. z1+1 are inside the level)
+			// The pieces of a tile plane that a pass can read.  A pass reads the tile at a lattice point p of the sphere (|p|^2 <= nin)
+			// and at its six axis neighbours, so a voxel at offset (dx, dy, dz) from the centre is read only if
+			// max(|dx| - 1, 0)^2 + max(|dy| - 1, 0)^2 + max(|dz| - 1, 0)^2 <= nin (a superset: p is the voxel or lies one step along ONE
+			// axis).  pd2[i] is the in-plane part of that sum for piece i, with |dx| of the piece's column nearest the centre; the planes
+			// requested inside the loop fetch only the pieces that pass -- what the window's box holds outside that region (46 % of
+			// the pieces of the largest default window) is not requested.  (A piece left out keeps whatever the registers and the LDS slot held: no point of the list reads it,
+			// and what a masked lane reads at its stand-in address is dropped by selection.)
+			f4o pf[kTilePc] = {};
+			// planes z0-1 .. z1+1 are inside the level.  part: only the pieces above (the list path; lanes without one issue nothing)
+			auto request = [&](int zp, bool part) {
 				const gfloat_p pl = base + sz * (size_t)zp;
+				const int az = max(abs(zp - czi) - 1, 0);
+				const int lim = part ? lut.nin - az * az : 0x7ffffffe;
 #pragma unroll
-				for (int i = 0; i < kTilePc; i++) pf[i] = *reinterpret_cast<const f4o __attribute__((address_space(1))) *>(pl + goff[i]);
+				for (int i = 0; i < kTilePc; i++)
+					if (pd2[i] <= lim) pf[i] = *reinterpret_cast<const f4o __attribute__((address_space(1))) *>(pl + goff[i]);
 			};
 			auto deposit = [&](int slot) {
 				float *dstp = tile + slot * (kTileW * kTileH);
@@ -321,43 +360,53 @@ __global__ void __launch_bounds__(256) k_orient(DevKp *__restrict__ kps, int *__
 				for (int i = 0; i < kTilePc; i++)
 					if (toff[i] >= 0) *reinterpret_cast<float4 *>(dstp + toff[i]) = make_float4(pf[i].x, pf[i].y, pf[i].z, pf[i].w);
 			};
-			request(z0 - 1); deposit(0);
-			request(z0);     deposit(1);
-			request(z0 + 1);
+			request(z0 - 1, false); deposit(0);
+			request(z0, false);     deposit(1);
+			request(z0 + 1, false);
 			int sm = 0, sc = 1, sp = 2;  // slots of planes z-1, z, z+1
 			// lattice list of the window sphere (see the plane loop): up to kEL entries per lane and plane, held in registers
 			constexpr int kEL = 8;
-			const unsigned *__restrict__ lst = reinterpret_cast<const unsigned *>(lutpool) + (lut.list_off >= 0 ? lut.list_off : 0);
-			const int LR = lut.list_R;
 			const unsigned *__restrict__ ent = lst + 2 * LR + 2;
-			const bool use_list = lut.list_off >= 0 && (int)lst[LR + 1] - (int)lst[LR] <= 64 * kEL;  // the central plane is the largest
+			// the central plane is the largest
+			const bool use_list = has_list && __builtin_amdgcn_readlane(starts, has_list ? LR + 1 : 0) - __builtin_amdgcn_readlane(starts, has_list ? LR : 0) <= 64 * kEL;
 			const int ox = cxi - x0 - 128, oy = cyi - y0 - 128;  // entry -> window coordinates
-			unsigned En[kEL];
-			int cntn = 0;
-			auto fetch_entries = [&](int dzp) {
+			// The entries of a plane: ceil(cnt / 64) slots of 64 (a default plane holds 1 .. 421 entries, 150 on average), slot i in
+			// E[i], each loaded from the plane's scalar base with a 32-bit lane offset; lanes past the end of the plane read its last
+			// entry and are masked.  ONE set of registers: the pass over slot i of plane z is followed by the load of slot i of plane
+			// z + 1 into the same register, a whole plane ahead of its use.
+			unsigned E[kEL] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+			int cnt = 0, cntn = 0;             // entries of this plane and of the next
+			const unsigned *__restrict__ pen = ent;  // the next plane's entries
+			auto plane_entries = [&](int dzp) {
 				const int pi = dzp + LR;
 				const bool has = use_list && pi >= 0 && pi <= 2 * LR;
-				const int e0 = has ? (int)lst[pi] : 0, e1 = has ? (int)lst[pi + 1] : 0;
+				const int e0 = has ? __builtin_amdgcn_readlane(starts, pi) : 0, e1 = has ? __builtin_amdgcn_readlane(starts, pi + 1) : 0;
 				cntn = e1 - e0;
-#pragma unroll
-				for (int i = 0; i < kEL; i++) {
-					const int idx = e0 + i * 64 + lane;
-					En[i] = ent[idx < e1 ? idx : e0];
-				}
+				pen = ent + e0;
 			};
-			fetch_entries(z0 - czi);
+			auto load_slot = [&](int i) { E[i] = pen[min((unsigned)(i * 64 + lane), (unsigned)(cntn - 1))]; };
+			plane_entries(z0 - czi);
+#pragma unroll
+			for (int i = 0; i < kEL; i++) {
+				if (i * 64 >= cntn) break;  // wave-uniform
+				load_slot(i);
+			}
 			for (int z = z0; z <= z1; z++) {
+				// The loop's one wait for memory, s_waitcnt vmcnt(0): tile plane z + 1 and this plane's entries, requested while plane
+				// z - 1 was processed.  Stated here so that no pass below waits: left to itself the compiler counts the loads behind
+				// the uniform branches at their fewest and drains the tile request of THIS plane in front of the second and third pass.
+				__builtin_amdgcn_s_waitcnt(0x0F70);
 #if !defined(S3D_ODIAG) || !(S3D_ODIAG & 2)  // (timing only: no tile traffic)
 				deposit(sp);                       // plane z+1 (requested one iteration ago)
-				request(min(z + 2, z1 + 1));       // in flight while plane z is processed
+				request(min(z + 2, z1 + 1), use_list);  // in flight while plane z is processed
 #endif
 				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 				__builtin_amdgcn_wave_barrier();
 				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 				const float *pm = tile + sm * (kTileW * kTileH), *pc = tile + sc * (kTileW * kTileH), *pp = tile + sp * (kTileW * kTileH);
 				const int dz = z - czi;
-				// kUn voxels per pass, all LDS reads (weights included) issued before the first use; inactive voxels read
-				// valid addresses and are masked, so the loop body is branch-free and pipelines
+				// box scan: kUn voxels per pass, all LDS reads (weights included) issued before the first use; inactive voxels read
+				// valid addresses and are masked
 				constexpr int kUn = S3D_ORI_UN;
 #ifdef S3D_ODIAG
 				if (S3D_ODIAG & 1) { } else  // timing only: no window arithmetic
@@ -367,37 +416,30 @@ __global__ void __launch_bounds__(256) k_orient(DevKp *__restrict__ kps, int *__
 					// outside the sphere, and the list also carries n = dx^2 + dy^2 + dz^2.  Windows clipped by the level border skip
 					// the entries outside their box.  This plane's entries were requested one plane ago (a load inside the pass loop
 					// would put a memory round trip in front of every pass).  The list is in (dy, dx) order: the reference's loop order.
-					unsigned E[kEL];
+					cnt = cntn;
+					plane_entries(dz + 1);
 #pragma unroll
-					for (int i = 0; i < kEL; i++) E[i] = En[i];
-					const int cnt = cntn;
-					fetch_entries(dz + 1);
-#pragma unroll
-					for (int p0 = 0; p0 < kEL; p0 += kUn) {
-						if (p0 * 64 >= cnt) break;  // wave-uniform
-						float nb[kUn][6], w[kUn];
-#pragma unroll
-						for (int q = 0; q < kUn; q++) {
-							const unsigned e = E[p0 + q];
+					for (int i = 0; i < kEL; i++) {
+						if (i * 64 >= cnt && i * 64 >= cntn) break;  // wave-uniform: an empty slot issues no read, no sum and no load
+						if (i * 64 < cnt) {
+							const unsigned e = E[i];
 							const int lx = (int)(e & 255u) + ox, ly = (int)((e >> 8) & 255u) + oy;
-							const bool ok = (p0 + q) * 64 + lane < cnt && (unsigned)lx < (unsigned)wx && (unsigned)ly < (unsigned)wy;
-							w[q] = ok ? wl[e >> 16] : -1.0f;
+							// outside the clipped box / past the end of the plane's list.  (Every entry is inside the sphere: its weight is
+							// >= 0, so `ok` alone decides -- the weight read need not come back before the neighbours are requested.)
+							const bool ok = i * 64 + lane < cnt && (unsigned)lx < (unsigned)wx && (unsigned)ly < (unsigned)wy;
+							const float w = ok ? wl[e >> 16] : -1.0f;
 							const int o = ok ? __mul24(ly + 1, kTileW) + lx + 1 : kTileW + 1;  // (24-bit multiply: full rate)
-							nb[q][0] = pc[o + 1]; nb[q][1] = pc[o - 1]; nb[q][2] = pc[o + kTileW]; nb[q][3] = pc[o - kTileW];
-							nb[q][4] = pp[o]; nb[q][5] = pm[o];
+							emit(ok, pc[o + 1], pc[o - 1], pc[o + kTileW], pc[o - kTileW], pp[o], pm[o], w, min(64, cnt - i * 64));
 						}
-#pragma unroll
-						for (int q = 0; q < kUn; q++) {
-							if (EXACT && (p0 + q) * 64 >= cnt) break;  // wave-uniform: nothing left in this plane
-							// w < 0: outside the clipped box / past the end of the plane's list
-							emit(!(w[q] < 0.0f), nb[q][0], nb[q][1], nb[q][2], nb[q][3], nb[q][4], nb[q][5], w[q], min(64, cnt - (p0 + q) * 64));
-						}
+						// slot i of plane z + 1 into the register this pass has just read.  (Requested BEFORE the pass, the register
+						// allocator keeps both values and copies one at the end of the plane -- behind a wait for the load.)
+						if (i * 64 < cntn) load_slot(i);
 					}
 				} else if (EXACT) {
 					for (int vb = 0; vb < plane; vb += 64) {  // wave-uniform passes of 64 consecutive box voxels
 						const int v = vb + lane;
 						const int ly = (int)(((float)v + 0.5f) * inv_wx);
-						const int lx = v - ly * wx;
+						const int lx = v - __mul24(ly, wx);  // (the tile path: ly < 32, wx <= 26)
 						const int dx = x0 + lx - cxi, dy = y0 + ly - cyi;
 						const int n = dx * dx + dy * dy + dz * dz;
 						const bool in = v < plane && n < lut.len;
@@ -406,13 +448,13 @@ __global__ void __launch_bounds__(256) k_orient(DevKp *__restrict__ kps, int *__
 						emit(!(ww < 0.0f), pc[o + 1], pc[o - 1], pc[o + kTileW], pc[o - kTileW], pp[o], pm[o], ww, min(64, plane - vb));
 					}
 				} else
-				for (int v0 = lane; v0 < plane; v0 += 64 * kUn) {
+				for (int vb = 0; vb < plane; vb += 64 * kUn) {  // wave-uniform trip count; lanes past the end of the plane are masked
 					float nb[kUn][6], w[kUn];
 #pragma unroll
 					for (int q = 0; q < kUn; q++) {
-						const int v = v0 + 64 * q;
+						const int v = vb + lane + 64 * q;
 						const int ly = (int)(((float)v + 0.5f) * inv_wx);
-						const int lx = v - ly * wx;
+						const int lx = v - __mul24(ly, wx);
 						const int dx = x0 + lx - cxi, dy = y0 + ly - cyi;
 						const int n = dx * dx + dy * dy + dz * dz;
 						const bool ok = v < plane && n < lut.len;
@@ -496,7 +538,9 @@ void launch_orient(DevKp *kps, int *codes, const unsigned *d_count, unsigned cap
                    hipStream_t st) {
 	// windows differ 3x in volume between the keypoint levels: many short-lived workgroups (1-2 windows per wave) balance better than a
 	// resident-sized grid (0.70 vs 0.75 ms at 512^3; S3D_ORI_GRID to measure)
-	static const int ori_grid = dev_tune_i("S3D_ORI_GRID", 256 * 32);
+	static const int dflt_grid = dev_tune_i("S3D_ORI_GRID", 256 * 32);
+	// SIFT3D_HOOK_ORI_GRID (tests): n workgroups, so that a wave of a small volume orients many windows one after the other
+	const int ori_grid = hook(SIFT3D_HOOK_ORI_GRID) > 0 ? hook(SIFT3D_HOOK_ORI_GRID) : dflt_grid;
 	(void)hipMemsetAsync(redo_count, 0, sizeof(unsigned), st);
 	hipLaunchKernelGGL(k_orient<false>, dim3(ori_grid), dim3(256), 0, st, kps, codes, d_count, cap, d_levels, d_luts, d_lutpool, max_eig, corner,
 	                   part_rank, part_world, (const int *)redo_list, (const unsigned *)redo_count);

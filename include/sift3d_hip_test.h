@@ -36,7 +36,8 @@ enum {
 	SIFT3D_HOOK_DESC_EXACT_CELLS = 12, /* 1: k_describe forms the cell coordinates of EVERY voxel with the reference's arithmetic (default: only next to a discontinuity) */
 	SIFT3D_HOOK_LAZY_GENERIC = 13,  /* 1: every parked candidate of the lazy last level takes the one-workgroup form (default: interior ones one wave each) */
 	SIFT3D_HOOK_SHARDED_FAIL_RANK = 14, /* r + 1: rank r of the native z-slab driver gives up behind its pyramid -> the failure protocol (the other ranks are released, the handle is dead) */
-	SIFT3D_HOOK_COUNT = 15
+	SIFT3D_HOOK_ORI_GRID = 15,      /* n > 0: both k_orient launches use n workgroups of 4 waves (default 0: the product's grid) -> a wave orients many windows in a row */
+	SIFT3D_HOOK_COUNT = 16
 };
 int sift3d_test_hook(int which, int value);
 /* how often the rare paths ran: c[0] list regrows of the last run, c[1] keypoints whose descriptor took the second pass in
