@@ -577,6 +577,10 @@ int sift3d_icgn(const float *ref, int rnx, int rny, int rnz, const float *tar, i
  *     m the mirror index map of period 2n - 2 (m(-j) = j, m(n - 1 + j) = n - 1 - j, folded repeatedly when n <= K; m = 0 when n = 1).
  *   Products and sums are fp32, not fused, the sum over k accumulated from k = K down to 1 and added to s[i] last.  No float
  *     atomics and a fixed order: two calls return the same bytes.
+ *   Every operation being fixed, dst has the bytes of the restatement's float32 form (bspline_ref.prefilter(T, f32=True)) -- tested
+ *     at every seam of the kernel's 64 x 64 tiles along each axis, on axes of length 1 to 17 and with all seams at once, on inputs
+ *     whose intermediates are zero or normal (tests/test_gpu_bspline_edges.py).  The tolerance against the fp64 form of the filter
+ *     stays as the accuracy statement.
  *   Consequences: a constant volume returns itself bit for bit; an axis of length 1 is the identity (on finite values); a single
  *     non-finite voxel in the interior makes exactly the (2K+1)^3 cube around it non-finite and nothing outside that cube changes;
  *     the truncated tail (|z1|^17 = 1.9e-10) is below fp32 resolution: the fp64 form of this formula differs from the exact filter

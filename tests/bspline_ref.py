@@ -26,23 +26,31 @@ def mirror(i, n):
     return np.where(j < n, j, p - j)
 
 
-def prefilter(T, f32=False):
+def prefilter_axis(s, axis, h, ks=None):
+    """one axis pass of the header's formula on s, in s's type (h in the same type): the sum over k runs over ks, K down to 1 unless
+    a test hands in a deliberately wrong order or set of taps, and is added to s last"""
+    n = s.shape[axis]
+    i = np.arange(n)
+    acc = np.zeros_like(s)
+    for k in (range(K, 0, -1) if ks is None else ks):
+        lo, hi = np.take(s, mirror(i - k, n), axis), np.take(s, mirror(i + k, n), axis)
+        acc = acc + h[k - 1] * ((lo - s) + (hi - s))
+    return s + acc
+
+
+def prefilter(T, f32=False, ks=None, passes=None):
     """the coefficients of T (nz, ny, nx): x, then y, then z.  fp64 by default; f32: the intermediate volumes, every product and
-    every sum are float32 (the sum over k runs from K down to 1 and is added to s last, as in the header)"""
+    every sum are float32 (the sum over k runs from K down to 1 and is added to s last, as in the header).  ks: prefilter_axis's;
+    passes: a list that receives the volume after each axis pass"""
     dt = np.float32 if f32 else np.float64
     h = taps().astype(dt)
     c = np.asarray(T, dt)
     with np.errstate(invalid="ignore", over="ignore"):
         for axis in (2, 1, 0):
-            n = c.shape[axis]
-            i = np.arange(n)
-            s = c
-            acc = np.zeros_like(s)
-            for k in range(K, 0, -1):
-                lo, hi = np.take(s, mirror(i - k, n), axis), np.take(s, mirror(i + k, n), axis)
-                acc = acc + h[k - 1] * ((lo - s) + (hi - s))
-            c = s + acc
+            c = prefilter_axis(c, axis, h, ks)
             assert c.dtype == dt
+            if passes is not None:
+                passes.append(c)
     return c
 
 

@@ -2,7 +2,9 @@
 include/sift3d_hip.h; tests/bspline_ref.py): the library exports the entry points, bad arguments are refused before any device call,
 the restated prefilter is scipy's exact filter to fp32 accuracy, reconstructs its input, keeps constants bit for bit and gives a NaN
 the footprint the contract names, and on the restatement the B-spline mode recovers known deformations at least four times more
-accurately than the Keys mode."""
+accurately than the Keys mode.  The last part asserts, on the restatement alone, what tests/test_gpu_bspline_edges.py relies on: the
+kernel's way of forming the taps, inputs free of subnormal intermediates, two wrong prefilters that the tolerance could not see, and
+the statuses, sensitivities and distances of the IC-GN cases (tests/bspline_cases.py)."""
 import ctypes as C
 import importlib
 import os
@@ -11,8 +13,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import bspline_cases as bc
 import bspline_ref as bref
 import icgn_ref as ref
+from test_gpu_icgn_edges import odd_volumes, spike_volume, status_scene, value_scene  # noqa: F401  (fixtures)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["sift3d_bspline_prefilter", "sift3d_icgn_bspline"]
@@ -232,3 +236,107 @@ def test_bspline_bias_is_a_quarter_of_keys(name, L, t, guess):
     eb = np.abs(bsp["p"] - tr)[:, [0, 4, 8]].max()
     print(f"{name}: max displacement error Keys {ek:.3e}, B-spline {eb:.3e}, ratio {ek / eb:.1f}")
     assert eb <= 0.25 * ek, (eb, ek)
+
+
+# ---- what tests/test_gpu_bspline_edges.py relies on, asserted on the restatement alone (the cases: tests/bspline_cases.py) --------------
+
+def test_kernel_taps_round_to_the_restatements():
+    """repeated multiplication from the literal and bspline_ref's power function differ in fp64, not after the rounding to float32"""
+    a, b = bc.kernel_taps(), bref.taps().astype(np.float32)
+    assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), (a, b)
+    assert len(bc.prefilter_shapes()) == len(set(bc.prefilter_shapes())) and bc.ALL_SEAMS in bc.prefilter_shapes()
+
+
+@pytest.mark.parametrize("kind", bc.KINDS)
+def test_prefilter_cases_have_no_subnormal(kind):
+    """bit parity is asked only where it cannot hang on how a device treats subnormal numbers: every output and every per-axis
+    intermediate of every case is zero or normal"""
+    for shape in bc.prefilter_shapes():
+        passes = []
+        bref.prefilter(bc.volume(shape, kind), f32=True, passes=passes)
+        assert len(passes) == 3 and all(bc.zero_or_normal(p) for p in passes), shape
+
+
+def test_what_the_old_prefilter_bar_could_not_see():
+    """two wrong restatements -- the taps accumulated k = 1 .. K, tap 16 dropped -- differ from the true one in bits and
+    lie inside the bar 4 e + 1e-7 max|T| of test_prefilter_agrees_with_restatement; a byte comparison tells them apart"""
+    T = bc.volume(bc.ALL_SEAMS, "noise")
+    exact, true32 = bref.prefilter(T), bref.prefilter(T, f32=True)
+    e = np.abs(true32 - exact).max()
+    bar = 4 * e + 1e-7 * np.abs(T).max()
+    for name, ks in bc.MUTANTS.items():
+        wrong = bref.prefilter(T, f32=True, ks=ks)
+        differ = int((wrong.view(np.uint32) != true32.view(np.uint32)).sum())
+        gap, err = np.abs(wrong.astype(np.float64) - true32).max(), np.abs(wrong - exact).max()
+        print(f"{name}: {differ} of {T.size} voxels differ in bits, max |wrong - true fp32| = {gap:.3e}, max |wrong - fp64| = {err:.3e}, "
+              f"e = {e:.3e}, old bar {bar:.3e}: {'inside' if err <= bar else 'OUTSIDE'} the old bar")
+        assert differ > 0, name
+        assert err <= bar, (name, err, bar)
+
+
+@pytest.mark.parametrize("r", [r for r in bc.SPIKE_R if r <= bc.SPIKE_ALL])
+def test_spike_cases_on_the_restatement(spike_volume, r):
+    """status 1 after 2 iterations for every sentinel, and zeroing the sentinel voxel in R alone moves p by >= 100 tolerances"""
+    least = np.inf
+    for name, c, at, amp in bc.spike_cases(spike_volume, r):
+        want = bc.restate(c)
+        assert want["status"][0] == 1 and want["iterations"][0] == 2, (name, want["status"], want["iterations"])
+        sens = bc.spike_sensitivity(c, at, amp, want)
+        least = min(least, sens)
+        assert sens >= 100, (r, name, sens)
+    print(f"r={r}: amplitude {amp:.1f}, smallest sensitivity over the sentinels {least:.0f} tolerances")
+
+
+@pytest.mark.parametrize("r", bc.ODD_R)
+def test_odd_volume_case_on_the_restatement(odd_volumes, r):
+    c = bc.odd_case(odd_volumes, r)
+    want = bc.restate(c)
+    print(f"odd volumes r={r}: status {want['status'].tolist()} iterations {want['iterations'].tolist()} last_step[7] {want['last_step'][7]:.3e}")
+    assert list(want["status"]) == bc.ODD_STATUS and list(want["iterations"]) == bc.ODD_ITERATIONS
+    assert ref.in_domain(c["T"].shape, c["init"][7], c["q"][7], r, True) and want["last_step"][7] > 0  # 7 started inside T and left it
+
+
+@pytest.mark.parametrize("axis,side", bc.T_EDGES, ids=bc.T_EDGE_IDS)
+def test_T_edge_cases_on_the_restatement(axis, side):
+    want = bc.restate(bc.t_edge_case(axis, side))
+    print(f"T edge {'xyz'[axis]} side {side}: status {want['status'].tolist()} iterations {want['iterations'].tolist()}")
+    assert list(want["status"]) == bc.T_EDGE_STATUS and list(want["iterations"]) == bc.T_EDGE_ITERATIONS
+
+
+def test_status_3_case_on_the_restatement():
+    """as under Keys weights, IC-GN's first step from within a voxel of the truth is nearly the whole error: every start leaves T
+    with its first update"""
+    c = bc.status_3_case()
+    want = bc.restate(c)
+    print("status 3 after a step: status", want["status"].tolist(), "iterations", want["iterations"].tolist(), "last_step", want["last_step"].round(3).tolist())
+    assert (want["status"] == 3).all() and (want["last_step"] > 0).all(), (want["status"], want["iterations"])
+    rot = bc.restate(bc.rotated_edge_case())
+    print("rotated edge: status", rot["status"].tolist(), "iterations", rot["iterations"].tolist())
+    assert (rot["status"] == 1).all() and (rot["iterations"] == 2).all()
+
+
+@pytest.mark.parametrize("axis,side", bc.NF_SITES, ids=bc.NF_IDS)
+def test_non_finite_reach_straddles(status_scene, axis, side):
+    """the pair of distances that the GPU test plants at: the farthest voxel that changes the restatement and the next, which does
+    not; the same pair for NaN, +Inf and -Inf, within the header's K + 2"""
+    R, T, _ = status_scene
+    pairs = [bc.nf_straddle(R, T, axis, side, v)[:2] for v in bc.NF_VALUES]
+    clean = bc.nf_restate(R, T, axis, side)
+    print(f"non-finite voxel {'xyz'[axis]} side {side}: changes the result up to {pairs[0][0]} voxels beyond the subset's face, "
+          f"not at {pairs[0][1]} (K + 2 = {bref.K + 2}); clean status {clean['status'].tolist()}")
+    assert pairs[0] == pairs[1] == pairs[2], pairs
+    assert clean["status"][0] == 1 and clean["iterations"][0] == 3
+
+
+def test_status_order_case_on_the_restatement(status_scene):
+    c, healthy = bc.status_order_case(status_scene)
+    assert list(bc.restate(c)["status"]) == bc.STATUS_ORDER
+
+
+def test_convergent_case_on_the_restatement(value_scene):
+    want = bc.restate(bc.convergent_case(value_scene), tolerance=bc.CONVERGENT_TOL)
+    near = bc.near_tolerance(want, bc.CONVERGENT_TOL)
+    print(f"convergent runs: {near.mean():.1%} left out ({int(near.sum())} of {len(near)}), {(want['status'] == 0).mean():.0%} end in status 0, "
+          f"iterations {np.bincount(want['iterations'])}")
+    assert near.mean() <= 0.10
+    assert (want["status"] == 0).mean() >= 0.8
