@@ -54,6 +54,8 @@ SYMBOLS = [
     "sift3d_default_validate_options", "sift3d_validate_input_from_icgn", "sift3d_validate_input_from_icgn2", "sift3d_validate_displacements",
     "sift3d_validate_keep", "sift3d_icgn_init_from_validation", "sift3d_validate_stage_capacity",
     "sift3d_device_count", "sift3d_error_string", "sift3d_last_error",
+    # typed input: 8 / 16-bit integer voxels uploaded at their own width and widened on the GPU
+    "sift3d_dtype_bytes", "sift3d_create_typed", "sift3d_volume_to_device", "sift3d_test_ingest_launch",
     # multi-GPU sharding (z-slabs of octave 0 + seeded replicated tail)
     "sift3d_slab_min_halo", "sift3d_slab_arena_floats", "sift3d_slab_create", "sift3d_slab_buffer", "sift3d_slab_upload",
     "sift3d_slab_input_absmax", "sift3d_slab_input_scale", "sift3d_slab_level", "sift3d_slab_level_hw", "sift3d_slab_halo_planes",
@@ -80,6 +82,8 @@ HOOKS = {"dog_eager": 0, "glast_eager": 1, "det_serial": 2, "separable": 3, "des
          "desc_mass_shift": 7, "list_cap": 8, "peer_copy": 9, "desc_nosplit": 10, "march_tiles": 11, "desc_exact_cells": 12, "lazy_generic": 13, "sharded_fail_rank": 14,
          "ori_grid": 15}
 ORIENT_WORDS = 34
+# SIFT3D_DT_ codes of include/sift3d_hip.h by numpy dtype name
+DTYPES = {"float32": 0, "uint8": 1, "int8": 2, "uint16": 3, "int16": 4}
 SHARDED_PARTIAL_WINDOWS = 1   # sift3d_sharded_create_ex flags
 SHARDED_WHOLE_WINDOWS = 2
 SHARDED_COPY_TRANSPORT = 4
@@ -208,6 +212,10 @@ def lib():
             pass
         L = C.CDLL(LIB_PATH)
         L.sift3d_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.c_int, C.c_int]
+        L.sift3d_create_typed.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.c_int, C.c_int]
+        L.sift3d_dtype_bytes.argtypes = [C.c_int, _ip]
+        L.sift3d_volume_to_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+        L.sift3d_test_ingest_launch.argtypes = [C.c_int, _ip, _ip, _ip, _ip]
         L.sift3d_destroy.argtypes = [C.c_void_p]
         L.sift3d_run.argtypes = [C.c_void_p]
         L.sift3d_run_async.argtypes = [C.c_void_p]
@@ -480,6 +488,56 @@ def _volume(a, name, on_dev):
     if h.ndim != 3:
         raise ValueError(f"{name}: a (nz, ny, nx) volume is needed")
     return _p(h), h
+
+
+def _dtype_code(dtype):
+    """the SIFT3D_DT_ code of a numpy / torch dtype or of its name; an int passes through (the library checks it)"""
+    if isinstance(dtype, (int, np.integer)):
+        return int(dtype)
+    name = str(dtype).replace("torch.", "")
+    try:
+        name = np.dtype(name).name
+    except TypeError:
+        pass
+    if name not in DTYPES:
+        raise ValueError(f"dtype {dtype}: one of {sorted(DTYPES)} is needed")
+    return DTYPES[name]
+
+
+def ingest_launch(dtype):
+    """sift3d_test_ingest_launch: (lanes per workgroup, elements per 16-byte piece, most workgroups of k_ingest (0: one piece per lane,
+    no cap), most workgroups of k_absmax_t) for an integer dtype.  Host only."""
+    v = [C.c_int(0) for _ in range(4)]
+    _check(lib().sift3d_test_ingest_launch(_dtype_code(dtype), *[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def to_device(vol, device=0, with_seconds=False, dtype=None):
+    """sift3d_volume_to_device: vol as a new float32 (nz, ny, nx) torch tensor on the device, ready for icgn, zncc_search,
+    bspline_prefilter and CSIFT3D(device_ptr=...): uploaded once, used often.  vol: a C-contiguous (nz, ny, nx) numpy array of float32,
+    uint8, int8, uint16 or int16 (uploaded at its own width through the pinned staging pool, integers widened on the GPU), or a
+    contiguous device tensor of one of those dtypes torch has.  dtype: how the voxels are to be read when that is not vol's own dtype of
+    the same width (uint16 data held in an int16 tensor: dtype="uint16").  with_seconds: also the device seconds of the widening."""
+    import torch
+
+    on_dev = _is_dev(vol)
+    if on_dev:
+        if not vol.is_contiguous() or vol.dim() != 3:
+            raise ValueError("vol: a contiguous (nz, ny, nx) device tensor is needed")
+        device = vol.device.index if vol.device.index is not None else device
+        ptr, width = C.c_void_p(vol.data_ptr()), vol.element_size()
+    else:
+        if not isinstance(vol, np.ndarray) or vol.ndim != 3 or not vol.flags.c_contiguous:
+            raise ValueError("vol: a C-contiguous (nz, ny, nx) numpy array is needed")
+        ptr, width = _p(vol), vol.dtype.itemsize
+    code = _dtype_code(vol.dtype if dtype is None else dtype)
+    if not isinstance(dtype, (int, np.integer)) and {0: 4, 1: 1, 2: 1, 3: 2, 4: 2}[code] != width:
+        raise ValueError(f"dtype {dtype} does not have the width of vol's {vol.dtype}")
+    nz, ny, nx = vol.shape
+    out = torch.empty((nz, ny, nx), dtype=torch.float32, device=f"cuda:{int(device)}")
+    sec = C.c_double(0)
+    _check(lib().sift3d_volume_to_device(ptr, code, nx, ny, nz, int(on_dev), int(device), C.c_void_p(out.data_ptr()), C.byref(sec)))
+    return (out, sec.value) if with_seconds else out
 
 
 def _volume_pair(ref, tar):
@@ -874,10 +932,12 @@ def device_count():
 
 class CSIFT3D:
     """Python mirror of CPUSIFT::CSIFT3D over the C-ABI (same method names as the reference class,
-    Include/cSIFT3D.h:118-181).  vol is [z, y, x] fp32 (x fastest)."""
+    Include/cSIFT3D.h:118-181).  vol is [z, y, x] fp32 (x fastest).  keep_dtype=True: a numpy volume of uint8, int8, uint16 or int16
+    goes to the library as it is (sift3d_create_typed: uploaded at its own width, widened on the GPU; the same extractor bit for bit);
+    the default converts to float32 on the host.  device_ptr with dtype=: the device volume holds voxels of that dtype."""
 
     def __init__(self, volume, num_kp_levels=3, sigma_default=1.6, sigma_n_default=1.15, peak_thresh=0.1,
-                 max_eig_thres=0.9, corner_thresh=0.4, device=0, device_ptr=None, shape=None):
+                 max_eig_thres=0.9, corner_thresh=0.4, device=0, device_ptr=None, shape=None, keep_dtype=False, dtype=None):
         L = lib()
         self._h = C.c_void_p()
         p = Params(num_kp_levels, sigma_default, sigma_n_default, peak_thresh, max_eig_thres, corner_thresh)
@@ -885,7 +945,15 @@ class CSIFT3D:
         if device_ptr is not None:
             nz, ny, nx = shape
             self.shape = tuple(shape)
-            _check(L.sift3d_create(C.byref(self._h), C.c_void_p(device_ptr), nx, ny, nz, C.byref(p), device, 1))
+            if dtype is not None:
+                _check(L.sift3d_create_typed(C.byref(self._h), C.c_void_p(device_ptr), _dtype_code(dtype), nx, ny, nz, C.byref(p), device, 1))
+            else:
+                _check(L.sift3d_create(C.byref(self._h), C.c_void_p(device_ptr), nx, ny, nz, C.byref(p), device, 1))
+        elif keep_dtype and isinstance(volume, np.ndarray) and volume.dtype.name in DTYPES:  # (float32: SIFT3D_DT_F32, which is sift3d_create)
+            vol = np.ascontiguousarray(volume)
+            nz, ny, nx = vol.shape
+            self.shape = vol.shape
+            _check(L.sift3d_create_typed(C.byref(self._h), vol.ctypes.data_as(C.c_void_p), DTYPES[vol.dtype.name], nx, ny, nz, C.byref(p), device, 0))
         else:
             vol = np.ascontiguousarray(volume, dtype=np.float32)
             nz, ny, nx = vol.shape

@@ -145,6 +145,7 @@ extern "C" int sift3d_destroy(sift3d_handle c) {
 	free_lists(c);
 	if (!c->ext_arena) hipFree(c->arena);
 	hipFree(c->in_own);
+	hipFree(c->in_raw);
 	hipFree(c->d_peer);
 	hipFree(c->d_words);
 	if (c->h_words) (void)hipHostFree(c->h_words);
@@ -291,11 +292,15 @@ int create_common(sift3d_handle *out, const CreateCfg &cfg, const sift3d_params 
 		const size_t V0 = c->in.n();
 		CHECKED(hipMalloc(&c->in_own, sizeof(float) * al64(V0)));
 		CHECKED(hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking));
-		const float *vol = cfg.host_volume;
+		const void *vol = cfg.host_volume;
+		// integer voxels (sift3d_create_typed) travel at their own width into a buffer of their own
+		const size_t bytes = (size_t)dtype_bytes(cfg.host_dtype) * V0;
+		if (cfg.host_dtype != SIFT3D_DT_F32) CHECKED(hipMalloc(&c->in_raw, bytes));
+		void *dst = c->in_raw ? c->in_raw : static_cast<void *>(c->in_own);
 		// (measured, 512^3: 14.5 ms with the copy behind the allocations, 15.6 with its own buffer but no thread, 12.0 like this)
-		c->uploader = std::thread([c, vol, V0, device] {
+		c->uploader = std::thread([c, vol, dst, bytes, device] {
 			int r = set_device(device);
-			if (r == SIFT3D_OK) r = staged_h2d(c->in_own, vol, sizeof(float) * V0, device, c->up_stream);
+			if (r == SIFT3D_OK) r = staged_h2d(dst, vol, bytes, device, c->up_stream);
 			if (r != SIFT3D_OK) c->upload_err = sift3d_last_error();  // (the error text is thread-local)
 			c->upload_rc = r;
 		});
@@ -428,9 +433,16 @@ int create_common(sift3d_handle *out, const CreateCfg &cfg, const sift3d_params 
 		// launch of one of its kernels: ~1 ms of the first KpSiftAlgorithm of a process went there, scripts/step_times_probe.py)
 		static std::atomic<unsigned long long> loaded{0};
 		const unsigned long long bit = 1ull << (device & 63);
-		if (!(loaded.fetch_or(bit) & bit)) { preload_march_kernels(); preload_small_kernels(); preload_detect_kernels(); preload_orient_kernels(); preload_desc_kernels(); preload_match_kernels(); }
+		if (!(loaded.fetch_or(bit) & bit)) { preload_march_kernels(); preload_small_kernels(); preload_detect_kernels(); preload_orient_kernels(); preload_desc_kernels(); preload_match_kernels(); preload_ingest_kernels(); }
 	}
 	*out = c;
+	return SIFT3D_OK;
+}
+
+int join_upload(sift3d_ctx *c) {
+	if (c->uploader.joinable()) c->uploader.join();
+	if (c->upload_rc != SIFT3D_OK) { set_last_error(c->upload_err); return c->upload_rc; }
+	S3D_HIP(hipStreamSynchronize(c->up_stream));  // every chunk has landed: the kernels behind it run on the handle's stream
 	return SIFT3D_OK;
 }
 
@@ -448,11 +460,7 @@ extern "C" int sift3d_create(sift3d_handle *out, const float *volume, int nx, in
 	const size_t V0 = (size_t)nx * ny * nz;
 	hipError_t e = hipSuccess;
 	if (volume_on_device) e = hipMemcpyAsync(c->in.d, volume, sizeof(float) * V0, hipMemcpyDeviceToDevice, c->stream);
-	else {
-		if (c->uploader.joinable()) c->uploader.join();
-		if (c->upload_rc != SIFT3D_OK) { rc = c->upload_rc; set_last_error(c->upload_err); sift3d_destroy(c); *out = nullptr; return rc; }
-		e = hipStreamSynchronize(c->up_stream);  // every chunk has landed: the kernels below run on the handle's stream
-	}
+	else if ((rc = join_upload(c)) != SIFT3D_OK) { sift3d_destroy(c); *out = nullptr; return rc; }
 	if (e == hipSuccess) {
 		unsigned *d_nonfinite = c->d_words + 1 + (size_t)std::max(1, c->noct * c->nd) + 8;
 		launch_absmax(c->in.d, V0, c->d_inmax, c->stream, d_nonfinite);

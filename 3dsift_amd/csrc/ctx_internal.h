@@ -46,6 +46,7 @@ struct sift3d_ctx {
 	// r05: a HOST volume gets its own input buffer, allocated first, and a thread that stages the volume into it (staging.hip) while the
 	// constructor allocates everything else (the 8 GB arena, the lists, the tables: 4 ms that used to come in front of the 10 ms copy)
 	float *in_own = nullptr;
+	void *in_raw = nullptr;       // sift3d_create_typed, host volume: the integer voxels as uploaded; freed before that call returns
 	hipStream_t up_stream = nullptr;
 	std::thread uploader;
 	int upload_rc = SIFT3D_OK;
@@ -125,7 +126,8 @@ struct CreateCfg {
 	bool seeded = false;
 	bool slab = false;
 	int z0 = 0, z1 = 0, halo = 0;
-	const float *host_volume = nullptr;  // plain extractor on a pageable host volume: uploaded beside the allocations (sift3d_ctx::uploader)
+	const void *host_volume = nullptr;   // plain extractor on a pageable host volume: uploaded beside the allocations (sift3d_ctx::uploader)
+	int host_dtype = SIFT3D_DT_F32;      // its voxels: fp32 lands in the input buffer, an integer type (sift3d_create_typed) in sift3d_ctx::in_raw
 	float *ext_arena = nullptr;   // slab: caller-owned device memory for the level buffers (so that the caller's
 	size_t ext_arena_floats = 0;  // communication layer can address halo planes directly), see sift3d_slab_arena_floats
 };
@@ -147,5 +149,6 @@ int upload_luts(sift3d_ctx *c, const std::vector<WinLut> &luts, std::vector<floa
 std::vector<WinLut> blank_luts(const sift3d_ctx *c);
 size_t arena_floats_of(const sift3d_ctx *c);
 int create_common(sift3d_handle *out, const CreateCfg &cfg, const sift3d_params *params, int device);
+int join_upload(sift3d_ctx *c);  // the uploader thread has ended and every chunk has landed; its error (and text) otherwise
 int run_impl(sift3d_ctx *c, int upto, bool part_orient = false);
 }  // namespace s3d

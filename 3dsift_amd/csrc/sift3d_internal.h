@@ -400,6 +400,17 @@ void preload_detect_kernels();
 void preload_orient_kernels();
 void preload_desc_kernels();
 void preload_match_kernels();
+void preload_ingest_kernels();
+
+// ---- kernels_ingest.hip: 8 / 16-bit integer voxels -> fp32 (dtype: SIFT3D_DT_U8 .. SIFT3D_DT_I16) -----------------------------
+int dtype_bytes(int dtype);  // 0: not a SIFT3D_DT_ code
+// launch_absmax for typed voxels: the fp32 bits of max |v| into d_max_bits (cleared first), |v| formed in 32-bit integers
+void launch_absmax_typed(const void *src, int dtype, size_t n, unsigned *d_max_bits, hipStream_t st);
+// dst[i] = (float)src[i], divided (IEEE, as k_scale) by the float in *d_max_bits when that is not null
+void launch_ingest(const void *src, int dtype, size_t n, float *dst, const unsigned *d_max_bits, hipStream_t st);
+// the launch constants (sift3d_test_ingest_launch): lanes per workgroup, elements per 16-byte piece, the cap on the workgroups of
+// k_ingest (0: one piece per lane, no cap) and of k_absmax_t
+void ingest_launch_info(int dtype, int *block, int *piece_elems, int *ingest_max_blocks, int *absmax_max_blocks);
 
 // ---- test hooks and development switches --------------------------------------------------------
 // Test hooks (include/sift3d_hip.h, sift3d_test_hook): process-wide integers that force code paths ordinary inputs rarely

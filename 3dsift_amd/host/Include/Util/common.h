@@ -9,6 +9,10 @@
 #define SIFT_LIBRARY_API /* every symbol has default visibility in libsift3d.so */
 #endif
 
+// How the voxels of a volume are stored (extension, no reference counterpart): the values of the SIFT3D_DT_ codes of
+// include/sift3d_hip.h.  readNiiFileTyped names it, CSIFT3DFactory::CreateCSIFT3DTyped and CPUSIFT::UploadVolume take it.
+enum class VoxelType : int { F32 = 0, U8 = 1, I8 = 2, U16 = 3, I16 = 4 };
+
 // Seconds per stage of one KpSiftAlgorithm(); filled from HIP events on the extractor's stream.
 // d_BuildDOG is ~0 because the DoG subtraction is fused into the Gaussian level kernel, d_Allocation
 // and d_release are 0 because the device arena is reserved by the constructor.

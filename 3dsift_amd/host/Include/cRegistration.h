@@ -93,6 +93,13 @@ SIFT_LIBRARY_API std::vector<SearchResult> SearchDisplacements(const float *ref,
 // against more than once is prefiltered once.  false: the call failed (message on stderr).  seconds (may be null): device time
 SIFT_LIBRARY_API bool PrefilterBSpline(const float *vol, int nx, int ny, int nz, float *coefficients, double *seconds = nullptr);
 
+// vol (nx x ny x nz voxels of `type`, host memory, x fastest) as an fp32 volume in d_dst, DEVICE memory of nx * ny * nz floats on the
+// selected GPU (SetDevice) that the caller owns: the shell's name for sift3d_volume_to_device (include/sift3d_hip.h).  The volume
+// travels through the pinned staging pool at its own width and 8 / 16-bit integers are widened on the GPU; d_dst is complete on
+// return and is what the on_device forms of the C-ABI (sift3d_icgn, sift3d_zncc_search, ...) take, uploaded once for many calls.
+// false: the call failed (message on stderr).  seconds (may be null): device time of the widening kernel
+SIFT_LIBRARY_API bool UploadVolume(const void *vol, VoxelType type, int nx, int ny, int nz, float *d_dst, double *seconds = nullptr);
+
 // IC-GN refinement of the displacement from ref (nx x ny x nz, fp32, x fastest) to tar (tnx x tny x tnz) at integral points of ref,
 // starting from the local affine fits (one per point, e.g. EstimateLocalAffine at the same points) or from zero; fallback (one per
 // point, e.g. SearchDisplacements at the same points) gives the start of a point whose fit has status != 0.  opts.interpolation 2

@@ -104,6 +104,9 @@ public:
 	SIFT_LIBRARY_API CSIFT3D();
 	SIFT_LIBRARY_API CSIFT3D(float *volume, int x_dim, int y_dim, int z_dim, int num_kp_levels_, float sigma_default_,
 	                         float sigma_n_default_, float peak_thresh_, float max_eig_thres_, float corner_thresh_);
+	// extension: a volume of 8 / 16-bit integer voxels as stored (VoxelType, Util/common.h), see CSIFT3DFactory::CreateCSIFT3DTyped
+	SIFT_LIBRARY_API CSIFT3D(const void *volume, VoxelType type, int x_dim, int y_dim, int z_dim, int num_kp_levels_, float sigma_default_,
+	                         float sigma_n_default_, float peak_thresh_, float max_eig_thres_, float corner_thresh_);
 	SIFT_LIBRARY_API ~CSIFT3D();
 	CSIFT3D(const CSIFT3D &) = delete;
 	CSIFT3D &operator=(const CSIFT3D &) = delete;
@@ -173,6 +176,16 @@ public:
 	                              float sigma_default = SIGMA_DEFAULT, float sigma_n_default = SIGMA_N_DEFAULT,
 	                              float peak_thresh = PEAK_THRESH, float max_eigo_thres = EIG_THRES,
 	                              float corner_thresh = CORNER_THRESH);
+
+	// extension (no reference counterpart): CreateCSIFT3D for a volume whose voxels are `type` (x fastest, like the float volume), e.g.
+	// what readNiiFileTyped returns.  8 / 16-bit integers are uploaded at their own width and widened on the GPU
+	// (sift3d_create_typed, include/sift3d_hip.h): the extractor is bit for bit the one CreateCSIFT3D makes from the same voxels
+	// converted to float.  VoxelType::F32 is CreateCSIFT3D.  An extractor sharded over several GPUs (SIFT3D_DEVICES /
+	// SIFT3D_SIM_RANKS) widens on the host.
+	static CSIFT3D *CreateCSIFT3DTyped(const void *volume, VoxelType type, int x_dim, int y_dim, int z_dim, int num_kp_levels = NUM_KP_LEVELS,
+	                                   float sigma_default = SIGMA_DEFAULT, float sigma_n_default = SIGMA_N_DEFAULT,
+	                                   float peak_thresh = PEAK_THRESH, float max_eigo_thres = EIG_THRES,
+	                                   float corner_thresh = CORNER_THRESH);
 
 	// raw-matrix file overload (12-byte int32 header m,n,p + fp32 payload)
 	static CSIFT3D *CreateCSIFT3D(std::string path_, int num_kp_levels = NUM_KP_LEVELS, float sigma_default = SIGMA_DEFAULT,

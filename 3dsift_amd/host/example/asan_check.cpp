@@ -46,6 +46,17 @@ int main(int argc, char **argv) {
 		} else {
 			printf("nii %s rejected\n", n.c_str());
 		}
+		// the typed reader on the same file: 8 / 16-bit integers as stored, freed with delete[] of the matching type
+		VoxelType type = VoxelType::F32;
+		void *t = readNiiFileTyped((dir + "/" + n).c_str(), nx, ny, nz, type);
+		printf("niit %s %d %d %d %d\n", n.c_str(), t ? (int)type : -1, nx, ny, nz);
+		switch (type) {
+		case VoxelType::F32: delete[] static_cast<float *>(t); break;
+		case VoxelType::U8: delete[] static_cast<unsigned char *>(t); break;
+		case VoxelType::I8: delete[] static_cast<signed char *>(t); break;
+		case VoxelType::U16: delete[] static_cast<unsigned short *>(t); break;
+		case VoxelType::I16: delete[] static_cast<short *>(t); break;
+		}
 	}
 	// raw matrix: read, write back, read again; plus a truncated file and a header with non-positive sizes
 	{

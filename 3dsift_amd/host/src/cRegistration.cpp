@@ -124,6 +124,12 @@ bool PrefilterBSpline(const float *vol, int nx, int ny, int nz, float *coefficie
 	return rc == SIFT3D_OK;
 }
 
+bool UploadVolume(const void *vol, VoxelType type, int nx, int ny, int nz, float *d_dst, double *seconds) {
+	const int rc = sift3d_volume_to_device(vol, (int)type, nx, ny, nz, 0, GetDevice(), d_dst, seconds);
+	if (rc != SIFT3D_OK) fprintf(stderr, "[3dsift_amd] UploadVolume: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+	return rc == SIFT3D_OK;
+}
+
 Cvec SearchResult::Displacement() const { return Cvec((float)d[0], (float)d[1], (float)d[2]); }
 
 std::vector<SearchResult> SearchDisplacements(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,

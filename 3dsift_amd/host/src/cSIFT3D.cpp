@@ -191,6 +191,18 @@ CSIFT3D::CSIFT3D() : impl(new Impl()) {}
 
 CSIFT3D::CSIFT3D(float *volume, int x_dim, int y_dim, int z_dim, int num_kp_levels_, float sigma_default_,
                  float sigma_n_default_, float peak_thresh_, float max_eig_thres_, float corner_thresh_)
+    : CSIFT3D(volume, VoxelType::F32, x_dim, y_dim, z_dim, num_kp_levels_, sigma_default_, sigma_n_default_, peak_thresh_, max_eig_thres_,
+              corner_thresh_) {}
+
+// the voxels of a typed volume as floats (the sharded driver takes fp32 only)
+template <typename T>
+static std::vector<float> widened(const void *volume, size_t n) {
+	const T *v = static_cast<const T *>(volume);
+	return std::vector<float>(v, v + n);
+}
+
+CSIFT3D::CSIFT3D(const void *volume, VoxelType type, int x_dim, int y_dim, int z_dim, int num_kp_levels_, float sigma_default_,
+                 float sigma_n_default_, float peak_thresh_, float max_eig_thres_, float corner_thresh_)
     : impl(new Impl()) {
 	sift3d_params p;
 	p.num_kp_levels = num_kp_levels_;
@@ -205,12 +217,22 @@ CSIFT3D::CSIFT3D(float *volume, int x_dim, int y_dim, int z_dim, int num_kp_leve
 	const int sim = sim_ranks();
 	if (devs.size() > 1 || sim > 1) {
 		const int one = impl->device;
-		const int rc = sift3d_sharded_create_ex(&impl->sh, volume, x_dim, y_dim, z_dim, &p, sim > 1 ? &one : devs.data(), sim > 1 ? 1 : (int)devs.size(),
+		std::vector<float> wide;
+		const size_t n = (volume && x_dim > 0 && y_dim > 0 && z_dim > 0) ? (size_t)x_dim * y_dim * z_dim : 0;
+		switch (type) {
+		case VoxelType::U8: wide = widened<unsigned char>(volume, n); break;
+		case VoxelType::I8: wide = widened<signed char>(volume, n); break;
+		case VoxelType::U16: wide = widened<unsigned short>(volume, n); break;
+		case VoxelType::I16: wide = widened<short>(volume, n); break;
+		default: break;
+		}
+		const float *fvol = type == VoxelType::F32 ? static_cast<const float *>(volume) : (n ? wide.data() : nullptr);
+		const int rc = sift3d_sharded_create_ex(&impl->sh, fvol, x_dim, y_dim, z_dim, &p, sim > 1 ? &one : devs.data(), sim > 1 ? 1 : (int)devs.size(),
 		                                        sim > 1 ? sim : 0, 0, shard_flags());
 		complain("CSIFT3D (sharded upload + normalise)", rc);
 		return;
 	}
-	complain("CSIFT3D (upload + normalise)", sift3d_create(&impl->h, volume, x_dim, y_dim, z_dim, &p, impl->device, 0));
+	complain("CSIFT3D (upload + normalise)", sift3d_create_typed(&impl->h, volume, (int)type, x_dim, y_dim, z_dim, &p, impl->device, 0));
 }
 
 CSIFT3D::~CSIFT3D() {
@@ -489,6 +511,13 @@ std::vector<CSIFT3D::PairMatch> CSIFT3D::AllPairsMatch(const std::vector<CSIFT3D
 CSIFT3D *CSIFT3DFactory::CreateCSIFT3D(float *volume, int x_dim, int y_dim, int z_dim, int num_kp_levels, float sigma_default,
                                        float sigma_n_default, float peak_thresh, float max_eig_thres, float corner_thresh) {
 	return new CSIFT3D(volume, x_dim, y_dim, z_dim, num_kp_levels, sigma_default, sigma_n_default, peak_thresh, max_eig_thres,
+	                   corner_thresh);
+}
+
+CSIFT3D *CSIFT3DFactory::CreateCSIFT3DTyped(const void *volume, VoxelType type, int x_dim, int y_dim, int z_dim, int num_kp_levels,
+                                            float sigma_default, float sigma_n_default, float peak_thresh, float max_eig_thres,
+                                            float corner_thresh) {
+	return new CSIFT3D(volume, type, x_dim, y_dim, z_dim, num_kp_levels, sigma_default, sigma_n_default, peak_thresh, max_eig_thres,
 	                   corner_thresh);
 }
 

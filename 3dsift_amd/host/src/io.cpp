@@ -107,8 +107,8 @@ std::string sibling(const std::string &name, const char *from, const char *to) {
 
 }  // namespace
 
-float *readNiiFile(const char *filename, int &nx, int &ny, int &nz) {
-	nx = ny = nz = 0;
+// the file's payload as stored (raw), its datatype code and byte order and its extents; false + message on anything readNiiFile refuses
+static bool read_nii_raw(const char *filename, std::vector<unsigned char> &raw, int &datatype, bool &swap, int &dx_, int &dy_, int &dz_) {
 	// a pair may be named by either file (the reference's reader resolves both ways, nifti_findhdrname / nifti_findimgname)
 	std::string hdr_name = filename ? filename : "", img_name;
 	{
@@ -116,10 +116,10 @@ float *readNiiFile(const char *filename, int &nx, int &ny, int &nz) {
 		if (!h.empty()) { img_name = hdr_name; hdr_name = h; }
 	}
 	gzFile f = gzopen(hdr_name.c_str(), "rb");  // transparently reads plain and gzip-compressed files
-	if (!f) { fprintf(stderr, "readNiiFile: cannot open %s\n", hdr_name.c_str()); return nullptr; }
+	if (!f) { fprintf(stderr, "readNiiFile: cannot open %s\n", hdr_name.c_str()); return false; }
 	NiiHeader H;
 	const char *why = "";
-	if (!read_nii_header(f, H, &why)) { gzclose(f); fprintf(stderr, "readNiiFile: %s: %s\n", hdr_name.c_str(), why); return nullptr; }
+	if (!read_nii_header(f, H, &why)) { gzclose(f); fprintf(stderr, "readNiiFile: %s: %s\n", hdr_name.c_str(), why); return false; }
 	// the header is untrusted input: dimensions must be positive and the element size must agree with the datatype code.  A payload
 	// offset below the header size of a single-file image is read as the header size, like the reference's reader does
 	// (nifti2_io.cpp:4917-4923, 5185-5189 "set ioff from vox_offset (but at least sizeof(header))"): lax writers leave vox_offset at 0 or
@@ -140,7 +140,7 @@ float *readNiiFile(const char *filename, int &nx, int &ny, int &nz) {
 		gzclose(f);
 		fprintf(stderr, "readNiiFile: bad or unsupported header (dim %lld: %lld %lld %lld, datatype %d, bitpix %d, vox_offset %g)\n", ndim, H.dim[1],
 		        H.dim[2], H.dim[3], H.datatype, H.bitpix, H.vox_offset);
-		return nullptr;
+		return false;
 	}
 	const int dx = (int)H.dim[1], dy = ndim >= 2 ? (int)H.dim[2] : 1, dz = ndim >= 3 ? (int)H.dim[3] : 1;
 	const size_t n = (size_t)dx * dy * dz, bytes = n * esize;
@@ -152,19 +152,19 @@ float *readNiiFile(const char *filename, int &nx, int &ny, int &nz) {
 	} else {
 		gzclose(f);
 		if (img_name.empty()) img_name = sibling(hdr_name, ".hdr", ".img");
-		if (img_name.empty()) { fprintf(stderr, "readNiiFile: %s is the header of a two-file image but is not named *.hdr\n", hdr_name.c_str()); return nullptr; }
+		if (img_name.empty()) { fprintf(stderr, "readNiiFile: %s is the header of a two-file image but is not named *.hdr\n", hdr_name.c_str()); return false; }
 		f = gzopen(img_name.c_str(), "rb");
-		if (!f) { fprintf(stderr, "readNiiFile: cannot open %s\n", img_name.c_str()); return nullptr; }
+		if (!f) { fprintf(stderr, "readNiiFile: cannot open %s\n", img_name.c_str()); return false; }
 		skip = H.vox_offset > 0 ? (long)H.vox_offset : 0;
 	}
 	for (unsigned char junk[4096]; skip > 0;) {
 		const int want = (int)std::min<long>(skip, (long)sizeof(junk));
-		if (gzread(f, junk, (unsigned)want) != want) { gzclose(f); fprintf(stderr, "readNiiFile: truncated before the payload\n"); return nullptr; }
+		if (gzread(f, junk, (unsigned)want) != want) { gzclose(f); fprintf(stderr, "readNiiFile: truncated before the payload\n"); return false; }
 		skip -= want;
 	}
 	// the payload is read in bounded pieces into a buffer that grows with the data that actually arrives: a header that claims
 	// terabytes on a short file ends as "truncated payload", not as an allocation of the claimed size
-	std::vector<unsigned char> raw;
+	raw.clear();
 	size_t got = 0;
 	try {
 		while (got < bytes) {
@@ -178,13 +178,18 @@ float *readNiiFile(const char *filename, int &nx, int &ny, int &nz) {
 				continue;
 			}
 		}
-	} catch (...) { gzclose(f); fprintf(stderr, "readNiiFile: out of memory\n"); return nullptr; }
+	} catch (...) { gzclose(f); fprintf(stderr, "readNiiFile: out of memory\n"); return false; }
 	gzclose(f);
-	if (got != bytes) { fprintf(stderr, "readNiiFile: truncated payload\n"); return nullptr; }
+	if (got != bytes) { fprintf(stderr, "readNiiFile: truncated payload\n"); return false; }
+	datatype = H.datatype; swap = H.swap; dx_ = dx; dy_ = dy; dz_ = dz;
+	return true;
+}
+
+// the payload converted to a new float[]; nullptr + message for a datatype without a conversion
+static float *nii_to_float(const std::vector<unsigned char> &raw, size_t n, int datatype, bool swap) {
 	float *out = new (std::nothrow) float[n];
 	if (!out) { fprintf(stderr, "readNiiFile: out of memory\n"); return nullptr; }
-	const bool swap = H.swap;
-	switch (H.datatype) {  // NIfTI datatype codes; slope/intercept deliberately ignored (see readNii.h)
+	switch (datatype) {  // NIfTI datatype codes; slope/intercept deliberately ignored (see readNii.h)
 	case 2: convert<uint8_t>(raw.data(), n, false, out); break;
 	case 4: convert<int16_t>(raw.data(), n, swap, out); break;
 	case 8: convert<int32_t>(raw.data(), n, swap, out); break;
@@ -194,11 +199,51 @@ float *readNiiFile(const char *filename, int &nx, int &ny, int &nz) {
 	case 512: convert<uint16_t>(raw.data(), n, swap, out); break;
 	case 768: convert<uint32_t>(raw.data(), n, swap, out); break;
 	default:
-		fprintf(stderr, "readNiiFile: unsupported datatype %d\n", H.datatype);
+		fprintf(stderr, "readNiiFile: unsupported datatype %d\n", datatype);
 		delete[] out;
 		return nullptr;
 	}
-	nx = dx; ny = dy; nz = dz;
+	return out;
+}
+
+float *readNiiFile(const char *filename, int &nx, int &ny, int &nz) {
+	nx = ny = nz = 0;
+	std::vector<unsigned char> raw;
+	int datatype = 0, dx = 0, dy = 0, dz = 0;
+	bool swap = false;
+	if (!read_nii_raw(filename, raw, datatype, swap, dx, dy, dz)) return nullptr;
+	float *out = nii_to_float(raw, (size_t)dx * dy * dz, datatype, swap);
+	if (out) { nx = dx; ny = dy; nz = dz; }
+	return out;
+}
+
+// the payload of an 8 / 16-bit integer file as a new T[] in host byte order
+template <typename T>
+static void *keep_typed(const std::vector<unsigned char> &raw, size_t n, bool swap) {
+	T *out = new (std::nothrow) T[n];
+	if (!out) { fprintf(stderr, "readNiiFile: out of memory\n"); return nullptr; }
+	memcpy(out, raw.data(), n * sizeof(T));
+	if (swap && sizeof(T) > 1) for (size_t i = 0; i < n; i++) out[i] = bswap(out[i]);
+	return out;
+}
+
+void *readNiiFileTyped(const char *filename, int &nx, int &ny, int &nz, VoxelType &type) {
+	nx = ny = nz = 0;
+	type = VoxelType::F32;
+	std::vector<unsigned char> raw;
+	int datatype = 0, dx = 0, dy = 0, dz = 0;
+	bool swap = false;
+	if (!read_nii_raw(filename, raw, datatype, swap, dx, dy, dz)) return nullptr;
+	const size_t n = (size_t)dx * dy * dz;
+	void *out = nullptr;
+	switch (datatype) {
+	case 2: type = VoxelType::U8; out = keep_typed<uint8_t>(raw, n, false); break;
+	case 256: type = VoxelType::I8; out = keep_typed<int8_t>(raw, n, false); break;
+	case 4: type = VoxelType::I16; out = keep_typed<int16_t>(raw, n, swap); break;
+	case 512: type = VoxelType::U16; out = keep_typed<uint16_t>(raw, n, swap); break;
+	default: out = nii_to_float(raw, n, datatype, swap); break;  // every other datatype: what readNiiFile returns
+	}
+	if (out) { nx = dx; ny = dy; nz = dz; }
 	return out;
 }
 

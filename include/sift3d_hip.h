@@ -79,6 +79,40 @@ void sift3d_default_params(sift3d_params *p);
 int sift3d_create(sift3d_handle *out, const float *volume, int nx, int ny, int nz,
                   const sift3d_params *params, int device, int volume_on_device);
 
+/* Typed input (no reference counterpart: the reference's callers widen 8 / 16-bit CT and MR voxels to float on the host, e.g.
+ * Src/Util/readNii.cpp:17-33).  The library takes the integer voxels as they are stored, moves them at their own width and widens
+ * them on the GPU.  Volumes are x fastest like every other volume; `dtype` is one of: */
+enum { SIFT3D_DT_F32 = 0, SIFT3D_DT_U8 = 1, SIFT3D_DT_I8 = 2, SIFT3D_DT_U16 = 3, SIFT3D_DT_I16 = 4 };
+/* bytes of one voxel: 4 / 1 / 1 / 2 / 2; SIFT3D_ERR_ARG outside the enum.  Host only, no GPU. */
+int sift3d_dtype_bytes(int dtype, int *bytes);
+/* sift3d_create for a typed volume: the same argument checks (the 2^31 voxel bound included), the same handle, the same everything
+ * downstream.  SIFT3D_DT_F32 simply is sift3d_create.  For the integer types a host volume travels through the pinned staging pool
+ * as nx*ny*nz*sizeof(T) bytes, beside the allocations like the float volume, into a temporary device buffer of that size; the maximum
+ * of |v| is taken in 32-bit integers (-32768 gives 32768) and one kernel widens and divides into the handle's fp32 input.  The
+ * temporary is freed before the call returns: the transient device peak is the handle's own memory plus nx*ny*nz*sizeof(T) bytes.
+ * volume_on_device != 0: `volume` is a typed device pointer on `device`, any multiple of sizeof(T), read where it lies (no temporary,
+ * no copy); as for sift3d_create it must be complete when the call is made.
+ * Contract: the handle is BIT FOR BIT the one sift3d_create makes from the same voxels widened to float on the host -- the widening
+ * is exact (every 8 / 16-bit integer is an fp32 number), the maximum is the same number (the maximum of the widened |v| is the widened
+ * maximum), and the division is the same IEEE division (never a reciprocal multiply; an all-zero volume gives the same 0 / 0).  So
+ * sift3d_copy_input, the pyramid, the extrema, the keypoint records and the descriptors are those of the float path.  An integer
+ * volume has no NaN or Inf: the handle always runs the fused kernels. */
+int sift3d_create_typed(sift3d_handle *out, const void *volume, int dtype, int nx, int ny, int nz,
+                        const sift3d_params *params, int device, int volume_on_device);
+/* Fills the caller's DEVICE buffer d_dst (nx*ny*nz floats on `device`, any 4-byte alignment: a hipMalloc, a torch tensor) with the
+ * unscaled voxels, dst[i] = (float)volume[i]: a plain fp32 device volume that every on_device entry below (sift3d_icgn,
+ * sift3d_zncc_search, sift3d_bspline_prefilter, ...) and sift3d_create(volume_on_device = 1) accept, uploaded once and used often.
+ * Host inputs of every dtype go through the pinned staging pool (a plain copy of pageable memory moves 0.5-0.8 GB/s on these
+ * systems): SIFT3D_DT_F32 straight into d_dst, the integer types at their own width into a grow-only device scratch that stays with
+ * the device (nx*ny*nz*sizeof(T) bytes and a quarter), from where one kernel widens them.  volume_on_device != 0: `volume` is a
+ * typed device pointer on `device`, read where it lies (SIFT3D_DT_F32: a device copy; volume == d_dst: nothing).  The call runs behind
+ * the work queued on the legacy default stream like every on_device entry and returns when d_dst is complete: the pointer is valid for
+ * any later call on any stream.  *seconds (may be NULL): device time of the kernel, the upload excluded (SIFT3D_DT_F32 has no kernel: next to 0).
+ * SIFT3D_ERR_ARG, before any device call, for a NULL pointer, a dimension < 1, a dtype outside the enum (and 2^40 voxels or more);
+ * SIFT3D_ERR_NO_DEVICE behind that check when no GPU is visible -- as sift3d_create_typed. */
+int sift3d_volume_to_device(const void *volume, int dtype, int nx, int ny, int nz, int volume_on_device,
+                            int device, float *d_dst, double *seconds);
+
 /* Replaces CSIFT3D::~CSIFT3D (Src/cSIFT3D.cc:140-144). */
 int sift3d_destroy(sift3d_handle h);
 

@@ -70,6 +70,11 @@ int sift3d_test_sharded_time_rank(sift3d_sharded_handle h, int rank, double *sec
  * that: the switch point, so that tests can put neighbour counts on both sides of it.  Host only, no GPU. */
 int sift3d_validate_stage_capacity(int *n);
 
+/* the launch constants of csrc/kernels_ingest.hip for a SIFT3D_DT_ integer dtype, so that tests can put element counts behind one
+ * full sweep of a launch: lanes per workgroup, elements of a 16-byte piece, the most workgroups k_ingest is launched with (0: one
+ * piece per lane, as many workgroups as pieces) and the most k_absmax_t is launched with (grid-stride beyond).  Host only, no GPU. */
+int sift3d_test_ingest_launch(int dtype, int *block, int *piece_elems, int *ingest_max_blocks, int *absmax_max_blocks);
+
 #ifdef __cplusplus
 }
 #endif
