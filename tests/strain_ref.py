@@ -1,7 +1,8 @@
 """NumPy fp64 restatement of the strain contract (sift3d_strain, include/sift3d_hip.h): the neighbours by the integer window test, the
 plane fit once from the normal equations as the header writes them (solve="normal") and once from numpy.linalg.lstsq on [1, d]
 (solve="lstsq"), the eigenvalues from numpy.linalg.eigvalsh.  Also the inputs of the GPU parity test and parity_error(): e, the
-largest absolute difference between the two solves over every field of every status-0 POI of those inputs."""
+largest absolute difference between the two solves over every field of every status-0 POI of those inputs; and the Cholesky pivots
+of a window in exact rational arithmetic (exact_pivot_ratios), which the edge cases (tests/strain_cases.py) are placed by."""
 import functools
 
 import numpy as np
@@ -135,3 +136,29 @@ def parity_error():
                 if ok.any():
                     e = max(e, float(np.abs(a[k][ok] - b[k][ok]).max()))
     return e
+
+
+def exact_pivot_ratios(d):
+    """the three Cholesky pivots of C = S2 - S1 S1^T / n (c00, c11 - l10^2, c22 - l20^2 - l21^2: the LDL^T pivots, which are the
+    squares of L's diagonal) over C's largest diagonal entry, as fractions.Fraction from the integer offsets d (n, 3).  A pivot behind
+    a zero one is 0 / 0 in the contract's arithmetic and None here; C = 0 gives (0, None, None)."""
+    from fractions import Fraction
+
+    d = [[int(v) for v in row] for row in np.asarray(d).reshape(-1, 3)]
+    n = len(d)
+    s1 = [sum(row[a] for row in d) for a in range(3)]
+    c = [[Fraction(sum(row[a] * row[b] for row in d)) - Fraction(s1[a] * s1[b], n) for b in range(3)] for a in range(3)]
+    top = max(c[0][0], c[1][1], c[2][2])
+    if top == 0 or c[0][0] == 0:
+        return Fraction(0), None, None
+    p1 = c[1][1] - c[0][1] ** 2 / c[0][0]
+    if p1 == 0:
+        return c[0][0] / top, Fraction(0), None
+    m12 = c[1][2] - c[0][2] * c[0][1] / c[0][0]
+    p2 = c[2][2] - c[0][2] ** 2 / c[0][0] - m12 ** 2 / p1
+    return c[0][0] / top, p1 / top, p2 / top
+
+
+def smallest_pivot_ratio(d):
+    """rho: the smallest defined entry of exact_pivot_ratios(d), as a float"""
+    return float(min(p for p in exact_pivot_ratios(d) if p is not None))
