@@ -53,6 +53,8 @@ SYMBOLS = [
     # outlier validation of the displacement field (normalised median test)
     "sift3d_default_validate_options", "sift3d_validate_input_from_icgn", "sift3d_validate_input_from_icgn2", "sift3d_validate_displacements",
     "sift3d_validate_keep", "sift3d_icgn_init_from_validation", "sift3d_validate_stage_capacity",
+    # subset screening: texture sums and a per-POI subset radius, the step in front of IC-GN
+    "sift3d_default_subset_options", "sift3d_subset_quality", "sift3d_subset_group_by_radius",
     "sift3d_device_count", "sift3d_error_string", "sift3d_last_error",
     # typed input: 8 / 16-bit integer voxels uploaded at their own width and widened on the GPU
     "sift3d_dtype_bytes", "sift3d_create_typed", "sift3d_volume_to_device", "sift3d_test_ingest_launch",
@@ -182,6 +184,21 @@ VALIDATE_DTYPE = np.dtype([("median", "<f8", (3,)), ("mad", "<f8", (3,)), ("scor
 assert VALIDATE_DTYPE.itemsize == 72
 
 
+class SubsetOptions(C.Structure):
+    """sift3d_subset_options (include/sift3d_hip.h)"""
+    _fields_ = [("r_min", C.c_int), ("r_max", C.c_int), ("criterion", C.c_int), ("reserved0", C.c_int), ("threshold", C.c_double),
+                ("level", C.c_double), ("fraction_min", C.c_double), ("reserved", C.c_int * 2)]
+
+
+assert C.sizeof(SubsetOptions) == 48
+
+# sift3d_subset_result: mean and dR of the reported cube, G (xx yy zz xy xz yz), its eigenvalues (descending), the reported radius,
+# the status, the largest feasible radius and the material count
+SUBSET_DTYPE = np.dtype([("mean", "<f8"), ("dR", "<f8"), ("G", "<f8", (6,)), ("eig", "<f8", (3,)), ("radius", "<i4"), ("status", "<i4"),
+                         ("feasible", "<i4"), ("material", "<i4")])
+assert SUBSET_DTYPE.itemsize == 104
+
+
 class SlabDesc(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("z0", C.c_int), ("z1", C.c_int), ("halo", C.c_int),
                 ("noct_total", C.c_int), ("octave", C.c_int)]
@@ -282,6 +299,11 @@ def lib():
         L.sift3d_validate_displacements.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ValidateOptions), C.c_int,
                                                     C.c_int, C.c_void_p, C.POINTER(C.c_double)]
         L.sift3d_validate_keep.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.sift3d_default_subset_options.argtypes = [C.POINTER(SubsetOptions)]
+        L.sift3d_default_subset_options.restype = None
+        L.sift3d_subset_quality.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(SubsetOptions), C.c_int,
+                                            C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+        L.sift3d_subset_group_by_radius.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.sift3d_icgn_init_from_validation.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _ip]
         L.sift3d_validate_stage_capacity.argtypes = [_ip]
         _sz = C.POINTER(C.c_size_t)
@@ -922,6 +944,56 @@ def icgn_init_from_validation(val, init=None):
     count = C.c_int(0)
     _check(lib().sift3d_icgn_init_from_validation(_p(buf), m, _p(out), C.byref(count)))
     return out[:m].copy(), count.value
+
+
+SUBSET_OPTIONS = ("r_min", "r_max", "criterion", "threshold", "level", "fraction_min")
+SUBSET_FIELDS = ("mean", "dR", "G", "eig", "radius", "status", "feasible", "material")
+
+
+def default_subset_options():
+    """sift3d_default_subset_options as a dict (needs no GPU)"""
+    o = _options(SubsetOptions, "sift3d_default_subset_options", SUBSET_OPTIONS, "subset", {})
+    return {k: getattr(o, k) for k in SUBSET_OPTIONS}
+
+
+def subset_quality(ref, points, device=0, **opts):
+    """sift3d_subset_quality: the texture sums of the subset around each point ((m, 3) int32 x, y, z of ref) and the smallest radius
+    of r_min .. r_max whose criterion reaches the threshold.  ref: an (nz, ny, nx) float32 numpy array or a contiguous float32 device
+    tensor.  Options: r_min, r_max, criterion (0 min(Gxx, Gyy, Gzz), 1 the smallest eigenvalue of G), threshold, level, fraction_min.
+    Returns mean, dR (m,), G (m, 6: xx yy zz xy xz yz), eig (m, 3), radius, status, feasible, material (m,), the records themselves
+    (SUBSET_DTYPE, for subset_groups) and the device seconds."""
+    o = _options(SubsetOptions, "sift3d_default_subset_options", SUBSET_OPTIONS, "subset", opts)
+    on_dev = int(_is_dev(ref))
+    rp, r = _volume(ref, "ref", on_dev)
+    qp, m, q = _table(points, np.int32, 3, ref)
+    out = np.zeros(max(m, 1), SUBSET_DTYPE)
+    sec = C.c_double(0)
+    _check(lib().sift3d_subset_quality(rp, *r.shape[::-1], qp, m, C.byref(o), on_dev, int(device), _p(out), C.byref(sec)))
+    d = _fields(out, m, SUBSET_FIELDS)
+    d["records"] = out[:m].copy()
+    d["seconds"] = sec.value
+    return d
+
+
+def subset_groups(res, r_min, r_max):
+    """sift3d_subset_group_by_radius: the status-0 records of subset_quality's dict (or of a SUBSET_DTYPE array) grouped by radius:
+    a list of (radius, indices) for the non-empty groups, radius ascending, indices (int32) ascending -- one icgn call per entry
+    with subset_radius = radius on points[indices].  Needs no GPU."""
+    if isinstance(res, dict):
+        radius, status = np.asarray(res["radius"]), np.asarray(res["status"])
+        rec = np.zeros(len(radius), SUBSET_DTYPE)
+        rec["radius"], rec["status"] = radius, status
+    else:
+        rec = np.ascontiguousarray(res, SUBSET_DTYPE)
+    m = len(rec)
+    buf = np.zeros(max(m, 1), SUBSET_DTYPE)
+    buf[:m] = rec
+    order = np.zeros(max(m, 1), np.int32)
+    offsets = np.zeros(max(int(r_max) - int(r_min) + 2, 2), np.int32)
+    count = C.c_int(0)
+    _check(lib().sift3d_subset_group_by_radius(_p(buf), m, int(r_min), int(r_max), _p(order), _p(offsets), C.byref(count)))
+    return [(int(r_min) + g, order[offsets[g]:offsets[g + 1]].copy()) for g in range(int(r_max) - int(r_min) + 1)
+            if offsets[g + 1] > offsets[g]]
 
 
 def device_count():

@@ -359,6 +359,14 @@ size_t search_score_bytes(int m, int s);   // score scratch of the launch (a tab
 void launch_zncc_search(IcgnVol R, IcgnVol T, const int *d_pts, int m, const int *d_guess, int r, int s, double *d_scores,
                         sift3d_search_result *d_out, hipStream_t st);
 
+// ---- kernels_subset.hip: subset screening (sift3d_subset_quality, include/sift3d_hip.h) -------------------------------------------
+struct SubsetParams {  // the checked options
+	int r_min, r_max, criterion;
+	double threshold, level, fraction_min;
+};
+// one workgroup per POI; d_out: m records
+void launch_subset_quality(IcgnVol R, const int *d_pts, int m, SubsetParams P, sift3d_subset_result *d_out, hipStream_t st);
+
 // ---- kernels_strain.hip: strain fields from the POIs' displacements (sift3d_strain, include/sift3d_hip.h) ------------------------
 // the cell grid over the bounding box of the contributing POIs: cell (cx, cy, cz) = (q - origin) / side per axis, cx fastest
 struct StrainGrid {

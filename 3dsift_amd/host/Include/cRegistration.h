@@ -1,10 +1,11 @@
-// cRegistration.h -- RANSAC affine fits of matched keypoints, ZNCC integer search, IC-GN displacement refinement, validation and strain fields (no
+// cRegistration.h -- RANSAC affine fits of matched keypoints, subset screening, ZNCC integer search, IC-GN displacement refinement, validation and strain fields (no
 // reference counterpart): the steps after enhancedMatch, on the GPU.
-// Over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_zncc_search / sift3d_icgn / sift3d_validate_displacements / sift3d_strain (include/sift3d_hip.h, which states the numerical contracts).  Both functions take
+// Over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_subset_quality / sift3d_zncc_search / sift3d_icgn / sift3d_validate_displacements / sift3d_strain (include/sift3d_hip.h, which states the numerical contracts).  Both functions take
 // exactly the two std::vector<Cvec> that muBruteMatcher::enhancedMatch fills (refMatch[i] <-> tarMatch[i]).
 #ifndef S3D_HOST_CREGISTRATION_H
 #define S3D_HOST_CREGISTRATION_H
 
+#include <cmath>
 #include <vector>
 
 #include "Util/common.h"
@@ -87,6 +88,36 @@ struct SIFT_LIBRARY_API SearchResult {
 SIFT_LIBRARY_API std::vector<SearchResult> SearchDisplacements(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
                                                                const std::vector<Cvec> &points, const std::vector<Cvec> *guesses = nullptr,
                                                                const SearchOptions &o = SearchOptions());
+
+struct SIFT_LIBRARY_API SubsetOptions {
+	int r_min = 8, r_max = 16;  // the radii walked, 2 <= r_min <= r_max <= 32
+	int criterion = 0;          // 0 min(Gxx, Gyy, Gzz), the per-axis SSSIG; 1 the smallest eigenvalue of G
+	double threshold = 0;       // the criterion a subset must reach (2 sigma_noise^2 / sigma_u^2); 0 accepts r_min everywhere
+	double level = -INFINITY;   // a voxel is material when its value is >= level
+	double fraction_min = 0;    // the fraction of material voxels a subset must hold, 0..1
+};
+
+// the texture sums of the subset around one point of interest and its radius (include/sift3d_hip.h); status 0 the radius qualifies,
+// 1 no radius does (the record is that of `feasible`), 2 the cube of r_min leaves ref, 3 too little material, -1 the call failed
+// (message on stderr, like EstimateAffine)
+struct SIFT_LIBRARY_API SubsetQuality {
+	double mean = 0, dR = 0;
+	double G[6] = {0, 0, 0, 0, 0, 0};  // xx yy zz xy xz yz
+	double eig[3] = {0, 0, 0};         // of G, descending
+	int radius = 0;
+	int status = -1;
+	int feasible = 0, material = 0;
+	double seconds = 0;                // device time of the call
+};
+
+// the step in front of RefineDisplacements: per integral point of ref the smallest subset radius of o.r_min .. o.r_max whose texture
+// reaches o.threshold, or that none does
+SIFT_LIBRARY_API std::vector<SubsetQuality> SelectSubsets(const float *ref, int nx, int ny, int nz, const std::vector<Cvec> &points,
+                                                          const SubsetOptions &o = SubsetOptions());
+// the indices of the status-0 records grouped by radius: groups[r - r_min] lists, in ascending order, the points whose subset has radius
+// r -- one RefineDisplacements call per non-empty group with IcgnOptions::subset_radius = r.  false: a bad range, or a status-0 radius
+// outside it (message on stderr)
+SIFT_LIBRARY_API bool GroupSubsetsByRadius(const std::vector<SubsetQuality> &quality, int r_min, int r_max, std::vector<std::vector<int>> &groups);
 
 // the cubic B-spline coefficients (mirror boundary) of vol (nx x ny x nz, fp32, x fastest) into coefficients, host memory of the same
 // size and not vol itself: what RefineDisplacements takes as tar with interpolation 2 and tar_is_coefficients, so a target refined

@@ -166,6 +166,61 @@ std::vector<SearchResult> SearchDisplacements(const float *ref, int nx, int ny, 
 	return res;
 }
 
+std::vector<SubsetQuality> SelectSubsets(const float *ref, int nx, int ny, int nz, const std::vector<Cvec> &points, const SubsetOptions &opts) {
+	const size_t m = points.size();
+	std::vector<SubsetQuality> res(m);
+	std::vector<int> q;
+	if (!int_triples("SelectSubsets", "point", points, q)) return res;
+	sift3d_subset_options o;
+	sift3d_default_subset_options(&o);
+	o.r_min = opts.r_min;
+	o.r_max = opts.r_max;
+	o.criterion = opts.criterion;
+	o.threshold = opts.threshold;
+	o.level = opts.level;
+	o.fraction_min = opts.fraction_min;
+	std::vector<sift3d_subset_result> r(m ? m : 1);
+	double sec = 0;
+	const int rc = sift3d_subset_quality(ref, nx, ny, nz, q.data(), (int)m, &o, 0, GetDevice(), r.data(), &sec);
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] SelectSubsets: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return res;
+	}
+	for (size_t i = 0; i < m; i++) {
+		res[i].mean = r[i].mean;
+		res[i].dR = r[i].dR;
+		memcpy(res[i].G, r[i].G, sizeof(res[i].G));
+		memcpy(res[i].eig, r[i].eig, sizeof(res[i].eig));
+		res[i].radius = r[i].radius;
+		res[i].status = r[i].status;
+		res[i].feasible = r[i].feasible;
+		res[i].material = r[i].material;
+		res[i].seconds = sec;
+	}
+	return res;
+}
+
+bool GroupSubsetsByRadius(const std::vector<SubsetQuality> &quality, int r_min, int r_max, std::vector<std::vector<int>> &groups) {
+	const size_t m = quality.size();
+	groups.clear();
+	std::vector<sift3d_subset_result> r(m ? m : 1);
+	memset(r.data(), 0, sizeof(sift3d_subset_result) * r.size());
+	for (size_t i = 0; i < m; i++) {
+		r[i].radius = quality[i].radius;
+		r[i].status = quality[i].status;
+	}
+	std::vector<int> order(m ? m : 1), offsets(64, 0);  // the library takes at most 31 groups
+	int count = 0;
+	const int rc = sift3d_subset_group_by_radius(r.data(), (int)m, r_min, r_max, order.data(), offsets.data(), &count);
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] GroupSubsetsByRadius: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return false;
+	}
+	groups.resize(r_max - r_min + 1);
+	for (int g = 0; g <= r_max - r_min; g++) groups[g].assign(order.begin() + offsets[g], order.begin() + offsets[g + 1]);
+	return true;
+}
+
 std::vector<IcgnResult> RefineDisplacements(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
                                             const std::vector<Cvec> &points, const std::vector<AffineFit> *init, const IcgnOptions &opts,
                                             const std::vector<SearchResult> *fallback) {

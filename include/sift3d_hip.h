@@ -922,6 +922,91 @@ int sift3d_validate_keep(const sift3d_validate_result *val, const unsigned char 
  * *count (may be NULL): rows written.  SIFT3D_ERR_ARG: m < 0, or NULL val / init12 with m > 0. */
 int sift3d_icgn_init_from_validation(const sift3d_validate_result *val, int m, double *init12, int *count);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Subset screening: the step in front of IC-GN (no reference counterpart: the SSSIG rule of DIC / DVC codes, Pan et al. 2008,
+ * Var(u) ~ 2 sigma_noise^2 / SSSIG_x).  Per POI it forms the texture sums of the subset -- the cube of voxels IC-GN would match -- at
+ * growing radius and reports the smallest radius at which the sum of squared intensity gradients reaches a threshold, or that no
+ * radius does: a subset in air, in a pore or in a phase with texture along one direction only cannot be correlated.
+ * Numerical contract (tests/subset_ref.py restates it in NumPy fp64):
+ *   Volume and POIs: those of sift3d_icgn: fp32 [z][y][x], a POI q an integer voxel (x, y, z) of R.
+ *   Gradient: IC-GN's, fp32 g_x = 0.5f * (R[x+1] - R[x-1]) (likewise y, z), widened to double; every product and sum is fp64.
+ *   Cube of radius rho: q + [-rho, rho]^3, N = (2 rho + 1)^3 voxels.  It is feasible when the cube plus a 1-voxel margin lies in R
+ *     (IC-GN's status-2 rule).  feasible = rho_f: the largest rho <= r_max that is, computed in 64-bit arithmetic for any int q.
+ *   Sums over a cube: Rc = R[q] is the shift and a = (double)R - (double)Rc (exact);  S = sum a;  Q = sum a^2;
+ *     mean = (double)Rc + S / N;  dR = sqrt(v) with v = Q - S * S / N and v < 0 replaced by 0 (a NaN stays);
+ *     G_ab = sum g_a g_b (xx yy zz xy xz yz);  material = the count of voxels with (double)R >= level.
+ *     The operations in these formulas are single correctly rounded ones (the library is built with -ffp-contract=off).
+ *   Eigenvalues: eig = those of G by cyclic Jacobi in fp64 (8 sweeps over the planes (0,1) (0,2) (1,2), as for sift3d_strain's
+ *     principal), descending: the largest, trace - largest - smallest, the smallest.  Where an entry of G is not finite eig is NaN.
+ *   Criterion: c(rho) = min(Gxx, Gyy, Gzz) (criterion 0, the per-axis SSSIG) or eig[2] (criterion 1); where an entry of G is not
+ *     finite c(rho) is NaN under either.
+ *   Selection: the reported radius is the smallest rho in [r_min, rho_f] whose c(rho) is finite and >= threshold; if there is none
+ *     the record is that of rho_f with status 1.
+ *   Status per POI (results of a successful call, not errors), checked in this order:
+ *     2 the cube of r_min plus its margin is outside R: no voxel is read; the doubles, radius, feasible and material are 0;
+ *     1 no radius qualifies;  3 a radius qualifies but (double)material < fraction_min * (double)N at that radius (the record is
+ *     that radius's);  0 otherwise.
+ *   Reach of a non-finite voxel: exactly the records whose cube or axial margin holds it.  A cube voxel's six axial neighbours are
+ *     read; the edges and corners of the margin shell are not.  A NaN there makes c(rho) NaN, an Inf or a difference that overflows
+ *     fp32 makes an entry of G non-finite: such a radius never qualifies.  A NaN or Inf at q itself reaches every sum through Rc.
+ *   Determinism and bounds: no float atomics, every sum has a fixed order (the cube of r_min as one block, then the Chebyshev shells
+ *     k = max(|dx|, |dy|, |dz|) outward, each added to the running totals); two calls return the same bytes; a POI's record does
+ *     not depend on the other POIs of the call or on their order; no voxel outside R is ever read.
+ *   Consequences: for integer-valued R (what 8 / 16-bit CT gives; sums below 2^53) S, Q and G are exact whatever the order, so
+ *     mean, dR, G, material, radius and status equal the restatement bit for bit.  Scaling R by 2^e scales G by 2^(2e) bit for bit.
+ *     A constant R gives all-zero sums exactly.  G, dR and mean at radius r are sift3d_icgn's H[0][0], H[4][4], H[8][8], H[0][4],
+ *     H[0][8], H[4][8], dR and Rm at that r (to the rounding of the sums: IC-GN forms dR in two passes).
+ * SIFT3D_ERR_ARG (checked before any device call): m < 0, a dimension < 1, r_min outside 2..32, r_max outside r_min..32, criterion
+ * outside 0..1, a threshold that is not finite and >= 0, a NaN level, fraction_min outside 0..1 (or NaN), a non-zero reserved word,
+ * NULL ref / out, NULL points3 with m > 0; m = 0 succeeds.  SIFT3D_ERR_NO_DEVICE after that check when no GPU is visible: there is
+ * no CPU fallback.  o may be NULL (defaults).  on_device != 0: ref and points3 are device pointers on `device`, ordered behind the
+ * legacy default stream; out is host memory, filled by one copy at the end.  *seconds (may be NULL): device time of the call (HIP
+ * events; the uploads of host inputs excluded).
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct sift3d_subset_options {
+	int r_min;             /* 2..32, default 8 */
+	int r_max;             /* r_min..32, default 16 */
+	int criterion;         /* 0 (default): min(Gxx, Gyy, Gzz), the per-axis SSSIG;  1: the smallest eigenvalue of G */
+	int reserved0;         /* must be 0 */
+	double threshold;      /* finite, >= 0, default 0 (accepts r_min everywhere: the caller sets it, 2 sigma_noise^2 / sigma_u^2) */
+	double level;          /* not NaN, default -INFINITY: a voxel is "material" when (double)R >= level */
+	double fraction_min;   /* 0..1, default 0 */
+	int reserved[2];       /* must be 0 */
+} sift3d_subset_options;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_subset_options) == 48, "sift3d_subset_options must be 48 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_subset_options, r_max) == 4 && offsetof(sift3d_subset_options, criterion) == 8 &&
+                     offsetof(sift3d_subset_options, reserved0) == 12 && offsetof(sift3d_subset_options, threshold) == 16 &&
+                     offsetof(sift3d_subset_options, level) == 24 && offsetof(sift3d_subset_options, fraction_min) == 32 &&
+                     offsetof(sift3d_subset_options, reserved) == 40, "sift3d_subset_options field offsets");
+
+typedef struct sift3d_subset_result {
+	double mean;           /* Rm over the reported cube */
+	double dR;             /* sqrt(sum (R - Rm)^2) */
+	double G[6];           /* xx yy zz xy xz yz: sums of products of the fp32 central differences */
+	double eig[3];         /* eigenvalues of G, descending */
+	int radius;            /* the reported radius */
+	int status;            /* the table above */
+	int feasible;          /* largest rho <= r_max whose cube + 1-voxel margin lies in R (0 with status 2) */
+	int material;          /* voxels of the reported cube with R >= level */
+} sift3d_subset_result;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_subset_result) == 104, "sift3d_subset_result must be 104 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_subset_result, dR) == 8 && offsetof(sift3d_subset_result, G) == 16 &&
+                     offsetof(sift3d_subset_result, eig) == 64 && offsetof(sift3d_subset_result, radius) == 88 &&
+                     offsetof(sift3d_subset_result, status) == 92 && offsetof(sift3d_subset_result, feasible) == 96 &&
+                     offsetof(sift3d_subset_result, material) == 100, "sift3d_subset_result field offsets");
+
+/* the defaults above; needs no GPU */
+void sift3d_default_subset_options(sift3d_subset_options *o);
+/* m POIs (x, y, z int triples) of ref screened; out: m records */
+int sift3d_subset_quality(const float *ref, int nx, int ny, int nz, const int *points3, int m, const sift3d_subset_options *o,
+                          int on_device, int device, sift3d_subset_result *out, double *seconds);
+/* host only: the status-0 records grouped by radius, for one sift3d_icgn call per non-empty group with that group's radius.
+ * order (m ints): the indices of the status-0 records by ascending radius, ascending index within a radius; offsets
+ * (r_max - r_min + 2 ints): group g = radius r_min + g is order[offsets[g] .. offsets[g + 1]); *count: how many records were listed.
+ * SIFT3D_ERR_ARG: m < 0, r_min outside 2..32, r_max outside r_min..32, a NULL pointer with m > 0 (with m = 0 offsets and count are
+ * filled where given), or a status-0 record whose radius lies outside r_min..r_max. */
+int sift3d_subset_group_by_radius(const sift3d_subset_result *res, int m, int r_min, int r_max, int *order, int *offsets, int *count);
+
 /* Test hooks, rare-path counters and the unit-level debug entry points live in include/sift3d_hip_test.h: this header is the
  * product boundary only. */
 const char *sift3d_error_string(int code);
