@@ -41,37 +41,17 @@ struct CallState {
 	int finish(double *seconds);                 // waits for e1; *seconds (may be NULL) = e0 -> e1
 };
 
-// the temporaries of one call whose sizes depend on the input (sift3d_strain, sift3d_validate_displacements): freed when the call
-// returns, however it returns
-struct CallTemps {
-	char *a = nullptr, *b = nullptr;
-	~CallTemps() {
-		if (a) (void)hipFree(a);
-		if (b) (void)hipFree(b);
-	}
-};
-
-// the cell grid of the strain kernels over the box launch_strain_mark left (min x, y, z, min -x, -y, -z; 0x7f7f7f7f where no POI
-// contributes): the side is the radius, enlarged until the grid has at most 2^24 cells.  The extents reach 2^25 + 1, so the products
-// are formed in 64 bits and stepwise.
-inline StrainGrid strain_choose_grid(const int *box, int radius) {
-	constexpr long long kMaxCells = 1 << 24;
-	StrainGrid g = {0, 0, 0, radius, 1, 1, 1};
-	if (box[0] == 0x7f7f7f7f) return g;
-	g.x0 = box[0]; g.y0 = box[1]; g.z0 = box[2];
-	const long long ex = (long long)-box[3] - box[0], ey = (long long)-box[4] - box[1], ez = (long long)-box[5] - box[2];
-	long long side = radius;
-	for (;;) {
-		const long long nx = ex / side + 1, ny = ey / side + 1, nz = ez / side + 1;
-		if (nx * ny <= kMaxCells && nx * ny * nz <= kMaxCells) {
-			g.side = (int)side; g.nx = (int)nx; g.ny = (int)ny; g.nz = (int)nz;
-			return g;
-		}
-		side += (side + 3) / 4;
-	}
-}
-
 int pick_device(int device);  // checks the index, makes the device current
+
+// an input table p of a call -> where the kernels read it.  Its piece of the scratch block at base + off: bytes > 0, the host table
+// is uploaded there and p moves to it; no bytes (a device input, an optional table that is absent), p stays as it is
+template <class T>
+hipError_t upload(const T *&p, char *base, size_t off, size_t bytes, hipStream_t st) {
+	if (!bytes) return hipSuccess;
+	const T *host = p;
+	p = reinterpret_cast<const T *>(base + off);
+	return hipMemcpyAsync(base + off, host, bytes, hipMemcpyHostToDevice, st);
+}
 
 // a HIP call of an entry that has work on stream st: the stream is drained before the error is returned
 #define S3D_HIP_ST(st, call)                                                                            \

@@ -95,14 +95,9 @@ extern "C" int sift3d_subset_quality(const float *ref, int nx, int ny, int nz, c
 	char *D = S.d.p, *H = S.h.p;
 	const float *d_ref = ref;
 	const int *d_pts = points3;
-	if (on_device) {
-		if ((rc = S.after_legacy_stream())) return rc;
-	} else {
-		S3D_HIP_ST(st, hipMemcpyAsync(D + o_ref, ref, b_ref, hipMemcpyHostToDevice, st));
-		S3D_HIP_ST(st, hipMemcpyAsync(D + o_pts, points3, b_pts, hipMemcpyHostToDevice, st));
-		d_ref = reinterpret_cast<const float *>(D + o_ref);
-		d_pts = reinterpret_cast<const int *>(D + o_pts);
-	}
+	if (on_device && (rc = S.after_legacy_stream())) return rc;
+	S3D_HIP_ST(st, upload(d_ref, D, o_ref, b_ref, st));
+	S3D_HIP_ST(st, upload(d_pts, D, o_pts, b_pts, st));
 	S3D_HIP_ST(st, hipEventRecord(S.e0, st));
 	launch_subset_quality(IcgnVol{d_ref, nx, ny, nz}, d_pts, m, P, reinterpret_cast<sift3d_subset_result *>(D), st);
 	S3D_HIP_ST(st, hipGetLastError());

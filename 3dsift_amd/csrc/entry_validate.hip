@@ -1,8 +1,9 @@
 // entry_validate.hip -- C-ABI of the displacement validation (include/sift3d_hip.h: sift3d_validate_displacements, its host-only
 // helpers and sift3d_default_validate_options; include/sift3d_hip_test.h: sift3d_validate_stage_capacity).  No reference counterpart.
 // Call state, scratch layout, timing and the order of the checks: DESIGN 4.10 (call_state.h).  As in entry_strain.hip the temporaries
-// depend on the input (the cell grid on the POIs' bounding box), so they are allocated and freed inside the call.
+// depend on the input (the cell grid of the POI index on the POIs' bounding box, poi_grid.h), so they are allocated and freed inside the call.
 #include "call_state.h"
+#include "poi_grid.h"
 #include "icgn_host.h"
 
 #include <math.h>
@@ -115,67 +116,39 @@ extern "C" int sift3d_validate_displacements(const int *points3, const double *d
 	if ((rc = D.ensure(0, 0))) return rc;
 	hipStream_t st = D.stream;
 	CallTemps T;
-	// block a: [results | box | cell of a POI | slots | sorted x y z idx | sorted u v w | pass of a flag | folded valid bytes | flags,
-	// twice | (host inputs) points | disp | grad | valid]
-	const size_t M = (size_t)m, wi = al256(sizeof(int) * M), wd = al256(sizeof(double) * M), wb = al256(M);
-	const size_t res_bytes = sizeof(sift3d_validate_result) * M;
+	// block a: [results | the index's pieces | pass of a flag | folded valid bytes | flags, twice | (host inputs) points | disp | grad | valid]
+	const size_t M = (size_t)m, wb = al256(M), res_bytes = sizeof(sift3d_validate_result) * M;
+	const size_t b_pts = on_device ? 0 : sizeof(int) * 3 * M, b_disp = on_device ? 0 : sizeof(double) * 3 * M;
+	const size_t b_grad = on_device || !grad9 ? 0 : sizeof(double) * 9 * M, b_valid = on_device || !valid ? 0 : M;
 	Layout L;
 	L.take(res_bytes);
-	const size_t o_box = L.take(sizeof(int) * 6), o_cell = L.take(wi), o_slots = L.take(wi), o_si = L.take(4 * wi), o_sd = L.take(3 * wd);
-	const size_t o_pass = L.take(wi), o_fold = L.take(wb), o_flags = L.take(2 * wb);
-	const size_t o_pts = L.take(on_device ? 0 : sizeof(int) * 3 * M), o_disp = L.take(on_device ? 0 : sizeof(double) * 3 * M);
-	const size_t o_grad = L.take(on_device || !grad9 ? 0 : sizeof(double) * 9 * M), o_valid = L.take(on_device || !valid ? 0 : M);
+	PoiGridPlan G;
+	G.take(L, m);
+	const size_t o_pass = L.take(sizeof(int) * M), o_fold = L.take(wb), o_flags = L.take(2 * wb);
+	const size_t o_pts = L.take(b_pts), o_disp = L.take(b_disp), o_grad = L.take(b_grad), o_valid = L.take(b_valid);
 	S3D_HIP(hipMalloc(&T.a, L.end));
 	char *A = T.a;
 	const int *d_pts = points3;
 	const double *d_disp = disp3, *d_grad = grad9;
 	const unsigned char *d_valid = valid;
-	if (on_device) {
-		if ((rc = D.after_legacy_stream())) return rc;
-	} else {
-		d_pts = reinterpret_cast<int *>(A + o_pts);
-		d_disp = reinterpret_cast<double *>(A + o_disp);
-		S3D_HIP_ST(st, hipMemcpyAsync(A + o_pts, points3, sizeof(int) * 3 * M, hipMemcpyHostToDevice, st));
-		S3D_HIP_ST(st, hipMemcpyAsync(A + o_disp, disp3, sizeof(double) * 3 * M, hipMemcpyHostToDevice, st));
-		if (grad9) {
-			d_grad = reinterpret_cast<double *>(A + o_grad);
-			S3D_HIP_ST(st, hipMemcpyAsync(A + o_grad, grad9, sizeof(double) * 9 * M, hipMemcpyHostToDevice, st));
-		}
-		if (valid) {
-			d_valid = reinterpret_cast<unsigned char *>(A + o_valid);
-			S3D_HIP_ST(st, hipMemcpyAsync(A + o_valid, valid, M, hipMemcpyHostToDevice, st));
-		}
-	}
-	int *d_box = reinterpret_cast<int *>(A + o_box), *d_cell = reinterpret_cast<int *>(A + o_cell), *d_slots = reinterpret_cast<int *>(A + o_slots);
+	if (on_device && (rc = D.after_legacy_stream())) return rc;
+	S3D_HIP_ST(st, upload(d_pts, A, o_pts, b_pts, st));
+	S3D_HIP_ST(st, upload(d_disp, A, o_disp, b_disp, st));
+	S3D_HIP_ST(st, upload(d_grad, A, o_grad, b_grad, st));
+	S3D_HIP_ST(st, upload(d_valid, A, o_valid, b_valid, st));
 	int *d_pass = reinterpret_cast<int *>(A + o_pass);
 	unsigned char *d_fold = reinterpret_cast<unsigned char *>(A + o_fold);
 	unsigned char *d_flags[2] = {reinterpret_cast<unsigned char *>(A + o_flags), reinterpret_cast<unsigned char *>(A + o_flags + wb)};
-	StrainSorted S;
-	S.x = reinterpret_cast<int *>(A + o_si); S.y = reinterpret_cast<int *>(A + o_si + wi); S.z = reinterpret_cast<int *>(A + o_si + 2 * wi);
-	S.idx = reinterpret_cast<int *>(A + o_si + 3 * wi);
-	S.u = reinterpret_cast<double *>(A + o_sd); S.v = reinterpret_cast<double *>(A + o_sd + wd); S.w = reinterpret_cast<double *>(A + o_sd + 2 * wd);
 	S3D_HIP_ST(st, hipEventRecord(D.e0, st));
-	S3D_HIP_ST(st, hipMemsetAsync(d_box, 0x7f, sizeof(int) * 6, st));
 	S3D_HIP_ST(st, hipMemsetAsync(d_pass, 0, sizeof(int) * M, st));
 	S3D_HIP_ST(st, hipMemsetAsync(d_flags[0], 0, M, st));
 	launch_validate_fold(d_grad, d_valid, m, d_fold, st);
-	launch_strain_mark(d_pts, d_disp, d_fold, m, d_cell, d_box, st);
-	S3D_HIP_ST(st, hipGetLastError());
-	int box[6];
-	S3D_HIP_ST(st, hipMemcpyAsync(box, d_box, sizeof(box), hipMemcpyDeviceToHost, st));
-	S3D_HIP_ST(st, hipStreamSynchronize(st));
-	const StrainGrid g = strain_choose_grid(box, P.radius);
-	// block b: [counts per cell (then the scatter's fill marks) | cell starts | the scan's tile sums]
-	const size_t cells = (size_t)g.nx * g.ny * g.nz, wc = al256(sizeof(int) * (cells + 1));
-	S3D_HIP(hipMalloc(&T.b, 2 * wc + sizeof(int) * strain_scan_tiles(cells + 1)));
-	int *d_cnt = reinterpret_cast<int *>(T.b), *d_start = reinterpret_cast<int *>(T.b + wc), *d_tiles = reinterpret_cast<int *>(T.b + 2 * wc);
-	S3D_HIP_ST(st, hipMemsetAsync(d_cnt, 0, sizeof(int) * (cells + 1), st));
-	S3D_HIP_ST(st, launch_strain_bin(d_pts, d_disp, m, g, d_cell, d_cnt, d_start, d_tiles, d_slots, S, st));
+	PoiIndex ix;
+	if ((rc = poi_grid_build(G, A, d_pts, d_disp, d_fold, m, P.radius, T, st, ix))) return rc;
 	sift3d_validate_result *d_out = reinterpret_cast<sift3d_validate_result *>(A);
 	// pass p reads the flags of pass p - 1 and writes its own into the other buffer; the report reads the last pass's
-	for (int p = 1; p <= passes; p++)
-		launch_validate_test(d_pts, d_disp, d_grad, d_cell, m, g, d_start, S, P, p, d_flags[(p - 1) & 1], d_flags[p & 1], d_pass, d_out, st);
-	launch_validate_test(d_pts, d_disp, d_grad, d_cell, m, g, d_start, S, P, 0, d_flags[passes & 1], nullptr, d_pass, d_out, st);
+	for (int p = 1; p <= passes; p++) launch_validate_test(d_pts, d_disp, d_grad, m, ix, P, p, d_flags[(p - 1) & 1], d_flags[p & 1], d_pass, d_out, st);
+	launch_validate_test(d_pts, d_disp, d_grad, m, ix, P, 0, d_flags[passes & 1], nullptr, d_pass, d_out, st);
 	S3D_HIP_ST(st, hipGetLastError());
 	S3D_HIP_ST(st, hipMemcpyAsync(out, A, res_bytes, hipMemcpyDeviceToHost, st));
 	S3D_HIP_ST(st, hipEventRecord(D.e1, st));

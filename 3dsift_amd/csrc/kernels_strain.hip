@@ -1,19 +1,11 @@
 // kernels_strain.hip -- strain fields from the displacements of the POIs (sift3d_strain, include/sift3d_hip.h, which states the
-// numerical contract).  No reference counterpart.  A POI's neighbours are found through a uniform cell grid over the bounding box of
-// the contributing POIs; the side of a cell is at least the window's half width, so a window touches at most 3 x 3 x 3 cells.
-//   mark       per POI: does it contribute (valid byte, finite displacement, |coordinate| <= 2^24)?  The bounding box of the
-//              contributing POIs by integer atomic min (the maxima as minima of the negated coordinate).  The host reads the box and
-//              chooses the grid (entry_strain.hip).
-//   bin        a count per cell by integer atomics, an exclusive scan (tiles of 4096 cells, the tile sums by one workgroup), then the
-//              placement: POIs take a slot of their cell's segment by atomic (any order), and every slot is then ranked by the number of
-//              POIs of its segment with a smaller index -- the sorted arrays list a cell's POIs in ascending index whatever order the
-//              atomics gave.  Cells consecutive in x are consecutive in memory: the cells a window touches are 9 contiguous runs.
-//              The ranking costs k^2 per cell of k POIs, which is what the fits of those k POIs cost as well.
+// numerical contract).  No reference counterpart.  A POI's neighbours come from the POI index (kernels_poigrid.hip), so a window is 9
+// contiguous runs of the sorted arrays (poi_window.h).
 //   fit        one wave per POI.  The 9 runs are walked as one sequence, lane l taking entries l, l + 64, ...: coordinates and
 //              displacements are SoA, so a wave reads them coalesced.  Three walks: count and lowest index (u0), the 21 sums, the
 //              residual.  Sums are fp64, reduced by an xor butterfly: a fixed order, the same value in every lane.  Every lane solves
 //              the 3 x 3 system (Cholesky) and the eigenvalues (cyclic Jacobi), lane 0 writes the record.  No float atomics.
-#include "sift3d_internal.h"
+#include "poi_window.h"
 
 #include <math.h>
 
@@ -22,148 +14,15 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kScanItems = 16;                      // cells per thread of a scan tile
-constexpr int kScanTile = kThreads * kScanItems;
-constexpr int kCoordMax = 1 << 24;
 constexpr double kPivotRel = 1e-9;
 
-__device__ inline bool coord_ok(int v) { return v <= kCoordMax && v >= -kCoordMax; }
 __device__ inline int wave_min(int x) {
 	for (int off = 32; off > 0; off >>= 1) x = min(x, __shfl_xor(x, off));
-	return x;
-}
-__device__ inline int wave_isum(int x) {
-	for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
 	return x;
 }
 __device__ inline double wave_sum(double x) {
 	for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
 	return x;
-}
-// floor(a / s), s > 0
-__device__ inline int floor_div(int a, int s) { return a >= 0 ? a / s : -((-a + s - 1) / s); }
-
-// cell[i] = 1 where POI i contributes, else -1; box = (min x, min y, min z, min -x, min -y, min -z), preset to a value above 2^24
-__global__ __launch_bounds__(kThreads) void k_strain_mark(const int *__restrict__ pts, const double *__restrict__ disp,
-                                                         const unsigned char *__restrict__ valid, int m, int *__restrict__ cell,
-                                                         int *__restrict__ box) {
-	const int i = blockIdx.x * kThreads + threadIdx.x;
-	bool on = false;
-	int q[3] = {0, 0, 0};
-	if (i < m) {
-		for (int a = 0; a < 3; a++) q[a] = pts[3 * (size_t)i + a];
-		on = (!valid || valid[i]) && coord_ok(q[0]) && coord_ok(q[1]) && coord_ok(q[2]);
-		for (int a = 0; a < 3; a++) on = on && isfinite(disp[3 * (size_t)i + a]);
-		cell[i] = on ? 1 : -1;
-	}
-	const int big = 0x7f7f7f7f;
-	for (int a = 0; a < 3; a++) {
-		const int lo = wave_min(on ? q[a] : big), hi = wave_min(on ? -q[a] : big);
-		if ((threadIdx.x & 63) == 0 && lo != big) {
-			atomicMin(&box[a], lo);
-			atomicMin(&box[3 + a], hi);
-		}
-	}
-}
-
-__device__ inline int cell_of(const StrainGrid &g, int x, int y, int z) {
-	return (((z - g.z0) / g.side) * g.ny + (y - g.y0) / g.side) * g.nx + (x - g.x0) / g.side;
-}
-
-// cell[i]: 1 -> the POI's cell; cnt[c] = POIs of cell c
-__global__ __launch_bounds__(kThreads) void k_strain_count(const int *__restrict__ pts, int m, StrainGrid g, int *__restrict__ cell,
-                                                          int *__restrict__ cnt) {
-	const int i = blockIdx.x * kThreads + threadIdx.x;
-	if (i >= m || cell[i] < 0) return;
-	const int c = cell_of(g, pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]);
-	cell[i] = c;
-	atomicAdd(&cnt[c], 1);
-}
-
-// inclusive scan of one value per thread over the workgroup; returns the thread's inclusive sum
-__device__ inline int block_scan(int v, int *sh) {
-	const int t = threadIdx.x;
-	sh[t] = v;
-	__syncthreads();
-	for (int off = 1; off < kThreads; off <<= 1) {
-		const int add = t >= off ? sh[t - off] : 0;
-		__syncthreads();
-		sh[t] += add;
-		__syncthreads();
-	}
-	const int r = sh[t];
-	__syncthreads();
-	return r;
-}
-
-// out[i] = sum of in[tile start .. i) within each tile of kScanTile entries; tiles[b] = the tile's total
-__global__ __launch_bounds__(kThreads) void k_strain_scan_tiles(const int *__restrict__ in, int *__restrict__ out, int n, int *__restrict__ tiles) {
-	__shared__ int sh[kThreads];
-	const size_t base = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kScanItems;
-	int v[kScanItems], sum = 0;
-#pragma unroll
-	for (int k = 0; k < kScanItems; k++) {
-		v[k] = base + k < (size_t)n ? in[base + k] : 0;
-		sum += v[k];
-	}
-	const int incl = block_scan(sum, sh);
-	int run = incl - sum;
-#pragma unroll
-	for (int k = 0; k < kScanItems; k++) {
-		if (base + k < (size_t)n) out[base + k] = run;
-		run += v[k];
-	}
-	if (threadIdx.x == kThreads - 1) tiles[blockIdx.x] = incl;
-}
-
-// tiles[0 .. nt) -> their exclusive sums, by one workgroup
-__global__ __launch_bounds__(kThreads) void k_strain_scan_sums(int *__restrict__ tiles, int nt) {
-	__shared__ int sh[kThreads];
-	int carry = 0;
-	for (int base = 0; base < nt; base += kThreads) {
-		const int i = base + threadIdx.x;
-		const int v = i < nt ? tiles[i] : 0;
-		const int incl = block_scan(v, sh);
-		if (i < nt) tiles[i] = carry + incl - v;
-		if (threadIdx.x == kThreads - 1) sh[0] = incl;
-		__syncthreads();
-		carry += sh[0];
-		__syncthreads();
-	}
-}
-
-__global__ __launch_bounds__(kThreads) void k_strain_scan_add(int *__restrict__ out, int n, const int *__restrict__ tiles) {
-	const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
-	if (i < (size_t)n) out[i] += tiles[i / kScanTile];
-}
-
-// a slot of the cell's segment per contributing POI, in the order the atomics give
-__global__ __launch_bounds__(kThreads) void k_strain_scatter(const int *__restrict__ cell, int m, const int *__restrict__ start,
-                                                            int *__restrict__ fill, int *__restrict__ slots) {
-	const int i = blockIdx.x * kThreads + threadIdx.x;
-	if (i >= m || cell[i] < 0) return;
-	const int c = cell[i];
-	slots[start[c] + atomicAdd(&fill[c], 1)] = i;
-}
-
-// slot s holds POI i of cell c: its place is the cell's start + the number of POIs of the cell with a smaller index
-__global__ __launch_bounds__(kThreads) void k_strain_place(const int *__restrict__ slots, const int *__restrict__ cell, const int *__restrict__ start,
-                                                          int ncells, const int *__restrict__ pts, const double *__restrict__ disp,
-                                                          StrainSorted S) {
-	const int s = blockIdx.x * kThreads + threadIdx.x;
-	if (s >= start[ncells]) return;
-	const int i = slots[s], c = cell[i];
-	const int a = start[c], b = start[c + 1];
-	int rank = 0;
-	for (int t = a; t < b; t++) rank += slots[t] < i ? 1 : 0;
-	const int d = a + rank;
-	S.x[d] = pts[3 * (size_t)i];
-	S.y[d] = pts[3 * (size_t)i + 1];
-	S.z[d] = pts[3 * (size_t)i + 2];
-	S.idx[d] = i;
-	S.u[d] = disp[3 * (size_t)i];
-	S.v[d] = disp[3 * (size_t)i + 1];
-	S.w[d] = disp[3 * (size_t)i + 2];
 }
 
 // one Jacobi rotation of the symmetric 3 x 3 matrix in the plane (p, q); r is the third index
@@ -190,8 +49,8 @@ __device__ inline void write_failed(sift3d_strain_result *o, int n, int status) 
 	o->status = status;
 }
 
-__global__ __launch_bounds__(kThreads) void k_strain_fit(const int *__restrict__ pts, const double *__restrict__ disp, int m, StrainGrid g,
-                                                        const int *__restrict__ start, int ncells, StrainSorted S, int radius, int min_nb,
+__global__ __launch_bounds__(kThreads) void k_strain_fit(const int *__restrict__ pts, const double *__restrict__ disp, int m, PoiGrid g,
+                                                        const int *__restrict__ start, int ncells, PoiSorted S, int radius, int min_nb,
                                                         int measure, sift3d_strain_result *__restrict__ out) {
 	const int lane = threadIdx.x & 63;
 	const int i = blockIdx.x * kWaves + (threadIdx.x >> 6);
@@ -201,40 +60,14 @@ __global__ __launch_bounds__(kThreads) void k_strain_fit(const int *__restrict__
 		if (lane == 0) write_failed(out + i, 0, 2);
 		return;
 	}
-	// the cells the window touches, per axis (none where the window misses the grid)
-	const int lox = max(floor_div(x - radius - g.x0, g.side), 0), hix = min(floor_div(x + radius - g.x0, g.side), g.nx - 1);
-	const int loy = max(floor_div(y - radius - g.y0, g.side), 0), hiy = min(floor_div(y + radius - g.y0, g.side), g.ny - 1);
-	const int loz = max(floor_div(z - radius - g.z0, g.side), 0), hiz = min(floor_div(z + radius - g.z0, g.side), g.nz - 1);
-	const int nc = start[ncells];
-	// the runs: rb[k] the first entry of run k, cum[k] the entries of the runs before it
-	int rb[9], cum[10];
-	cum[0] = 0;
-#pragma unroll
-	for (int k = 0; k < 9; k++) {
-		const int zz = loz + k / 3, yy = loy + k % 3;
-		int b = 0, e = 0;
-		if (zz <= hiz && yy <= hiy && lox <= hix) {
-			const int row = (zz * g.ny + yy) * g.nx;
-			b = min(max(start[row + lox], 0), nc);
-			e = min(max(start[row + hix + 1], b), nc);
-		}
-		rb[k] = b;
-		cum[k + 1] = cum[k] + (e - b);
-	}
-	const int total = cum[9];
-	auto entry = [&](int t) {
-		int j = rb[0] + t;
-#pragma unroll
-		for (int k = 1; k < 9; k++)
-			if (t >= cum[k]) j = rb[k] + (t - cum[k]);
-		return j;
-	};
+	const PoiWindow<false> W(g, start, ncells, x, y, z, radius);
+	const int total = W.total;
 	auto inside = [&](int j) { return abs(S.x[j] - x) <= radius && abs(S.y[j] - y) <= radius && abs(S.z[j] - z) <= radius; };
 
 	// walk 1: the neighbour count and the lowest index among them
 	int n = 0, first = 0x7fffffff;
 	for (int t = lane; t < total; t += 64) {
-		const int j = entry(t);
+		const int j = W.entry(t);
 		if (inside(j)) {
 			n++;
 			first = min(first, S.idx[j]);
@@ -251,7 +84,7 @@ __global__ __launch_bounds__(kThreads) void k_strain_fit(const int *__restrict__
 	// walk 2: S1 = sum d, S2 = sum d d^T, U = sum (u - u0), P[c][a] = sum (u_c - u0_c) d_a
 	double s1[3] = {0, 0, 0}, s2[6] = {0, 0, 0, 0, 0, 0}, U[3] = {0, 0, 0}, P[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
 	for (int t = lane; t < total; t += 64) {
-		const int j = entry(t);
+		const int j = W.entry(t);
 		if (!inside(j)) continue;
 		const double d[3] = {(double)(S.x[j] - x), (double)(S.y[j] - y), (double)(S.z[j] - z)};
 		const double a[3] = {S.u[j] - u0[0], S.v[j] - u0[1], S.w[j] - u0[2]};
@@ -306,7 +139,7 @@ __global__ __launch_bounds__(kThreads) void k_strain_fit(const int *__restrict__
 	// walk 3: the residual of the fitted plane
 	double rs = 0;
 	for (int t = lane; t < total; t += 64) {
-		const int j = entry(t);
+		const int j = W.entry(t);
 		if (!inside(j)) continue;
 		const double d[3] = {(double)(S.x[j] - x), (double)(S.y[j] - y), (double)(S.z[j] - z)};
 		const double uj[3] = {S.u[j], S.v[j], S.w[j]};
@@ -362,30 +195,9 @@ __global__ __launch_bounds__(kThreads) void k_strain_fit(const int *__restrict__
 int blocks_for(size_t n, int per) { return (int)((n + per - 1) / per); }
 }  // namespace
 
-size_t strain_scan_tiles(size_t n) { return (n + kScanTile - 1) / kScanTile; }
-
-void launch_strain_mark(const int *d_pts, const double *d_disp, const unsigned char *d_valid, int m, int *d_cell, int *d_box, hipStream_t st) {
-	hipLaunchKernelGGL(k_strain_mark, dim3(blocks_for(m, kThreads)), dim3(kThreads), 0, st, d_pts, d_disp, d_valid, m, d_cell, d_box);
-}
-
-hipError_t launch_strain_bin(const int *d_pts, const double *d_disp, int m, StrainGrid g, int *d_cell, int *d_cnt, int *d_start, int *d_tiles,
-                             int *d_slots, StrainSorted S, hipStream_t st) {
-	const int ncells = g.nx * g.ny * g.nz, n = ncells + 1, nt = (int)strain_scan_tiles(n);
-	const int bm = blocks_for(m, kThreads);
-	hipLaunchKernelGGL(k_strain_count, dim3(bm), dim3(kThreads), 0, st, d_pts, m, g, d_cell, d_cnt);
-	hipLaunchKernelGGL(k_strain_scan_tiles, dim3(nt), dim3(kThreads), 0, st, d_cnt, d_start, n, d_tiles);
-	hipLaunchKernelGGL(k_strain_scan_sums, dim3(1), dim3(kThreads), 0, st, d_tiles, nt);
-	hipLaunchKernelGGL(k_strain_scan_add, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, st, d_start, n, d_tiles);
-	const hipError_t e = hipMemsetAsync(d_cnt, 0, sizeof(int) * (size_t)ncells, st);  // the counts become the fill marks of the scatter
-	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(k_strain_scatter, dim3(bm), dim3(kThreads), 0, st, d_cell, m, d_start, d_cnt, d_slots);
-	hipLaunchKernelGGL(k_strain_place, dim3(bm), dim3(kThreads), 0, st, d_slots, d_cell, d_start, ncells, d_pts, d_disp, S);
-	return hipGetLastError();
-}
-
-void launch_strain_fit(const int *d_pts, const double *d_disp, int m, StrainGrid g, const int *d_start, StrainSorted S, int radius, int min_nb,
-                       int measure, sift3d_strain_result *d_out, hipStream_t st) {
-	hipLaunchKernelGGL(k_strain_fit, dim3(blocks_for(m, kWaves)), dim3(kThreads), 0, st, d_pts, d_disp, m, g, d_start, g.nx * g.ny * g.nz, S, radius,
+void launch_strain_fit(const int *d_pts, const double *d_disp, int m, const PoiIndex &ix, int radius, int min_nb, int measure,
+                       sift3d_strain_result *d_out, hipStream_t st) {
+	hipLaunchKernelGGL(k_strain_fit, dim3(blocks_for(m, kWaves)), dim3(kThreads), 0, st, d_pts, d_disp, m, ix.g, ix.start, ix.ncells, ix.S, radius,
 	                   min_nb, measure, d_out);
 }
 

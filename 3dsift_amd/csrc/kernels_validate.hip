@@ -1,6 +1,6 @@
 // kernels_validate.hip -- the normalised median test of the POIs' displacements (sift3d_validate_displacements, include/sift3d_hip.h,
-// which states the numerical contract).  No reference counterpart.  The neighbours come from the strain kernels' cell grid
-// (kernels_strain.hip: mark, bin), so a window is 9 contiguous runs of the sorted arrays.
+// which states the numerical contract).  No reference counterpart.  The neighbours come from the POI index
+// (kernels_poigrid.hip), so a window is 9 contiguous runs of the sorted arrays (poi_window.h).
 //   fold       per POI: the valid byte and the finiteness of its nine gradients in one byte, which mark then takes as the valid byte.
 //   test       one wave per POI (one wave per workgroup: the wave's LDS is its own and a barrier costs nothing).  The runs are walked
 //              as in k_strain_fit, lane l taking entries l, l + 64, ...; S.idx[j] skips the POI itself, reads the flag of the pass before
@@ -13,7 +13,7 @@
 //              there; the absolute deviations replace them in place for the MAD.
 //   walked     n > kCap: every round walks the runs again and forms the estimate anew; nothing is stored, so n has no bound.
 // For even n the upper middle value is the lower one if enough keys are <= it, else the smallest key above it: one more read.
-#include "sift3d_internal.h"
+#include "poi_window.h"
 
 #include <math.h>
 
@@ -24,14 +24,7 @@ typedef unsigned long long u64;
 
 constexpr int kFoldThreads = 256;
 constexpr int kCap = 1024;  // staged keys of a wave: 8 KB of LDS beside the 1 KB histogram
-constexpr int kCoordMax = 1 << 24;
 
-__device__ inline bool coord_ok(int v) { return v <= kCoordMax && v >= -kCoordMax; }
-__device__ inline int floor_div(int a, int s) { return a >= 0 ? a / s : -((-a + s - 1) / s); }
-__device__ inline int wave_isum(int x) {
-	for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-	return x;
-}
 __device__ inline u64 wave_min64(u64 x) {
 	for (int off = 32; off > 0; off >>= 1) {
 		const u64 y = __shfl_xor(x, off);
@@ -165,8 +158,8 @@ __device__ inline void write_record(sift3d_validate_result *o, const double *med
 }
 
 __global__ __launch_bounds__(64) void k_validate_test(const int *__restrict__ pts, const double *__restrict__ disp, const double *__restrict__ grad,
-                                                      const int *__restrict__ cell, int m, StrainGrid g, const int *__restrict__ start, int ncells,
-                                                      StrainSorted S, ValidateParams P, int pass, const unsigned char *__restrict__ fin,
+                                                      const int *__restrict__ cell, int m, PoiGrid g, const int *__restrict__ start, int ncells,
+                                                      PoiSorted S, ValidateParams P, int pass, const unsigned char *__restrict__ fin,
                                                       unsigned char *__restrict__ fout, int *__restrict__ pass_of,
                                                       sift3d_validate_result *__restrict__ out) {
 	__shared__ u64 keys[kCap];
@@ -188,34 +181,9 @@ __global__ __launch_bounds__(64) void k_validate_test(const int *__restrict__ pt
 		if (lane == 0) write_record(out + i, nullptr, nullptr, 0.0, 0, 2, 0, 0);
 		return;
 	}
-	// the cells the window touches, per axis (none where the window misses the grid), and the 9 runs: k_strain_fit's
 	const int radius = P.radius;
-	const int lox = max(floor_div(x - radius - g.x0, g.side), 0), hix = min(floor_div(x + radius - g.x0, g.side), g.nx - 1);
-	const int loy = max(floor_div(y - radius - g.y0, g.side), 0), hiy = min(floor_div(y + radius - g.y0, g.side), g.ny - 1);
-	const int loz = max(floor_div(z - radius - g.z0, g.side), 0), hiz = min(floor_div(z + radius - g.z0, g.side), g.nz - 1);
-	const int nc = start[ncells];
-	int rb[9], cum[10];
-	cum[0] = 0;
-#pragma unroll
-	for (int k = 0; k < 9; k++) {
-		const int zz = loz + k / 3, yy = loy + k % 3;
-		int b = 0, e = 0;
-		if (zz <= hiz && yy <= hiy && lox <= hix) {
-			const int row = (zz * g.ny + yy) * g.nx;
-			b = min(max(start[row + lox], 0), nc);
-			e = min(max(start[row + hix + 1], b), nc);
-		}
-		rb[k] = uniform(b);
-		cum[k + 1] = uniform(cum[k] + (e - b));
-	}
-	const int total = cum[9];
-	auto entry = [&](int t) {
-		int j = rb[0] + t;
-#pragma unroll
-		for (int k = 1; k < 9; k++)
-			if (t >= cum[k]) j = rb[k] + (t - cum[k]);
-		return j;
-	};
+	const PoiWindow<true> W(g, start, ncells, x, y, z, radius);
+	const int total = W.total;
 	// a neighbour of this launch: inside the window, not the POI itself, not flagged by the pass before
 	auto keep = [&](int j) {
 		if (!(abs(S.x[j] - x) <= radius && abs(S.y[j] - y) <= radius && abs(S.z[j] - z) <= radius)) return false;
@@ -234,7 +202,7 @@ __global__ __launch_bounds__(64) void k_validate_test(const int *__restrict__ pt
 	};
 
 	int n = 0;
-	for (int t = lane; t < total; t += 64) n += keep(entry(t)) ? 1 : 0;
+	for (int t = lane; t < total; t += 64) n += keep(W.entry(t)) ? 1 : 0;
 	n = uniform(wave_isum(n));
 	if (n < P.min_nb) {
 		if (lane == 0) {
@@ -256,7 +224,7 @@ __global__ __launch_bounds__(64) void k_validate_test(const int *__restrict__ pt
 				bool k = false;
 				u64 key = 0;
 				if (t < total) {
-					const int j = entry(t);
+					const int j = W.entry(t);
 					if (keep(j)) {
 						k = true;
 						key = key_of(estimate(j, c));
@@ -280,14 +248,14 @@ __global__ __launch_bounds__(64) void k_validate_test(const int *__restrict__ pt
 		} else {
 			auto walked = [&](auto f) {
 				for (int t = lane; t < total; t += 64) {
-					const int j = entry(t);
+					const int j = W.entry(t);
 					if (keep(j)) f(key_of(estimate(j, c)));
 				}
 			};
 			const double mc = median_of(walked, n, hist, lane);
 			auto deviations = [&](auto f) {
 				for (int t = lane; t < total; t += 64) {
-					const int j = entry(t);
+					const int j = W.entry(t);
 					if (keep(j)) f(key_of(fabs(estimate(j, c) - mc)));
 				}
 			};
@@ -323,11 +291,10 @@ void launch_validate_fold(const double *d_grad, const unsigned char *d_valid, in
 	hipLaunchKernelGGL(k_validate_fold, dim3(blocks_for(m, kFoldThreads)), dim3(kFoldThreads), 0, st, d_grad, d_valid, m, d_fold);
 }
 
-void launch_validate_test(const int *d_pts, const double *d_disp, const double *d_grad, const int *d_cell, int m, StrainGrid g,
-                          const int *d_start, StrainSorted S, ValidateParams P, int pass, const unsigned char *d_fin, unsigned char *d_fout,
-                          int *d_pass, sift3d_validate_result *d_out, hipStream_t st) {
-	hipLaunchKernelGGL(k_validate_test, dim3(m), dim3(64), 0, st, d_pts, d_disp, d_grad, d_cell, m, g, d_start, g.nx * g.ny * g.nz, S, P, pass,
-	                   d_fin, d_fout, d_pass, d_out);
+void launch_validate_test(const int *d_pts, const double *d_disp, const double *d_grad, int m, const PoiIndex &ix, ValidateParams P, int pass,
+                          const unsigned char *d_fin, unsigned char *d_fout, int *d_pass, sift3d_validate_result *d_out, hipStream_t st) {
+	hipLaunchKernelGGL(k_validate_test, dim3(m), dim3(64), 0, st, d_pts, d_disp, d_grad, ix.cell, m, ix.g, ix.start, ix.ncells, ix.S, P, pass, d_fin,
+	                   d_fout, d_pass, d_out);
 }
 
 }  // namespace s3d

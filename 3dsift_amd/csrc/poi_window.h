@@ -1,0 +1,64 @@
+// poi_window.h -- device code of the POI index (poi_grid.h): the coordinate bound, and the window of a POI as the kernels walk it.
+// The side of a cell is at least the window's half width, so a window touches at most 3 x 3 x 3 cells; cells consecutive in x are
+// consecutive in memory, so these are 9 contiguous runs of the sorted arrays, walked as one sequence.
+#pragma once
+#include "poi_grid.h"
+
+namespace s3d {
+
+constexpr int kCoordMax = 1 << 24;  // a POI with a coordinate beyond +-2^24 neither contributes nor gets a window
+
+__device__ inline bool coord_ok(int v) { return v <= kCoordMax && v >= -kCoordMax; }
+// floor(a / s), s > 0
+__device__ inline int floor_div(int a, int s) { return a >= 0 ? a / s : -((-a + s - 1) / s); }
+__device__ inline int wave_isum(int x) {
+	for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+	return x;
+}
+
+// The window of half width radius around (x, y, z), the same in every lane of the wave: rb[k] the first entry of run k, cum[k] the
+// entries of the runs before it, total those of all nine.  Pinned: the tables are stated wave-uniform (readfirstlane), which keeps
+// them in scalar registers.
+template <bool Pinned>
+struct PoiWindow {
+	int rb[9], cum[10], total;
+
+	__device__ PoiWindow(const PoiGrid &g, const int *__restrict__ start, int ncells, int x, int y, int z, int radius) {
+		// the cells the window touches, per axis (none where the window misses the grid)
+		const int lox = max(floor_div(x - radius - g.x0, g.side), 0), hix = min(floor_div(x + radius - g.x0, g.side), g.nx - 1);
+		const int loy = max(floor_div(y - radius - g.y0, g.side), 0), hiy = min(floor_div(y + radius - g.y0, g.side), g.ny - 1);
+		const int loz = max(floor_div(z - radius - g.z0, g.side), 0), hiz = min(floor_div(z + radius - g.z0, g.side), g.nz - 1);
+		const int nc = start[ncells];
+		cum[0] = 0;
+#pragma unroll
+		for (int k = 0; k < 9; k++) {
+			const int zz = loz + k / 3, yy = loy + k % 3;
+			int b = 0, e = 0;
+			if (zz <= hiz && yy <= hiy && lox <= hix) {
+				const int row = (zz * g.ny + yy) * g.nx;
+				b = min(max(start[row + lox], 0), nc);
+				e = min(max(start[row + hix + 1], b), nc);
+			}
+			rb[k] = pin(b);
+			cum[k + 1] = pin(cum[k] + (e - b));
+		}
+		total = cum[9];
+	}
+
+	// sequence position t in [0, total) -> its entry of the sorted arrays
+	__device__ int entry(int t) const {
+		int j = rb[0] + t;
+#pragma unroll
+		for (int k = 1; k < 9; k++)
+			if (t >= cum[k]) j = rb[k] + (t - cum[k]);
+		return j;
+	}
+
+private:
+	__device__ static int pin(int v) {
+		if constexpr (Pinned) v = __builtin_amdgcn_readfirstlane(v);
+		return v;
+	}
+};
+
+}  // namespace s3d

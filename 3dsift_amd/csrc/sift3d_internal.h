@@ -367,27 +367,15 @@ struct SubsetParams {  // the checked options
 // one workgroup per POI; d_out: m records
 void launch_subset_quality(IcgnVol R, const int *d_pts, int m, SubsetParams P, sift3d_subset_result *d_out, hipStream_t st);
 
+// ---- kernels_poigrid.hip: the POI index that the next two walk -- declared in poi_grid.h --------------------------------------------
+struct PoiIndex;
+
 // ---- kernels_strain.hip: strain fields from the POIs' displacements (sift3d_strain, include/sift3d_hip.h) ------------------------
-// the cell grid over the bounding box of the contributing POIs: cell (cx, cy, cz) = (q - origin) / side per axis, cx fastest
-struct StrainGrid {
-	int x0, y0, z0, side, nx, ny, nz;
-};
-// the contributing POIs in cell order, a cell's POIs in ascending index
-struct StrainSorted {
-	int *x, *y, *z, *idx;
-	double *u, *v, *w;
-};
-size_t strain_scan_tiles(size_t n);  // entries of the scan's tile scratch for n scanned values
-// d_cell: m ints (1 contributes, -1 does not); d_box: 6 ints preset to 0x7f7f7f7f -> min x, y, z and min -x, -y, -z of the contributing POIs
-void launch_strain_mark(const int *d_pts, const double *d_disp, const unsigned char *d_valid, int m, int *d_cell, int *d_box, hipStream_t st);
-// d_cnt (zeroed), d_start: cells + 1 ints; d_tiles: strain_scan_tiles(cells + 1) ints; d_slots: m ints; fills d_start and S
-hipError_t launch_strain_bin(const int *d_pts, const double *d_disp, int m, StrainGrid g, int *d_cell, int *d_cnt, int *d_start, int *d_tiles,
-                             int *d_slots, StrainSorted S, hipStream_t st);
-void launch_strain_fit(const int *d_pts, const double *d_disp, int m, StrainGrid g, const int *d_start, StrainSorted S, int radius, int min_nb,
-                       int measure, sift3d_strain_result *d_out, hipStream_t st);
+void launch_strain_fit(const int *d_pts, const double *d_disp, int m, const PoiIndex &ix, int radius, int min_nb, int measure,
+                       sift3d_strain_result *d_out, hipStream_t st);
 
 // ---- kernels_validate.hip: the normalised median test of the displacements (sift3d_validate_displacements, include/sift3d_hip.h) --
-// It runs on the strain kernels' cell grid: launch_strain_mark / launch_strain_bin with d_fold as the valid bytes.
+// It runs on an index built with d_fold as the valid bytes.
 struct ValidateParams {
 	int radius, min_nb;
 	double threshold, eps;
@@ -396,10 +384,9 @@ int validate_stage_capacity();  // neighbour counts up to this are selected in L
 // d_fold[i] = (d_valid null or d_valid[i]) and, with d_grad, nine finite gradients
 void launch_validate_fold(const double *d_grad, const unsigned char *d_valid, int m, unsigned char *d_fold, hipStream_t st);
 // pass > 0: one pass of the test -- reads the flags d_fin, writes d_fout (m bytes each) and the pass number of a new flag into d_pass;
-// pass 0: the report from the final flags d_fin and d_pass into d_out.  d_cell: what launch_strain_bin left (negative: no contributor)
-void launch_validate_test(const int *d_pts, const double *d_disp, const double *d_grad, const int *d_cell, int m, StrainGrid g,
-                          const int *d_start, StrainSorted S, ValidateParams P, int pass, const unsigned char *d_fin, unsigned char *d_fout,
-                          int *d_pass, sift3d_validate_result *d_out, hipStream_t st);
+// pass 0: the report from the final flags d_fin and d_pass into d_out
+void launch_validate_test(const int *d_pts, const double *d_disp, const double *d_grad, int m, const PoiIndex &ix, ValidateParams P, int pass,
+                          const unsigned char *d_fin, unsigned char *d_fout, int *d_pass, sift3d_validate_result *d_out, hipStream_t st);
 
 // code-object preload of the translation units whose kernels would otherwise be loaded by the first KpSiftAlgorithm of a process
 void preload_march_kernels();

@@ -180,7 +180,7 @@ def shift_disagreement(a, b, e):
 
 # ---- the cell grid -------------------------------------------------------------------------------------------------------------------
 def choose_grid(extent, radius):
-    """strain_choose_grid restated: (side, (nx, ny, nz)) for a box of the given extents (max - min per axis).  The side is the radius
+    """poi_choose_grid restated: (side, (nx, ny, nz)) for a box of the given extents (max - min per axis).  The side is the radius
     and grows by (side + 3) / 4 (integer division) until nx * ny and nx * ny * nz are at most 2^24"""
     side = int(radius)
     while True:

@@ -2,7 +2,7 @@
 restatement (tests/strain_ref.py) and exact rational arithmetic, before the case reaches a GPU (tests/test_gpu_strain_edges.py).  The
 windows at the pivot floor keep 5 % off it and get the status their exact pivot ratio rho asks for; the tilted ones print their measured
 error and bar; the restatement has the invariances the GPU test asks of the kernel; the restated cell grid keeps the caps, equals
-strain_choose_grid (a host program against call_state.h) and every planted block spans the cell borders it is planted across."""
+poi_choose_grid (a host program against poi_grid.h) and every planted block spans the cell borders it is planted across."""
 import os
 import shutil
 import subprocess
@@ -136,13 +136,13 @@ def test_grid_restatement():
 GRID_PROGRAM = r"""
 #include <stdio.h>
 #include <stdlib.h>
-#include "call_state.h"
+#include "poi_grid.h"
 int main(int argc, char **argv) {
 	for (int i = 1; i + 6 < argc; i += 7) {
 		int v[7];
 		for (int k = 0; k < 7; k++) v[k] = atoi(argv[i + k]);
 		const int box[6] = {v[0], v[1], v[2], -(v[0] + v[3]), -(v[1] + v[4]), -(v[2] + v[5])};
-		const s3d::StrainGrid g = s3d::strain_choose_grid(box, v[6]);
+		const s3d::PoiGrid g = s3d::poi_choose_grid(box, v[6]);
 		printf("%d %d %d %d %d %d %d\n", g.x0, g.y0, g.z0, g.side, g.nx, g.ny, g.nz);
 	}
 	return 0;
@@ -151,7 +151,7 @@ int main(int argc, char **argv) {
 
 
 def test_grid_restatement_equals_strain_choose_grid(tmp_path):
-    """call_state.h needs the HIP headers (no runtime: nothing of it is called or linked), so the program is built where they are"""
+    """poi_grid.h needs the HIP headers (no runtime: nothing of it is called or linked), so the program is built where they are"""
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     cxx = shutil.which("g++")
     if not cxx or not os.path.exists(os.path.join(rocm, "include", "hip", "hip_runtime.h")):
