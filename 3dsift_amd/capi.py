@@ -40,6 +40,8 @@ SYMBOLS = [
     "sift3d_default_detect_options", "sift3d_set_detect_options", "sift3d_get_detect_options", "sift3d_get_refined",
     # RANSAC affine fits of matched pairs, global and per point
     "sift3d_default_ransac_options", "sift3d_fit_affine", "sift3d_fit_affine_local",
+    # RANSAC rigid / similarity fits of the same pairs, and the rotation a fit holds
+    "sift3d_fit_rigid", "sift3d_fit_rigid_local", "sift3d_fit_rotation",
     # IC-GN displacement refinement (digital volume correlation)
     "sift3d_default_icgn_options", "sift3d_icgn_init_from_fits", "sift3d_icgn",
     # cubic B-spline interpolation of the target: the prefilter and the IC-GN mode on its coefficients
@@ -270,6 +272,11 @@ def lib():
                                         C.POINTER(C.c_double)]
         L.sift3d_fit_affine_local.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(RansacOptions), C.c_int,
                                               C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        L.sift3d_fit_rigid.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RansacOptions), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_double)]
+        L.sift3d_fit_rigid_local.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(RansacOptions),
+                                             C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        L.sift3d_fit_rotation.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sift3d_default_icgn_options.argtypes = [C.POINTER(IcgnOptions)]
         L.sift3d_default_icgn_options.restype = None
         L.sift3d_icgn_init_from_fits.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -588,26 +595,48 @@ def _fit_dict(f, m):
     return d
 
 
-def fit_affine(pairs, device=0, **opts):
-    """sift3d_fit_affine: RANSAC affine t = L r + b over all rows of pairs ((n, 6) float32: ref rx ry rz, tar rx ry rz; numpy or a
-    device tensor).  Returns the fit's fields (A and hyp as (3, 4) float64, scalars as Python numbers), the inlier mask (bool [n])
-    and the device seconds."""
+FIT_MODELS = {"rigid": 0, "similarity": 1}
+
+
+def _model_code(model):
+    """the model argument of sift3d_fit_rigid[_local] of a name; an int passes through (the library checks it)"""
+    if isinstance(model, (int, np.integer)):
+        return int(model)
+    if model not in FIT_MODELS:
+        raise ValueError(f"model {model!r}: one of {sorted(FIT_MODELS)} is needed")
+    return FIT_MODELS[model]
+
+
+def _fit_global(pairs, model, device, opts):
+    """the global fit of one model (None: affine)"""
     o = _ransac_options(opts)
     pp, n, keep, on_dev = _rows(pairs, 6, "pairs")
     out = np.zeros((), FIT_DTYPE)
     mask = np.zeros(max(n, 1), np.uint8)
     sec = C.c_double(0)
-    _check(lib().sift3d_fit_affine(pp, n, C.byref(o), on_dev, int(device), _p(out), _p(mask), C.byref(sec)))
+    tail = (C.byref(o), on_dev, int(device), _p(out), _p(mask), C.byref(sec))
+    _check(lib().sift3d_fit_affine(pp, n, *tail) if model is None else lib().sift3d_fit_rigid(pp, n, _model_code(model), *tail))
     d = {k: (v if k in ("A", "hyp") else v.item()) for k, v in _fit_dict(out, None).items()}
     d["mask"] = mask[:n].astype(bool)
     d["seconds"] = sec.value
     return d
 
 
-def fit_affine_local(pairs, points, k=32, radius=0.0, device=0, **opts):
-    """sift3d_fit_affine_local: one RANSAC affine per query point ((m, 3) reference coordinates) on its k nearest pairs (within radius
-    when radius > 0).  Returns per-point arrays (A, hyp: (m, 3, 4); status, counts, rms: (m,)), neighbours (m, k) int32 (-1 padded)
+def fit_affine(pairs, device=0, **opts):
+    """sift3d_fit_affine: RANSAC affine t = L r + b over all rows of pairs ((n, 6) float32: ref rx ry rz, tar rx ry rz; numpy or a
+    device tensor).  Returns the fit's fields (A and hyp as (3, 4) float64, scalars as Python numbers), the inlier mask (bool [n])
     and the device seconds."""
+    return _fit_global(pairs, None, device, opts)
+
+
+def fit_rigid(pairs, model="rigid", device=0, **opts):
+    """sift3d_fit_rigid: RANSAC rigid (t = R r + b) or similarity (t = s R r + b) fit over all rows of pairs; what fit_affine takes
+    and returns, with A = hyp = [s R | b].  Three pairs that are not collinear fix the fit, so coplanar pairs are fitted."""
+    return _fit_global(pairs, model, device, opts)
+
+
+def _fit_local(pairs, points, k, radius, model, device, opts):
+    """the local fits of one model (None: affine)"""
     o = _ransac_options(opts)
     pp, n, keep_p, dev_p = _rows(pairs, 6, "pairs")
     qp, m, keep_q, dev_q = _rows(points, 3, "points")
@@ -616,11 +645,43 @@ def fit_affine_local(pairs, points, k=32, radius=0.0, device=0, **opts):
     out = np.zeros(max(m, 1), FIT_DTYPE)
     nb = np.zeros((max(m, 1), max(int(k), 1)), np.int32)
     sec = C.c_double(0)
-    _check(lib().sift3d_fit_affine_local(pp, n, qp, m, int(k), float(radius), C.byref(o), dev_p, int(device), _p(out), _p(nb), C.byref(sec)))
+    head, tail = (pp, n, qp, m, int(k), float(radius)), (C.byref(o), dev_p, int(device), _p(out), _p(nb), C.byref(sec))
+    _check(lib().sift3d_fit_affine_local(*head, *tail) if model is None else lib().sift3d_fit_rigid_local(*head, _model_code(model), *tail))
     d = _fit_dict(out, m)
     d["neighbours"] = nb[:m].copy()
     d["seconds"] = sec.value
     return d
+
+
+def fit_affine_local(pairs, points, k=32, radius=0.0, device=0, **opts):
+    """sift3d_fit_affine_local: one RANSAC affine per query point ((m, 3) reference coordinates) on its k nearest pairs (within radius
+    when radius > 0).  Returns per-point arrays (A, hyp: (m, 3, 4); status, counts, rms: (m,)), neighbours (m, k) int32 (-1 padded)
+    and the device seconds."""
+    return _fit_local(pairs, points, k, radius, None, device, opts)
+
+
+def fit_rigid_local(pairs, points, k=16, radius=0.0, model="rigid", device=0, **opts):
+    """sift3d_fit_rigid_local: one RANSAC rigid or similarity fit per query point on its k nearest pairs, k in 3..64; what
+    fit_affine_local takes and returns.  icgn_init_from_fits takes the result as it takes an affine one."""
+    return _fit_local(pairs, points, k, radius, model, device, opts)
+
+
+def fit_rotation(fits):
+    """sift3d_fit_rotation (needs no GPU): the rotation each fit holds, from the dict fit_rigid / fit_rigid_local returns (A (3, 4) or
+    (m, 3, 4), status).  Returns quat ((m, 4): w, x, y, z with w >= 0), scale (m,) and angle_deg (m,) -- without the leading axis for
+    one fit; a failed fit gives NaN."""
+    A = np.asarray(fits["A"], np.float64)
+    single = A.ndim == 2
+    A = A.reshape(-1, 12)
+    m = len(A)
+    f = np.zeros(max(m, 1), FIT_DTYPE)
+    f["A"][:m] = A
+    f["status"][:m] = np.asarray(fits["status"]).reshape(-1)
+    quat, scale, angle = np.zeros((max(m, 1), 4)), np.zeros(max(m, 1)), np.zeros(max(m, 1))
+    _check(lib().sift3d_fit_rotation(_p(f), m, _p(quat), _p(scale), _p(angle)))
+    if single:
+        return {"quat": quat[0].copy(), "scale": float(scale[0]), "angle_deg": float(angle[0])}
+    return {"quat": quat[:m].copy(), "scale": scale[:m].copy(), "angle_deg": angle[:m].copy()}
 
 
 ICGN_OPTIONS = ("subset_radius", "max_iterations", "tolerance", "interpolation")

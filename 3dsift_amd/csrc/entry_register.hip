@@ -1,4 +1,6 @@
-// entry_register.hip -- C-ABI of the RANSAC affine fits (include/sift3d_hip.h: sift3d_fit_affine, sift3d_fit_affine_local).
+// entry_register.hip -- C-ABI of the RANSAC fits (include/sift3d_hip.h: sift3d_fit_affine[_local], sift3d_fit_rigid[_local],
+// sift3d_fit_rotation).  The affine and the rigid / similarity entries share one body each: they differ in the kernels launched
+// and in the candidates a fit needs (4 and 3).
 // No reference counterpart.  Call state, scratch layout, timing and the order of the checks: DESIGN 4.10 (call_state.h).
 #include "call_state.h"
 
@@ -8,7 +10,10 @@
 using namespace s3d;
 
 namespace {
-CallState g_ransac[kMaxDev];  // the global and the local fit share it
+CallState g_ransac[kMaxDev];  // the global and the local fits of every model share it
+constexpr int kAffine = -1;    // `model` of the bodies below: -1 affine, else the checked model argument of sift3d_fit_rigid (0, 1)
+
+int min_candidates(int model) { return model == kAffine ? 4 : 3; }
 
 // options (NULL: defaults) -> checked values; H = the hypotheses per problem
 bool take_options(const sift3d_ransac_options *o, bool local, int &H, double &tau2, double &min_det, int &refine, uint32_t &s) {
@@ -44,19 +49,20 @@ extern "C" void sift3d_default_ransac_options(sift3d_ransac_options *o) {
 	o->min_det = 1.0f;
 }
 
-extern "C" int sift3d_fit_affine(const float *pairs6, int n, const sift3d_ransac_options *o, int on_device, int device, sift3d_affine_fit *out,
-                                 unsigned char *inlier_mask, double *seconds) {
+namespace {
+int fit_global(const char *who, int model, const float *pairs6, int n, const sift3d_ransac_options *o, int on_device, int device,
+               sift3d_affine_fit *out, unsigned char *inlier_mask, double *seconds) {
 	int H, refine;
 	double tau2, min_det;
 	uint32_t s;
 	if (n < 0 || !out || (n > 0 && !pairs6) || !take_options(o, false, H, tau2, min_det, refine, s)) {
-		set_last_error("sift3d_fit_affine: bad argument");
+		set_last_error(who);
 		return SIFT3D_ERR_ARG;
 	}
 	if (seconds) *seconds = 0;
 	int rc = pick_device(device);
 	if (rc) return rc;
-	if (n < 4) {  // status 1 is a result: nothing to run
+	if (n < min_candidates(model)) {  // status 1 is a result: nothing to run
 		empty_fit(out, 1, n);
 		if (inlier_mask && n) memset(inlier_mask, 0, (size_t)n);
 		return SIFT3D_OK;
@@ -79,8 +85,12 @@ extern "C" int sift3d_fit_affine(const float *pairs6, int n, const sift3d_ransac
 		S3D_HIP_ST(st, hipMemcpyAsync(D + o_pairs, pairs6, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice, st));
 	}
 	S3D_HIP_ST(st, hipEventRecord(S.e0, st));
-	launch_ransac_global(d_pairs, n, H, s, tau2, min_det, refine, reinterpret_cast<double *>(D + o_hyp), reinterpret_cast<int *>(D + o_cnt),
-	                     reinterpret_cast<sift3d_affine_fit *>(D), reinterpret_cast<unsigned char *>(D + o_mask), st);
+	double *d_hyp = reinterpret_cast<double *>(D + o_hyp);
+	int *d_cnt = reinterpret_cast<int *>(D + o_cnt);
+	sift3d_affine_fit *d_fit = reinterpret_cast<sift3d_affine_fit *>(D);
+	unsigned char *d_mask = reinterpret_cast<unsigned char *>(D + o_mask);
+	if (model == kAffine) launch_ransac_global(d_pairs, n, H, s, tau2, min_det, refine, d_hyp, d_cnt, d_fit, d_mask, st);
+	else launch_rigid_global(d_pairs, n, H, s, tau2, min_det, model, refine, d_hyp, d_cnt, d_fit, d_mask, st);
 	S3D_HIP_ST(st, hipGetLastError());
 	S3D_HIP_ST(st, hipMemcpyAsync(P, D, inlier_mask ? o_mask + n : sizeof(sift3d_affine_fit), hipMemcpyDeviceToHost, st));
 	S3D_HIP_ST(st, hipEventRecord(S.e1, st));
@@ -90,14 +100,14 @@ extern "C" int sift3d_fit_affine(const float *pairs6, int n, const sift3d_ransac
 	return SIFT3D_OK;
 }
 
-extern "C" int sift3d_fit_affine_local(const float *pairs6, int n, const float *points3, int m, int k, float radius, const sift3d_ransac_options *o,
-                                       int on_device, int device, sift3d_affine_fit *out, int *neighbours, double *seconds) {
+int fit_local(const char *who, int model, const float *pairs6, int n, const float *points3, int m, int k, float radius,
+              const sift3d_ransac_options *o, int on_device, int device, sift3d_affine_fit *out, int *neighbours, double *seconds) {
 	int H, refine;
 	double tau2, min_det;
 	uint32_t s;
-	if (n < 0 || m < 0 || k < 4 || k > 64 || !std::isfinite(radius) || (n > 0 && !pairs6) || (m > 0 && (!points3 || !out)) ||
-	    !take_options(o, true, H, tau2, min_det, refine, s)) {
-		set_last_error("sift3d_fit_affine_local: bad argument");
+	if (n < 0 || m < 0 || k < min_candidates(model) || k > 64 || !std::isfinite(radius) || (n > 0 && !pairs6) ||
+	    (m > 0 && (!points3 || !out)) || !take_options(o, true, H, tau2, min_det, refine, s)) {
+		set_last_error(who);
 		return SIFT3D_ERR_ARG;
 	}
 	if (seconds) *seconds = 0;
@@ -126,13 +136,84 @@ extern "C" int sift3d_fit_affine_local(const float *pairs6, int n, const float *
 	}
 	const float r2 = radius > 0.f ? radius * radius : -1.f;  // (-1: no limit, whatever radius^2 rounds to)
 	S3D_HIP_ST(st, hipEventRecord(S.e0, st));
-	launch_ransac_local(d_pairs, n, d_pts, m, k, r2, H, s, tau2, min_det, refine, reinterpret_cast<sift3d_affine_fit *>(D),
-	                    neighbours ? reinterpret_cast<int *>(D + o_nb) : nullptr, st);
+	sift3d_affine_fit *d_fit = reinterpret_cast<sift3d_affine_fit *>(D);
+	int *d_nb = neighbours ? reinterpret_cast<int *>(D + o_nb) : nullptr;
+	if (model == kAffine) launch_ransac_local(d_pairs, n, d_pts, m, k, r2, H, s, tau2, min_det, refine, d_fit, d_nb, st);
+	else launch_rigid_local(d_pairs, n, d_pts, m, k, r2, H, s, tau2, min_det, model, refine, d_fit, d_nb, st);
 	S3D_HIP_ST(st, hipGetLastError());
 	S3D_HIP_ST(st, hipMemcpyAsync(P, D, o_nb + nb_bytes, hipMemcpyDeviceToHost, st));
 	S3D_HIP_ST(st, hipEventRecord(S.e1, st));
 	if ((rc = S.finish(seconds))) return rc;
 	memcpy(out, P, fit_bytes);
 	if (neighbours) memcpy(neighbours, P + o_nb, nb_bytes);
+	return SIFT3D_OK;
+}
+}  // namespace
+
+extern "C" int sift3d_fit_affine(const float *pairs6, int n, const sift3d_ransac_options *o, int on_device, int device, sift3d_affine_fit *out,
+                                 unsigned char *inlier_mask, double *seconds) {
+	return fit_global("sift3d_fit_affine: bad argument", kAffine, pairs6, n, o, on_device, device, out, inlier_mask, seconds);
+}
+
+extern "C" int sift3d_fit_affine_local(const float *pairs6, int n, const float *points3, int m, int k, float radius, const sift3d_ransac_options *o,
+                                       int on_device, int device, sift3d_affine_fit *out, int *neighbours, double *seconds) {
+	return fit_local("sift3d_fit_affine_local: bad argument", kAffine, pairs6, n, points3, m, k, radius, o, on_device, device, out, neighbours,
+	                 seconds);
+}
+
+extern "C" int sift3d_fit_rigid(const float *pairs6, int n, int model, const sift3d_ransac_options *o, int on_device, int device,
+                                sift3d_affine_fit *out, unsigned char *inlier_mask, double *seconds) {
+	if (model != 0 && model != 1) {
+		set_last_error("sift3d_fit_rigid: bad argument");
+		return SIFT3D_ERR_ARG;
+	}
+	return fit_global("sift3d_fit_rigid: bad argument", model, pairs6, n, o, on_device, device, out, inlier_mask, seconds);
+}
+
+extern "C" int sift3d_fit_rigid_local(const float *pairs6, int n, const float *points3, int m, int k, float radius, int model,
+                                      const sift3d_ransac_options *o, int on_device, int device, sift3d_affine_fit *out, int *neighbours,
+                                      double *seconds) {
+	if (model != 0 && model != 1) {
+		set_last_error("sift3d_fit_rigid_local: bad argument");
+		return SIFT3D_ERR_ARG;
+	}
+	return fit_local("sift3d_fit_rigid_local: bad argument", model, pairs6, n, points3, m, k, radius, o, on_device, device, out,
+	                 neighbours, seconds);
+}
+
+extern "C" int sift3d_fit_rotation(const sift3d_affine_fit *fits, int m, double *quat4, double *scale, double *angle_deg) {
+	if (m < 0 || (m > 0 && (!fits || !quat4 || !scale || !angle_deg))) {
+		set_last_error("sift3d_fit_rotation: bad argument");
+		return SIFT3D_ERR_ARG;
+	}
+	for (int p = 0; p < m; p++) {
+		double *q = quat4 + 4 * (size_t)p;
+		if (fits[p].status != 0) {
+			q[0] = q[1] = q[2] = q[3] = scale[p] = angle_deg[p] = NAN;
+			continue;
+		}
+		const double *A = fits[p].A;
+		const double det = (A[0] * (A[5] * A[10] - A[6] * A[9]) - A[1] * (A[4] * A[10] - A[6] * A[8])) + A[2] * (A[4] * A[9] - A[5] * A[8]);
+		const double s = cbrt(det);
+		double R[3][3];
+		for (int i = 0; i < 3; i++)
+			for (int j = 0; j < 3; j++) R[i][j] = A[4 * i + j] / s;
+		// Shepperd: the branch of the largest of (trace, R00, R11, R22) keeps the divisor away from zero
+		const double tr = (R[0][0] + R[1][1]) + R[2][2];
+		double w, x, y, z;
+		if (tr >= R[0][0] && tr >= R[1][1] && tr >= R[2][2]) {
+			w = 1.0 + tr; x = R[2][1] - R[1][2]; y = R[0][2] - R[2][0]; z = R[1][0] - R[0][1];
+		} else if (R[0][0] >= R[1][1] && R[0][0] >= R[2][2]) {
+			w = R[2][1] - R[1][2]; x = (1.0 + R[0][0]) - (R[1][1] + R[2][2]); y = R[0][1] + R[1][0]; z = R[0][2] + R[2][0];
+		} else if (R[1][1] >= R[2][2]) {
+			w = R[0][2] - R[2][0]; x = R[0][1] + R[1][0]; y = (1.0 + R[1][1]) - (R[0][0] + R[2][2]); z = R[1][2] + R[2][1];
+		} else {
+			w = R[1][0] - R[0][1]; x = R[0][2] + R[2][0]; y = R[1][2] + R[2][1]; z = (1.0 + R[2][2]) - (R[0][0] + R[1][1]);
+		}
+		const double nq = (w < 0.0 ? -1.0 : 1.0) * sqrt((w * w + x * x) + (y * y + z * z));
+		q[0] = w / nq; q[1] = x / nq; q[2] = y / nq; q[3] = z / nq;
+		scale[p] = s;
+		angle_deg[p] = 2.0 * atan2(sqrt((q[1] * q[1] + q[2] * q[2]) + q[3] * q[3]), q[0]) * (180.0 / M_PI);
+	}
 	return SIFT3D_OK;
 }

@@ -1,7 +1,8 @@
 // kernels_ransac.hip -- RANSAC affine fits of matched pairs (sift3d_fit_affine / sift3d_fit_affine_local, include/sift3d_hip.h).
 // No reference counterpart.  The numerical contract (sampler, minimal solve, scoring, refit, neighbour order) is written out in the
 // header; every fp64 expression here follows it term by term (the library builds with -ffp-contract=off, and the pragma of
-// sift3d_internal.h keeps FMA contraction off in this unit as well).
+// sift3d_internal.h keeps FMA contraction off in this unit as well).  The sampler, the scoring expression, the running top-k and the
+// record writer are shared with the rigid fits (kernels_rigid.hip) through ransac_kit.h.
 //
 // Global fit, three launches on one stream:
 //   k_ransac_hyp     one thread per hypothesis: 4 draws + the minimal solve; 12 doubles SoA, count = 0 (-1: degenerate)
@@ -15,6 +16,8 @@
 // one per lane (candidates read by readlane: scalar broadcast), and the refit with wave sums.
 #include "sift3d_internal.h"
 
+#include "ransac_kit.h"
+
 #include <float.h>
 #include <limits.h>
 
@@ -23,33 +26,7 @@
 namespace s3d {
 namespace {
 
-constexpr int kChunk = 256;     // pairs per scoring workgroup
-constexpr int kRefitThreads = 256;
-
-__host__ __device__ inline uint32_t fmix32(uint32_t x) {
-	x ^= x >> 16;
-	x *= 0x85ebca6bu;
-	x ^= x >> 13;
-	x *= 0xc2b2ae35u;
-	x ^= x >> 16;
-	return x;
-}
-
-// the four candidate positions of hypothesis h; sp = fmix32(s + p)
-__device__ inline void draw4(uint32_t sp, uint32_t h, uint32_t c, uint32_t idx[4]) {
-#pragma unroll
-	for (int j = 0; j < 4; j++) {
-		const uint32_t u = fmix32(sp + (4u * h + (uint32_t)j));
-		uint32_t i = (uint32_t)(((uint64_t)u * c) >> 32);
-		for (;;) {
-			bool dup = false;
-			for (int q = 0; q < j; q++) dup |= (idx[q] == i);
-			if (!dup) break;
-			i = (i + 1 == c) ? 0u : i + 1;
-		}
-		idx[j] = i;
-	}
-}
+using namespace ransac_kit;
 
 // cofactor inverse of M; false when |det| >= min_det does not hold (NaN included)
 __device__ inline bool inv3(const double M[3][3], double min_det, double inv[3][3]) {
@@ -95,19 +72,6 @@ __device__ inline bool solve_minimal(const double P[4][3], const double T[4][3],
 	return true;
 }
 
-__device__ inline double resid2(const double A[12], double rx, double ry, double rz, double tx, double ty, double tz) {
-	const double e0 = (((A[0] * rx + A[1] * ry) + A[2] * rz) + A[3]) - tx;
-	const double e1 = (((A[4] * rx + A[5] * ry) + A[6] * rz) + A[7]) - ty;
-	const double e2 = (((A[8] * rx + A[9] * ry) + A[10] * rz) + A[11]) - tz;
-	return (e0 * e0 + e1 * e1) + e2 * e2;
-}
-
-__device__ inline double wave_sum(double x) {
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-	return x;  // (a + b == b + a: every lane ends with the same bits)
-}
-
 // The refit rounds of the contract on the inliers of A (hyp on entry).  each(f) calls f(r, t) for the calling thread's candidates;
 // sum(v) replaces each element of the array v by its total over all threads of the problem, the same bits in every thread.
 template <class Each, class Sum>
@@ -150,18 +114,6 @@ __device__ void refit(const Each &each, const Sum &sum, double A[12], double tau
 	}
 }
 
-__device__ inline void write_fit(sift3d_affine_fit *o, const double A[12], const double hyp[12], int status, int cand, int best_h, int best_count,
-                                 int inliers, double sumd2) {
-	for (int i = 0; i < 12; i++) { o->A[i] = A[i]; o->hyp[i] = hyp[i]; }
-	o->status = status;
-	o->candidates = cand;
-	o->best_hypothesis = best_h;
-	o->best_count = best_count;
-	o->inliers = inliers;
-	o->rms = inliers > 0 ? (float)sqrt(sumd2 / (double)inliers) : 0.f;
-	o->reserved[0] = o->reserved[1] = 0;
-}
-
 // ---- global fit -----------------------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void k_ransac_hyp(const float *__restrict__ pairs, int n, int H, uint32_t s, double min_det,
@@ -169,7 +121,7 @@ __global__ __launch_bounds__(256) void k_ransac_hyp(const float *__restrict__ pa
 	const int h = blockIdx.x * 256 + threadIdx.x;
 	if (h >= H) return;
 	uint32_t idx[4];
-	draw4(fmix32(s + 0u), (uint32_t)h, (uint32_t)n, idx);
+	draw<4>(fmix32(s + 0u), (uint32_t)h, (uint32_t)n, idx);
 	double P[4][3], T[4][3], A[12];
 	for (int j = 0; j < 4; j++)
 		for (int i = 0; i < 3; i++) { P[j][i] = pairs[(size_t)idx[j] * 6 + i]; T[j][i] = pairs[(size_t)idx[j] * 6 + 3 + i]; }
@@ -208,17 +160,7 @@ __global__ __launch_bounds__(kRefitThreads) void k_ransac_refit(const float *__r
 	__shared__ double red[NW][16];
 	__shared__ unsigned long long kred[NW];
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-	// best: the most inliers, ties to the smallest h; key 0 = degenerate
-	unsigned long long key = 0;
-	for (int h = tid; h < H; h += kRefitThreads) {
-		const int c = count[h];
-		if (c >= 0) key = max(key, ((unsigned long long)(unsigned)c << 32) | (0xFFFFFFFFu - (unsigned)h));
-	}
-	for (int off = 32; off > 0; off >>= 1) key = max(key, (unsigned long long)__shfl_xor(key, off));
-	if (lane == 0) kred[wv] = key;
-	__syncthreads();
-	key = 0;
-	for (int w = 0; w < NW; w++) key = max(key, kred[w]);
+	const unsigned long long key = best_key(count, H, kred);  // the most inliers, ties to the smallest h; 0 = degenerate
 	if (key == 0) {
 		const double Z[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 		if (tid == 0) write_fit(out, Z, Z, 2, n, -1, 0, 0, 0.0);
@@ -265,8 +207,6 @@ __global__ __launch_bounds__(kRefitThreads) void k_ransac_refit(const float *__r
 
 // ---- local fits -----------------------------------------------------------------------------------------------------------------
 
-__device__ inline float readlane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-
 __global__ __launch_bounds__(256) void k_ransac_local(const float *__restrict__ pairs, int n, const float *__restrict__ pts, int m, int k,
                                                       float r2 /* radius^2 (fp32), < 0: no limit */, int H, uint32_t s, double tau2, double min_det,
                                                       int refine, sift3d_affine_fit *__restrict__ out, int *__restrict__ nbrs /* may be null */) {
@@ -274,39 +214,10 @@ __global__ __launch_bounds__(256) void k_ransac_local(const float *__restrict__ 
 	if (p >= m) return;  // (whole waves: no workgroup barrier below)
 	const float qx = pts[(size_t)p * 3], qy = pts[(size_t)p * 3 + 1], qz = pts[(size_t)p * 3 + 2];
 
-	// phase 1: lane l < k holds entry l of the sorted list (d2, i); empty entries are (+inf, INT_MAX)
-	float myd = __int_as_float(0x7f800000);
-	int myi = INT_MAX, c = 0;
-	for (int base = 0; base < n; base += 64) {
-		const int i = base + lane;
-		float d2 = 0.f;
-		bool ok = false;
-		if (i < n) {
-			const float *pp = pairs + (size_t)i * 6;
-			const float dx = pp[0] - qx, dy = pp[1] - qy, dz = pp[2] - qz;
-			d2 = (dx * dx + dy * dy) + dz * dz;
-			ok = (d2 == d2) && (r2 < 0.f || d2 <= r2);
-		}
-		const float kd = __shfl(myd, k - 1);
-		const int ki = __shfl(myi, k - 1);
-		unsigned long long b = __ballot(ok && (d2 < kd || (d2 == kd && i < ki)));
-		while (b) {
-			const int src = __ffsll((long long)b) - 1;
-			b &= b - 1;
-			const float nd = readlane_f(d2, src);
-			const int ni = __builtin_amdgcn_readlane(i, src);
-			const float cd = __shfl(myd, k - 1);
-			const int ci = __shfl(myi, k - 1);
-			if (!(nd < cd || (nd == cd && ni < ci))) continue;  // (the list filled up or tightened since the ballot)
-			const bool less = lane < k && (myd < nd || (myd == nd && myi < ni));
-			const int pos = __popcll(__ballot(less));
-			const float pd = __shfl_up(myd, 1);
-			const int pi = __shfl_up(myi, 1);
-			if (lane > pos) { myd = pd; myi = pi; }
-			else if (lane == pos) { myd = nd; myi = ni; }
-			c = min(c + 1, k);
-		}
-	}
+	// phase 1: lane l < k holds entry l of the sorted list (d2, i)
+	float myd;
+	int myi;
+	const int c = topk_neighbours(pairs, n, qx, qy, qz, k, r2, lane, myd, myi);
 	if (nbrs && lane < k) nbrs[(size_t)p * k + lane] = lane < c ? myi : -1;
 	const double Z[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 	if (c < 4) {
@@ -322,7 +233,7 @@ __global__ __launch_bounds__(256) void k_ransac_local(const float *__restrict__ 
 	for (int hb = 0; hb < H; hb += 64) {
 		const int h = hb + lane;
 		uint32_t idx[4];
-		draw4(sp, (uint32_t)h, (uint32_t)c, idx);
+		draw<4>(sp, (uint32_t)h, (uint32_t)c, idx);
 		double P[4][3], T[4][3], A[12];
 		for (int j = 0; j < 4; j++)
 			for (int i = 0; i < 3; i++) { P[j][i] = __shfl(cr[i], (int)idx[j]); T[j][i] = __shfl(cr[3 + i], (int)idx[j]); }
@@ -343,7 +254,7 @@ __global__ __launch_bounds__(256) void k_ransac_local(const float *__restrict__ 
 	double A[12], A0[12];
 	{
 		uint32_t idx[4];
-		draw4(sp, (uint32_t)bh, (uint32_t)c, idx);
+		draw<4>(sp, (uint32_t)bh, (uint32_t)c, idx);
 		double P[4][3], T[4][3];
 		for (int j = 0; j < 4; j++)
 			for (int i = 0; i < 3; i++) { P[j][i] = __shfl(cr[i], (int)idx[j]); T[j][i] = __shfl(cr[3 + i], (int)idx[j]); }
@@ -371,10 +282,14 @@ __global__ __launch_bounds__(256) void k_ransac_local(const float *__restrict__ 
 
 uint32_t ransac_seed(uint32_t seed) { return fmix32(seed ^ 0x9E3779B9u); }
 
+void launch_ransac_score(const float *d_pairs, int n, int H, const double *d_hyp, double tau2, int *d_count, hipStream_t st) {
+	hipLaunchKernelGGL(k_ransac_score, dim3((H + 255) / 256, std::min((n + kChunk - 1) / kChunk, 65535)), dim3(256), 0, st, d_pairs, n, H, d_hyp, tau2, d_count);
+}
+
 void launch_ransac_global(const float *d_pairs, int n, int H, uint32_t s, double tau2, double min_det, int refine, double *d_hyp, int *d_count,
                           sift3d_affine_fit *d_out, unsigned char *d_mask, hipStream_t st) {
 	hipLaunchKernelGGL(k_ransac_hyp, dim3((H + 255) / 256), dim3(256), 0, st, d_pairs, n, H, s, min_det, d_hyp, d_count);
-	hipLaunchKernelGGL(k_ransac_score, dim3((H + 255) / 256, std::min((n + kChunk - 1) / kChunk, 65535)), dim3(256), 0, st, d_pairs, n, H, d_hyp, tau2, d_count);
+	launch_ransac_score(d_pairs, n, H, d_hyp, tau2, d_count, st);
 	hipLaunchKernelGGL(k_ransac_refit, dim3(1), dim3(kRefitThreads), 0, st, d_pairs, n, H, d_hyp, d_count, tau2, min_det, refine, d_out, d_mask);
 }
 

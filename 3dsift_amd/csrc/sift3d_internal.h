@@ -328,6 +328,15 @@ void launch_ransac_global(const float *d_pairs, int n, int H, uint32_t s, double
 // d_out: m records; d_nbrs: m * k ints or null
 void launch_ransac_local(const float *d_pairs, int n, const float *d_pts, int m, int k, float r2, int H, uint32_t s, double tau2, double min_det,
                          int refine, sift3d_affine_fit *d_out, int *d_nbrs, hipStream_t st);
+// the scoring launch alone: adds each live hypothesis's inliers to d_count (the rigid fits score with it too)
+void launch_ransac_score(const float *d_pairs, int n, int H, const double *d_hyp, double tau2, int *d_count, hipStream_t st);
+
+// ---- kernels_rigid.hip: RANSAC rigid / similarity fits (sift3d_fit_rigid / sift3d_fit_rigid_local, include/sift3d_hip.h) --------
+// model: 0 rigid, 1 similarity; the other arguments as for the affine launches above
+void launch_rigid_global(const float *d_pairs, int n, int H, uint32_t s, double tau2, double min_det, int model, int refine, double *d_hyp,
+                         int *d_count, sift3d_affine_fit *d_out, unsigned char *d_mask, hipStream_t st);
+void launch_rigid_local(const float *d_pairs, int n, const float *d_pts, int m, int k, float r2, int H, uint32_t s, double tau2, double min_det,
+                        int model, int refine, sift3d_affine_fit *d_out, int *d_nbrs, hipStream_t st);
 
 // ---- kernels_icgn.hip: IC-GN displacement refinement (sift3d_icgn, include/sift3d_hip.h) ---------------------------------------
 // a volume on the device: fp32 [z][y][x]

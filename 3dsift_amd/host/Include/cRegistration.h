@@ -1,6 +1,6 @@
 // cRegistration.h -- RANSAC affine fits of matched keypoints, subset screening, ZNCC integer search, IC-GN displacement refinement, validation and strain fields (no
 // reference counterpart): the steps after enhancedMatch, on the GPU.
-// Over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_subset_quality / sift3d_zncc_search / sift3d_icgn / sift3d_validate_displacements / sift3d_strain (include/sift3d_hip.h, which states the numerical contracts).  Both functions take
+// Over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_fit_rigid / sift3d_fit_rigid_local / sift3d_subset_quality / sift3d_zncc_search / sift3d_icgn / sift3d_validate_displacements / sift3d_strain (include/sift3d_hip.h, which states the numerical contracts).  Both functions take
 // exactly the two std::vector<Cvec> that muBruteMatcher::enhancedMatch fills (refMatch[i] <-> tarMatch[i]).
 #ifndef S3D_HOST_CREGISTRATION_H
 #define S3D_HOST_CREGISTRATION_H
@@ -43,6 +43,19 @@ SIFT_LIBRARY_API AffineFit EstimateAffine(const std::vector<Cvec> &ref, const st
 // one fit per point (reference coordinates) on its k nearest pairs by reference position (within radius when radius > 0), k in 4..64
 SIFT_LIBRARY_API std::vector<AffineFit> EstimateLocalAffine(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, const std::vector<Cvec> &points,
                                                             int k = 32, float radius = 0, const RansacOptions &opts = RansacOptions());
+
+// Rigid (t = R r + b) and similarity (t = s R r + b) fits over sift3d_fit_rigid / sift3d_fit_rigid_local: the same pairs, options and
+// record as the affine fits, with A = hyp = [s R | b].  A fit needs 3 pairs that are not collinear (status 1: fewer than 3), so coplanar
+// pairs are fitted; k in 3..64.  RefineDisplacements takes these fits as its init like affine ones.
+enum FitModel { Rigid = 0, Similarity = 1 };
+SIFT_LIBRARY_API AffineFit EstimateRigid(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, FitModel model = Rigid,
+                                         const RansacOptions &opts = RansacOptions(), std::vector<int> *inlierMask = nullptr);
+SIFT_LIBRARY_API std::vector<AffineFit> EstimateLocalRigid(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, const std::vector<Cvec> &points,
+                                                           FitModel model = Rigid, int k = 16, float radius = 0,
+                                                           const RansacOptions &opts = RansacOptions());
+// the rotation a fit holds (sift3d_fit_rotation, host only): unit quaternion (w, x, y, z; w >= 0), scale and angle in degrees; NaN and
+// false for a fit whose status is not 0.  scale and angleDeg may be null.
+SIFT_LIBRARY_API bool FitRotation(const AffineFit &fit, double quat[4], double *scale = nullptr, double *angleDeg = nullptr);
 
 struct SIFT_LIBRARY_API IcgnOptions {
 	int subset_radius = 16;   // r: the subset is (2r+1)^3 voxels, 2..32

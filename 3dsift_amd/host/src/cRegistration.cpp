@@ -74,7 +74,10 @@ void AffineFit::Gradient(double G[9]) const {
 		for (int j = 0; j < 3; j++) G[3 * i + j] = A[4 * i + j] - (i == j ? 1.0 : 0.0);
 }
 
-AffineFit EstimateAffine(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, const RansacOptions &opts, std::vector<int> *inlierMask) {
+namespace {
+// the global fit of one model (-1: affine)
+AffineFit estimate_global(const char *who, int model, const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, const RansacOptions &opts,
+                          std::vector<int> *inlierMask) {
 	AffineFit a;
 	const size_t n = ref.size() < tar.size() ? ref.size() : tar.size();
 	const std::vector<float> p = pairs6(ref, tar, n);
@@ -82,9 +85,10 @@ AffineFit EstimateAffine(const std::vector<Cvec> &ref, const std::vector<Cvec> &
 	std::vector<unsigned char> mask(n ? n : 1);
 	sift3d_affine_fit f;
 	double sec = 0;
-	const int rc = sift3d_fit_affine(p.data(), (int)n, &o, 0, GetDevice(), &f, mask.data(), &sec);
+	const int rc = model < 0 ? sift3d_fit_affine(p.data(), (int)n, &o, 0, GetDevice(), &f, mask.data(), &sec)
+	                         : sift3d_fit_rigid(p.data(), (int)n, model, &o, 0, GetDevice(), &f, mask.data(), &sec);
 	if (rc != SIFT3D_OK) {
-		fprintf(stderr, "[3dsift_amd] EstimateAffine: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		fprintf(stderr, "[3dsift_amd] %s: %s (%s)\n", who, sift3d_error_string(rc), sift3d_last_error());
 		if (inlierMask) inlierMask->assign(n, 0);
 		return a;
 	}
@@ -93,8 +97,9 @@ AffineFit EstimateAffine(const std::vector<Cvec> &ref, const std::vector<Cvec> &
 	return a;
 }
 
-std::vector<AffineFit> EstimateLocalAffine(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, const std::vector<Cvec> &points, int k, float radius,
-                                           const RansacOptions &opts) {
+// the local fits of one model (-1: affine)
+std::vector<AffineFit> estimate_local(const char *who, int model, const std::vector<Cvec> &ref, const std::vector<Cvec> &tar,
+                                      const std::vector<Cvec> &points, int k, float radius, const RansacOptions &opts) {
 	const size_t n = ref.size() < tar.size() ? ref.size() : tar.size(), m = points.size();
 	std::vector<AffineFit> res(m);
 	const std::vector<float> p = pairs6(ref, tar, n);
@@ -103,13 +108,47 @@ std::vector<AffineFit> EstimateLocalAffine(const std::vector<Cvec> &ref, const s
 	const sift3d_ransac_options o = to_c(opts);
 	std::vector<sift3d_affine_fit> f(m ? m : 1);
 	double sec = 0;
-	const int rc = sift3d_fit_affine_local(p.data(), (int)n, q.data(), (int)m, k, radius, &o, 0, GetDevice(), f.data(), nullptr, &sec);
+	const int rc = model < 0 ? sift3d_fit_affine_local(p.data(), (int)n, q.data(), (int)m, k, radius, &o, 0, GetDevice(), f.data(), nullptr, &sec)
+	                         : sift3d_fit_rigid_local(p.data(), (int)n, q.data(), (int)m, k, radius, model, &o, 0, GetDevice(), f.data(), nullptr, &sec);
 	if (rc != SIFT3D_OK) {
-		fprintf(stderr, "[3dsift_amd] EstimateLocalAffine: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		fprintf(stderr, "[3dsift_amd] %s: %s (%s)\n", who, sift3d_error_string(rc), sift3d_last_error());
 		return res;
 	}
 	for (size_t i = 0; i < m; i++) from_c(f[i], sec, res[i]);
 	return res;
+}
+}  // namespace
+
+AffineFit EstimateAffine(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, const RansacOptions &opts, std::vector<int> *inlierMask) {
+	return estimate_global("EstimateAffine", -1, ref, tar, opts, inlierMask);
+}
+
+std::vector<AffineFit> EstimateLocalAffine(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, const std::vector<Cvec> &points, int k, float radius,
+                                           const RansacOptions &opts) {
+	return estimate_local("EstimateLocalAffine", -1, ref, tar, points, k, radius, opts);
+}
+
+AffineFit EstimateRigid(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, FitModel model, const RansacOptions &opts,
+                        std::vector<int> *inlierMask) {
+	return estimate_global("EstimateRigid", (int)model, ref, tar, opts, inlierMask);
+}
+
+std::vector<AffineFit> EstimateLocalRigid(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, const std::vector<Cvec> &points, FitModel model,
+                                          int k, float radius, const RansacOptions &opts) {
+	return estimate_local("EstimateLocalRigid", (int)model, ref, tar, points, k, radius, opts);
+}
+
+bool FitRotation(const AffineFit &fit, double quat[4], double *scale, double *angleDeg) {
+	sift3d_affine_fit f;
+	memset(&f, 0, sizeof(f));
+	memcpy(f.A, fit.A, sizeof(f.A));
+	f.status = fit.status;
+	double s = 0, a = 0;
+	const int rc = sift3d_fit_rotation(&f, 1, quat, &s, &a);
+	if (rc != SIFT3D_OK) fprintf(stderr, "[3dsift_amd] FitRotation: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+	if (scale) *scale = s;
+	if (angleDeg) *angleDeg = a;
+	return rc == SIFT3D_OK && fit.status == 0;
 }
 
 Cvec IcgnResult::Displacement() const { return Cvec((float)p[0], (float)p[4], (float)p[8]); }

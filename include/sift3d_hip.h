@@ -501,7 +501,7 @@ SIFT3D_STATIC_ASSERT(offsetof(sift3d_ransac_options, inlier_thresh) == 4 && offs
 typedef struct sift3d_affine_fit {
 	double A[12];          /* final transform, row-major 3x4: [L | b] */
 	double hyp[12];        /* the best hypothesis's minimal-sample transform (bit exact against the contract) */
-	int status;            /* 0 ok, 1 fewer than 4 candidates, 2 every hypothesis degenerate, 3 refit singular */
+	int status;            /* 0 ok, 1 fewer than 4 candidates (rigid fits: 3), 2 every hypothesis degenerate, 3 refit singular */
 	int candidates;        /* pairs the problem drew from (n, or the neighbours found) */
 	int best_hypothesis;   /* h of the best hypothesis, -1 with status 1 / 2 */
 	int best_count;        /* its inliers */
@@ -523,6 +523,57 @@ int sift3d_fit_affine(const float *pairs6, int n, const sift3d_ransac_options *o
 /* m local fits; out: m records; neighbours: m*k pair indices in candidate order, -1 padded, may be NULL */
 int sift3d_fit_affine_local(const float *pairs6, int n, const float *points3, int m, int k, float radius, const sift3d_ransac_options *o,
                             int on_device, int device, sift3d_affine_fit *out, int *neighbours, double *seconds);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * RANSAC rigid and similarity fits of matched keypoints (no reference counterpart; Rister et al. fit rigid transforms before affine
+ * ones; Horn, "Closed-form solution of absolute orientation using unit quaternions").  model 0: rigid, t = R r + b with R a proper
+ * rotation; model 1: similarity, t = s R r + b, s > 0.  Input, options, record, statuses, neighbour lists, on_device and *seconds are
+ * those of the affine fits above; A and hyp hold [s R | b], so sift3d_icgn_init_from_fits and everything after it take the record
+ * unchanged.  A fit needs 3 candidates: status 1 means fewer than 3, and 3 <= k <= 64.  A rotation is fixed by 3 pairs that are not
+ * collinear, so coplanar pairs -- where every affine hypothesis is degenerate -- are fitted.
+ * Numerical contract (fp64 on the fp32 inputs, every expression evaluated in the order written, no FMA contraction, sqrt and / are the
+ * correctly rounded IEEE operations; tests/rigid_ref.py restates it and checks the GPU bit for bit on hyp):
+ *   u.v = (u0 v0 + u1 v1) + u2 v2;  u x v = (u1 v2 - u2 v1, u2 v0 - u0 v2, u0 v1 - u1 v0).
+ *   Sampler: draws 0..2 of the affine sampler (u_j = fmix32(fmix32(s + p) + (4h + j)), j < 3, the duplicate rule among these three);
+ *     its draw 3 is not made, so c = 3 candidates are drawn in some order of the three.
+ *   Minimal solve (triad): samples P0..P2 (ref), T0..T2 (tar); a = P1 - P0, b = P2 - P0, c = a x b; x = a / sqrt(a.a),
+ *     z = c / sqrt(c.c), y = z x x; a', b', c', x', y', z' alike from T.  DEGENERATE unless c.c >= min_det * min_det and c'.c' > 0
+ *     (NaN: degenerate): min_det bounds twice the area of the sample's triangle.  R_ij = (x'_i x_j + y'_i y_j) + z'_i z_j.
+ *     Rigid: L = R.  Similarity: s = sqrt(((a'.a' + b'.b') + (b' - a').(b' - a')) / ((a.a + b.b) + (b - a).(b - a))), L_ij = s R_ij.
+ *     b_i = T0_i - ((L_i0 P0x + L_i1 P0y) + L_i2 P0z).
+ *   Scoring, threshold and best hypothesis: those of the affine fits.
+ *   Refit (`refine` rounds, Horn's quaternion method): on the current inlier set (at least 3, else stop) the means rbar, tbar; with
+ *     d = r - rbar, e = t - tbar the sums Cov = sum d d^T, S_ab = sum d_a e_b, E = sum e.e.
+ *     e2 = ((C00 C11 - C01 C01) + (C00 C22 - C02 C02)) + (C11 C22 - C12 C12); unless e2 >= min_det * min_det (NaN included: collinear
+ *     inliers) stop, keep the previous transform, status 3 (for 3 points e2 = c.c / 3: the units of the sample's rule).
+ *     The symmetric 4x4 N: N00 = (Sxx + Syy) + Szz, N11 = (Sxx - Syy) - Szz, N22 = (-Sxx + Syy) - Szz, N33 = (-Sxx - Syy) + Szz,
+ *     N01 = Syz - Szy, N02 = Szx - Sxz, N03 = Sxy - Syx, N12 = Sxy + Syx, N13 = Szx + Sxz, N23 = Syz + Szy.
+ *     Eigenvectors by cyclic Jacobi, V = I at the start, 8 sweeps over the planes (p, q) = (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); a plane
+ *     with N_pq == 0 is skipped, else theta = (N_qq - N_pp) / (2 N_pq), t = (theta >= 0 ? 1 : -1) / (|theta| + sqrt(theta theta + 1))
+ *     (theta theta may overflow: t = +-0), c = 1 / sqrt(t t + 1), s = t c; N_pp -= t N_pq, N_qq += t N_pq, N_pq = 0; for the other rows r:
+ *     (N_rp, N_rq) <- (c N_rp - s N_rq, s N_rp + c N_rq); for every row r of V: (V_rp, V_rq) <- (c V_rp - s V_rq, s V_rp + c V_rq).
+ *     q = (w, x, y, z) = the column of V under the largest diagonal entry of N (ties: the lowest index), divided by
+ *     sqrt(((q0 q0 + q1 q1) + q2 q2) + q3 q3).  R00 = ((ww + xx) - yy) - zz, R11 = ((ww - xx) + yy) - zz, R22 = ((ww - xx) - yy) + zz,
+ *     R01 = 2 (xy - wz), R10 = 2 (xy + wz), R02 = 2 (xz + wy), R20 = 2 (xz - wy), R12 = 2 (yz - wx), R21 = 2 (yz + wx): even in q, so its
+ *     sign does not matter.  Rigid: L = R.  Similarity: s = sqrt(E / ((C00 + C11) + C22)), L_ij = s R_ij.  b = tbar - L rbar (as b_i
+ *     above).  Re-scored after every accepted round.  Sums run in a fixed order of the implementation: two calls give the same bits
+ *     (A is checked to tolerance).
+ *   Non-finite values go where these IEEE operations carry them: a NaN in a sampled position makes the sample degenerate, an infinity
+ *     in a sampled target gives a NaN transform that counts no inlier; min_det = 0 accepts c.c = 0 and divides by it.
+ * SIFT3D_ERR_ARG (checked before any device call): what the affine fits refuse, with k outside 3..64, and model outside 0..1.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* the global fit; inlier_mask: n bytes (1 inlier of A, 0 not), may be NULL */
+int sift3d_fit_rigid(const float *pairs6, int n, int model, const sift3d_ransac_options *o, int on_device, int device,
+                     sift3d_affine_fit *out, unsigned char *inlier_mask, double *seconds);
+/* m local fits; out: m records; neighbours: m*k pair indices in candidate order, -1 padded, may be NULL */
+int sift3d_fit_rigid_local(const float *pairs6, int n, const float *points3, int m, int k, float radius, int model,
+                           const sift3d_ransac_options *o, int on_device, int device, sift3d_affine_fit *out,
+                           int *neighbours, double *seconds);
+/* host only, no GPU: per fit the unit quaternion (w, x, y, z; w >= 0) of the rotation, the scale s = cbrt(det L) and the rotation
+ * angle 2 atan2(sqrt(xx + yy + zz), w) in degrees of the linear part L of A: R = L / s, q from R by Shepperd's branch on the largest
+ * of (trace, R00, R11, R22).  Meant for rigid and similarity fits; a fit with status != 0 gives NaN.  quat4: 4 m doubles, scale and
+ * angle_deg: m each.  SIFT3D_ERR_ARG: m < 0, or a NULL pointer with m > 0. */
+int sift3d_fit_rotation(const sift3d_affine_fit *fits, int m, double *quat4, double *scale, double *angle_deg);
 
 /* ------------------------------------------------------------------------------------------------------------
  * IC-GN displacement refinement for digital volume correlation (no reference counterpart: what the DVC users of the reference run on
