@@ -42,6 +42,8 @@ SYMBOLS = [
     "sift3d_default_ransac_options", "sift3d_fit_affine", "sift3d_fit_affine_local",
     # RANSAC rigid / similarity fits of the same pairs, and the rotation a fit holds
     "sift3d_fit_rigid", "sift3d_fit_rigid_local", "sift3d_fit_rotation",
+    # guided matching: best and second best within a spatial gate around the position a fit predicts
+    "sift3d_predict_positions", "sift3d_match_guided",
     # IC-GN displacement refinement (digital volume correlation)
     "sift3d_default_icgn_options", "sift3d_icgn_init_from_fits", "sift3d_icgn",
     # cubic B-spline interpolation of the target: the prefilter and the IC-GN mode on its coefficients
@@ -277,6 +279,9 @@ def lib():
         L.sift3d_fit_rigid_local.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(RansacOptions),
                                              C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         L.sift3d_fit_rotation.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sift3d_predict_positions.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.sift3d_match_guided.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_double,
+                                          C.c_int, C.c_int, C.c_int, _ip, _ip, _fp, _fp, _ip, _fp, _ip, C.POINTER(C.c_double)]
         L.sift3d_default_icgn_options.argtypes = [C.POINTER(IcgnOptions)]
         L.sift3d_default_icgn_options.restype = None
         L.sift3d_icgn_init_from_fits.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -682,6 +687,52 @@ def fit_rotation(fits):
     if single:
         return {"quat": quat[0].copy(), "scale": float(scale[0]), "angle_deg": float(angle[0])}
     return {"quat": quat[:m].copy(), "scale": scale[:m].copy(), "angle_deg": angle[:m].copy()}
+
+
+def predict_positions(fit, xyz):
+    """sift3d_predict_positions (needs no GPU): where a fit sends the reference positions xyz ((n, 3) float32 rx, ry, rz), as (n, 3)
+    float32 -- the `pred` of match_guided.  fit: the dict fit_affine / fit_rigid returns (A (3, 4): one fit for all rows) or the one
+    fit_affine_local / fit_rigid_local returns when queried at xyz itself (A (n, 3, 4)); a failed fit (status != 0) gives a NaN row,
+    whose gate is empty."""
+    A = np.asarray(fit["A"], np.float64)
+    A = A.reshape(-1, 12)
+    r = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    f = np.zeros(max(len(A), 1), FIT_DTYPE)
+    f["A"][:len(A)] = A
+    f["status"][:len(A)] = np.asarray(fit["status"]).reshape(-1)
+    out = np.zeros((max(len(r), 1), 3), np.float32)
+    _check(lib().sift3d_predict_positions(_p(f), len(A), _p(r), len(r), _p(out)))
+    return out[:len(r)].copy()
+
+
+MATCH_MODES = {"inject": 1, "biject": 2, "enhanced": 3}
+
+
+def match_guided(ref_desc, ref_xyz, tar_desc, tar_xyz, pred, radius, thresHold=0.85, mode="enhanced", device=0):
+    """sift3d_match_guided: muBruteMatcher's match with every row's targets limited to its gate -- the targets within `radius` of
+    pred[i] on each axis (fp32).  The five tables are numpy arrays or contiguous float32 device tensors, all of one kind (desc (n, 768)
+    / (m, 768), xyz and pred (n, 3) / (m, 3)); mode: "inject" | "biject" | "enhanced" or 1..3.  Returns gIdx, sIdx, gDist, sDist,
+    candidates (n,), pairs (k, 6) and the device seconds."""
+    tabs = [_rows(ref_desc, DESC, "ref_desc"), _rows(ref_xyz, 3, "ref_xyz"), _rows(tar_desc, DESC, "tar_desc"), _rows(tar_xyz, 3, "tar_xyz"),
+            _rows(pred, 3, "pred")]
+    if len({t[3] for t in tabs}) != 1:
+        raise ValueError("the five tables must all be host arrays or all device tensors")
+    n, m = tabs[0][1], tabs[2][1]
+    if tabs[1][1] != n or tabs[4][1] != n or tabs[3][1] != m:
+        raise ValueError("ref_xyz and pred need one row per reference descriptor, tar_xyz one per target descriptor")
+    if not isinstance(mode, (int, np.integer)):
+        if mode not in MATCH_MODES:
+            raise ValueError(f"mode {mode!r}: one of {sorted(MATCH_MODES)} is needed")
+        mode = MATCH_MODES[mode]
+    nn = max(n, 1)
+    gi = np.zeros(nn, np.int32); si = np.zeros(nn, np.int32); cand = np.zeros(nn, np.int32)
+    gd = np.zeros(nn, np.float32); sd = np.zeros(nn, np.float32)
+    pairs = np.zeros((nn, 6), np.float32)
+    k = C.c_int(0); sec = C.c_double(0)
+    _check(lib().sift3d_match_guided(tabs[0][0], tabs[1][0], n, tabs[2][0], tabs[3][0], m, tabs[4][0], float(radius), float(thresHold),
+                                     int(mode), tabs[0][3], int(device), gi.ctypes.data_as(_ip), si.ctypes.data_as(_ip),
+                                     _f(gd), _f(sd), cand.ctypes.data_as(_ip), _f(pairs), C.byref(k), C.byref(sec)))
+    return dict(gIdx=gi[:n], sIdx=si[:n], gDist=gd[:n], sDist=sd[:n], candidates=cand[:n], pairs=pairs[:k.value].copy(), seconds=sec.value)
 
 
 ICGN_OPTIONS = ("subset_radius", "max_iterations", "tolerance", "interpolation")

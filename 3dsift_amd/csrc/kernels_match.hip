@@ -700,26 +700,19 @@ int match_rows_device(const float *d_a, const int *d_row_ids, int nrows, const f
 // ---------------------------------------------------------------------------------------------
 // C-ABI: muBruteMatcher::bijectMatchBase (Src/cMatcher.cc:146-215).  The O(N*M*768) passes run on
 // the device; the O(N) bookkeeping (ratio filter, countMatched, toMask, bijectFilter, toCvec) is
-// replayed on the host exactly as written in the reference, including its sign-flip quirks.
+// replayed on the host exactly as written in the reference, including its sign-flip quirks (match_host.h).
 // ---------------------------------------------------------------------------------------------
 #include <algorithm>
 #include <vector>
 
 using namespace s3d;
 
-static void ratio_filter(std::vector<int> &gi, const std::vector<float> &gd, const std::vector<float> &sd, double thresHold) {
-	const double t2 = thresHold * thresHold;  // filter, Src/cMatcher.cc:81-97
-	for (size_t i = 0; i < gi.size(); i++) {
-		if (gi[i] < 0) continue;
-		if ((double)(gd[i] / sd[i]) >= t2) gi[i] *= -1;
-	}
-}
-
 // Per-device matcher state (call_state.h; r03: a call used to do 3-5 hipMalloc / hipFree and ran on the null stream).  d holds
 // everything but the descriptor matrices, h the results of a pass (+ the coordinates of device-resident inputs).
 #include <chrono>
 
 #include "call_state.h"
+#include "match_host.h"
 
 namespace {
 struct MatchState : CallState {
@@ -833,14 +826,11 @@ extern "C" int sift3d_match(const float *ref_desc, const float *ref_xyz, int n, 
 			// no targets: every dot loop is empty -> d = 2 - 2*FLT_MIN, idx -1
 			for (int i = 0; i < n; i++) { gd[i] = sd[i] = (float)(2 - 2 * (double)FLT_MIN); }
 		}
-		ratio_filter(gi, gd, sd, thresHold);
+		match_ratio_filter(gi, gd, sd, thresHold);
 
 		if (mode != 1) {
-			const int mask_thres = (mode == 2) ? 0 : 1;
-			std::vector<int> cnt(m, 0);
-			for (int i = 0; i < n; i++) if (gi[i] >= 0) cnt[gi[i]] += 1;               // countMatched :114-120
-			std::vector<int> rows;
-			for (int j = 0; j < m; j++) { cnt[j] = cnt[j] > mask_thres ? 1 : 0; if (cnt[j]) rows.push_back(j); }  // toMask :122-131
+			std::vector<int> cnt;
+			const std::vector<int> rows = match_mask_rows(gi, m, mode, cnt);
 			// ---- tar -> ref over the masked targets only (masked-out rows keep gIdx2 = -1) ----
 			if (!rows.empty() && n > 0) {
 				S3D_HIP_ST(st, hipMemcpyAsync(d_rows, rows.data(), sizeof(int) * rows.size(), hipMemcpyHostToDevice, st));
@@ -852,25 +842,13 @@ extern "C" int sift3d_match(const float *ref_desc, const float *ref_xyz, int n, 
 				for (int j : rows) { gd2[j] = h_gd[j]; sd2[j] = h_sd[j]; gi2[j] = h_gi[j]; si2[j] = h_si[j]; }
 				redo_rows += h_redo[0];
 			}
-			ratio_filter(gi2, gd2, sd2, thresHold);
-			for (int i = 0; i < n; i++) {                                              // bijectFilter :133-144
-				const int j = gi[i];
-				if (j < 0 || cnt[j] == 0) continue;
-				if (gi2[j] != i) gi[i] *= -1;
-			}
+			match_ratio_filter(gi2, gd2, sd2, thresHold);
+			match_biject(gi, cnt, gi2);
 		}
 		if ((rc = S.finish(&t_match_dev))) return rc;
 		if (seconds) *seconds = t_match_dev;
 
-		int np = 0;
-		for (int i = 0; i < n; i++) {                                                  // toCvec :99-112
-			const int j = gi[i];
-			if (j < 0) continue;
-			if (pairs6) {
-				for (int c = 0; c < 3; c++) { pairs6[(size_t)np * 6 + c] = rx[(size_t)i * 3 + c]; pairs6[(size_t)np * 6 + 3 + c] = tx[(size_t)j * 3 + c]; }
-			}
-			np++;
-		}
+		const int np = match_to_cvec(gi, rx, tx, pairs6);
 		if (npairs) *npairs = np;
 		for (int i = 0; i < n; i++) {
 			if (gIdx) gIdx[i] = gi[i];

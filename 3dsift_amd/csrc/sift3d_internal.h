@@ -397,6 +397,16 @@ void launch_validate_fold(const double *d_grad, const unsigned char *d_valid, in
 void launch_validate_test(const int *d_pts, const double *d_disp, const double *d_grad, int m, const PoiIndex &ix, ValidateParams P, int pass,
                           const unsigned char *d_fin, unsigned char *d_fout, int *d_pass, sift3d_validate_result *d_out, hipStream_t st);
 
+// ---- kernels_match_guided.hip: the matcher inside a spatial gate (sift3d_match_guided, include/sift3d_hip.h) -----------------------
+// d_xyz: n fp32 positions -> what poi_grid_build indexes: d_pts their floors (3 n ints; a position no gate holds gets a floor the index
+// refuses), d_disp the exact values (3 n doubles)
+void launch_gate_points(const float *d_xyz, int n, int *d_pts, double *d_disp, hipStream_t st);
+// best / second best of every listed row of A (d_row_ids null: rows 0 .. nrows - 1) over the rows of B whose position, indexed by ix
+// (built with half_width = ceil(radius) + 1), lies within radius of the row's position d_qxyz[row] on every axis in fp32.  Outputs
+// are indexed by the ORIGINAL row id; d_cnt (may be null): the columns in the row's gate.
+void launch_match_gated(const float *d_a, const float *d_qxyz, const int *d_row_ids, int nrows, const float *d_b, const PoiIndex &ix,
+                        float radius, int half_width, float *d_gd, float *d_sd, int *d_gi, int *d_si, int *d_cnt, hipStream_t st);
+
 // code-object preload of the translation units whose kernels would otherwise be loaded by the first KpSiftAlgorithm of a process
 void preload_march_kernels();
 void preload_small_kernels();

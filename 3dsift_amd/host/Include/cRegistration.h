@@ -1,6 +1,6 @@
-// cRegistration.h -- RANSAC affine fits of matched keypoints, subset screening, ZNCC integer search, IC-GN displacement refinement, validation and strain fields (no
+// cRegistration.h -- RANSAC affine fits of matched keypoints, guided matching, subset screening, ZNCC integer search, IC-GN displacement refinement, validation and strain fields (no
 // reference counterpart): the steps after enhancedMatch, on the GPU.
-// Over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_fit_rigid / sift3d_fit_rigid_local / sift3d_subset_quality / sift3d_zncc_search / sift3d_icgn / sift3d_validate_displacements / sift3d_strain (include/sift3d_hip.h, which states the numerical contracts).  Both functions take
+// Over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_fit_rigid / sift3d_fit_rigid_local / sift3d_predict_positions / sift3d_match_guided / sift3d_subset_quality / sift3d_zncc_search / sift3d_icgn / sift3d_validate_displacements / sift3d_strain (include/sift3d_hip.h, which states the numerical contracts).  Both functions take
 // exactly the two std::vector<Cvec> that muBruteMatcher::enhancedMatch fills (refMatch[i] <-> tarMatch[i]).
 #ifndef S3D_HOST_CREGISTRATION_H
 #define S3D_HOST_CREGISTRATION_H
@@ -56,6 +56,33 @@ SIFT_LIBRARY_API std::vector<AffineFit> EstimateLocalRigid(const std::vector<Cve
 // the rotation a fit holds (sift3d_fit_rotation, host only): unit quaternion (w, x, y, z; w >= 0), scale and angle in degrees; NaN and
 // false for a fit whose status is not 0.  scale and angleDeg may be null.
 SIFT_LIBRARY_API bool FitRotation(const AffineFit &fit, double quat[4], double *scale = nullptr, double *angleDeg = nullptr);
+
+// Guided matching over sift3d_predict_positions / sift3d_match_guided: the matcher run again with every reference keypoint's targets
+// limited to its gate, the targets within `radius` of its predicted position on each axis (fp32) -- the chain is enhancedMatch ->
+// EstimateAffine (or EstimateRigid) -> PredictPositions -> GuidedMatch -> the fit again -> EstimateLocalAffine.  Where texture repeats,
+// a keypoint's partner and a look-alike elsewhere in the volume score alike and the ratio test rejects the pair; inside the gate the
+// look-alike is not a candidate.
+// where a fit sends the keypoints' positions (rx, ry, rz): one fit for all of them, or one per keypoint (EstimateLocalAffine /
+// EstimateLocalRigid queried at the keypoints' own positions).  A fit whose status is not 0 gives a NaN position, whose gate is empty;
+// so does a failed call (message on stderr)
+SIFT_LIBRARY_API std::vector<Cvec> PredictPositions(const AffineFit &fit, const std::vector<Keypoint> &ref_kp);
+SIFT_LIBRARY_API std::vector<Cvec> PredictPositions(const std::vector<AffineFit> &fits, const std::vector<Keypoint> &ref_kp);
+
+enum MatchMode { Inject = 1, Biject = 2, Enhanced = 3 };  // muBruteMatcher's injectMatch / bijectMatch / enhancedMatch
+// per reference keypoint what muBruteMatcher's getters return after a match (an index negated by a filter, -1 where the gate held no
+// usable target) and the number of targets in its gate; ok false: the call failed (message on stderr) and the vectors are empty
+struct SIFT_LIBRARY_API GuidedMatchResult {
+	std::vector<int> glodenIdx, silverIdx, candidates;
+	std::vector<float> glodenDistSquare, silverDistSquare;
+	double seconds = 0;  // device time of the call
+	bool ok = false;
+};
+// appends the matched pairs to refMatch / tarMatch as muBruteMatcher does; predicted: one position per reference keypoint; radius in
+// (0, 2^20] full-resolution voxels.  A keypoint with one target in its gate is accepted on its distance alone
+// (glodenDistSquare / 2 < thresHold^2)
+SIFT_LIBRARY_API GuidedMatchResult GuidedMatch(std::vector<Cvec> &refMatch, std::vector<Cvec> &tarMatch, const std::vector<Keypoint> &ref_kp,
+                                               const std::vector<Keypoint> &tar_kp, const std::vector<Cvec> &predicted, float radius,
+                                               double thresHold = 0.85, MatchMode mode = Enhanced);
 
 struct SIFT_LIBRARY_API IcgnOptions {
 	int subset_radius = 16;   // r: the subset is (2r+1)^3 voxels, 2..32

@@ -1,5 +1,5 @@
-// cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine / SearchDisplacements / RefineDisplacements / ValidateDisplacements /
-// ComputeStrains over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_zncc_search / sift3d_icgn / sift3d_icgn_bspline /
+// cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine / PredictPositions / GuidedMatch / SearchDisplacements / RefineDisplacements / ValidateDisplacements /
+// ComputeStrains over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_predict_positions / sift3d_match_guided / sift3d_zncc_search / sift3d_icgn / sift3d_icgn_bspline /
 // sift3d_validate_displacements / sift3d_strain, and
 // CPUSIFT::PrefilterBSpline over sift3d_bspline_prefilter (include/sift3d_hip.h).
 #include "../Include/cRegistration.h"
@@ -149,6 +149,77 @@ bool FitRotation(const AffineFit &fit, double quat[4], double *scale, double *an
 	if (scale) *scale = s;
 	if (angleDeg) *angleDeg = a;
 	return rc == SIFT3D_OK && fit.status == 0;
+}
+
+namespace {
+std::vector<Cvec> predict(const AffineFit *fits, size_t nfits, const std::vector<Keypoint> &kp) {
+	const size_t n = kp.size();
+	std::vector<Cvec> out(n, Cvec(NAN, NAN, NAN));
+	if (nfits != 1 && nfits != n) {
+		fprintf(stderr, "[3dsift_amd] PredictPositions: %zu fits for %zu keypoints (one fit, or one per keypoint)\n", nfits, n);
+		return out;
+	}
+	std::vector<sift3d_affine_fit> f(nfits);
+	for (size_t i = 0; i < nfits; i++) {
+		memset(&f[i], 0, sizeof(f[i]));
+		memcpy(f[i].A, fits[i].A, sizeof(f[i].A));
+		f[i].status = fits[i].status;
+	}
+	std::vector<float> r(3 * (n ? n : 1)), p(3 * (n ? n : 1));
+	for (size_t i = 0; i < n; i++) { r[3 * i] = kp[i].rx; r[3 * i + 1] = kp[i].ry; r[3 * i + 2] = kp[i].rz; }
+	const int rc = sift3d_predict_positions(f.data(), (int)nfits, r.data(), (int)n, p.data());
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] PredictPositions: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return out;
+	}
+	for (size_t i = 0; i < n; i++) out[i] = Cvec(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
+	return out;
+}
+}  // namespace
+
+std::vector<Cvec> PredictPositions(const AffineFit &fit, const std::vector<Keypoint> &ref_kp) { return predict(&fit, 1, ref_kp); }
+std::vector<Cvec> PredictPositions(const std::vector<AffineFit> &fits, const std::vector<Keypoint> &ref_kp) {
+	return predict(fits.data(), fits.size(), ref_kp);
+}
+
+GuidedMatchResult GuidedMatch(std::vector<Cvec> &refMatch, std::vector<Cvec> &tarMatch, const std::vector<Keypoint> &ref_kp,
+                              const std::vector<Keypoint> &tar_kp, const std::vector<Cvec> &predicted, float radius, double thresHold,
+                              MatchMode mode) {
+	GuidedMatchResult res;
+	const size_t n = ref_kp.size(), m = tar_kp.size();
+	if (predicted.size() != n) {
+		fprintf(stderr, "[3dsift_amd] GuidedMatch: %zu predicted positions for %zu reference keypoints\n", predicted.size(), n);
+		return res;
+	}
+	// gather the (possibly scattered) descriptor rows, as muBruteMatcher does; Keypoint::desc points into extractor-owned memory
+	std::vector<float> a(n * SIFT3D_DESC_NUMEL), b(m * SIFT3D_DESC_NUMEL), ax(3 * (n ? n : 1)), bx(3 * (m ? m : 1)), px(3 * (n ? n : 1));
+	for (size_t i = 0; i < n; i++) {
+		if (ref_kp[i].desc) memcpy(&a[i * SIFT3D_DESC_NUMEL], ref_kp[i].desc, sizeof(float) * SIFT3D_DESC_NUMEL);
+		ax[3 * i] = ref_kp[i].rx; ax[3 * i + 1] = ref_kp[i].ry; ax[3 * i + 2] = ref_kp[i].rz;
+		px[3 * i] = predicted[i].x; px[3 * i + 1] = predicted[i].y; px[3 * i + 2] = predicted[i].z;
+	}
+	for (size_t j = 0; j < m; j++) {
+		if (tar_kp[j].desc) memcpy(&b[j * SIFT3D_DESC_NUMEL], tar_kp[j].desc, sizeof(float) * SIFT3D_DESC_NUMEL);
+		bx[3 * j] = tar_kp[j].rx; bx[3 * j + 1] = tar_kp[j].ry; bx[3 * j + 2] = tar_kp[j].rz;
+	}
+	std::vector<int> gi(n ? n : 1), si(n ? n : 1), cand(n ? n : 1);
+	std::vector<float> gd(n ? n : 1), sd(n ? n : 1), pairs(6 * (n ? n : 1));
+	int np = 0;
+	const int rc = sift3d_match_guided(a.data(), ax.data(), (int)n, b.data(), bx.data(), (int)m, px.data(), radius, thresHold, (int)mode, 0,
+	                                   GetDevice(), gi.data(), si.data(), gd.data(), sd.data(), cand.data(), pairs.data(), &np, &res.seconds);
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] GuidedMatch: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return res;
+	}
+	for (int i = 0; i < np; i++) {
+		refMatch.push_back(Cvec(pairs[6 * i], pairs[6 * i + 1], pairs[6 * i + 2]));
+		tarMatch.push_back(Cvec(pairs[6 * i + 3], pairs[6 * i + 4], pairs[6 * i + 5]));
+	}
+	res.glodenIdx.assign(gi.begin(), gi.begin() + n); res.silverIdx.assign(si.begin(), si.begin() + n);
+	res.candidates.assign(cand.begin(), cand.begin() + n);
+	res.glodenDistSquare.assign(gd.begin(), gd.begin() + n); res.silverDistSquare.assign(sd.begin(), sd.begin() + n);
+	res.ok = true;
+	return res;
 }
 
 Cvec IcgnResult::Displacement() const { return Cvec((float)p[0], (float)p[4], (float)p[8]); }

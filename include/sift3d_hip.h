@@ -576,6 +576,45 @@ int sift3d_fit_rigid_local(const float *pairs6, int n, const float *points3, int
 int sift3d_fit_rotation(const sift3d_affine_fit *fits, int m, double *quat4, double *scale, double *angle_deg);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Guided matching (no reference counterpart for the gate: the step registration pipelines take after a first fit -- match again
+ * where the fit says the partner must be, then refit).  sift3d_match's ratio test compares a row's best target with the second best
+ * anywhere in the volume; where texture repeats, the true partner and a look-alike far away score alike and the pair is rejected.
+ * sift3d_match_guided is sift3d_match with three additions: pred_xyz (n x 3 fp32, the place in the target where reference keypoint i
+ * is expected), radius, and the optional per-row output `candidates`.
+ *   The gate: gate(i) = { j : fabsf(tar_xyz[j][c] - pred_xyz[i][c]) <= radius for c = 0, 1, 2 }, evaluated in fp32 exactly as written
+ *     (one rounded subtraction per component).  A position with a non-finite coordinate, predicted or target, is in no gate and has
+ *     an empty one (the comparison is false); so is a position with a coordinate beyond +-2^24, the bound of the spatial index the
+ *     gates are found with.  0 < radius <= 2^20, finite.
+ *   Forward pass: row i gets what muBruteMatcher::calMatches (Src/cMatcher.cc:40-79) returns when the target set is gate(i) in
+ *     ascending j: score s += (double)(a[k] * b[k]) with k ascending, strict '>' from FLT_MIN, ties keep the lower column,
+ *     d = 2 - 2 s stored as float, an empty place holds index -1 and d = 2 - 2 * FLT_MIN (2.0f).  The value contract written at
+ *     sift3d_match above holds word for word: a column whose score is NaN or <= FLT_MIN is never chosen, +-inf / NaN components
+ *     follow the reference's arithmetic.
+ *   Modes and bookkeeping: the ratio filter and the modes 1 / 2 / 3 are the reference's (Src/cMatcher.cc:81-144), unchanged.  In modes
+ *     2 and 3 the reverse pass of a masked target j scans { i : j in gate(i) } in ascending i -- the same relation transposed, so the
+ *     bijection test stays symmetric.  pairs6, npairs, gIdx, sIdx, gDist, sDist and seconds are as in sift3d_match; candidates[i]
+ *     (n ints, may be NULL) = |gate(i)|.
+ *   A row with ONE candidate has sIdx = -1 and sDist = 2.0f, so it passes the ratio filter when gDist / 2 < thresHold * thresHold:
+ *     alone in its gate, a target is accepted on its distance alone.
+ *   Consequences: with a gate that holds every target the call returns sift3d_match's bytes in every mode; in mode 1 a pair that
+ *     sift3d_match accepts and whose target lies in the row's gate is accepted by the guided call as well whenever sDist > 0 (the second
+ *     best inside the gate is no closer than the second best anywhere).
+ * on_device != 0: the five input tables are device pointers on `device`; outputs are host memory.  Two calls return the same bytes.
+ * SIFT3D_ERR_ARG (checked before any device call): n < 0, m < 0, mode outside 1..3, radius not in (0, 2^20] (NaN included), a NULL
+ * table that has rows.  n = 0 or m = 0 succeeds with empty gates.  Above a radius where the gates hold a large share of the targets
+ * the brute-force pass of sift3d_match is the faster one (DESIGN 4.5a has the measured crossover).
+ * ------------------------------------------------------------------------------------------------------------ */
+int sift3d_match_guided(const float *ref_desc, const float *ref_xyz, int n, const float *tar_desc, const float *tar_xyz, int m,
+                        const float *pred_xyz, float radius, double thresHold, int mode, int on_device, int device, int *gIdx,
+                        int *sIdx, float *gDist, float *sDist, int *candidates, float *pairs6, int *npairs,
+                        double *seconds /* device time of the call, may be NULL */);
+/* host only, no GPU: where the fits send the reference positions xyz3 (n x 3 fp32: rx, ry, rz).  pred = A (r, 1) in fp64,
+ * ((A_i0 rx + A_i1 ry) + A_i2 rz) + A_i3, rounded to float.  nfits is 1 (one global fit for all rows) or n (row i takes fits[i]: the
+ * local fits queried at the keypoints' own coordinates).  A fit with a non-zero status gives a NaN row, whose gate is empty.  Takes
+ * affine, rigid and similarity records alike.  SIFT3D_ERR_ARG: n < 0, nfits neither 1 nor n, or a NULL pointer with n > 0. */
+int sift3d_predict_positions(const sift3d_affine_fit *fits, int nfits, const float *xyz3, int n, float *pred3);
+
+/* ------------------------------------------------------------------------------------------------------------
  * IC-GN displacement refinement for digital volume correlation (no reference counterpart: what the DVC users of the reference run on
  * the initial guess of sift3d_fit_affine_local; Pan et al., inverse-compositional Gauss-Newton with a first-order shape function).
  * Numerical contract (a tolerance contract, not bit for bit; tests/icgn_ref.py restates it in NumPy fp64):
