@@ -59,6 +59,8 @@ SYMBOLS = [
     "sift3d_validate_keep", "sift3d_icgn_init_from_validation", "sift3d_validate_stage_capacity",
     # subset screening: texture sums and a per-POI subset radius, the step in front of IC-GN
     "sift3d_default_subset_options", "sift3d_subset_quality", "sift3d_subset_group_by_radius",
+    # masked IC-GN: subsets limited to a voxel mask of the reference, and the mask of a grey level
+    "sift3d_icgn_masked", "sift3d_mask_from_level",
     "sift3d_device_count", "sift3d_error_string", "sift3d_last_error",
     # typed input: 8 / 16-bit integer voxels uploaded at their own width and widened on the GPU
     "sift3d_dtype_bytes", "sift3d_create_typed", "sift3d_volume_to_device", "sift3d_test_ingest_launch",
@@ -317,6 +319,11 @@ def lib():
                                             C.c_int, C.c_void_p, C.POINTER(C.c_double)]
         L.sift3d_subset_group_by_radius.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.sift3d_icgn_init_from_validation.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _ip]
+        L.sift3d_icgn_masked.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_int, C.c_void_p, C.POINTER(IcgnOptions), C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.POINTER(C.c_double)]
+        L.sift3d_mask_from_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_int,
+                                             C.POINTER(C.c_double)]
         L.sift3d_validate_stage_capacity.argtypes = [_ip]
         _sz = C.POINTER(C.c_size_t)
         L.sift3d_slab_min_halo.argtypes = [C.POINTER(Params), _ip]
@@ -772,9 +779,10 @@ def icgn(ref, tar, points, init=None, device=0, **opts):
     return _icgn(1, "sift3d_icgn", ref, tar, points, init, device, opts, None)
 
 
-def _icgn(order, entry, ref, tar, points, init, device, opts, coefficients):
-    """the call behind icgn, icgn_bspline (order 1) and icgn2 (order 2); entry: the exported function's name; coefficients None: the
-    entry has no tar_is_coefficients argument"""
+def _icgn(order, entry, ref, tar, points, init, device, opts, coefficients, mask=None, min_fraction=0.0):
+    """the call behind icgn, icgn_bspline, icgn_masked (order 1) and icgn2 (order 2); entry: the exported function's name;
+    coefficients None: the entry has no tar_is_coefficients argument; mask: icgn_masked's, with its min_fraction (the entry then takes
+    the mask behind the volumes, min_fraction behind the options and the active counts behind the records)"""
     width, dtype = {1: (12, ICGN_DTYPE), 2: (30, ICGN2_DTYPE)}[order]
     o = _icgn_options(opts)
     (rp, tp), (rdim, tdim), on_dev, keep = _volume_pair(ref, tar)
@@ -785,8 +793,15 @@ def _icgn(order, entry, ref, tar, points, init, device, opts, coefficients):
     out = np.zeros(max(m, 1), dtype)
     sec = C.c_double(0)
     coef = () if coefficients is None else (int(bool(coefficients)),)
-    _check(getattr(lib(), entry)(rp, *rdim, tp, *tdim, qp, m, ip, C.byref(o), *coef, on_dev, int(device), _p(out), C.byref(sec)))
+    mp = mf = ap = ()
+    if mask is not None:
+        active = np.zeros(max(m, 1), np.int32)
+        mptr, mkeep = _mask(mask, keep[0].shape, on_dev)  # (mkeep: the array behind the pointer lives until the call returns)
+        mp, mf, ap = (mptr,), (float(min_fraction),), (_p(active),)
+    _check(getattr(lib(), entry)(rp, *rdim, tp, *tdim, *mp, qp, m, ip, C.byref(o), *mf, *coef, on_dev, int(device), _p(out), *ap, C.byref(sec)))
     d = _fields(out, m, ("p", "zncc", "last_step", "iterations", "status"))
+    if mask is not None:
+        d["active"] = active[:m].copy()
     e = d["p"].reshape(-1, 3, width // 3)
     d["displacement"] = e[:, :, 0].copy()
     d["gradient"] = e[:, :, 1:4].copy()
@@ -841,6 +856,51 @@ def icgn2(ref, tar, points, init=None, coefficients=False, device=0, **opts):
     Returns p (m, 30), displacement (m, 3), gradient (m, 3, 3) (rows u, v, w; columns x, y, z), second (m, 3, 6) (columns xx, yy, zz,
     xy, xz, yz), zncc, last_step, iterations, status (m,) and the device seconds."""
     return _icgn(2, "sift3d_icgn2", ref, tar, points, init, device, opts, bool(coefficients))
+
+
+def _mask(a, shape, on_dev):
+    """(pointer, keep-alive) of a uint8 mask of `shape` that lies where the volumes lie"""
+    if on_dev:
+        if not _is_dev(a) or str(a.dtype) != "torch.uint8" or not a.is_contiguous() or tuple(a.shape) != tuple(shape):
+            raise ValueError(f"mask: a contiguous uint8 device tensor of shape {tuple(shape)} is needed")
+        return C.c_void_p(a.data_ptr()), a
+    if _is_dev(a):
+        raise ValueError("mask must lie where ref and tar lie")
+    h = np.ascontiguousarray(a)
+    if h.dtype == np.bool_:
+        h = h.view(np.uint8)
+    if h.dtype != np.uint8 or h.shape != tuple(shape):
+        raise ValueError(f"mask: a uint8 or bool array of shape {tuple(shape)} is needed")
+    return _p(h), h
+
+
+def icgn_masked(ref, tar, mask, points, init=None, min_fraction=0.0, tar_is_coefficients=False, device=0, **opts):
+    """sift3d_icgn_masked: icgn limited to the active voxels of each subset -- those that, with their six face neighbours, are in mask,
+    an (nz, ny, nx) uint8 (or bool) numpy array, or a contiguous uint8 device tensor where ref and tar are device tensors; any non-zero
+    byte is "in".  Options: icgn's, with interpolation 0 tricubic Keys, 1 trilinear, 2 cubic B-spline (tar_is_coefficients True: tar is
+    bspline_prefilter's output, interpolation 2 only).  A point whose subset holds no active voxel, or fewer than min_fraction (0..1)
+    of its (2r+1)^3, returns status 7.  Returns what icgn returns and active (m,) int32, the active voxels of each subset."""
+    return _icgn(1, "sift3d_icgn_masked", ref, tar, points, init, device, opts, bool(tar_is_coefficients), mask, min_fraction)
+
+
+def mask_from_level(vol, level, device=0, with_seconds=False):
+    """sift3d_mask_from_level: the uint8 mask icgn_masked takes, 1 where float64(vol) >= level (subset_quality's rule for `material`; a
+    NaN voxel is 0), else 0.  vol: an (nz, ny, nx) float32 numpy array or a contiguous float32 device tensor; returns an array / a
+    tensor of the same kind (with_seconds: and the device seconds)."""
+    on_dev = _is_dev(vol)
+    vp, v = _volume(vol, "vol", on_dev)
+    if on_dev:
+        import torch
+
+        out = torch.empty(v.shape, dtype=torch.uint8, device=v.device)
+        op = C.c_void_p(out.data_ptr())
+        device = v.device.index if v.device.index is not None else device
+    else:
+        out = np.empty(v.shape, np.uint8)
+        op = _p(out)
+    sec = C.c_double(0)
+    _check(lib().sift3d_mask_from_level(vp, *v.shape[::-1], float(level), op, int(on_dev), int(device), C.byref(sec)))
+    return (out, sec.value) if with_seconds else out
 
 
 SEARCH_OPTIONS = ("subset_radius", "search_radius")

@@ -1,5 +1,5 @@
 // entry_icgn.hip -- C-ABI of the IC-GN displacement refinement of both orders (include/sift3d_hip.h: sift3d_icgn, sift3d_icgn_bspline,
-// sift3d_icgn2, sift3d_icgn_init_from_fits, sift3d_icgn2_init_from_icgn, sift3d_strain_input_from_icgn2, sift3d_default_icgn_options).
+// sift3d_icgn2, sift3d_icgn_masked, sift3d_icgn_init_from_fits, sift3d_icgn2_init_from_icgn, sift3d_strain_input_from_icgn2, sift3d_default_icgn_options).
 // No reference counterpart.  Call state, scratch layout, timing and the order of the checks: DESIGN 4.10 (call_state.h).  The three
 // calls run through one shell on one state per device: the two orders are used one after the other in one chain, so a second mutex
 // would never be contended, the grown scratch block is reused, and the process creates no further stream.  The host-only logic lives
@@ -72,16 +72,25 @@ struct SecondOrder {
 	static constexpr auto launch = launch_icgn2;
 };
 
-// the call behind sift3d_icgn, sift3d_icgn_bspline and sift3d_icgn2 (max_interpolation, bspline: icgn_args_ok's, which states each
-// call's rules).  B-spline coefficients the caller did not bring (coef 0) are made here, in the call's scratch.
-template <class Order>
+// a masked call's own arguments (sift3d_icgn_masked): the mask lies where the volumes lie, active is host memory (may be null)
+struct MaskCall {
+	const unsigned char *mask;
+	float min_fraction;
+	int *active;
+};
+
+// the call behind sift3d_icgn, sift3d_icgn_bspline, sift3d_icgn2 and sift3d_icgn_masked (max_interpolation, bspline: icgn_args_ok's,
+// which states each call's rules; MASKED with mc: the masked call, first order only -- the other three pass neither).  B-spline coefficients the caller did not
+// bring (coef 0) are made here, in the call's scratch.
+template <class Order, bool MASKED = false>
 int run_icgn(const char *who, int max_interpolation, bool bspline, const float *ref, int rnx, int rny, int rnz, const float *tar, int tnx, int tny,
              int tnz, const int *points3, int m, const double *init, const sift3d_icgn_options *o, int coef, int on_device, int device,
-             typename Order::Result *out, double *seconds) {
+             typename Order::Result *out, double *seconds, const MaskCall *mc = nullptr) {
+	static_assert(!MASKED || Order::kParameters == 12, "only the first-order kernels have masked instantiations");
 	int r, max_it, kind;
 	double tol;
 	if (!icgn_args_ok(ref, rnx, rny, rnz, tar, tnx, tny, tnz, points3, m, o, max_interpolation, bspline, coef, out, r, max_it, tol, kind) ||
-	    (kind == 2 && !coef && !bspline_prefilter_fits(tnx, tny, tnz))) {
+	    (MASKED && !icgn_mask_args_ok(mc->mask, mc->min_fraction)) || (kind == 2 && !coef && !bspline_prefilter_fits(tnx, tny, tnz))) {
 		set_last_error(std::string(who) + ": bad argument");
 		return SIFT3D_ERR_ARG;
 	}
@@ -93,14 +102,20 @@ int run_icgn(const char *who, int max_interpolation, bool bspline, const float *
 	CallState &S = g_icgn[device];
 	std::lock_guard<std::mutex> lock(S.mu);
 	const IcgnLayout L = icgn_layout(m, (size_t)rnx * rny * rnz, (size_t)tnx * tny * tnz, on_device != 0, init != nullptr, filter,
-	                                 Order::state_bytes(), sizeof(typename Order::Result), Order::kParameters);
-	if ((rc = S.ensure(L.end, L.res_bytes))) return rc;
+	                                 Order::state_bytes(), sizeof(typename Order::Result), Order::kParameters, MASKED);
+	const size_t p_count = MASKED ? al256(L.res_bytes) : L.res_bytes;  // masked: the active counts follow the results in the pinned block
+	if ((rc = S.ensure(L.end, p_count + L.count_bytes))) return rc;
 	hipStream_t st = S.stream;
 	char *D = S.d.p, *P = S.h.p;
 	const float *d_ref = ref, *d_tar = tar;
 	const int *d_pts = points3;
 	const void *d_init = init;
 	if ((rc = S.stage_pair(L, on_device != 0, d_ref, d_tar, d_pts, d_init))) return rc;
+	const unsigned char *d_mask = nullptr;
+	if constexpr (MASKED) {
+		d_mask = mc->mask;
+		S3D_HIP_ST(st, upload(d_mask, D, L.o_mask, L.b_mask, st));
+	}
 	S3D_HIP_ST(st, hipEventRecord(S.e0, st));
 	if (filter) {
 		float *d_coef = reinterpret_cast<float *>(D + L.o_coef);
@@ -108,13 +123,25 @@ int run_icgn(const char *who, int max_interpolation, bool bspline, const float *
 		S3D_HIP_ST(st, hipGetLastError());
 		d_tar = d_coef;
 	}
-	Order::launch(IcgnVol{d_ref, rnx, rny, rnz}, IcgnVol{d_tar, tnx, tny, tnz}, d_pts, m, static_cast<const double *>(d_init), r, max_it, tol, kind,
-	              D + L.o_state, reinterpret_cast<typename Order::Result *>(D), st);
+	const IcgnVol R{d_ref, rnx, rny, rnz}, T{d_tar, tnx, tny, tnz};
+	if constexpr (MASKED) {
+		unsigned char *d_act = reinterpret_cast<unsigned char *>(D + L.o_act);
+		launch_mask_active(d_mask, rnx, rny, rnz, d_act, st);
+		S3D_HIP_ST(st, hipGetLastError());
+		launch_icgn_masked(R, T, d_pts, m, static_cast<const double *>(d_init), r, max_it, tol, kind, D + L.o_state,
+		                   reinterpret_cast<sift3d_icgn_result *>(D), IcgnMask{d_act, reinterpret_cast<int *>(D + L.o_count), mc->min_fraction}, st);
+	} else {
+		Order::launch(R, T, d_pts, m, static_cast<const double *>(d_init), r, max_it, tol, kind, D + L.o_state,
+		              reinterpret_cast<typename Order::Result *>(D), st);
+	}
 	S3D_HIP_ST(st, hipGetLastError());
 	S3D_HIP_ST(st, hipMemcpyAsync(P, D, L.res_bytes, hipMemcpyDeviceToHost, st));
+	if constexpr (MASKED) S3D_HIP_ST(st, hipMemcpyAsync(P + p_count, D + L.o_count, L.count_bytes, hipMemcpyDeviceToHost, st));
 	S3D_HIP_ST(st, hipEventRecord(S.e1, st));
 	if ((rc = S.finish(seconds))) return rc;
 	memcpy(out, P, L.res_bytes);
+	if constexpr (MASKED)
+		if (mc->active) memcpy(mc->active, P + p_count, L.count_bytes);
 	return SIFT3D_OK;
 }
 }  // namespace
@@ -138,4 +165,13 @@ extern "C" int sift3d_icgn2(const float *ref, int rnx, int rny, int rnz, const f
                             sift3d_icgn2_result *out, double *seconds) {
 	return run_icgn<SecondOrder>("sift3d_icgn2", 2, false, ref, rnx, rny, rnz, tar, tnx, tny, tnz, points3, m, init30, o, tar_is_coefficients,
 	                             on_device, device, out, seconds);
+}
+
+extern "C" int sift3d_icgn_masked(const float *ref, int rnx, int rny, int rnz, const float *tar, int tnx, int tny, int tnz,
+                                  const unsigned char *mask, const int *points3, int m, const double *init12, const sift3d_icgn_options *o,
+                                  float min_fraction, int tar_is_coefficients, int on_device, int device, sift3d_icgn_result *out, int *active,
+                                  double *seconds) {
+	const MaskCall mc = {mask, min_fraction, active};
+	return run_icgn<FirstOrder, true>("sift3d_icgn_masked", 2, false, ref, rnx, rny, rnz, tar, tnx, tny, tnz, points3, m, init12, o, tar_is_coefficients,
+	                            on_device, device, out, seconds, &mc);
 }

@@ -41,13 +41,18 @@ inline bool icgn_args_ok(const void *ref, int rnx, int rny, int rnz, const void 
 	return kind == 2 ? (coef == 0 || coef == 1) : coef == 0;
 }
 
+// sift3d_icgn_masked's own refusals, beside icgn_args_ok's with sift3d_icgn2's rules (max_interpolation 2, bspline 0)
+inline bool icgn_mask_args_ok(const void *mask, float min_fraction) { return mask && min_fraction >= 0.f && min_fraction <= 1.f; }  // (a NaN fails both)
+
 // device scratch of a call: [results m | state m | (host inputs) ref | tar | points | init | (prefilter) coefficients | the y pass's
-// output]; the pinned host block holds the results.  o_opt (PairPlan) is the init table's offset.
+// output | (masked) the active bytes of R's voxels | the active counts m | (masked, host inputs) mask]; the pinned host block holds
+// the results and, 256-aligned behind them, the active counts.  o_opt (PairPlan) is the init table's offset.  The pieces of a masked
+// call come last: an unmasked call's layout does not know of them.
 struct IcgnLayout : PairPlan {
-	size_t res_bytes, o_state, o_coef, o_tmp, end;
+	size_t res_bytes, o_state, o_coef, o_tmp, o_act, o_count, o_mask, b_mask, count_bytes, end;
 };
 inline IcgnLayout icgn_layout(int m, size_t nr, size_t nt, bool on_device, bool has_init, bool filter, size_t state_bytes, size_t result_bytes,
-                              int parameters) {
+                              int parameters, bool masked = false) {
 	IcgnLayout g;
 	Layout L;
 	g.res_bytes = result_bytes * (size_t)m;
@@ -56,6 +61,11 @@ inline IcgnLayout icgn_layout(int m, size_t nr, size_t nt, bool on_device, bool 
 	g.plan(L, on_device, nr, nt, m, has_init ? sizeof(double) * parameters : 0);
 	g.o_coef = L.take(filter ? sizeof(float) * nt : 0);
 	g.o_tmp = L.take(filter ? sizeof(float) * nt : 0);
+	g.count_bytes = masked ? sizeof(int) * (size_t)m : 0;
+	g.b_mask = masked && !on_device ? nr : 0;
+	g.o_act = L.take(masked ? nr : 0);
+	g.o_count = L.take(g.count_bytes);
+	g.o_mask = L.take(g.b_mask);
 	g.end = L.end;
 	return g;
 }

@@ -115,28 +115,52 @@ __device__ inline float sample_shifted(const IcgnVol &T, const int ci[3], const 
 
 // Rm: the mean of R over the subset of radius r at q, fp64 in a fixed order through red[][0]; every thread returns the same value.
 // Two barriers: red is free again on return.
-template <int K>
-__device__ __forceinline__ double subset_mean(const IcgnVol &R, const int q[3], int r, double (*red)[K]) {
+// MASKED (sift3d_icgn_masked): Aq is the active byte of the voxel q (the volume k_mask_active wrote, in R's layout); an inactive voxel
+// is skipped -- R is not read there -- while the walk advances as it does unmasked, and the mean is that of the *n active voxels: their
+// count, an integer sum in the wave (through red[][1], exact in fp64).  n = 0 returns NaN.  The unmasked form reads neither argument.
+template <int K, bool MASKED = false>
+__device__ __forceinline__ double subset_mean(const IcgnVol &R, const int q[3], int r, double (*red)[K], const unsigned char *Aq = nullptr,
+                                              int *n = nullptr) {
 	const int D = 2 * r + 1, N = D * D * D;
 	const SubsetWalk W(r);
 	const float *Rq = R.d + vidx(R, q[0], q[1], q[2]);
 	const int sy = R.nx, sz = R.nx * R.ny;
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	double s = 0.0;
+	int cnt = 0;
 	{
 		int dx, dy, dz;
 		W.start(tid, dx, dy, dz);
 		for (int i = tid; i < N; i += kThreads) {
-			s += (double)Rq[dz * sz + dy * sy + dx];
+			if constexpr (MASKED) {
+				if (Aq[dz * sz + dy * sy + dx]) {
+					s += (double)Rq[dz * sz + dy * sy + dx];
+					cnt++;
+				}
+			} else {
+				s += (double)Rq[dz * sz + dy * sy + dx];
+			}
 			W.next(dx, dy, dz);
 		}
 	}
 	s = wave_sum(s);
-	if (lane == 0) red[wv][0] = s;
+	if constexpr (MASKED)
+		for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+	if (lane == 0) {
+		red[wv][0] = s;
+		if constexpr (MASKED) red[wv][1] = (double)cnt;
+	}
 	__syncthreads();
-	const double Rm = (((red[0][0] + red[1][0]) + red[2][0]) + red[3][0]) / (double)N;
-	__syncthreads();
-	return Rm;
+	if constexpr (MASKED) {
+		*n = (int)(((red[0][1] + red[1][1]) + red[2][1]) + red[3][1]);
+		const double Rm = (((red[0][0] + red[1][0]) + red[2][0]) + red[3][0]) / (double)*n;
+		__syncthreads();
+		return Rm;
+	} else {
+		const double Rm = (((red[0][0] + red[1][0]) + red[2][0]) + red[3][0]) / (double)N;
+		__syncthreads();
+		return Rm;
+	}
 }
 
 // Cholesky H = L L^T in the lower triangle of A (LDS, filled by the caller before the call), a column per step, the trailing update

@@ -14,6 +14,10 @@
 // (fp64: the variance is their difference); the reduction is fp64.  No float atomics: two calls give the same bits.
 // sift3d_icgn_bspline runs the same two launches with the cubic B-spline weights on the prefiltered T (kernels_bspline.hip): the
 // third instantiation of k_icgn_iterate.
+// sift3d_icgn_masked runs the MASKED instantiations of both kernels behind k_mask_active: every sum skips the voxels that are not
+// active (one byte load per voxel and pass; a wave whose voxels are all inactive branches over the body), the walk is the unmasked
+// one, and the active count n of a POI -- an int per POI beside the state records, IcgnState keeps its size -- takes N's place.  The
+// unmasked instantiations are the kernels as they were: every masked piece stands under `if constexpr`.
 #include "icgn_subset.h"
 
 #include <math.h>
@@ -84,8 +88,17 @@ __device__ inline int h_piece(int i, int j) {  // H(i, j) -> index into the 60 H
 	return pp * 10 + mm;
 }
 
+// The masked instantiations take one more kernel argument, the IcgnMask; the unmasked ones take none (MASK is empty), so their
+// signature and kernel-argument segment are what they were.
+__device__ inline IcgnMask mask_of() { return IcgnMask{nullptr, nullptr, 0.f}; }
+__device__ inline IcgnMask mask_of(IcgnMask m) { return m; }
+
+template <bool MASKED, class... MASK>
 __global__ __launch_bounds__(kThreads) void k_icgn_prepare(IcgnVol R, IcgnVol T, const int *__restrict__ pts, const double *__restrict__ init,
-                                                          int r, int cubic, IcgnState *__restrict__ state, sift3d_icgn_result *__restrict__ out) {
+                                                          int r, int cubic, IcgnState *__restrict__ state, sift3d_icgn_result *__restrict__ out,
+                                                          MASK... mask) {
+	static_assert(sizeof...(MASK) == (MASKED ? 1 : 0), "the masked instantiation takes the IcgnMask");
+	const IcgnMask M = mask_of(mask...);
 	__shared__ double red[kWaves][kPrepSums];
 	__shared__ double A[12][13];
 	__shared__ int s_fail;
@@ -108,6 +121,7 @@ __global__ __launch_bounds__(kThreads) void k_icgn_prepare(IcgnVol R, IcgnVol T,
 		if (tid == 0) {
 			S->status = status;
 			write_result(out + poi, p, 0.0, 0.0, 0, status);
+			if constexpr (MASKED) M.n[poi] = 0;  // no voxel is read
 		}
 		return;
 	}
@@ -115,8 +129,21 @@ __global__ __launch_bounds__(kThreads) void k_icgn_prepare(IcgnVol R, IcgnVol T,
 	const SubsetWalk W(r);
 	const float *Rq = R.d + vidx(R, q[0], q[1], q[2]);
 	const int sy = R.nx, sz = R.nx * R.ny;
-	// pass 1: Rm
-	const double Rm = subset_mean(R, q, r, red);
+	// pass 1: Rm (masked: and the active count, status 7)
+	const unsigned char *Aq = MASKED ? M.act + vidx(R, q[0], q[1], q[2]) : nullptr;
+	int n = N;
+	const double Rm = subset_mean<kPrepSums, MASKED>(R, q, r, red, Aq, &n);
+	if constexpr (MASKED) {
+		const bool few = n == 0 || (double)n < (double)M.min_fraction * (double)N;  // uniform: every thread holds the same n
+		if (tid == 0) {
+			M.n[poi] = n;
+			if (few) {
+				S->status = 7;
+				write_result(out + poi, p, 0.0, 0.0, 0, 7);
+			}
+		}
+		if (few) return;
+	}
 	const float rmf = (float)Rm;
 	// pass 2: the constants
 	double acc[kPrepSums];
@@ -126,32 +153,36 @@ __global__ __launch_bounds__(kThreads) void k_icgn_prepare(IcgnVol R, IcgnVol T,
 		int dx, dy, dz;
 		W.start(tid, dx, dy, dz);
 		for (int i = tid; i < N; i += kThreads) {
-			const float *c = Rq + (dz * sz + dy * sy + dx);
-			const float gxf = 0.5f * (c[1] - c[-1]), gyf = 0.5f * (c[sy] - c[-sy]), gzf = 0.5f * (c[sz] - c[-sz]);
-			const double rv = (double)c[0] - Rm;
-			const double g[3] = {(double)gxf, (double)gyf, (double)gzf};
-			const double v[4] = {1.0, (double)dx, (double)dy, (double)dz};
-			acc[0] += rv * rv;
-			acc[1] += (double)(c[0] - rmf);
+			bool on = true;
+			if constexpr (MASKED) on = Aq[dz * sz + dy * sy + dx] != 0;
+			if (on) {
+				const float *c = Rq + (dz * sz + dy * sy + dx);
+				const float gxf = 0.5f * (c[1] - c[-1]), gyf = 0.5f * (c[sy] - c[-sy]), gzf = 0.5f * (c[sz] - c[-sz]);
+				const double rv = (double)c[0] - Rm;
+				const double g[3] = {(double)gxf, (double)gyf, (double)gzf};
+				const double v[4] = {1.0, (double)dx, (double)dy, (double)dz};
+				acc[0] += rv * rv;
+				acc[1] += (double)(c[0] - rmf);
 #pragma unroll
-			for (int a = 0; a < 3; a++)
+				for (int a = 0; a < 3; a++)
 #pragma unroll
-				for (int k = 0; k < 4; k++) {
-					acc[2 + 4 * a + k] += g[a] * v[k];
-					acc[14 + 4 * a + k] += (g[a] * v[k]) * rv;
-				}
-			int pp = 0;
+					for (int k = 0; k < 4; k++) {
+						acc[2 + 4 * a + k] += g[a] * v[k];
+						acc[14 + 4 * a + k] += (g[a] * v[k]) * rv;
+					}
+				int pp = 0;
 #pragma unroll
-			for (int a = 0; a < 3; a++)
+				for (int a = 0; a < 3; a++)
 #pragma unroll
-				for (int b = a; b < 3; b++, pp++) {
-					const double w = g[a] * g[b];
-					int mm = 0;
+					for (int b = a; b < 3; b++, pp++) {
+						const double w = g[a] * g[b];
+						int mm = 0;
 #pragma unroll
-					for (int mi = 0; mi < 4; mi++)
+						for (int mi = 0; mi < 4; mi++)
 #pragma unroll
-						for (int mj = mi; mj < 4; mj++, mm++) acc[26 + pp * 10 + mm] += w * (v[mi] * v[mj]);
-				}
+							for (int mj = mi; mj < 4; mj++, mm++) acc[26 + pp * 10 + mm] += w * (v[mi] * v[mj]);
+					}
+			}
 			W.next(dx, dy, dz);
 		}
 	}
@@ -216,9 +247,10 @@ __global__ __launch_bounds__(kThreads) void k_icgn_prepare(IcgnVol R, IcgnVol T,
 // the taps leaves the interpolation's rounding.  Tc is one voxel: an outlier there (a hot voxel |Tc - Tm| >> dT) makes every T' large
 // and costs the fp32 sums that many ulps, as a T far brighter than R did under the shift by Rm; a mean of T would need a pass of its
 // own.  Returns Tc - (float)Rm, which turns the sums into those of T - Rm.
-template <int KIND>
+// MASKED: Aq is the active byte of the voxel q; the body is skipped for an inactive voxel (neither R nor T is read there).
+template <int KIND, bool MASKED>
 __device__ inline double subset_pass(const IcgnVol &R, const IcgnVol &T, const int q[3], int r, float rmf, const double p[12],
-                                   double (*red)[kIterSums], double sums[kIterSums]) {
+                                   double (*red)[kIterSums], double sums[kIterSums], const unsigned char *Aq) {
 	constexpr bool CUBIC = KIND != kLinear;  // 64 taps
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	const int D = 2 * r + 1, N = D * D * D;
@@ -249,24 +281,28 @@ __device__ inline double subset_pass(const IcgnVol &R, const IcgnVol &T, const i
 	W.start(tid, dx, dy, dz);
 #pragma unroll 1
 	for (int i = tid; i < N; i += kThreads) {
-		const float fx = (float)dx, fy = (float)dy, fz = (float)dz;
-		float o[3];
+		bool on = true;
+		if constexpr (MASKED) on = Aq[dz * sz + dy * sy + dx] != 0;
+		if (on) {
+			const float fx = (float)dx, fy = (float)dy, fz = (float)dz;
+			float o[3];
 #pragma unroll
-		for (int a = 0; a < 3; a++) o[a] = cf[a] + ((F[3 * a] * fx + F[3 * a + 1] * fy) + F[3 * a + 2] * fz);
-		const float tv = sample_shifted<KIND>(T, ci, o, tc, lo, hx, hy, hz, tsy, tsz);
-		const float *c = Rq + (dz * sz + dy * sy + dx);
-		const float g[3] = {0.5f * (c[1] - c[-1]), 0.5f * (c[sy] - c[-sy]), 0.5f * (c[sz] - c[-sz])};
-		const float tp = tv, rp = c[0] - rmf;
-		sT += (double)tp;
-		sTT = fma((double)tp, (double)tp, sTT);
-		acc[12] = fmaf(rp, tp, acc[12]);
+			for (int a = 0; a < 3; a++) o[a] = cf[a] + ((F[3 * a] * fx + F[3 * a + 1] * fy) + F[3 * a + 2] * fz);
+			const float tv = sample_shifted<KIND>(T, ci, o, tc, lo, hx, hy, hz, tsy, tsz);
+			const float *c = Rq + (dz * sz + dy * sy + dx);
+			const float g[3] = {0.5f * (c[1] - c[-1]), 0.5f * (c[sy] - c[-sy]), 0.5f * (c[sz] - c[-sz])};
+			const float tp = tv, rp = c[0] - rmf;
+			sT += (double)tp;
+			sTT = fma((double)tp, (double)tp, sTT);
+			acc[12] = fmaf(rp, tp, acc[12]);
 #pragma unroll
-		for (int a = 0; a < 3; a++) {
-			const float gt = g[a] * tp;
-			acc[4 * a] += gt;
-			acc[4 * a + 1] = fmaf(gt, fx, acc[4 * a + 1]);
-			acc[4 * a + 2] = fmaf(gt, fy, acc[4 * a + 2]);
-			acc[4 * a + 3] = fmaf(gt, fz, acc[4 * a + 3]);
+			for (int a = 0; a < 3; a++) {
+				const float gt = g[a] * tp;
+				acc[4 * a] += gt;
+				acc[4 * a + 1] = fmaf(gt, fx, acc[4 * a + 1]);
+				acc[4 * a + 2] = fmaf(gt, fy, acc[4 * a + 2]);
+				acc[4 * a + 3] = fmaf(gt, fz, acc[4 * a + 3]);
+			}
 		}
 		W.next(dx, dy, dz);
 	}
@@ -286,10 +322,12 @@ __device__ inline double subset_pass(const IcgnVol &R, const IcgnVol &T, const i
 	return (double)tc - (double)rmf;
 }
 
-template <int KIND>
+template <int KIND, bool MASKED, class... MASK>
 __global__ __launch_bounds__(kThreads) void k_icgn_iterate(IcgnVol R, IcgnVol T, const int *__restrict__ pts, const double *__restrict__ init,
                                                           int r, int max_it, double tol, const IcgnState *__restrict__ state,
-                                                          sift3d_icgn_result *__restrict__ out) {
+                                                          sift3d_icgn_result *__restrict__ out, MASK... mask) {
+	static_assert(sizeof...(MASK) == (MASKED ? 1 : 0), "the masked instantiation takes the IcgnMask");
+	const IcgnMask M = mask_of(mask...);
 	__shared__ double red[2][kWaves][kIterSums];  // by pass parity: one barrier per pass
 	__shared__ double cst[168];                   // H^-1, c1, c2: read in the solve only (not held in registers across the passes)
 	const int poi = blockIdx.x;
@@ -301,14 +339,16 @@ __global__ __launch_bounds__(kThreads) void k_icgn_iterate(IcgnVol R, IcgnVol T,
 	double p[12];
 #pragma unroll
 	for (int k = 0; k < 12; k++) p[k] = init ? init[12 * (size_t)poi + k] : 0.0;
-	const double N = (double)((2 * r + 1) * (2 * r + 1) * (2 * r + 1)), dr = S->dr, sr = S->sr, r2 = (double)r * (double)r;
+	// (masked: N is the POI's active count, which the prepare kernel left beside the state records)
+	const double N = MASKED ? (double)M.n[poi] : (double)((2 * r + 1) * (2 * r + 1) * (2 * r + 1)), dr = S->dr, sr = S->sr, r2 = (double)r * (double)r;
+	const unsigned char *Aq = MASKED ? M.act + vidx(R, q[0], q[1], q[2]) : nullptr;
 	const float rmf = S->rm;
 	int it = 0, status = kRun;
 	double last = 0.0;
 	bool done = false;
 	for (int pass = 0;; pass++) {
 		double s[kIterSums];
-		const double sh = subset_pass<KIND>(R, T, q, r, rmf, p, red[pass & 1], s);
+		const double sh = subset_pass<KIND, MASKED>(R, T, q, r, rmf, p, red[pass & 1], s, Aq);
 		// s: 0 sum T', 1 sum T'^2, 2..13 sum SD T', 14 sum R'T'
 		const double tm = s[0] / N;
 		const double dt2 = s[1] - s[0] * tm;
@@ -400,9 +440,17 @@ size_t icgn_state_bytes() { return sizeof(IcgnState); }
 void launch_icgn(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_init, int r, int max_it, double tol, int kind, void *d_state,
                  sift3d_icgn_result *d_out, hipStream_t st) {
 	IcgnState *S = static_cast<IcgnState *>(d_state);
-	hipLaunchKernelGGL(k_icgn_prepare, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, kind != kLinear, S, d_out);
-	hipLaunchKernelGGL(by_kind(kind, k_icgn_iterate<kKeys>, k_icgn_iterate<kLinear>, k_icgn_iterate<kBspline>), dim3(m), dim3(kThreads), 0, st, R, T,
-	                   d_pts, d_init, r, max_it, tol, S, d_out);
+	hipLaunchKernelGGL(k_icgn_prepare<false>, dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, kind != kLinear, S, d_out);
+	hipLaunchKernelGGL(by_kind(kind, k_icgn_iterate<kKeys, false>, k_icgn_iterate<kLinear, false>, k_icgn_iterate<kBspline, false>), dim3(m),
+	                   dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out);
+}
+
+void launch_icgn_masked(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_init, int r, int max_it, double tol, int kind, void *d_state,
+                        sift3d_icgn_result *d_out, IcgnMask M, hipStream_t st) {
+	IcgnState *S = static_cast<IcgnState *>(d_state);
+	hipLaunchKernelGGL((k_icgn_prepare<true, IcgnMask>), dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, kind != kLinear, S, d_out, M);
+	hipLaunchKernelGGL(by_kind(kind, k_icgn_iterate<kKeys, true, IcgnMask>, k_icgn_iterate<kLinear, true, IcgnMask>, k_icgn_iterate<kBspline, true, IcgnMask>), dim3(m),
+	                   dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out, M);
 }
 
 }  // namespace s3d

@@ -349,6 +349,23 @@ size_t icgn_state_bytes();  // per-POI scratch record of the prepare kernel
 // Keys, 1 trilinear, 2 cubic B-spline (T then holds the prefilter's coefficients)
 void launch_icgn(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_init, int r, int max_it, double tol, int kind, void *d_state,
                  sift3d_icgn_result *d_out, hipStream_t st);
+// what the masked instantiations of the two kernels read beside the volumes (sift3d_icgn_masked): act, the active bytes of R's voxels
+// (launch_mask_active's output); n, m ints, the active count per POI (written by the prepare kernel, read by the iterate kernel and
+// returned as `active`); min_fraction, status 7's bound
+struct IcgnMask {
+	const unsigned char *act;
+	int *n;
+	float min_fraction;
+};
+// launch_icgn limited to the active voxels
+void launch_icgn_masked(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_init, int r, int max_it, double tol, int kind, void *d_state,
+                        sift3d_icgn_result *d_out, IcgnMask M, hipStream_t st);
+
+// ---- kernels_mask.hip: the byte volumes of the masked IC-GN (sift3d_icgn_masked, sift3d_mask_from_level) --------------------------
+// d_act[i] = 1 where voxel i and its six face neighbours lie in the volume and have a non-zero byte in d_mask, else 0; d_act != d_mask
+void launch_mask_active(const unsigned char *d_mask, int nx, int ny, int nz, unsigned char *d_act, hipStream_t st);
+// d_mask[i] = 1 where (double)d_vol[i] >= level, else 0
+void launch_mask_threshold(const float *d_vol, size_t n, double level, unsigned char *d_mask, hipStream_t st);
 
 // ---- kernels_icgn2.hip: second-order IC-GN (sift3d_icgn2, include/sift3d_hip.h) --------------------------------------------------
 size_t icgn2_state_bytes();  // per-POI scratch record of the prepare kernel

@@ -93,7 +93,7 @@ struct SIFT_LIBRARY_API IcgnOptions {
 
 // the refined first-order shape function at one point of interest: p = (u, ux, uy, uz, v, vx, vy, vz, w, wx, wy, wz) (include/sift3d_hip.h);
 // status 0 converged, 1 max_iterations reached, 2 subset outside ref, 3 warped subset outside tar, 4 flat subset, 5 init not finite,
-// 6 singular step, -1 the call failed (message on stderr, like EstimateAffine)
+// 6 singular step, 7 too few active voxels (RefineDisplacementsMasked only), -1 the call failed (message on stderr, like EstimateAffine)
 struct SIFT_LIBRARY_API IcgnResult {
 	double p[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 	double zncc = 0, last_step = 0;
@@ -185,6 +185,22 @@ SIFT_LIBRARY_API std::vector<IcgnResult> RefineDisplacements(const float *ref, i
                                                              const std::vector<Cvec> &points, const std::vector<AffineFit> *init,
                                                              const IcgnOptions &opts, const std::vector<SearchResult> *fallback,
                                                              bool tar_is_coefficients);
+
+// mask (nx x ny x nz bytes, host memory, x fastest) = 1 where vol >= level, else 0 (a NaN voxel is 0): SelectSubsets' rule for a material
+// voxel, and the mask RefineDisplacementsMasked takes.  false: the call failed (message on stderr).  seconds (may be null): device time
+SIFT_LIBRARY_API bool MaskFromLevel(const float *vol, int nx, int ny, int nz, double level, unsigned char *mask, double *seconds = nullptr);
+
+// RefineDisplacements at a specimen's surface, at pores and cracks and where two bodies touch: every sum of the correlation runs over
+// the active voxels of the subset only -- those that, with their six face neighbours, are in mask (one byte per voxel of ref, any
+// non-zero byte is "in"; include/sift3d_hip.h, sift3d_icgn_masked).  A point whose subset holds no active voxel, or fewer than
+// min_fraction (0..1) of its (2r+1)^3, returns status 7.  init: one local affine fit per point or null (zero); opts.interpolation 0, 1
+// or 2, tar_is_coefficients as for RefineDisplacements (interpolation 2 only).  active (may be null): resized to one count of active
+// voxels per point
+SIFT_LIBRARY_API std::vector<IcgnResult> RefineDisplacementsMasked(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny,
+                                                                   int tnz, const unsigned char *mask, const std::vector<Cvec> &points,
+                                                                   const std::vector<AffineFit> *init = nullptr,
+                                                                   const IcgnOptions &opts = IcgnOptions(), float min_fraction = 0.f,
+                                                                   std::vector<int> *active = nullptr, bool tar_is_coefficients = false);
 
 // the refined second-order shape function at one point of interest: p = (c, cx, cy, cz, cxx, cyy, czz, cxy, cxz, cyz) of u, then v, then w
 // -- the displacement and its first and second derivatives at the point (include/sift3d_hip.h); status as IcgnResult's

@@ -1,6 +1,6 @@
-// cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine / PredictPositions / GuidedMatch / SearchDisplacements / RefineDisplacements / ValidateDisplacements /
-// ComputeStrains over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_predict_positions / sift3d_match_guided / sift3d_zncc_search / sift3d_icgn / sift3d_icgn_bspline /
-// sift3d_validate_displacements / sift3d_strain, and
+// cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine / PredictPositions / GuidedMatch / SearchDisplacements / RefineDisplacements / RefineDisplacementsMasked / MaskFromLevel / ValidateDisplacements /
+// ComputeStrains over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_predict_positions / sift3d_match_guided / sift3d_zncc_search / sift3d_icgn / sift3d_icgn_bspline / sift3d_icgn_masked /
+// sift3d_mask_from_level / sift3d_validate_displacements / sift3d_strain, and
 // CPUSIFT::PrefilterBSpline over sift3d_bspline_prefilter (include/sift3d_hip.h).
 #include "../Include/cRegistration.h"
 
@@ -331,6 +331,50 @@ bool GroupSubsetsByRadius(const std::vector<SubsetQuality> &quality, int r_min, 
 	return true;
 }
 
+// what RefineDisplacements and RefineDisplacementsMasked share: the initial parameters of the fits (a failed fit: a NaN row, or, with
+// fallback, the search's displacement), the options record (without the interpolation, which the two calls map differently) and the
+// conversion of the result records
+static void icgn_init_rows(const std::vector<AffineFit> &init, const std::vector<SearchResult> *fallback, const std::vector<int> &q, size_t m,
+                           std::vector<double> &p0) {
+	std::vector<sift3d_affine_fit> f(m ? m : 1);
+	memset(f.data(), 0, sizeof(sift3d_affine_fit) * f.size());
+	for (size_t i = 0; i < m; i++) {
+		memcpy(f[i].A, init[i].A, sizeof(f[i].A));
+		f[i].status = init[i].status;
+	}
+	p0.assign(12 * (m ? m : 1), 0.0);
+	sift3d_icgn_init_from_fits(f.data(), q.data(), (int)m, p0.data());
+	if (fallback) {  // the NaN rows of the failed fits take the search's displacement
+		std::vector<sift3d_search_result> sr(m ? m : 1);
+		memset(sr.data(), 0, sizeof(sift3d_search_result) * sr.size());
+		for (size_t i = 0; i < m; i++) {
+			memcpy(sr[i].d, (*fallback)[i].d, sizeof(sr[i].d));
+			sr[i].status = (*fallback)[i].status;
+		}
+		sift3d_icgn_init_from_search(sr.data(), (int)m, 1, p0.data());
+	}
+}
+
+static sift3d_icgn_options icgn_options_of(const IcgnOptions &opts) {
+	sift3d_icgn_options o;
+	sift3d_default_icgn_options(&o);
+	o.subset_radius = opts.subset_radius;
+	o.max_iterations = opts.max_iterations;
+	o.tolerance = opts.tolerance;
+	return o;
+}
+
+static void icgn_records(const std::vector<sift3d_icgn_result> &r, double sec, std::vector<IcgnResult> &res) {
+	for (size_t i = 0; i < res.size(); i++) {
+		memcpy(res[i].p, r[i].p, sizeof(res[i].p));
+		res[i].zncc = r[i].zncc;
+		res[i].last_step = r[i].last_step;
+		res[i].iterations = r[i].iterations;
+		res[i].status = r[i].status;
+		res[i].seconds = sec;
+	}
+}
+
 std::vector<IcgnResult> RefineDisplacements(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
                                             const std::vector<Cvec> &points, const std::vector<AffineFit> *init, const IcgnOptions &opts,
                                             const std::vector<SearchResult> *fallback) {
@@ -353,30 +397,8 @@ std::vector<IcgnResult> RefineDisplacements(const float *ref, int nx, int ny, in
 		return res;
 	}
 	std::vector<double> p0;
-	if (init) {
-		std::vector<sift3d_affine_fit> f(m ? m : 1);
-		memset(f.data(), 0, sizeof(sift3d_affine_fit) * f.size());
-		for (size_t i = 0; i < m; i++) {
-			memcpy(f[i].A, (*init)[i].A, sizeof(f[i].A));
-			f[i].status = (*init)[i].status;
-		}
-		p0.assign(12 * (m ? m : 1), 0.0);
-		sift3d_icgn_init_from_fits(f.data(), q.data(), (int)m, p0.data());
-		if (fallback) {  // the NaN rows of the failed fits take the search's displacement
-			std::vector<sift3d_search_result> sr(m ? m : 1);
-			memset(sr.data(), 0, sizeof(sift3d_search_result) * sr.size());
-			for (size_t i = 0; i < m; i++) {
-				memcpy(sr[i].d, (*fallback)[i].d, sizeof(sr[i].d));
-				sr[i].status = (*fallback)[i].status;
-			}
-			sift3d_icgn_init_from_search(sr.data(), (int)m, 1, p0.data());
-		}
-	}
-	sift3d_icgn_options o;
-	sift3d_default_icgn_options(&o);
-	o.subset_radius = opts.subset_radius;
-	o.max_iterations = opts.max_iterations;
-	o.tolerance = opts.tolerance;
+	if (init) icgn_init_rows(*init, fallback, q, m, p0);
+	sift3d_icgn_options o = icgn_options_of(opts);
 	const bool bspline = opts.interpolation == 2;  // the C entry of its own: sift3d_icgn's option stays 0 / 1
 	o.interpolation = bspline ? 0 : opts.interpolation;
 	std::vector<sift3d_icgn_result> r(m ? m : 1);
@@ -389,14 +411,44 @@ std::vector<IcgnResult> RefineDisplacements(const float *ref, int nx, int ny, in
 		fprintf(stderr, "[3dsift_amd] RefineDisplacements: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
 		return res;
 	}
-	for (size_t i = 0; i < m; i++) {
-		memcpy(res[i].p, r[i].p, sizeof(res[i].p));
-		res[i].zncc = r[i].zncc;
-		res[i].last_step = r[i].last_step;
-		res[i].iterations = r[i].iterations;
-		res[i].status = r[i].status;
-		res[i].seconds = sec;
+	icgn_records(r, sec, res);
+	return res;
+}
+
+bool MaskFromLevel(const float *vol, int nx, int ny, int nz, double level, unsigned char *mask, double *seconds) {
+	const int rc = sift3d_mask_from_level(vol, nx, ny, nz, level, mask, 0, GetDevice(), seconds);
+	if (rc != SIFT3D_OK) fprintf(stderr, "[3dsift_amd] MaskFromLevel: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+	return rc == SIFT3D_OK;
+}
+
+std::vector<IcgnResult> RefineDisplacementsMasked(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
+                                                  const unsigned char *mask, const std::vector<Cvec> &points, const std::vector<AffineFit> *init,
+                                                  const IcgnOptions &opts, float min_fraction, std::vector<int> *active,
+                                                  bool tar_is_coefficients) {
+	const size_t m = points.size();
+	std::vector<IcgnResult> res(m);
+	if (active) active->assign(m, 0);
+	std::vector<int> q;
+	if (!int_triples("RefineDisplacementsMasked", "point", points, q)) return res;
+	if (init && init->size() != m) {
+		fprintf(stderr, "[3dsift_amd] RefineDisplacementsMasked: %zu initial fits for %zu points\n", init->size(), m);
+		return res;
 	}
+	std::vector<double> p0;
+	if (init) icgn_init_rows(*init, nullptr, q, m, p0);
+	sift3d_icgn_options o = icgn_options_of(opts);
+	o.interpolation = opts.interpolation;  // 0, 1 or 2: one C entry for the three
+	std::vector<sift3d_icgn_result> r(m ? m : 1);
+	std::vector<int> n(m ? m : 1, 0);
+	double sec = 0;
+	const int rc = sift3d_icgn_masked(ref, nx, ny, nz, tar, tnx, tny, tnz, mask, q.data(), (int)m, init ? p0.data() : nullptr, &o, min_fraction,
+	                                  tar_is_coefficients ? 1 : 0, 0, GetDevice(), r.data(), n.data(), &sec);
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] RefineDisplacementsMasked: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return res;
+	}
+	icgn_records(r, sec, res);
+	if (active) active->assign(n.begin(), n.begin() + m);
 	return res;
 }
 

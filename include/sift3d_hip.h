@@ -1097,6 +1097,51 @@ int sift3d_subset_quality(const float *ref, int nx, int ny, int nz, const int *p
  * filled where given), or a status-0 record whose radius lies outside r_min..r_max. */
 int sift3d_subset_group_by_radius(const sift3d_subset_result *res, int m, int r_min, int r_max, int *order, int *offsets, int *count);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Masked IC-GN: subsets limited to a voxel mask of the reference (no reference counterpart: what DVC codes do at a specimen's surface,
+ * at pores and cracks and where two bodies touch -- they correlate over "the voxels of the subset that are material").  A POI closer
+ * than r to such an edge has a full cube [-r, r]^3 that holds air or the other body; sift3d_icgn converges there with a high zncc and
+ * a displacement that is wrong by tenths of a voxel, and the screening can only reject the point (status 3).
+ * Numerical contract (a tolerance contract like sift3d_icgn's; tests/icgn_mask_ref.py restates it in NumPy fp64):
+ *   Mask: one unsigned char per voxel of R, in R's layout [z][y][x]; any non-zero byte is "in".
+ *   Active voxel: it and its six face neighbours lie in R and are in the mask, so the central differences of R never straddle the
+ *     mask's edge.  R's own boundary voxels are never active.
+ *   sift3d_icgn_masked is sift3d_icgn (o->interpolation 0 or 1) or sift3d_icgn_bspline (2) with one change: every sum over the subset
+ *     runs over the active voxels of the cube only -- Rm, dR, sum SD, sum SD^T R', H, the correction term of zncc and the sums of each
+ *     pass (sum T', sum T'^2, sum R'T', sum SD^T T') -- in the same walk order, an inactive voxel being skipped, not multiplied by
+ *     zero: neither R nor T is read there.  The active count n of the cube takes N's place in Rm, Tm and sum (T - Rm)^2.
+ *   Everything else is sift3d_icgn's contract word for word: the 8-corner domain test of the full box, status 2 on the full cube plus
+ *     its margin, Tc (T's voxel under the subset's centre, active or not), the update, the norm with r^2 and the status table.
+ *   Status 7 (new): n == 0, or (double)n < (double)min_fraction * (double)N with N = (2r+1)^3 (the form of the screening's status-3
+ *     rule).  Checked after 5 and 2 and before 4; returns the init as given, iterations 0, zncc 0.  A mask that leaves H not positive
+ *     definite (fewer than 12 active voxels, or active voxels in one plane) gives status 4 as a flat subset does.
+ *   active[i] (may be NULL): n of POI i; 0 with status 5 or 2, where no voxel is read.
+ *   Consequences (tests/test_gpu_icgn_mask.py):
+ *     (a) with a mask whose bytes are all non-zero every field of every record has the bits of sift3d_icgn / sift3d_icgn_bspline on
+ *         the same inputs (n = N; the walk, the per-thread sums and the reduction are the unmasked kernel's);
+ *     (b) R's values at voxels that are neither active nor a face neighbour of an active voxel, non-finite ones included, do not
+ *         influence the result;
+ *     (c) two calls return the same bytes;
+ *     (d) a POI's record does not depend on the other POIs of the call.
+ * o->interpolation: 0 Keys, 1 trilinear, 2 cubic B-spline; tar_is_coefficients as for sift3d_icgn2 (0 unless interpolation is 2).
+ * SIFT3D_ERR_ARG (checked before any device call): sift3d_icgn's rules with these, a NULL mask, min_fraction outside 0..1 or NaN;
+ * m = 0 succeeds.  SIFT3D_ERR_NO_DEVICE after that check when no GPU is visible: there is no CPU fallback.  on_device != 0: ref, tar,
+ * mask, points3 and init12 are device pointers on `device`; out and active are host memory.  The call keeps one byte per voxel of R
+ * (two for host inputs) and 4 bytes per POI on the device beside sift3d_icgn's scratch; *seconds includes the pass that marks the
+ * active voxels.
+ *
+ * sift3d_mask_from_level: mask[i] = 1 where (double)vol[i] >= level, else 0 (a NaN voxel is 0): the screening's rule for `material`, so
+ * the mask and sift3d_subset_quality's count agree.  SIFT3D_ERR_ARG (before any device call): NULL vol / mask, a dimension < 1, 2^39
+ * voxels or more, a NaN level (+-INFINITY are levels).  on_device != 0: vol and mask are device pointers on `device`, ordered behind the
+ * legacy default stream; otherwise both are host memory.  *seconds (may be NULL): device time of the kernel.
+ * ------------------------------------------------------------------------------------------------------------ */
+int sift3d_icgn_masked(const float *ref, int rnx, int rny, int rnz, const float *tar, int tnx, int tny, int tnz,
+                       const unsigned char *mask /* rnx*rny*rnz */, const int *points3, int m, const double *init12,
+                       const sift3d_icgn_options *o, float min_fraction /* 0..1 */, int tar_is_coefficients, int on_device, int device,
+                       sift3d_icgn_result *out, int *active /* m, may be NULL */, double *seconds);
+int sift3d_mask_from_level(const float *vol, int nx, int ny, int nz, double level, unsigned char *mask, int on_device, int device,
+                           double *seconds);
+
 /* Test hooks, rare-path counters and the unit-level debug entry points live in include/sift3d_hip_test.h: this header is the
  * product boundary only. */
 const char *sift3d_error_string(int code);
