@@ -83,7 +83,7 @@ SYMBOLS = [
     # native driver of the z-slab sharding
     "sift3d_sharded_create", "sift3d_sharded_create_ex", "sift3d_sharded_run", "sift3d_sharded_num_keypoints", "sift3d_sharded_get_keypoints", "sift3d_sharded_info",
     "sift3d_sharded_error", "sift3d_sharded_destroy",
-    "sift3d_test_hook", "sift3d_debug_counters", "sift3d_debug_face_lookup", "sift3d_match_times", "sift3d_debug_copy_bandwidth",
+    "sift3d_test_hook", "sift3d_debug_counters", "sift3d_test_run_plan", "sift3d_debug_face_lookup", "sift3d_match_times", "sift3d_debug_copy_bandwidth",
     "sift3d_match_warmup", "sift3d_test_staging_slice", "sift3d_test_slab_plan", "sift3d_test_sharded_time_rank",
 ]
 HOOKS = {"dog_eager": 0, "glast_eager": 1, "det_serial": 2, "separable": 3, "desc_nocache": 4, "match_nodma": 5, "one_stream": 6,
@@ -379,6 +379,7 @@ def lib():
         L.sift3d_sharded_plan.argtypes = [C.c_void_p, _ip, _ip, _ip, _ip]
         L.sift3d_test_hook.argtypes = [C.c_int, C.c_int]
         L.sift3d_debug_counters.argtypes = [C.c_void_p, _ip]
+        L.sift3d_test_run_plan.argtypes = [C.c_void_p, _ip, C.c_int, _ip]
         L.sift3d_debug_face_lookup.argtypes = [_fp, C.c_int, C.c_int, _ip, _fp, C.c_int]
         L.sift3d_debug_copy_bandwidth.argtypes = [C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_double)]
         L.sift3d_match_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -1343,6 +1344,18 @@ class CSIFT3D:
         a = (C.c_int * 4)()
         _check(lib().sift3d_debug_counters(self._h, a))
         return {"list_regrows": a[0], "desc_second_passes": a[1], "match_exact_rows": a[2]}
+
+    def run_plan(self):
+        """the schedule of the last prepared run (sift3d_test_run_plan, layout: include/sift3d_hip_test.h): a dict of the run's values and
+        "octaves", one (head stream, tail stream, tail_moved, prio, head_slots, tail_slots) per octave; stream -1 = the chain stream"""
+        a = (C.c_int * 256)()
+        n = C.c_int(0)
+        _check(lib().sift3d_test_run_plan(self._h, a, 256, C.byref(n)))
+        keys = ["noct", "small_first", "chain", "small_hwp", "small_build_mask", "small_dog_mask", "dog_elide", "g_last_elide", "run_full",
+                "run_refine", "det_two", "det_early", "det_rest_stream", "det_rest_own", "emit"]
+        out = dict(zip(keys, a[:15]))
+        out["octaves"] = [tuple(a[15 + 6 * o:21 + 6 * o]) for o in range(out["noct"])]
+        return out
 
 
 def _params(kw):

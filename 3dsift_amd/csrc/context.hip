@@ -154,7 +154,6 @@ extern "C" int sift3d_destroy(sift3d_handle c) {
 	hipFree(c->d_masks2); hipFree(c->d_counts2); hipFree(c->d_offsets2);
 	if (c->ev_det_fork) hipEventDestroy(c->ev_det_fork);
 	if (c->ev_det_join) hipEventDestroy(c->ev_det_join);
-	if (c->ev_det_fork2) hipEventDestroy(c->ev_det_fork2);
 	if (c->ev_det_join2) hipEventDestroy(c->ev_det_join2);
 	hipFree(c->d_levels); hipFree(c->d_luts); hipFree(c->d_lutpool);
 	for (auto &e : c->ev) if (e) hipEventDestroy(e);
@@ -250,6 +249,9 @@ size_t arena_floats_of(const sift3d_ctx *c) {
 	return total;
 }
 
+// The heads of the octaves >= 1 gain from one in-order chain stream only where they are short launches: volumes of at most 4 M voxels
+static bool chain_stream_fits(const sift3d_ctx *c) { return (size_t)c->nx * c->ny * c->nz <= ((size_t)1 << 22); }
+
 int create_common(sift3d_handle *out, const CreateCfg &cfg, const sift3d_params *params, int device) {
 	*out = nullptr;
 	if (cfg.nx <= 0 || cfg.ny <= 0 || cfg.nz <= 0) { set_last_error("bad dimensions"); return SIFT3D_ERR_ARG; }
@@ -309,24 +311,10 @@ int create_common(sift3d_handle *out, const CreateCfg &cfg, const sift3d_params 
 	const bool one_stream = hook(SIFT3D_HOOK_ONE_STREAM) != 0;
 	for (size_t o = 0; o < c->ostream.size(); o++) {
 		if (o > 0 && one_stream) c->ostream[o] = c->stream;
-		else if (o > 0) {
-#ifndef S3D_STREAM_PRIO
-#define S3D_STREAM_PRIO 0  /* first octave whose stream is created with the highest queue priority (0: none) */
-#endif
-			int pr_lo = 0, pr_hi = 0;
-			if (S3D_STREAM_PRIO > 0 && (int)o >= S3D_STREAM_PRIO && hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi) == hipSuccess && pr_hi != pr_lo)
-				CHECKED(hipStreamCreateWithPriority(&c->ostream[o], hipStreamNonBlocking, pr_hi));
-			else
-				CHECKED(hipStreamCreateWithFlags(&c->ostream[o], hipStreamNonBlocking));
-		}
-		if (o == 1 && !one_stream && !c->slab) {
-#ifndef S3D_CHAIN_STREAM
-#define S3D_CHAIN_STREAM 1
-#endif
-			// (only for the volumes that use it, see run_enqueue: HIP deals streams to its four hardware queues in creation order, so one more
-			// stream changes which octave streams share a queue -- 480 x 500 x 300: pyramid 1.43 -> 1.61 ms, the simulated 8-rank run 40.5 -> 43.6 ms)
-			if (S3D_CHAIN_STREAM && (size_t)c->nx * c->ny * c->nz <= ((size_t)1 << 22)) CHECKED(hipStreamCreateWithFlags(&c->cstream, hipStreamNonBlocking));
-		}
+		else if (o > 0) CHECKED(hipStreamCreateWithFlags(&c->ostream[o], hipStreamNonBlocking));
+		// the chain stream, only for the volumes whose plan uses it (plan_run): HIP deals streams onto its hardware queues in creation
+		// order, so one more stream changes which octave streams share a queue (docs/experiments.md, "One stream more")
+		if (o == 1 && !one_stream && !c->slab && chain_stream_fits(c)) CHECKED(hipStreamCreateWithFlags(&c->cstream, hipStreamNonBlocking));
 		CHECKED(hipEventCreateWithFlags(&c->ev_seed[o], hipEventDisableTiming));
 		CHECKED(hipEventCreateWithFlags(&c->ev_done[o], hipEventDisableTiming));
 	}
@@ -398,7 +386,6 @@ int create_common(sift3d_handle *out, const CreateCfg &cfg, const sift3d_params 
 			}
 			CHECKED(hipEventCreateWithFlags(&c->ev_det_fork, hipEventDisableTiming));
 			CHECKED(hipEventCreateWithFlags(&c->ev_det_join, hipEventDisableTiming));
-			CHECKED(hipEventCreateWithFlags(&c->ev_det_fork2, hipEventDisableTiming));
 			CHECKED(hipEventCreateWithFlags(&c->ev_det_join2, hipEventDisableTiming));
 		}
 	}
@@ -481,44 +468,27 @@ extern "C" int sift3d_create(sift3d_handle *out, const float *volume, int nx, in
 
 // GaussianSmooth_3D (Src/cSIFT3D.cc:535-622) on device buffers: X -> Y -> Z(+DoG)
 #ifndef S3D_FUSED_MIN_DEFAULT
-#define S3D_FUSED_MIN_DEFAULT 33  /* levels with a dimension <= 32 (octaves 4+ of a 512^3 volume) take the generic separable kernels: 3.88 vs 4.02 ms */
-#endif
-#ifndef S3D_FUSED_HALF
-#define S3D_FUSED_HALF 1  /* the seed level's march kernel also writes level 0 of the next octave (no decimation launch on the octave -> octave chain) */
+#define S3D_FUSED_MIN_DEFAULT 33  /* levels with a dimension <= 32 (octaves 4+ of a 512^3 volume) take the generic separable kernels */
 #endif
 #ifndef S3D_O0_TAIL_SLOTS_DEFAULT
-#define S3D_O0_TAIL_SLOTS_DEFAULT 512  /* r02 (march kernel): 2.92 vs 3.05 ms with bg 256 */
+#define S3D_O0_TAIL_SLOTS_DEFAULT 512
 #endif
 #ifndef S3D_BG_SLOTS_DEFAULT
 #define S3D_BG_SLOTS_DEFAULT 256
 #endif
+// One level of octave o on stream st, with the wave priority and the slot plan the RunPlan gives its part of the octave.
 // half_out (optional): level 0 of the next octave; returns true when the march kernel wrote it together with dst (the caller then
 // skips the decimation launch)
-static bool smooth_level(sift3d_ctx *c, int o, const float *src, const Level &dst, const Taps &t, const float *prev, float *dog,
-                         unsigned *dogmax, int level = 0, const Level *half_out = nullptr, hipStream_t st_override = nullptr) {
-	hipStream_t st = st_override ? st_override : c->ostream[o];
-	// Slot planning across the octave streams (single-round launches keep every slot they take until they end): the levels of
-	// octave 0 behind the seed level G[0][num_kp_levels] leave a third of the machine to the chains of the smaller octaves, which
-	// are planned for that third; otherwise those chains starve and run as a tail after octave 0 has finished.
-	static const int tail_slots = dev_tune_i("S3D_O0_TAIL_SLOTS", S3D_O0_TAIL_SLOTS_DEFAULT);
-	static const int bg_slots = dev_tune_i("S3D_BG_SLOTS", S3D_BG_SLOTS_DEFAULT);
-	// wave priority: the launches of octaves >= 2 (1/64 of the work, but each octave waits for level 3 of the one above, and beside the
-	// big launches their workgroups crawl) run at the highest wave priority: 2.82 -> 2.71 ms per 512^3 pyramid.  Raising octave 1 too
-	// (S3D_PRIO=1) costs octave 0 as much as it gains.
-	// r04 (scripts/sweep_sched3.sh, with the small octaves in one launch): octave 1 at the top priority too -- 2.20 vs 2.23 ms; its slot
-	// plan (S3D_BG1_SLOTS 256 / 384 / 512) and more slots for the octaves behind it (S3D_BG_SLOTS 512 / 768: 2.23-2.27) change nothing
-	static const int prio_mode = dev_tune_i("S3D_PRIO", 3);  // 1: octave 1 at wave priority 1; 2: at 0; 3: octave 1 at the top priority like the octaves behind it
-	static const int bg1_slots = dev_tune_i("S3D_BG1_SLOTS", 0);  // slot plan of octave 1's levels (0: bg_slots)
-	const int prio = (prio_mode && c->noct > 1) ? (o >= 2 ? 2 : (o == 1 ? (prio_mode == 1 ? 1 : (prio_mode == 3 ? 2 : 0)) : 0)) : 0;
-	const int plan_slots = c->noct > 1 ? (o == 0 ? (level > c->p.num_kp_levels ? tail_slots : 0) : (o == 1 && bg1_slots > 0 ? bg1_slots : bg_slots)) : 0;
-	// hot path: one fused pass (x, y, z blur + DoG + abs-max; kernels_march.hip); prev == src for every DoG-producing level
+static bool smooth_level(sift3d_ctx *c, int o, hipStream_t st, int prio, int plan_slots, const float *src, const Level &dst, const Taps &t,
+                         const float *prev, float *dog, unsigned *dogmax, const Level *half_out = nullptr) {
+	// hot path: one fused pass (x, y, z blur + DoG + abs-max; kernels_march.hip); prev == src for every DoG-producing level.
+	// The plane size decides, not the depth: a thin volume marches its few planes like any other chunk; launch_march_level declines a
+	// level whose column is shorter than its kernel (nz < 2 hw + 2), which then takes the separable passes.
 	static const int fused_min = dev_tune_i("S3D_FUSED_MIN", S3D_FUSED_MIN_DEFAULT);
-	// r04 (shape cliff #2): the plane size decides, not the depth -- a thin volume (512 x 512 x 24: common MR / CT slabs) has planes of
-	// many tiles and marches its few planes like any other chunk (the z ends are a feed order); launch_march_level declines a level
-	// whose column is shorter than its kernel (nz < 2 hw + 2), which then takes the separable passes.  Cubes of <= 32 stay separable.
 	if (c->use_fused && (prev == nullptr || prev == src) && std::min(dst.nx, dst.ny) >= fused_min) {
 		MarchHalf hf;
-		const bool want_half = S3D_FUSED_HALF && half_out != nullptr && march_half_ok(dst.nx, dst.ny, dst.zr_all());
+		// (the seed level's kernel also writes level 0 of the next octave: no decimation launch on the octave -> octave chain)
+		const bool want_half = half_out != nullptr && march_half_ok(dst.nx, dst.ny, dst.zr_all());
 		if (want_half) { hf.d = half_out->d; hf.nx = half_out->nx; hf.ny = half_out->ny; hf.nz = half_out->nz; }
 		if (launch_march_level(src, dst.d, dog, dogmax, dst.nx, dst.ny, dst.zr_all(), t, st, plan_slots, prio, want_half ? &hf : nullptr))
 			return want_half;
@@ -549,6 +519,112 @@ void fill_detect_levels(const sift3d_ctx *c, int o, DetectLevels &DL) {
 	}
 }
 
+// the DoG levels launch_refine reads, every octave of the context
+static void fill_dog_table(const sift3d_ctx *c, DogTable &T) {
+	memset(&T, 0, sizeof(T));
+	T.octave_base = c->octave_base;
+	for (int o = 0; o < c->noct && o < kDogTabOct; o++) {
+		const Level &D0 = c->dog[(size_t)o * c->nd];
+		T.nx[o] = D0.nx; T.ny[o] = D0.ny;
+		for (int i = 0; i < c->nd && i < kDogTabLv; i++) T.d[o][i] = c->dog[(size_t)o * c->nd + i].d;
+	}
+}
+
+// ---- the schedule of a run (RunPlan, ctx_internal.h; DESIGN.md, "The schedule of a run"; measurements: docs/experiments.md) ----
+// The SMALL octaves (16^3-class and below) run in ONE launch of one workgroup that keeps the octave in LDS (kernels_small.hip) instead
+// of ~16 launches of a few microseconds per octave on the stage's critical chain: the first octave of that launch, -1 for none, and
+// the launch's arguments
+static void plan_small_launch(const sift3d_ctx *c, RunPlan &plan) {
+	plan.small_first = -1;
+	unsigned build_mask = 0, dog_mask = 0;
+	int max_hw = 0;
+	bool ok = c->use_fused && !c->slab && c->ng <= kSmallMaxLv;
+	for (int i = 1; i < c->ng && ok; i++) {
+		if (c->g_last_elide && i == c->ng - 1) continue;
+		build_mask |= 1u << i;
+		if (!(c->dog_elide && (i - 1 == 0 || i - 1 == c->nd - 1))) dog_mask |= 1u << (i - 1);
+		const Taps &t = c->taps[i];
+		for (int d = 1; d <= t.hw && ok; d++) ok = memcmp(&t.w[t.hw + d], &t.w[t.hw - d], sizeof(float)) == 0;  // symmetric bit for bit
+		max_hw = std::max(max_hw, t.hw);
+	}
+	if (!ok || small_padded_hw(max_hw) <= 0) return;
+	auto fits = [&](int o) { const Level &L = c->gss[(size_t)o * c->ng]; return small_octave_fits(L.nx, L.ny, L.nz, max_hw); };
+	int first = -1;
+	for (int o = 0; o < c->noct && first < 0; o++) if (c->noct - o <= kSmallMaxOct && fits(o)) first = o;
+	// EVERY octave of the launch must satisfy hw <= n - 2 (the extended-line form of the boundary rule): the octaves behind the first
+	// are smaller, which makes the capacity limits easier and THIS one harder (sigma_default 1.7: hw 7 at the 8^3 octave of a
+	// power-of-two volume; the glast_eager hook: hw 8).  One that fails sends the whole chain down the separable kernels.
+	for (int o = first; first >= 0 && o < c->noct; o++) if (!fits(o)) first = -1;
+	if (first < 0) return;
+	plan.small_first = first;
+	SmallArgs &sa = plan.small;
+	memset(&sa, 0, sizeof(sa));
+	sa.noct = c->noct - first; sa.ng = c->ng; sa.nd = c->nd; sa.seed = c->p.num_kp_levels;
+	sa.build_mask = build_mask; sa.dog_mask = dog_mask;
+	sa.dogmax = c->d_dogmax + (size_t)first * c->nd;
+	sa.hwp = small_padded_hw(max_hw);
+	for (int i = 1; i < c->ng; i++) {
+		const Taps &t = c->taps[i];
+		if (t.hw > sa.hwp) continue;  // (a level the launch does not build)
+		for (int k = 0; k <= sa.hwp; k++) sa.w[i][k] = k >= sa.hwp - t.hw ? t.w[k - (sa.hwp - t.hw)] : 0.0f;
+	}
+	for (int o = first; o < c->noct; o++) {
+		SmallOct &so = sa.oct[o - first];
+		const Level &L = c->gss[(size_t)o * c->ng];
+		so.nx = L.nx; so.ny = L.ny; so.nz = L.nz;
+		for (int i = 0; i < c->ng; i++) so.g[i] = c->gss[(size_t)o * c->ng + i].d;
+		for (int i = 0; i < c->nd; i++) so.dog[i] = c->dog[(size_t)o * c->nd + i].d;
+	}
+}
+
+// Streams, wave priority and slot plan of every octave's head and tail
+static void plan_octaves(const sift3d_ctx *c, RunPlan &plan) {
+	static const int tail_slots = dev_tune_i("S3D_O0_TAIL_SLOTS", S3D_O0_TAIL_SLOTS_DEFAULT);
+	static const int bg_slots = dev_tune_i("S3D_BG_SLOTS", S3D_BG_SLOTS_DEFAULT);
+	const int sf = plan.small_first;
+	plan.chain = c->cstream != nullptr;  // (create_common: volumes of at most 4 M voxels, chain_stream_fits)
+	plan.oct.assign((size_t)std::max(1, c->noct), RunPlan::Oct{});
+	for (int o = 0; o < c->noct; o++) {
+		RunPlan::Oct &oc = plan.oct[(size_t)o];
+		const bool in_small = sf >= 0 && o >= sf;
+		// the octaves of the small launch share the stream of the first of them; with a chain stream the heads of the octaves >= 1
+		// and the small launch run on it, in order: a dependency across streams costs 13-16 us, consecutive launches of one stream none
+		const int own = in_small ? sf : o;
+		oc.head = plan.chain && o >= 1 ? kChainStream : own;
+		oc.tail = plan.chain && o >= 1 && in_small ? kChainStream : own;
+		// HIP deals the streams onto its hardware queues in the pattern 1 2 3 4 4 3 2 1: with the small launch on the fourth stream the
+		// tail of the octave above it would queue BEHIND that launch; it goes to the stream of the octave above, idle by then
+		oc.tail_moved = sf >= 3 && o == sf - 1 && !plan.chain;
+		if (oc.tail_moved) oc.tail = o - 1;
+		// Single-round launches keep every slot they take until they end: the tail of octave 0 leaves a third of the machine to the
+		// chains of the smaller octaves, which are planned for that third and run at the top wave priority (each waits for the seed
+		// level of the one above, and beside the big launches their workgroups crawl)
+		oc.prio = c->noct > 1 && o >= 1 ? 2 : 0;
+		oc.head_slots = c->noct > 1 && o >= 1 ? bg_slots : 0;
+		oc.tail_slots = c->noct > 1 ? (o == 0 ? tail_slots : bg_slots) : 0;
+	}
+}
+
+// Detection: the masks of octave 0, octave 1 and the octaves >= 2 on up to three streams, one ordered compaction
+static void plan_detect(const sift3d_ctx *c, int upto, RunPlan &plan) {
+	plan.det_two = upto >= 3 && c->det_o.size() > 1;
+	// det_o exists only where create_common gave octave 1 a stream of its own (noct > 1, no one_stream / det_serial hook, no slab), and
+	// sift3d_set_stream only replaces entries equal to the handle's stream: with a second scratch every ostream[o] is distinct
+	plan.det_early = plan.det_two;
+	plan.det_rest_stream = !plan.det_two ? 0 : (c->noct > 2 ? 2 : 1);
+	// the masks of an octave >= 2 follow ITS pyramid (the event its last level recorded), not every octave's
+	plan.det_rest_own = plan.det_early && plan.det_rest_stream == 2;
+	// one scan + one emit launch for all octaves; k_emit_multi's table holds eight: a ninth octave keeps octave 0's own launches in
+	// front, more than nine keep every octave's
+	plan.emit = !plan.det_two || c->noct - 1 > 8 ? kEmitPerOctave : (c->noct <= 8 ? kEmitMultiAll : kEmitMultiRest);
+}
+
+static void plan_run(const sift3d_ctx *c, int upto, RunPlan &plan) {
+	plan_small_launch(c, plan);
+	plan_octaves(c, plan);
+	plan_detect(c, upto, plan);
+}
+
 // One run = prepare (flags of the run) -> enqueue (the whole pipeline on the handle's streams, up to the asynchronous read-back of the
 // five counters into pinned memory; no host synchronisation) -> finish (synchronise, check the list capacity, fill state and times;
 // on overflow: regrow and enqueue again).  sift3d_run / sift3d_run_stages do all three; sift3d_run_async stops behind the first
@@ -574,267 +650,200 @@ static int run_prepare(sift3d_ctx *c, int &upto) {
 	if (c->run_full) { c->dog_elide = false; c->g_last_elide = false; }
 	c->g_last_built.assign((size_t)std::max(1, c->noct), 0);
 	c->n_regrow = 0;
+	plan_run(c, upto, c->plan);
 	return SIFT3D_OK;
 }
 
-static int run_enqueue(sift3d_ctx *c, int upto, bool part_orient) {
-	int rc = set_device(c->device);
-	if (rc) return rc;
-	hipStream_t st = c->stream;
+static hipStream_t plan_stream(const sift3d_ctx *c, int index) { return index == kChainStream ? c->cstream : c->ostream[(size_t)index]; }
+
+// a part of the pyramid that starts behind the seed level of `seed_octave`: the fork of the run first (the main stream reached the run)
+static int wait_fork_and_seed(sift3d_ctx *c, hipStream_t so, int seed_octave) {
+	S3D_HIP(hipStreamWaitEvent(so, c->ev_fork, 0));
+	S3D_HIP(hipStreamWaitEvent(so, c->ev_seed[(size_t)seed_octave], 0));
+	return SIFT3D_OK;
+}
+
+// level (0,0): the base blur of the input volume (a seeded context's was written by sift3d_seed_upload)
+static void enqueue_base_blur(sift3d_ctx *c, const RunPlan &plan) {
+	const RunPlan::Oct &oc = plan.oct[0];
+	if (!c->seeded) smooth_level(c, 0, plan_stream(c, oc.head), oc.prio, oc.head_slots, c->in.d, c->gss[0], c->base_taps, nullptr, nullptr, nullptr);
+}
+
+// The head (levels up to the seed level G[o][num_kp_levels]) or the tail (the levels behind it) of octave o, with the events the
+// other octaves and the detection wait for.  half_written[o]: level 0 of octave o was written by the seed level's kernel of octave o - 1
+static int enqueue_octave_part(sift3d_ctx *c, const RunPlan &plan, int o, bool head, std::vector<char> &half_written) {
+	const RunPlan::Oct &oc = plan.oct[(size_t)o];
+	hipStream_t so = plan_stream(c, head ? oc.head : oc.tail);
+	const int seed = c->p.num_kp_levels;
+	int rc = SIFT3D_OK;
+	if (head && o > 0 && (rc = wait_fork_and_seed(c, so, o - 1)) != SIFT3D_OK) return rc;
+	if (plan.small_first >= 0 && o >= plan.small_first) {  // the whole octave is in the small launch, enqueued with the head of its first octave
+		if (head && o == plan.small_first) {
+			SmallArgs sa = plan.small;
+			if (o == 0) enqueue_base_blur(c, plan);
+			else if (!half_written[(size_t)o]) {  // the launch decimates the parent's seed level itself (no decimation launch)
+				const Level &P = c->gss[(size_t)(o - 1) * c->ng + seed];
+				sa.parent = P.d; sa.pnx = P.nx; sa.pny = P.ny;
+			}
+			launch_small_octaves(sa, so);
+		}
+		if (head) S3D_HIP(hipEventRecord(c->ev_seed[(size_t)o], so));
+		if (!head && o > 0) S3D_HIP(hipEventRecord(c->ev_done[(size_t)o], so));
+		return SIFT3D_OK;
+	}
+	// a tail on another stream than its head (chain stream, moved tail) follows the seed level by its event
+	if (!head && o >= 1 && (plan.chain || oc.tail_moved) && (rc = wait_fork_and_seed(c, so, o)) != SIFT3D_OK) return rc;
+	const int slots = head ? oc.head_slots : oc.tail_slots;
+	for (int i = head ? 0 : seed + 1; i < (head ? seed + 1 : c->ng); i++) {
+		const Level &L = c->gss[(size_t)o * c->ng + i];
+		if (o == 0 && i == 0) enqueue_base_blur(c, plan);
+		else if (i == 0) {
+			const Level &P = c->gss[(size_t)(o - 1) * c->ng + seed];
+			if (!half_written[(size_t)o]) launch_downsample(P.d, P.nx, P.ny, L.d, L.nx, L.ny, L.nz, so);
+		} else {
+			const Level &P = c->gss[(size_t)o * c->ng + i - 1];
+			if (c->g_last_elide && i == c->ng - 1) continue;  // never built (k_lazy_next / sift3d_copy_level form what is asked for)
+			// the seed level also leaves decimated, as level 0 of the next octave
+			const Level *half = (i == seed && o + 1 < c->noct) ? &c->gss[(size_t)(o + 1) * c->ng] : nullptr;
+			const bool elided = c->dog_elide && (i - 1 == 0 || i - 1 == c->nd - 1);  // a DoG level the pyramid does not write
+			const bool hw = smooth_level(c, o, so, oc.prio, slots, P.d, L, c->taps[i], elided ? nullptr : P.d, elided ? nullptr : c->dog[(size_t)o * c->nd + i - 1].d,
+			                             elided ? nullptr : c->d_dogmax + (size_t)o * c->nd + i - 1, half);
+			if (half) half_written[(size_t)o + 1] = hw ? 1 : 0;
+		}
+		if (i == seed) S3D_HIP(hipEventRecord(c->ev_seed[(size_t)o], so));
+	}
+	if (!head && o > 0) S3D_HIP(hipEventRecord(c->ev_done[(size_t)o], so));
+	return SIFT3D_OK;
+}
+
+// ---- Build_Gaussian_Scale_Space (Src/cSIFT3D.cc:268-319) with the DoG (346-360) fused into the z pass ----
+// Every octave starts after the main stream reached this point (ev_fork); octave o is seeded by G[o-1][num_kp_levels] (DownSample_3D),
+// everything else of octave o-1 overlaps with octave o.  Enqueue order: head(0), head(1), tail(0), head(2), tail(1), ...  The critical
+// path of the stage is the chain of heads; the tail of octave 0 (its widest Gaussian) is machine-filling work off that path and starts
+// together with head(1).
+static int enqueue_pyramid(sift3d_ctx *c, const RunPlan &plan) {
+	S3D_HIP(hipEventRecord(c->ev_fork, c->stream));
+	std::vector<char> half_written((size_t)c->noct + 1, 0);
+	int rc = SIFT3D_OK;
+	for (int o = 0; o <= c->noct; o++) {
+		if (o < c->noct && (rc = enqueue_octave_part(c, plan, o, true, half_written)) != SIFT3D_OK) return rc;
+		if (o >= 1 && (rc = enqueue_octave_part(c, plan, o - 1, false, half_written)) != SIFT3D_OK) return rc;
+	}
+	return SIFT3D_OK;
+}
+
+// ---- the end of the pyramid stage and Detect_KeyPoints (Src/cSIFT3D.cc:362-425) ----
+// With early masks octave 0's start right behind its last level, BESIDE the chains of the small octaves.  The pyramid stage still ends
+// when EVERY octave's pyramid has: ev[1] is recorded on the second detection stream after it has waited for all of them, so the
+// pyramid's time is its wall time and the detection's is what is left of it behind the pyramid.  ev[2]: the DoG is fused, a zero-length stage.
+static int enqueue_detect(sift3d_ctx *c, const RunPlan &plan, int upto) {
+	hipStream_t st = c->stream, sb = plan_stream(c, plan.det_two ? 1 : 0), sc = plan_stream(c, plan.det_rest_stream);
+	std::vector<DetectLevels> DLs((size_t)c->noct);
+	const int nl = c->nd - 2;  // DoG levels 1 .. nd-2 (Src/cSIFT3D.cc:376)
+	const Taps *lt = c->g_last_elide ? &c->taps[c->ng - 1] : nullptr;
+	DetectOpts dopt;
+	dopt.neighbours = c->dopt.neighbours; dopt.refine = c->dopt.refine;
+	dopt.max_offset = c->dopt.max_offset; dopt.contrast_thresh = c->dopt.contrast_thresh; dopt.edge_ratio = c->dopt.edge_ratio;
+	const DetectOpts *dop = c->run_full ? &dopt : nullptr;  // null: the reference rule (k_mark)
+	if (upto >= 3)
+		for (int o = 0; o < c->noct; o++) fill_detect_levels(c, o, DLs[(size_t)o]);
+	auto bufs = [&](int o) -> const DetectBufs & { return plan.det_two && o > 0 ? c->det_o[(size_t)o] : c->det; };
+	auto mark = [&](int o, hipStream_t s) {
+		const Level &C = c->dog[(size_t)o * c->nd + 1];
+		launch_detect_mark(DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), c->p.peak_thresh, o + c->octave_base, bufs(o), s, lt, dop);
+	};
+	hipStream_t join = plan.det_early ? sb : st;  // the stream that sees every octave's pyramid complete
+	if (plan.det_early) {
+		S3D_HIP(hipEventRecord(c->ev_det_fork, st));  // octave 0's pyramid is complete (the main stream is its stream)
+		mark(0, st);
+		S3D_HIP(hipStreamWaitEvent(sb, c->ev_det_fork, 0));
+	}
+	// (octave 1 too: its levels are in sb's own order only when neither the chain stream nor the small-octave launch took them)
+	for (int o = 1; o < c->noct; o++) S3D_HIP(hipStreamWaitEvent(join, c->ev_done[(size_t)o], 0));
+	S3D_HIP(hipEventRecord(c->ev[1], join));
+	S3D_HIP(hipEventRecord(c->ev[2], join));
+	if (upto < 3) return SIFT3D_OK;
+	if (plan.det_two) {
+		// the masks of the octaves >= 2 (launches of a few microseconds) beside octave 1's candidate pass; every octave has its own scratch
+		for (int o = 1; o < c->noct; o++) {
+			if (plan.det_rest_own && o >= 2) S3D_HIP(hipStreamWaitEvent(sc, c->ev_done[(size_t)o], 0));
+			mark(o, o == 1 ? sb : sc);
+		}
+		S3D_HIP(hipEventRecord(c->ev_det_join, sb));
+		if (sc != sb) S3D_HIP(hipEventRecord(c->ev_det_join2, sc));  // (the main stream waits for both itself: one hop across queues each, not two in a row)
+	}
+	std::vector<DetectEmitItem> multi;
+	for (int o = 0; o < c->noct; o++) {
+		const Level &C = c->dog[(size_t)o * c->nd + 1];
+		if (!plan.det_two) mark(o, st);
+		if (plan.det_two && o == 1) {
+			S3D_HIP(hipStreamWaitEvent(st, c->ev_det_join, 0));
+			if (sc != sb) S3D_HIP(hipStreamWaitEvent(st, c->ev_det_join2, 0));
+		}
+		if (plan.emit == kEmitMultiAll || (plan.emit == kEmitMultiRest && o > 0)) multi.push_back(DetectEmitItem{&DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), o + c->octave_base, &bufs(o)});
+		else launch_detect_emit(DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), o + c->octave_base, bufs(o), c->d_ext, c->ext_cap, st);
+	}
+	if (!multi.empty()) launch_detect_emit_multi(multi.data(), (int)multi.size(), c->d_ext, c->ext_cap, c->d_total, st);
+	return SIFT3D_OK;
+}
+
+// ---- Assign_Orientation (Src/cSIFT3D.cc:427-482) and Extract_Description (Src/cSIFT3D.cc:484-502) ----
+void enqueue_slots(sift3d_ctx *c) {
+	launch_slots(c->d_ext, c->d_codes, c->d_total, c->ext_cap, c->d_nkp, c->d_order, c->kp_cap, c->d_slots_part, c->stream);
+}
+void enqueue_orient(sift3d_ctx *c, int rank, int world) {
+	launch_orient(c->d_ext, c->d_codes, c->d_total, c->ext_cap, c->d_levels, c->d_luts, c->d_lutpool, c->p.max_eig_thres, c->p.corner_thresh,
+	              rank, world, c->d_order, c->d_nkp + 3, c->stream);
+	enqueue_slots(c);
+}
+void enqueue_describe(sift3d_ctx *c, int rank, int world, bool with_desc) {
+	if (with_desc)
+		launch_describe(c->d_ext, c->d_total, c->ext_cap, c->d_levels, c->d_luts, c->d_lutpool, c->d_desc, c->kp_cap, rank, world, c->d_order,
+		                c->d_nkp, c->d_nkp + 1, c->stream, c->desc_lut_lds, &c->dsplit);
+	launch_finalize(c->d_ext, c->d_total, c->ext_cap, with_desc, c->d_kpout, c->d_xyz, c->kp_cap, c->stream);
+}
+
+// scratch of a run that the lists' capacity or an earlier error decides
+static int run_scratch(sift3d_ctx *c, int upto) {
 	if (c->run_refine && upto >= 4 && c->refined_cap < c->kp_cap) {  // (first refining run, or the lists were regrown)
 		hipFree(c->d_refined); c->d_refined = nullptr; c->refined_cap = 0;
 		S3D_HIP(hipMalloc(&c->d_refined, sizeof(sift3d_refined) * (size_t)c->kp_cap));
 		c->refined_cap = c->kp_cap;
 	}
 	if (c->dsplit_dirty && c->dsplit.gacc) {  // (a run cut short by an error may have left partial sums / arrival counts behind)
-		S3D_HIP(hipMemsetAsync(c->dsplit.gacc, 0, sizeof(int) * (size_t)c->dsplit.cap * (kDesc + 8 + 1), st));
+		S3D_HIP(hipMemsetAsync(c->dsplit.gacc, 0, sizeof(int) * (size_t)c->dsplit.cap * (kDesc + 8 + 1), c->stream));
 		c->dsplit_dirty = false;
-	}
-	{
-		if (c->gate) { S3D_HIP(hipStreamWaitEvent(st, c->gate, 0)); c->gate = nullptr; }
-		S3D_HIP(hipMemsetAsync(c->d_dogmax, 0, sizeof(unsigned) * (size_t)(std::max(1, c->noct * c->nd) + 6), st));
-		S3D_HIP(hipEventRecord(c->ev[0], st));
-		// ---- Build_Gaussian_Scale_Space (Src/cSIFT3D.cc:268-319) with the DoG (346-360) fused into the z pass ----
-		// fork: every octave stream starts after the main stream reached this point; octave o is seeded by
-		// G[o-1][num_kp_levels] (DownSample_3D), everything else of octave o-1 overlaps with octave o
-		S3D_HIP(hipEventRecord(c->ev_fork, st));
-		// Enqueue order: head(0), head(1), tail(0), head(2), tail(1), ... -- head(o) = the levels of octave o up to its seed level
-		// G[o][num_kp_levels], tail(o) = the levels behind it.  The critical path of the stage is the chain of heads (every octave
-		// waits for the seed level of the one above); the tail of octave 0 (its widest Gaussian) is machine-filling work that is off
-		// that path and starts together with head(1).  Measured and rejected (r03, again r04): tail(0) waiting for the seed of
-		// octave 1, so that head(1) -- 351 us alone, 604 us beside tail(0) in the rocprofv3 timeline -- runs undisturbed and tail(0)
-		// fills the machine under the launch-latency chain of the small octaves instead: 2.36 -> 2.51 ms at 512^3 for every slot
-		// planning tried (the tail is longer than that chain).
-		std::vector<char> half_written((size_t)c->noct + 1, 0);  // level 0 of octave o was written by the seed level's kernel of octave o - 1
-		// r04: the SMALL octaves (16^3-class and below) run in ONE launch of one workgroup that keeps the octave in LDS
-		// (kernels_small.hip) instead of ~16 launches of a few microseconds per octave on the stage's critical chain
-		int small_first = -1;
-		SmallArgs sa;
-		{
-			static const int small_on = dev_tune_i("S3D_SMALL_OCT", 1);
-			unsigned build_mask = 0, dog_mask = 0;
-			int max_hw = 0;
-			bool ok = small_on != 0 && c->use_fused && !c->slab && c->ng <= kSmallMaxLv;
-			for (int i = 1; i < c->ng && ok; i++) {
-				if (c->g_last_elide && i == c->ng - 1) continue;
-				build_mask |= 1u << i;
-				if (!(c->dog_elide && (i - 1 == 0 || i - 1 == c->nd - 1))) dog_mask |= 1u << (i - 1);
-				const Taps &t = c->taps[i];
-				for (int d = 1; d <= t.hw && ok; d++) ok = memcmp(&t.w[t.hw + d], &t.w[t.hw - d], sizeof(float)) == 0;  // symmetric bit for bit
-				max_hw = std::max(max_hw, t.hw);
-			}
-			if (ok && small_padded_hw(max_hw) > 0)
-				for (int o = 0; o < c->noct; o++) {
-					const Level &L = c->gss[(size_t)o * c->ng];
-					if (c->noct - o <= kSmallMaxOct && small_octave_fits(L.nx, L.ny, L.nz, max_hw)) { small_first = o; break; }
-				}
-			// EVERY octave of the launch must satisfy hw <= n - 2 (the extended-line form of the boundary rule): the octaves behind the first
-			// are smaller, which makes the capacity limits easier and THIS one harder (sigma_default 1.7: hw 7 at the 8^3 octave of a
-			// power-of-two volume; the glast_eager hook: hw 8).  One that fails sends the whole chain down the separable kernels.
-			for (int o = small_first; small_first >= 0 && o < c->noct; o++) {
-				const Level &L = c->gss[(size_t)o * c->ng];
-				if (!small_octave_fits(L.nx, L.ny, L.nz, max_hw)) small_first = -1;
-			}
-			if (small_first >= 0) {
-				memset(&sa, 0, sizeof(sa));
-				sa.noct = c->noct - small_first; sa.ng = c->ng; sa.nd = c->nd; sa.seed = c->p.num_kp_levels;
-				sa.build_mask = build_mask; sa.dog_mask = dog_mask;
-				sa.dogmax = c->d_dogmax + (size_t)small_first * c->nd;
-				sa.hwp = small_padded_hw(max_hw);
-				for (int i = 1; i < c->ng; i++) {
-					const Taps &t = c->taps[i];
-					if (t.hw > sa.hwp) continue;  // (a level the launch does not build)
-					for (int k = 0; k <= sa.hwp; k++) sa.w[i][k] = k >= sa.hwp - t.hw ? t.w[k - (sa.hwp - t.hw)] : 0.0f;
-				}
-				for (int o = small_first; o < c->noct; o++) {
-					SmallOct &so = sa.oct[o - small_first];
-					const Level &L = c->gss[(size_t)o * c->ng];
-					so.nx = L.nx; so.ny = L.ny; so.nz = L.nz;
-					for (int i = 0; i < c->ng; i++) so.g[i] = c->gss[(size_t)o * c->ng + i].d;
-					for (int i = 0; i < c->nd; i++) so.dog[i] = c->dog[(size_t)o * c->nd + i].d;
-				}
-			}
-		}
-		auto enqueue = [&](int o, bool head) -> int {
-			// (the octaves of the small launch share the stream of the first of them; heads of octaves >= 1: the chain stream)
-			// measured (scripts/small_volume_times.py, A/B in one process per setting): 64^3 / 128^3 pyramid 0.238 / 0.348 -> 0.220 / 0.320 ms,
-			// but 256^3 0.600 -> 0.656 and 512^3 2.13 -> 2.16 ms (the heads of the big octaves are long launches that gain nothing from a
-			// gap of 8 instead of 15 us and lose the hardware queue they had to themselves): volumes of at most 4 M voxels only
-			static const int chain_mode = dev_tune_i("S3D_CHAIN", 1);  // 0 never, 1 small volumes (the stream exists for them only)
-			const bool chain_on = chain_mode != 0;
-			const bool chained = c->cstream != nullptr && chain_on && o >= 1 && (head || (small_first >= 0 && o >= small_first));
-			hipStream_t so = chained ? c->cstream : c->ostream[(small_first >= 0 && o > small_first) ? small_first : o];
-			// late r04: HIP deals the streams onto its four hardware queues in the pattern 1 2 3 4 4 3 2 1 (profiles/r04e_timeline.txt, queue
-			// ids), so with the small launch on stream 4 (256^3-class volumes: six octaves) the levels behind the seed level of octave 3 sat in
-			// the same hardware queue BEHIND that launch and ended the stage 25 us after it.  They go to the stream of the octave above
-			// (idle by then: its own last level is a 128^3-class launch that ended long before) -- off the critical chain either way
-			const bool tail_moved = !head && small_first >= 3 && o == small_first - 1 && c->cstream == nullptr;
-			if (tail_moved) so = c->ostream[o - 1];
-			if (small_first >= 0 && o >= small_first) {
-				if (head && o > 0) {
-					S3D_HIP(hipStreamWaitEvent(so, c->ev_fork, 0));
-					S3D_HIP(hipStreamWaitEvent(so, c->ev_seed[o - 1], 0));
-				}
-				if (head && o == small_first) {
-					const Level &L = c->gss[(size_t)o * c->ng];
-					if (o == 0) {
-						if (!c->seeded) smooth_level(c, o, c->in.d, L, c->base_taps, nullptr, nullptr, nullptr);
-					} else if (!half_written[(size_t)o]) {  // the launch decimates the parent's seed level itself (no decimation launch)
-						const Level &P = c->gss[(size_t)(o - 1) * c->ng + c->p.num_kp_levels];
-						sa.parent = P.d; sa.pnx = P.nx; sa.pny = P.ny;
-					}
-					launch_small_octaves(sa, so);
-				}
-				if (head) S3D_HIP(hipEventRecord(c->ev_seed[o], so));
-				if (!head && o > 0) S3D_HIP(hipEventRecord(c->ev_done[o], so));
-				return SIFT3D_OK;
-			}
-			if (head && o > 0) {
-				S3D_HIP(hipStreamWaitEvent(so, c->ev_fork, 0));
-				S3D_HIP(hipStreamWaitEvent(so, c->ev_seed[o - 1], 0));
-			}
-			if (!head && o >= 1 && ((c->cstream != nullptr && chain_on) || tail_moved)) {  // the levels behind the seed level: the octave's own stream, behind its head on the chain stream
-				S3D_HIP(hipStreamWaitEvent(so, c->ev_fork, 0));
-				S3D_HIP(hipStreamWaitEvent(so, c->ev_seed[o], 0));
-			}
-			const int i0 = head ? 0 : c->p.num_kp_levels + 1, i1 = head ? c->p.num_kp_levels + 1 : c->ng;
-			for (int i = i0; i < i1; i++) {
-				const Level &L = c->gss[(size_t)o * c->ng + i];
-				if (o == 0 && i == 0) {
-					if (!c->seeded) smooth_level(c, o, c->in.d, L, c->base_taps, nullptr, nullptr, nullptr);
-					// seeded: G[octave_base][0] was written by sift3d_seed_upload
-				} else if (i == 0) {
-					const Level &P = c->gss[(size_t)(o - 1) * c->ng + c->p.num_kp_levels];
-					if (!half_written[(size_t)o]) launch_downsample(P.d, P.nx, P.ny, L.d, L.nx, L.ny, L.nz, so);
-				} else {
-					const Level &P = c->gss[(size_t)o * c->ng + i - 1];
-					const Level &D = c->dog[(size_t)o * c->nd + i - 1];
-					if (c->g_last_elide && i == c->ng - 1) continue;  // never built (k_lazy_next / sift3d_copy_level form what is asked for)
-					// the seed level also leaves decimated, as level 0 of the next octave (whole volumes, not seeded / partitioned contexts' inputs)
-					const Level *half = (i == c->p.num_kp_levels && o + 1 < c->noct) ? &c->gss[(size_t)(o + 1) * c->ng] : nullptr;
-					bool hw_ = false;
-					if (c->dog_elide && (i - 1 == 0 || i - 1 == c->nd - 1)) hw_ = smooth_level(c, o, P.d, L, c->taps[i], nullptr, nullptr, nullptr, i, half, so);
-					else hw_ = smooth_level(c, o, P.d, L, c->taps[i], P.d, D.d, c->d_dogmax + (size_t)o * c->nd + i - 1, i, half, so);
-					if (half) half_written[(size_t)o + 1] = hw_ ? 1 : 0;
-				}
-				if (i == c->p.num_kp_levels) S3D_HIP(hipEventRecord(c->ev_seed[o], so));
-			}
-			if (!head && o > 0) S3D_HIP(hipEventRecord(c->ev_done[o], so));
-			return SIFT3D_OK;
-		};
-		for (int o = 0; o <= c->noct; o++) {
-			if (o < c->noct && (rc = enqueue(o, true)) != SIFT3D_OK) return rc;
-			if (o >= 1 && (rc = enqueue(o - 1, false)) != SIFT3D_OK) return rc;
-		}
-		// r03, an option that is OFF (S3D_DET_EARLY_DEFAULT) -- octave 0's extremum masks start right behind its last level, BESIDE the chains of the small octaves: after octave 0's
-		// widest level the stage used to end with ~0.3 ms of launch-latency-bound chain (octaves 2..6: 60 launches of a few
-		// microseconds, each octave waiting for the seed level of the one above) on a nearly idle machine, while k_mark of octave 0
-		// -- 0.38 ms, memory bound -- waited behind the join.  The pyramid stage still ends when EVERY octave's pyramid has
-		// (ev[1] is recorded on the second detection stream after it has waited for all of them), so the stage times stay honest:
-		// the pyramid's is its wall time, the detection's is what is left of it behind the pyramid.
-		const bool two = upto >= 3 && c->det_o.size() > 1;  // masks of octaves >= 1 on a second stream beside octave 0's
-#ifndef S3D_DET_EARLY_DEFAULT
-#define S3D_DET_EARLY_DEFAULT 1  /* r04: ON -- with the small octaves in one launch the chain no longer starves behind k_mark's workgroups: detection 0.87 -> 0.82 ms, pyramid 2.18 -> 2.19 ms, step 7.41 -> 7.38 ms (r03, ~60 chain launches: detection 0.87 -> 0.73 but pyramid 2.31 -> 2.40, off) */
-#endif
-		static const int det_early_mode = dev_tune_i("S3D_DET_EARLY", S3D_DET_EARLY_DEFAULT);
-		const bool early = two && det_early_mode != 0 && c->noct > 1 && c->ostream.size() > 1 && c->ostream[1] != st;
-		std::vector<DetectLevels> DLs((size_t)c->noct);
-		const int nl = c->nd - 2;  // DoG levels 1 .. nd-2 (Src/cSIFT3D.cc:376)
-		const Taps *lt = c->g_last_elide ? &c->taps[c->ng - 1] : nullptr;
-		DetectOpts dopt;
-		dopt.neighbours = c->dopt.neighbours; dopt.refine = c->dopt.refine;
-		dopt.max_offset = c->dopt.max_offset; dopt.contrast_thresh = c->dopt.contrast_thresh; dopt.edge_ratio = c->dopt.edge_ratio;
-		const DetectOpts *dop = c->run_full ? &dopt : nullptr;  // null: the reference rule (k_mark)
-		if (upto >= 3)
-			for (int o = 0; o < c->noct; o++) fill_detect_levels(c, o, DLs[(size_t)o]);
-		hipStream_t sb = two ? c->ostream[1] : st;
-		if (early) {
-			const Level &C0 = c->dog[(size_t)0 * c->nd + 1];
-			S3D_HIP(hipEventRecord(c->ev_det_fork, st));  // octave 0's pyramid is complete (the main stream is its stream)
-			launch_detect_mark(DLs[0], nl, C0.nx, C0.ny, C0.zr_all(), c->p.peak_thresh, 0 + c->octave_base, c->det, st, lt, dop);
-			S3D_HIP(hipStreamWaitEvent(sb, c->ev_det_fork, 0));
-			// (octave 1 too: its levels are in sb's own order only when neither the chain stream nor the small-octave launch took them)
-			for (int o = 1; o < c->noct; o++) S3D_HIP(hipStreamWaitEvent(sb, c->ev_done[o], 0));
-			S3D_HIP(hipEventRecord(c->ev[1], sb));  // every octave's pyramid is complete
-			S3D_HIP(hipEventRecord(c->ev[2], sb));  // DoG is fused: zero-length stage
-		} else {
-			for (int o = 1; o < c->noct; o++) S3D_HIP(hipStreamWaitEvent(st, c->ev_done[o], 0));  // join
-			S3D_HIP(hipEventRecord(c->ev[1], st));
-			S3D_HIP(hipEventRecord(c->ev[2], st));  // DoG is fused: zero-length stage
-		}
-		// ---- Detect_KeyPoints (Src/cSIFT3D.cc:362-425) ----
-		if (upto >= 3) {
-			if (two && !early) { S3D_HIP(hipEventRecord(c->ev_det_fork, st)); S3D_HIP(hipStreamWaitEvent(sb, c->ev_det_fork, 0)); }
-			bool join2 = false;  // the octaves >= 2 ran on a stream of their own
-			if (two) {
-				// late r04: the masks of the octaves >= 2 (twelve launches of a few microseconds at 512^3) on a THIRD stream beside octave
-				// 1's: they used to queue behind octave 1's candidate pass (0.35 ms beside octave 0's masks) and ended the stage 0.13 ms
-				// after octave 0's emit (profiles/r04e_timeline_full.txt); every octave has its own scratch
-				hipStream_t sc = (c->noct > 2 && c->ostream.size() > 2 && c->ostream[2] != st && c->ostream[2] != sb) ? c->ostream[2] : sb;
-				// r05: with the early start the masks of an octave >= 2 follow ITS pyramid (the event its last level recorded), not every
-				// octave's: the chains of these octaves -- three launches of a few microseconds each per octave, the last thing the stage waited
-				// for whenever HIP dealt sb and sc onto one hardware queue -- start beside the tail of the pyramid.  Measured (scripts/ab_full.py,
-				// three pairs): extrema 0.75 -> 0.69 ms, pyramid 2.02 -> 2.02; octave 1's masks behind octave 1's pyramid as well: extrema 0.67
-				// but pyramid 2.06 (its 0.2 ms of k_mark beside octave 0's widest level) -- not taken
-				const bool own = early && sc != sb;
-				if (sc != sb && !own) { S3D_HIP(hipEventRecord(c->ev_det_fork2, sb)); S3D_HIP(hipStreamWaitEvent(sc, c->ev_det_fork2, 0)); }  // every pyramid is complete
-				for (int o = 1; o < c->noct; o++) {
-					const Level &C = c->dog[(size_t)o * c->nd + 1];
-					if (own && o >= 2) S3D_HIP(hipStreamWaitEvent(sc, c->ev_done[o], 0));
-					launch_detect_mark(DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), c->p.peak_thresh, o + c->octave_base, c->det_o[(size_t)o], o == 1 ? sb : sc, lt, dop);
-				}
-				S3D_HIP(hipEventRecord(c->ev_det_join, sb));
-				join2 = sc != sb;
-				if (join2) S3D_HIP(hipEventRecord(c->ev_det_join2, sc));  // (the main stream waits for both itself: one hop across queues each, not two in a row)
-			}
-			// two streams: one scan + one emit launch for the octaves' ordered compaction -- r07: octave 0 included (it had a scan and an emit
-			// launch of its own in front of the others'); only a volume of more than eight octaves (k_emit_multi's table) keeps them apart
-			const bool all = two && c->noct <= 8;
-			std::vector<DetectEmitItem> rest;
-			for (int o = 0; o < c->noct; o++) {
-				const Level &C = c->dog[(size_t)o * c->nd + 1];
-				const DetectBufs &b = (two && o > 0) ? c->det_o[(size_t)o] : c->det;
-				if (!(two && o > 0) && !(early && o == 0)) launch_detect_mark(DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), c->p.peak_thresh, o + c->octave_base, b, st, lt, dop);
-				if (two && o == 1) {
-					S3D_HIP(hipStreamWaitEvent(st, c->ev_det_join, 0));
-					if (join2) S3D_HIP(hipStreamWaitEvent(st, c->ev_det_join2, 0));
-				}
-				if (two && (o > 0 || all) && c->noct - 1 <= 8) rest.push_back(DetectEmitItem{&DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), o + c->octave_base, &b});
-				else launch_detect_emit(DLs[(size_t)o], nl, C.nx, C.ny, C.zr_all(), o + c->octave_base, b, c->d_ext, c->ext_cap, st);
-			}
-			if (!rest.empty()) launch_detect_emit_multi(rest.data(), (int)rest.size(), c->d_ext, c->ext_cap, c->d_total, st);
-		}
-		S3D_HIP(hipEventRecord(c->ev[3], st));
-		// ---- Assign_Orientation (Src/cSIFT3D.cc:427-482) ----
-		if (upto >= 4) {
-			launch_orient(c->d_ext, c->d_codes, c->d_total, c->ext_cap, c->d_levels, c->d_luts, c->d_lutpool, c->p.max_eig_thres,
-			              c->p.corner_thresh, part_orient ? c->part_rank : 0, part_orient ? c->part_world : 1, c->d_order, c->d_nkp + 3, st);
-			launch_slots(c->d_ext, c->d_codes, c->d_total, c->ext_cap, c->d_nkp, c->d_order, c->kp_cap, c->d_slots_part, st);
-		}
-		S3D_HIP(hipEventRecord(c->ev[4], st));
-		// ---- Extract_Description (Src/cSIFT3D.cc:484-502) ----
-		if (upto >= 5) {
-			launch_describe(c->d_ext, c->d_total, c->ext_cap, c->d_levels, c->d_luts, c->d_lutpool, c->d_desc, c->kp_cap, c->part_rank,
-			                c->part_world, c->d_order, c->d_nkp, c->d_nkp + 1, st, c->desc_lut_lds, &c->dsplit);
-		}
-		if (upto >= 4) launch_finalize(c->d_ext, c->d_total, c->ext_cap, upto >= 5, c->d_kpout, c->d_xyz, c->kp_cap, st);
-		if (upto >= 4 && c->run_refine) {  // refined records of the accepted keypoints (timed with the descriptor stage)
-			DogTable T;
-			memset(&T, 0, sizeof(T));
-			T.octave_base = c->octave_base;
-			for (int o = 0; o < c->noct && o < kDogTabOct; o++) {
-				const Level &D0 = c->dog[(size_t)o * c->nd];
-				T.nx[o] = D0.nx; T.ny[o] = D0.ny;
-				for (int i = 0; i < c->nd && i < kDogTabLv; i++) T.d[o][i] = c->dog[(size_t)o * c->nd + i].d;
-			}
-			launch_refine(c->d_ext, c->d_total, c->ext_cap, c->kp_cap, T, c->p.num_kp_levels, c->d_refined, st);
-		}
-		S3D_HIP(hipEventRecord(c->ev[5], st));
-		// total, overflow, nkp, describe work counter, describe second passes -> pinned host words
-		S3D_HIP(hipMemcpyAsync(c->h_words, c->d_total, sizeof(unsigned) * 5, hipMemcpyDeviceToHost, st));
 	}
 	return SIFT3D_OK;
 }
+
+// the stages of c->plan, one after the other, between the events that time them (ev[1] and ev[2]: enqueue_detect)
+static int run_enqueue(sift3d_ctx *c, int upto, bool part_orient) {
+	int rc = set_device(c->device);
+	if (rc) return rc;
+	if ((rc = run_scratch(c, upto)) != SIFT3D_OK) return rc;
+	hipStream_t st = c->stream;
+	const RunPlan &plan = c->plan;
+	if (c->gate) { S3D_HIP(hipStreamWaitEvent(st, c->gate, 0)); c->gate = nullptr; }
+	S3D_HIP(hipMemsetAsync(c->d_dogmax, 0, sizeof(unsigned) * (size_t)(std::max(1, c->noct * c->nd) + 6), st));
+	S3D_HIP(hipEventRecord(c->ev[0], st));
+	if ((rc = enqueue_pyramid(c, plan)) != SIFT3D_OK) return rc;
+	if ((rc = enqueue_detect(c, plan, upto)) != SIFT3D_OK) return rc;
+	S3D_HIP(hipEventRecord(c->ev[3], st));
+	if (upto >= 4) enqueue_orient(c, part_orient ? c->part_rank : 0, part_orient ? c->part_world : 1);
+	S3D_HIP(hipEventRecord(c->ev[4], st));
+	if (upto >= 4) enqueue_describe(c, c->part_rank, c->part_world, upto >= 5);
+	if (upto >= 4 && c->run_refine) {  // refined records of the accepted keypoints (timed with the descriptor stage)
+		DogTable T;
+		fill_dog_table(c, T);
+		launch_refine(c->d_ext, c->d_total, c->ext_cap, c->kp_cap, T, c->p.num_kp_levels, c->d_refined, st);
+	}
+	S3D_HIP(hipEventRecord(c->ev[5], st));
+	// total, overflow, nkp, describe work counter, describe second passes -> pinned host words
+	S3D_HIP(hipMemcpyAsync(c->h_words, c->d_total, sizeof(unsigned) * 5, hipMemcpyDeviceToHost, st));
+	return SIFT3D_OK;
+}
+
 
 // synchronise with the enqueued run and take its results; again = the lists overflowed and were regrown: enqueue once more
 static int run_finish(sift3d_ctx *c, int upto, bool &again) {
@@ -1081,7 +1090,8 @@ extern "C" int sift3d_copy_level(sift3d_handle c, int is_dog, int idx, float *ou
 		const int o = is_dog ? idx / c->nd : idx / c->ng, i = is_dog ? idx % c->nd : idx % c->ng;
 		if (((is_dog && i == c->nd - 1) || (!is_dog && i == c->ng - 1)) && !c->g_last_built[(size_t)o]) {
 			const Level &G = c->gss[(size_t)o * c->ng + c->ng - 1], &P = c->gss[(size_t)o * c->ng + c->ng - 2];
-			smooth_level(c, o, P.d, G, c->taps[c->ng - 1], nullptr, nullptr, nullptr, c->ng - 1);
+			const RunPlan::Oct &oc = c->plan.oct[(size_t)o];  // (launched as the run would have launched it)
+			smooth_level(c, o, c->ostream[o], oc.prio, oc.tail_slots, P.d, G, c->taps[c->ng - 1], nullptr, nullptr, nullptr);
 			S3D_HIP(hipStreamSynchronize(c->ostream[o]));
 			c->g_last_built[(size_t)o] = 1;
 		}

@@ -17,6 +17,34 @@ using s3d::DescSplit; using s3d::DetectBufs; using s3d::DevKp; using s3d::Level;
 
 
 // ---------------------------------------------------------------------------------------------
+// The schedule of a whole-volume run as data ("The schedule of a run"): plan_run decides, once per run, from the geometry,
+// the flags of the run (sift3d_ctx::dog_elide, g_last_elide, run_full: not repeated here) and the streams the context owns; the
+// enqueue_* functions of context.hip only walk it.  Plain values and indices, no handles.  A stream index is an octave's
+// (sift3d_ctx::ostream) or kChainStream (sift3d_ctx::cstream).
+// ---------------------------------------------------------------------------------------------
+constexpr int kChainStream = -1;
+enum { kEmitPerOctave = 0, kEmitMultiRest = 1, kEmitMultiAll = 2 };
+struct RunPlan {
+	// head = the levels of an octave up to its seed level G[o][num_kp_levels], tail = the levels behind it
+	struct Oct {
+		int head = 0, tail = 0;         // stream index of either part
+		bool tail_moved = false;        // the tail runs on the stream of the octave above
+		int prio = 0;                   // wave priority of the octave's launches
+		int head_slots = 0, tail_slots = 0;  // slot plan of its levels (0: the launch's own)
+	};
+	std::vector<Oct> oct;
+	bool chain = false;               // the chain stream exists: heads of the octaves >= 1 and the small launch run on it
+	int small_first = -1;             // first octave of the small-octave launch (every octave behind it is in it too); -1: none
+	s3d::SmallArgs small{};           // its arguments, short of `parent` (known when the seed level above has been enqueued)
+	// detection
+	bool det_two = false;             // octaves >= 1 form their masks in the second scratch, on octave 1's stream
+	bool det_early = false;           // octave 0's masks start behind octave 0's pyramid, not behind every octave's
+	int det_rest_stream = 0;          // stream index of the masks of the octaves >= 2
+	bool det_rest_own = false;        // ... each behind its own pyramid (ev_done) instead of behind all of them
+	int emit = kEmitPerOctave;        // how the ordered compaction is launched: per octave, one launch for the octaves >= 1, one for all
+};
+
+// ---------------------------------------------------------------------------------------------
 // the context
 // ---------------------------------------------------------------------------------------------
 struct sift3d_ctx {
@@ -55,13 +83,9 @@ struct sift3d_ctx {
 	Level in;
 	std::vector<Level> gss, dog;
 	std::vector<float *> tmpA, tmpB;        // per-octave scratch of the generic separable passes (octaves may overlap)
-	// octave o >= 1 only depends on G[o-1][num_kp_levels]: each octave chain runs on its own stream so the small
-	// octaves fill the machine next to the tail of the big ones (ostream[0] == stream)
+	// one stream per octave (ostream[0] == stream) and, for volumes of at most 4 M voxels, one chain stream for the heads of the
+	// octaves >= 1 (nullptr otherwise).  Which part of which octave runs where is the RunPlan's business: DESIGN.md, "The schedule of a run"
 	std::vector<hipStream_t> ostream;
-	// r04: the HEADS of the octaves >= 1 (levels up to the seed level) run on ONE stream, in order: each head waits for the seed level of
-	// the octave above anyway, and a dependency across streams costs 13-16 us (event -> barrier packet on another queue) where
-	// consecutive launches of one stream follow each other without a gap -- four hops of the 512^3 chain; the levels behind the seed
-	// level stay on the octave's own stream (cstream == nullptr: every octave wholly on its own stream, as before)
 	hipStream_t cstream = nullptr;
 	std::vector<hipEvent_t> ev_seed, ev_done;
 	hipEvent_t ev_fork = nullptr;
@@ -76,7 +100,7 @@ struct sift3d_ctx {
 	std::vector<DetectBufs> det_o;
 	unsigned long long *d_masks2 = nullptr;
 	unsigned *d_counts2 = nullptr, *d_offsets2 = nullptr, *d_prov2 = nullptr;
-	hipEvent_t ev_det_fork = nullptr, ev_det_join = nullptr, ev_det_fork2 = nullptr, ev_det_join2 = nullptr;
+	hipEvent_t ev_det_fork = nullptr, ev_det_join = nullptr, ev_det_join2 = nullptr;
 	DevKp *d_ext = nullptr;
 	int *d_codes = nullptr, *d_order = nullptr;  // d_order: slot -> extremum index
 	unsigned ext_cap = 0, kp_cap = 0;
@@ -101,6 +125,7 @@ struct sift3d_ctx {
 	// COMPLETED run refined its keypoints (d_refined holds n_kp records, sized kp_cap and reallocated behind a list regrow)
 	sift3d_detect_options dopt{};
 	bool run_full = false, run_refine = false, last_refine = false;
+	RunPlan plan;  // the schedule of the run prepared last (run_prepare); a list regrow enqueues the same plan again
 	sift3d_refined *d_refined = nullptr;
 	unsigned refined_cap = 0;
 
@@ -145,6 +170,11 @@ int alloc_lists(sift3d_ctx *c, unsigned ext_cap);
 float level_scale(const sift3d_params &p, int octave, int s);  // scale of level s of the ABSOLUTE octave (Src/cUtil.cc:215-225)
 void plan_pyramid(sift3d_ctx *c, int noct_total);
 void fill_detect_levels(const sift3d_ctx *c, int o, DetectLevels &DL);
+// Assign_Orientation + the slots of the accepted keypoints, Extract_Description (with_desc) + the final records, on the context's
+// stream: the whole-volume run, the replicated octaves (sift3d_run_describe) and the slab stages share them
+void enqueue_slots(sift3d_ctx *c);
+void enqueue_orient(sift3d_ctx *c, int rank, int world);
+void enqueue_describe(sift3d_ctx *c, int rank, int world, bool with_desc);
 int upload_luts(sift3d_ctx *c, const std::vector<WinLut> &luts, std::vector<float> &pool);
 std::vector<WinLut> blank_luts(const sift3d_ctx *c);
 size_t arena_floats_of(const sift3d_ctx *c);

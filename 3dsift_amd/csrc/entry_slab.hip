@@ -187,10 +187,8 @@ extern "C" int sift3d_run_describe(sift3d_handle c) {
 	if (rc) return rc;
 	hipStream_t st = c->stream;
 	S3D_HIP(hipEventRecord(c->ev[6], st));
-	launch_slots(c->d_ext, c->d_codes, c->d_total, c->ext_cap, c->d_nkp, c->d_order, c->kp_cap, c->d_slots_part, st);
-	launch_describe(c->d_ext, c->d_total, c->ext_cap, c->d_levels, c->d_luts, c->d_lutpool, c->d_desc, c->kp_cap, c->part_rank,
-	                c->part_world, c->d_order, c->d_nkp, c->d_nkp + 1, st, c->desc_lut_lds, &c->dsplit);
-	launch_finalize(c->d_ext, c->d_total, c->ext_cap, 1, c->d_kpout, c->d_xyz, c->kp_cap, st);
+	enqueue_slots(c);  // (again: the imported orientation results decide the slots)
+	enqueue_describe(c, c->part_rank, c->part_world, true);
 	S3D_HIP(hipEventRecord(c->ev[7], st));
 	unsigned host_words[3] = {0, 0, 0};
 	S3D_HIP(hipMemcpyAsync(host_words, c->d_total, sizeof(unsigned) * 3, hipMemcpyDeviceToHost, st));
@@ -492,23 +490,13 @@ static int slab_enqueue_detect(sift3d_ctx *c) {
 	                     c->d_ext, c->ext_cap, c->stream, c->g_last_elide ? &c->taps[c->ng - 1] : nullptr);
 	return SIFT3D_OK;
 }
-// Assign_Orientation (Src/cSIFT3D.cc:427-482) of the slab's extrema and the slots of the accepted ones
-static void slab_enqueue_orient(sift3d_ctx *c) {
-	launch_orient(c->d_ext, c->d_codes, c->d_total, c->ext_cap, c->d_levels, c->d_luts, c->d_lutpool, c->p.max_eig_thres,
-	              c->p.corner_thresh, 0, 1, c->d_order, c->d_nkp + 3, c->stream);
-	launch_slots(c->d_ext, c->d_codes, c->d_total, c->ext_cap, c->d_nkp, c->d_order, c->kp_cap, c->d_slots_part, c->stream);
-}
-// Extract_Description (Src/cSIFT3D.cc:484-502) with WHOLE windows from the slab's own level buffers, and the final records
-static void slab_enqueue_describe(sift3d_ctx *c) {
-	launch_describe(c->d_ext, c->d_total, c->ext_cap, c->d_levels, c->d_luts, c->d_lutpool, c->d_desc, c->kp_cap, 0, 1, c->d_order, c->d_nkp,
-	                c->d_nkp + 1, c->stream, c->desc_lut_lds, &c->dsplit);
-	launch_finalize(c->d_ext, c->d_total, c->ext_cap, 1, c->d_kpout, c->d_xyz, c->kp_cap, c->stream);
-}
+// Orientation and description are the whole-volume run's stages (enqueue_orient / enqueue_describe, context.hip) as rank 0 of 1: a slab
+// orients all of its own extrema and describes them with WHOLE windows from its own level buffers
 // detection + orientation, and the three counters on their way to pinned memory in front of ev[6]
 static int slab_keypoints_enqueue(sift3d_ctx *c) {
 	int rc = slab_enqueue_detect(c);
 	if (rc) return rc;
-	slab_enqueue_orient(c);
+	enqueue_orient(c, 0, 1);
 	S3D_HIP(hipMemcpyAsync(c->h_words, c->d_total, sizeof(unsigned) * 3, hipMemcpyDeviceToHost, c->stream));
 	S3D_HIP(hipEventRecord(c->ev[6], c->stream));
 	return SIFT3D_OK;
@@ -578,8 +566,8 @@ extern "C" int sift3d_slab_describe(sift3d_handle c) {
 	}
 	int rc = set_device(c->device);
 	if (rc) return rc;
-	slab_enqueue_orient(c);
-	slab_enqueue_describe(c);
+	enqueue_orient(c, 0, 1);
+	enqueue_describe(c, 0, 1, true);
 	if ((rc = slab_take_counts_final(c, "sift3d_slab_describe")) != SIFT3D_OK) return rc;
 	c->stage = 5;
 	return SIFT3D_OK;
@@ -622,7 +610,7 @@ extern "C" int sift3d_slab_orient_launch(sift3d_handle c) {
 	if (c->halo < slab_window_halo(c, false)) { set_last_error("the level buffers' halo is smaller than the orientation windows' reach"); return SIFT3D_ERR_STATE; }
 	int rc = set_device(c->device);
 	if (rc) return rc;
-	slab_enqueue_orient(c);
+	enqueue_orient(c, 0, 1);
 	return SIFT3D_OK;
 }
 extern "C" int sift3d_slab_orient_count(sift3d_handle c, int *n_kp) {
@@ -768,7 +756,7 @@ extern "C" int sift3d_slab_describe_launch(sift3d_handle c) {
 	}
 	int rc = set_device(c->device);
 	if (rc) return rc;
-	slab_enqueue_describe(c);
+	enqueue_describe(c, 0, 1, true);
 	c->stage = 5;
 	return SIFT3D_OK;
 }

@@ -89,6 +89,25 @@ extern "C" int sift3d_debug_counters(sift3d_handle c, int out[4]) {
 	return SIFT3D_OK;
 }
 
+extern "C" int sift3d_test_run_plan(sift3d_handle c, int *out, int cap, int *n) {
+	if (!c || !out || !n) return SIFT3D_ERR_ARG;
+	const RunPlan &p = c->plan;
+	if (p.oct.empty()) { set_last_error("no run has been prepared on this handle"); return SIFT3D_ERR_STATE; }
+	*n = SIFT3D_RUN_PLAN_HEAD + SIFT3D_RUN_PLAN_PER_OCTAVE * c->noct;
+	if (cap < *n) return SIFT3D_ERR_ARG;
+	const bool small = p.small_first >= 0;
+	const int head[SIFT3D_RUN_PLAN_HEAD] = {c->noct, p.small_first, p.chain, small ? p.small.hwp : 0, small ? (int)p.small.build_mask : 0,
+	                                        small ? (int)p.small.dog_mask : 0, c->dog_elide, c->g_last_elide, c->run_full, c->run_refine,
+	                                        p.det_two, p.det_early, p.det_rest_stream, p.det_rest_own, p.emit};
+	memcpy(out, head, sizeof(head));
+	for (int o = 0; o < c->noct; o++) {
+		const RunPlan::Oct &oc = p.oct[(size_t)o];
+		const int row[SIFT3D_RUN_PLAN_PER_OCTAVE] = {oc.head, oc.tail, oc.tail_moved, oc.prio, oc.head_slots, oc.tail_slots};
+		memcpy(out + SIFT3D_RUN_PLAN_HEAD + SIFT3D_RUN_PLAN_PER_OCTAVE * o, row, sizeof(row));
+	}
+	return SIFT3D_OK;
+}
+
 extern "C" int sift3d_debug_face_lookup(const float *grad3, int n, int route, int *face, float *bary3, int device) {
 	if (!grad3 || !face || !bary3 || n < 0) return SIFT3D_ERR_ARG;
 	int rc = set_device(device);

@@ -44,6 +44,20 @@ int sift3d_test_hook(int which, int value);
  * the last run, c[2] rows the calling thread's last sift3d_match re-scored exactly (near-tie guard), c[3] second passes of the calling thread's last
  * sift3d_describe_keypoint (0 or 1; h may be NULL) */
 int sift3d_debug_counters(sift3d_handle h, int c[4]);
+/* The schedule of the handle's last prepared whole-volume run (sift3d_run, sift3d_run_stages, sift3d_run_async, ...) as *n ints in
+ * plan[cap] (SIFT3D_ERR_ARG when cap is too small, SIFT3D_ERR_STATE before the first run).  A stream index is an octave's stream
+ * (0 = the handle's own) or -1, the chain stream.  Layout:
+ *   [0] octaves            [1] first octave of the small-octave launch (-1: none)   [2] 1: the chain stream exists
+ *   [3] half width the small launch pads to (0 without one)   [4] its mask of built Gaussian levels   [5] its mask of written DoG levels
+ *   [6] dog_elide  [7] g_last_elide  [8] run_full  [9] run_refine                  (flags of the run)
+ *   [10] 1: octaves >= 1 form their masks in a second scratch on octave 1's stream   [11] 1: octave 0's masks start behind its own pyramid
+ *   [12] stream index of the masks of the octaves >= 2   [13] 1: each of them behind its own octave's pyramid
+ *   [14] emit launches: 0 one per octave, 1 one for the octaves >= 1, 2 one for all
+ *   then six per octave o, at 15 + 6 o: stream index of its head (levels up to the seed level), of its tail (the levels behind), 1: the
+ *   tail was moved to the stream of the octave above, wave priority, slot plan of the head's levels, of the tail's (0: the launch's own) */
+#define SIFT3D_RUN_PLAN_HEAD 15
+#define SIFT3D_RUN_PLAN_PER_OCTAVE 6
+int sift3d_test_run_plan(sift3d_handle h, int *plan, int cap, int *n);
 /* GB/s (read + write, best of `iters`) of a float4 device-to-device copy of `bytes` bytes on `device`: the measured copy ceiling
  * reported beside the 8 TB/s spec peak */
 int sift3d_debug_copy_bandwidth(size_t bytes, int iters, int device, double *gbs);
