@@ -57,6 +57,9 @@ SYMBOLS = [
     # outlier validation of the displacement field (normalised median test)
     "sift3d_default_validate_options", "sift3d_validate_input_from_icgn", "sift3d_validate_input_from_icgn2", "sift3d_validate_displacements",
     "sift3d_validate_keep", "sift3d_icgn_init_from_validation", "sift3d_validate_stage_capacity",
+    # the displacement field at real-valued positions (moving least squares) and the chaining of load steps
+    "sift3d_default_field_options", "sift3d_field_eval", "sift3d_field_queries_from_displacements", "sift3d_field_unpack",
+    "sift3d_compose_displacements", "sift3d_icgn_init_from_field",
     # subset screening: texture sums and a per-POI subset radius, the step in front of IC-GN
     "sift3d_default_subset_options", "sift3d_subset_quality", "sift3d_subset_group_by_radius",
     # masked IC-GN: subsets limited to a voxel mask of the reference, and the mask of a grey level
@@ -188,6 +191,21 @@ assert C.sizeof(ValidateOptions) == 48
 VALIDATE_DTYPE = np.dtype([("median", "<f8", (3,)), ("mad", "<f8", (3,)), ("score", "<f8"), ("neighbours", "<i4"), ("status", "<i4"),
                            ("flagged", "<i4"), ("pass", "<i4")])
 assert VALIDATE_DTYPE.itemsize == 72
+
+
+class FieldOptions(C.Structure):
+    """sift3d_field_options (include/sift3d_hip.h)"""
+    _fields_ = [("radius", C.c_int), ("min_neighbours", C.c_int), ("weighting", C.c_int), ("require_enclosed", C.c_int),
+                ("reserved", C.c_int * 4)]
+
+
+assert C.sizeof(FieldOptions) == 32
+
+# sift3d_field_result: the field at the query, its gradient (rows u v w, columns x y z), the weighted residual, the sum of the weights,
+# the counted members, the sides they lie on and the status
+FIELD_DTYPE = np.dtype([("disp", "<f8", (3,)), ("G", "<f8", (9,)), ("rms", "<f8"), ("wsum", "<f8"), ("neighbours", "<i4"), ("sides", "<i4"),
+                        ("status", "<i4"), ("reserved", "<i4")])
+assert FIELD_DTYPE.itemsize == 128
 
 
 class SubsetOptions(C.Structure):
@@ -325,6 +343,14 @@ def lib():
         L.sift3d_mask_from_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_int,
                                              C.POINTER(C.c_double)]
         L.sift3d_validate_stage_capacity.argtypes = [_ip]
+        L.sift3d_default_field_options.argtypes = [C.POINTER(FieldOptions)]
+        L.sift3d_default_field_options.restype = None
+        L.sift3d_field_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(FieldOptions), C.c_int,
+                                        C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+        L.sift3d_field_queries_from_displacements.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.sift3d_field_unpack.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sift3d_compose_displacements.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sift3d_icgn_init_from_field.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, _ip]
         _sz = C.POINTER(C.c_size_t)
         L.sift3d_slab_min_halo.argtypes = [C.POINTER(Params), _ip]
         L.sift3d_slab_arena_floats.argtypes = [C.POINTER(SlabDesc), C.POINTER(Params), _sz]
@@ -1116,6 +1142,118 @@ def icgn_init_from_validation(val, init=None):
         out[:m] = ini
     count = C.c_int(0)
     _check(lib().sift3d_icgn_init_from_validation(_p(buf), m, _p(out), C.byref(count)))
+    return out[:m].copy(), count.value
+
+
+FIELD_OPTIONS = ("radius", "min_neighbours", "weighting", "require_enclosed")
+FIELD_FIELDS = ("disp", "G", "rms", "wsum", "neighbours", "sides", "status")
+
+
+def default_field_options():
+    """sift3d_default_field_options as a dict (needs no GPU)"""
+    o = _options(FieldOptions, "sift3d_default_field_options", FIELD_OPTIONS, "field", {})
+    return {k: getattr(o, k) for k in FIELD_OPTIONS}
+
+
+def field_eval(points, disp, valid, queries, device=0, **opts):
+    """sift3d_field_eval: the displacement field of the POIs ((m, 3) int32 x, y, z with displacements (m, 3) float64 and validity bytes
+    (m,) or None) at the real-valued positions queries ((nq, 3) float64): a plane fitted to the POIs within `radius` voxels (Chebyshev)
+    of each query, weighted by the tensor biweight (weighting 1) or uniformly (0).  points / disp / valid / queries: numpy arrays or
+    contiguous device tensors, all of the same kind.  Options: radius, min_neighbours, weighting, require_enclosed.  Returns disp
+    (nq, 3), G (nq, 3, 3) (rows u, v, w; columns x, y, z), rms, wsum, neighbours, sides, status (nq,), the records themselves as
+    `records` (FIELD_DTYPE: what field_unpack and compose_displacements take) and the device seconds."""
+    o = _options(FieldOptions, "sift3d_default_field_options", FIELD_OPTIONS, "field", opts)
+    dev = [_is_dev(a) for a in (points, disp, valid, queries) if a is not None]
+    if any(dev) != all(dev):
+        raise ValueError("points, disp, valid and queries must all be numpy arrays or all device tensors")
+    qp, m, q = _table(points, np.int32, 3, points)
+    up, mu, u = _table(disp, np.float64, 3, points)
+    ok = None if valid is None else (valid.ne(0) if dev[0] else np.asarray(valid) != 0)
+    vp, mv, ok = _table(ok, np.uint8, 0, points)
+    xp, nq, x = _table(queries, np.float64, 3, points)
+    if mu != m or (ok is not None and mv != m):
+        raise ValueError("disp, valid: one row per point")
+    out = np.zeros(max(nq, 1), FIELD_DTYPE)
+    sec = C.c_double(0)
+    _check(lib().sift3d_field_eval(qp, up, vp, m, xp, nq, C.byref(o), int(dev[0]), int(device), _p(out), C.byref(sec)))
+    d = _fields(out, nq, FIELD_FIELDS)
+    d["G"] = d["G"].reshape(-1, 3, 3)
+    d["records"] = out[:nq].copy()
+    d["seconds"] = sec.value
+    return d
+
+
+def _field_records(res):
+    rec = res["records"] if isinstance(res, dict) else res
+    return np.ascontiguousarray(rec, FIELD_DTYPE).reshape(-1)
+
+
+def field_queries(points, disp):
+    """sift3d_field_queries_from_displacements: the positions (m, 3) float64 the POIs ((m, 3) int32) moved to under disp ((m, 3)
+    float64), x = p + u: the queries of the next load step.  Non-finite where disp is.  Needs no GPU."""
+    q = np.ascontiguousarray(points, np.int32).reshape(-1, 3)
+    u = np.ascontiguousarray(disp, np.float64).reshape(-1, 3)
+    if len(u) != len(q):
+        raise ValueError("disp: one row per point")
+    m = len(q)
+    out = np.zeros((max(m, 1), 3), np.float64)
+    _check(lib().sift3d_field_queries_from_displacements(_p(q), _p(u), m, _p(out)))
+    return out[:m].copy()
+
+
+def field_unpack(res):
+    """sift3d_field_unpack: disp (n, 3), grad (n, 9) float64 and valid (n,) uint8 (status 0) of what field_eval returns (or its
+    records).  Needs no GPU."""
+    rec = _field_records(res)
+    n = len(rec)
+    buf = np.zeros(max(n, 1), FIELD_DTYPE)
+    buf[:n] = rec
+    disp, grad, valid = np.zeros((max(n, 1), 3)), np.zeros((max(n, 1), 9)), np.zeros(max(n, 1), np.uint8)
+    _check(lib().sift3d_field_unpack(_p(buf), n, _p(disp), _p(grad), _p(valid)))
+    return disp[:n].copy(), grad[:n].copy(), valid[:n].copy()
+
+
+def compose_displacements(disp_a, grad_a, valid_a, at_b):
+    """sift3d_compose_displacements: step A's displacements (m, 3), gradients (m, 9) or None and validity bytes (m,) or None at its
+    POIs, and step B's field evaluated where those POIs moved to (what field_eval returned at field_queries(points, disp_a), or its
+    records) -> the total in step A's frame: disp (m, 3) = u_A + u_B, grad (m, 9) = G_A + G_B + G_B G_A (None without grad_a) and
+    valid (m,) uint8.  Invalid rows are zero.  Needs no GPU."""
+    rec = _field_records(at_b)
+    m = len(rec)
+    ua = np.ascontiguousarray(disp_a, np.float64).reshape(-1, 3)
+    ga = None if grad_a is None else np.ascontiguousarray(grad_a, np.float64).reshape(-1, 9)
+    va = None if valid_a is None else np.ascontiguousarray(np.asarray(valid_a) != 0, np.uint8).reshape(-1)
+    if len(ua) != m or (ga is not None and len(ga) != m) or (va is not None and len(va) != m):
+        raise ValueError("disp_a, grad_a, valid_a: one row per record")
+    buf = np.zeros(max(m, 1), FIELD_DTYPE)
+    buf[:m] = rec
+    disp, valid = np.zeros((max(m, 1), 3)), np.zeros(max(m, 1), np.uint8)
+    grad = None if ga is None else np.zeros((max(m, 1), 9))
+    _check(lib().sift3d_compose_displacements(_p(ua) if m else None, None if ga is None or m == 0 else _p(ga),
+                                              None if va is None or m == 0 else _p(va), _p(buf), m, _p(disp),
+                                              None if grad is None else _p(grad), _p(valid)))
+    return disp[:m].copy(), None if grad is None else grad[:m].copy(), valid[:m].copy()
+
+
+def icgn_init_from_field(disp, grad=None, valid=None, only_valid=True, init=None):
+    """sift3d_icgn_init_from_field: (m, 12) float64 initial parameters of icgn from a measured field and the number of rows written.
+    Row i becomes (u, G00, G01, G02, v, G10, ..) of disp (m, 3) and grad ((m, 9), None: zero).  With only_valid only the rows whose
+    valid byte is set are written and the others are returned as given in init (None: all NaN).  Needs no GPU."""
+    u = np.ascontiguousarray(disp, np.float64).reshape(-1, 3)
+    m = len(u)
+    g = None if grad is None else np.ascontiguousarray(grad, np.float64).reshape(-1, 9)
+    v = None if valid is None else np.ascontiguousarray(np.asarray(valid) != 0, np.uint8).reshape(-1)
+    if (g is not None and len(g) != m) or (v is not None and len(v) != m):
+        raise ValueError("grad, valid: one row per displacement")
+    out = np.full((max(m, 1), 12), np.nan)
+    if init is not None:
+        ini = np.asarray(init, np.float64).reshape(-1, 12)
+        if len(ini) != m:
+            raise ValueError("init: one row of 12 per displacement")
+        out[:m] = ini
+    count = C.c_int(0)
+    _check(lib().sift3d_icgn_init_from_field(_p(u) if m else None, None if g is None or m == 0 else _p(g),
+                                             None if v is None or m == 0 else _p(v), m, int(bool(only_valid)), _p(out), C.byref(count)))
     return out[:m].copy(), count.value
 
 

@@ -1,6 +1,6 @@
 // poi_grid.h -- the spatial index over a call's POIs: a uniform cell grid over the bounding box of the contributing POIs
-// and the POIs sorted by cell, which sift3d_strain, sift3d_validate_displacements and sift3d_match_guided (its POIs are keypoint
-// positions) walk window by window (poi_window.h).  Built by
+// and the POIs sorted by cell, which sift3d_strain, sift3d_validate_displacements, sift3d_field_eval (around real-valued centres) and
+// sift3d_match_guided (its POIs are keypoint positions) walk window by window (poi_window.h).  Built by
 // poi_grid_build (kernels_poigrid.hip).  Host-compilable: a stand-alone program can use the grid rule (tests/test_strain_cases_cpu.py).
 #pragma once
 #include "scratch_layout.h"

@@ -400,6 +400,11 @@ struct PoiIndex;
 void launch_strain_fit(const int *d_pts, const double *d_disp, int m, const PoiIndex &ix, int radius, int min_nb, int measure,
                        sift3d_strain_result *d_out, hipStream_t st);
 
+// ---- kernels_field.hip: the displacement field at real-valued queries (sift3d_field_eval, include/sift3d_hip.h) --------------------
+// ix: the index built with radius + 1; d_out: nq records
+void launch_field_eval(const double *d_queries, int nq, const double *d_disp, const PoiIndex &ix, int radius, int min_nb, int weighting,
+                       int enclosed, sift3d_field_result *d_out, hipStream_t st);
+
 // ---- kernels_validate.hip: the normalised median test of the displacements (sift3d_validate_displacements, include/sift3d_hip.h) --
 // It runs on an index built with d_fold as the valid bytes.
 struct ValidateParams {

@@ -1,6 +1,6 @@
-// cRegistration.h -- RANSAC affine fits of matched keypoints, guided matching, subset screening, ZNCC integer search, IC-GN displacement refinement, validation and strain fields (no
+// cRegistration.h -- RANSAC affine fits of matched keypoints, guided matching, subset screening, ZNCC integer search, IC-GN displacement refinement, validation, strain fields and field evaluation (no
 // reference counterpart): the steps after enhancedMatch, on the GPU.
-// Over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_fit_rigid / sift3d_fit_rigid_local / sift3d_predict_positions / sift3d_match_guided / sift3d_subset_quality / sift3d_zncc_search / sift3d_icgn / sift3d_validate_displacements / sift3d_strain (include/sift3d_hip.h, which states the numerical contracts).  Both functions take
+// Over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_fit_rigid / sift3d_fit_rigid_local / sift3d_predict_positions / sift3d_match_guided / sift3d_subset_quality / sift3d_zncc_search / sift3d_icgn / sift3d_validate_displacements / sift3d_strain / sift3d_field_eval (include/sift3d_hip.h, which states the numerical contracts).  Both functions take
 // exactly the two std::vector<Cvec> that muBruteMatcher::enhancedMatch fills (refMatch[i] <-> tarMatch[i]).
 #ifndef S3D_HOST_CREGISTRATION_H
 #define S3D_HOST_CREGISTRATION_H
@@ -301,6 +301,43 @@ SIFT_LIBRARY_API std::vector<StrainResult> ComputeStrains(const std::vector<Cvec
 // from the affine map of its own result, L = I + G and b with L q + b - q = u, status 0; any other point gets status 1 (no start)
 SIFT_LIBRARY_API std::vector<AffineFit> SeedsFromValidation(const std::vector<Cvec> &points, const std::vector<IcgnResult> &first,
                                                             const std::vector<ValidationResult> &validation);
+
+struct SIFT_LIBRARY_API FieldOptions {
+	int radius = 16;               // window half width in voxels (Chebyshev), 1..4095
+	int min_neighbours = 10;       // 4..1048576
+	int weighting = 1;             // 1 tensor biweight, 0 uniform
+	bool require_enclosed = true;  // status 5 unless the query has neighbours on both sides of every axis
+};
+
+// the displacement field at one real-valued position (include/sift3d_hip.h, sift3d_field_eval): status 0 fitted, 1 fewer than
+// min_neighbours neighbours, 2 position not finite or out of range, 4 degenerate window, 5 not enclosed, -1 the call failed (message on
+// stderr, like EstimateAffine) or, from ComposeDisplacements, no value
+struct SIFT_LIBRARY_API FieldResult {
+	double disp[3] = {0, 0, 0};                 // the field at the position
+	double G[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // its gradient, row-major: rows u, v, w; columns x, y, z
+	double rms = 0, wsum = 0;
+	int neighbours = 0, sides = 0;
+	int status = -1;
+	double seconds = 0;  // device time of the call
+};
+
+// the field of the displacements RefineDisplacements returned at `points`, evaluated at the positions queries3 (x, y, z triples): a
+// point contributes under ComputeStrains' rule (zncc_min, accept_unconverged)
+SIFT_LIBRARY_API std::vector<FieldResult> EvaluateField(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp,
+                                                        const std::vector<double> &queries3, const FieldOptions &o = FieldOptions(),
+                                                        double zncc_min = 0, bool accept_unconverged = false);
+// the same at the positions the points of an earlier load step moved to, p + u_A(p): the second step of a load series with an updated
+// reference.  A point of step A whose displacement is not finite gets status 2
+SIFT_LIBRARY_API std::vector<FieldResult> EvaluateField(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp,
+                                                        const std::vector<Cvec> &pointsA, const std::vector<IcgnResult> &stepA,
+                                                        const FieldOptions &o = FieldOptions(), double zncc_min = 0,
+                                                        bool accept_unconverged = false);
+// the total of two load steps in step A's frame: disp = u_A + u_B, G = G_A + G_B + G_B G_A, status 0 where step A converged (status 0)
+// and atB -- EvaluateField at the moved points -- has status 0; -1 (all zero) elsewhere, or everywhere when the sizes differ
+SIFT_LIBRARY_API std::vector<FieldResult> ComposeDisplacements(const std::vector<IcgnResult> &stepA, const std::vector<FieldResult> &atB);
+// starts of RefineDisplacements (its init) at `points` from a field evaluated or composed there: A = [I + G | b] with
+// (I + G) q + b - q = u, status 0 where the field's status is 0; status 1 (no start) elsewhere
+SIFT_LIBRARY_API std::vector<AffineFit> SeedsFromField(const std::vector<Cvec> &points, const std::vector<FieldResult> &field);
 
 }  // namespace CPUSIFT
 #endif

@@ -729,4 +729,139 @@ std::vector<AffineFit> SeedsFromValidation(const std::vector<Cvec> &points, cons
 	return seeds;
 }
 
+// the C records of shell field results (the seconds dropped)
+static std::vector<sift3d_field_result> c_field(const std::vector<FieldResult> &f) {
+	std::vector<sift3d_field_result> r(f.size() ? f.size() : 1);
+	memset(r.data(), 0, sizeof(sift3d_field_result) * r.size());
+	for (size_t i = 0; i < f.size(); i++) {
+		memcpy(r[i].disp, f[i].disp, sizeof(r[i].disp));
+		memcpy(r[i].G, f[i].G, sizeof(r[i].G));
+		r[i].rms = f[i].rms;
+		r[i].wsum = f[i].wsum;
+		r[i].neighbours = f[i].neighbours;
+		r[i].sides = f[i].sides;
+		r[i].status = f[i].status;
+	}
+	return r;
+}
+
+std::vector<FieldResult> EvaluateField(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const std::vector<double> &queries3,
+                                       const FieldOptions &opts, double zncc_min, bool accept_unconverged) {
+	const size_t m = points.size(), nq = queries3.size() / 3;
+	std::vector<FieldResult> res(nq);
+	std::vector<int> q;
+	if (!int_triples("EvaluateField", "point", points, q)) return res;
+	if (disp.size() != m || queries3.size() != 3 * nq) {
+		fprintf(stderr, "[3dsift_amd] EvaluateField: %zu displacements for %zu points, %zu query coordinates\n", disp.size(), m, queries3.size());
+		return res;
+	}
+	const std::vector<sift3d_icgn_result> ic = c_records<sift3d_icgn_result>(disp, m);
+	std::vector<double> u(3 * (m ? m : 1));
+	std::vector<unsigned char> valid(m ? m : 1);
+	int rc = sift3d_strain_input_from_icgn(ic.data(), (int)m, zncc_min, accept_unconverged ? 1 : 0, u.data(), valid.data());
+	sift3d_field_options o;
+	sift3d_default_field_options(&o);
+	o.radius = opts.radius;
+	o.min_neighbours = opts.min_neighbours;
+	o.weighting = opts.weighting;
+	o.require_enclosed = opts.require_enclosed ? 1 : 0;
+	std::vector<sift3d_field_result> r(nq ? nq : 1);
+	double sec = 0;
+	if (rc == SIFT3D_OK) rc = sift3d_field_eval(q.data(), u.data(), valid.data(), (int)m, queries3.data(), (int)nq, &o, 0, GetDevice(), r.data(), &sec);
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] EvaluateField: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return res;
+	}
+	for (size_t i = 0; i < nq; i++) {
+		memcpy(res[i].disp, r[i].disp, sizeof(res[i].disp));
+		memcpy(res[i].G, r[i].G, sizeof(res[i].G));
+		res[i].rms = r[i].rms;
+		res[i].wsum = r[i].wsum;
+		res[i].neighbours = r[i].neighbours;
+		res[i].sides = r[i].sides;
+		res[i].status = r[i].status;
+		res[i].seconds = sec;
+	}
+	return res;
+}
+
+std::vector<FieldResult> EvaluateField(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const std::vector<Cvec> &pointsA,
+                                       const std::vector<IcgnResult> &stepA, const FieldOptions &opts, double zncc_min, bool accept_unconverged) {
+	const size_t mA = pointsA.size();
+	std::vector<int> qa;
+	if (!int_triples("EvaluateField", "step A point", pointsA, qa)) return std::vector<FieldResult>(mA);
+	if (stepA.size() != mA) {
+		fprintf(stderr, "[3dsift_amd] EvaluateField: %zu step A results for %zu points\n", stepA.size(), mA);
+		return std::vector<FieldResult>(mA);
+	}
+	std::vector<double> ua(3 * (mA ? mA : 1)), x(3 * mA);
+	for (size_t i = 0; i < mA; i++)
+		for (int c = 0; c < 3; c++) ua[3 * i + c] = stepA[i].p[4 * c];
+	sift3d_field_queries_from_displacements(qa.data(), ua.data(), (int)mA, x.data());
+	return EvaluateField(points, disp, x, opts, zncc_min, accept_unconverged);
+}
+
+std::vector<FieldResult> ComposeDisplacements(const std::vector<IcgnResult> &stepA, const std::vector<FieldResult> &atB) {
+	const size_t m = stepA.size();
+	std::vector<FieldResult> res(m);
+	if (atB.size() != m) {
+		fprintf(stderr, "[3dsift_amd] ComposeDisplacements: %zu field records for %zu results\n", atB.size(), m);
+		return res;
+	}
+	std::vector<double> ua(3 * (m ? m : 1)), ga(9 * (m ? m : 1)), u(3 * (m ? m : 1)), g(9 * (m ? m : 1));
+	std::vector<unsigned char> va(m ? m : 1), v(m ? m : 1);
+	for (size_t i = 0; i < m; i++) {
+		for (int c = 0; c < 3; c++) {
+			ua[3 * i + c] = stepA[i].p[4 * c];
+			for (int a = 0; a < 3; a++) ga[9 * i + 3 * c + a] = stepA[i].p[4 * c + 1 + a];
+		}
+		va[i] = stepA[i].status == 0 ? 1 : 0;
+	}
+	const int rc = sift3d_compose_displacements(ua.data(), ga.data(), va.data(), c_field(atB).data(), (int)m, u.data(), g.data(), v.data());
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] ComposeDisplacements: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return res;
+	}
+	for (size_t i = 0; i < m; i++) {
+		if (!v[i]) continue;
+		memcpy(res[i].disp, u.data() + 3 * i, sizeof(res[i].disp));
+		memcpy(res[i].G, g.data() + 9 * i, sizeof(res[i].G));
+		res[i].rms = atB[i].rms;
+		res[i].wsum = atB[i].wsum;
+		res[i].neighbours = atB[i].neighbours;
+		res[i].sides = atB[i].sides;
+		res[i].status = 0;
+	}
+	return res;
+}
+
+std::vector<AffineFit> SeedsFromField(const std::vector<Cvec> &points, const std::vector<FieldResult> &field) {
+	const size_t m = points.size();
+	std::vector<AffineFit> seeds(m);
+	for (size_t i = 0; i < m; i++) seeds[i].status = 1;
+	if (field.size() != m) {
+		fprintf(stderr, "[3dsift_amd] SeedsFromField: %zu field records for %zu points\n", field.size(), m);
+		return seeds;
+	}
+	const std::vector<sift3d_field_result> rec = c_field(field);
+	std::vector<double> u(3 * (m ? m : 1)), g(9 * (m ? m : 1)), p0(12 * (m ? m : 1), (double)NAN);
+	std::vector<unsigned char> v(m ? m : 1);
+	sift3d_field_unpack(rec.data(), (int)m, u.data(), g.data(), v.data());
+	sift3d_icgn_init_from_field(u.data(), g.data(), v.data(), (int)m, 1, p0.data(), nullptr);
+	for (size_t i = 0; i < m; i++) {
+		if (!v[i]) continue;
+		const double *p = p0.data() + 12 * i;
+		const double q[3] = {points[i].x, points[i].y, points[i].z};
+		for (int c = 0; c < 3; c++) {
+			double L[3];
+			for (int a = 0; a < 3; a++) L[a] = (a == c ? 1.0 : 0.0) + p[4 * c + 1 + a];
+			// b_c = q_c + u_c - L_c . q
+			for (int a = 0; a < 3; a++) seeds[i].A[4 * c + a] = L[a];
+			seeds[i].A[4 * c + 3] = (q[c] + p[4 * c]) - ((L[0] * q[0] + L[1] * q[1]) + L[2] * q[2]);
+		}
+		seeds[i].status = 0;
+	}
+	return seeds;
+}
+
 }  // namespace CPUSIFT

@@ -1013,6 +1013,96 @@ int sift3d_validate_keep(const sift3d_validate_result *val, const unsigned char 
 int sift3d_icgn_init_from_validation(const sift3d_validate_result *val, int m, double *init12, int *count);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Evaluating the displacement field at any position (no reference counterpart: the moving least squares of scattered-data codes).
+ * Every other result lives at the integer POIs of one call; this is the field at a real-valued position: a plane fitted to the
+ * displacements of the POIs around the query, weighted so that the value moves continuously with the query.  It is what a load
+ * series with an updated reference needs (the total at a reference POI p is u_A(p) + u_B(p + u_A(p)), and p + u_A(p) is no POI of
+ * step B), what seeds a denser POI grid from a coarse one, and what samples the field on a lattice.
+ * Numerical contract (a tolerance contract like sift3d_strain's, not bit for bit; tests/field_ref.py restates it in NumPy fp64):
+ *   Inputs: points3, disp3, valid as for sift3d_strain, and a POI contributes under its rule: a non-zero valid byte (NULL: all),
+ *     three finite displacements, every |coordinate| <= 2^24.  Duplicates each count.  queries3: nq rows (x, y, z) in fp64.
+ *   Offsets: d_a = (double)q_j,a - x_a, one rounded subtraction, of contributing POI j from the query x.
+ *   Members of query x: the contributing POIs with fabs(d_a) <= (double)radius on all three axes.
+ *   Weights: weighting 0: w = 1.  Weighting 1 (tensor biweight): t_a = d_a / radius, f_a = 1 - t_a * t_a, g_a = f_a * f_a,
+ *     w = (g_0 * g_1) * g_2.  A member on a face of the window has w = 0 exactly.  neighbours, sides and every sum count the members
+ *     with w > 0 only.  sides: bit 2a is set when a counted member has d_a <= 0, bit 2a + 1 when one has d_a >= 0 (63: the query
+ *     has neighbours on both sides of every axis).
+ *   Fit: u0 is the displacement of the counted member with the lowest index and every sum of displacements is formed on u - u0.
+ *     W = sum w;  S1 = sum w d;  S2 = sum w d d^T;  U_c = sum w (u_c - u0_c);  P_ca = sum w (u_c - u0_c) d_a, all fp64;
+ *     C = S2 - S1 S1^T / W;  B_ca = P_ca - S1_a U_c / W;  C = L L^T (3 x 3 Cholesky, sift3d_strain's pivot rule: a pivot <= 1e-9 x
+ *     the largest diagonal entry of C, or NaN, is a degenerate window);  row c of G = C^-1 B_c;
+ *     disp_c = u0_c + U_c / W - G_c . S1 / W;
+ *     rms = sqrt(sum w sum_c (u_c - disp_c - G_c . d)^2 / (3 W)), from a second pass over the members.
+ *     With weighting 0 this is sift3d_strain's fit with n in place of W.  A constant field returns the constant, G = 0 and rms = 0
+ *     exactly.
+ *   Status per query (results of a successful call, not errors), checked in this order:
+ *     2 a query coordinate is non-finite or beyond 2^24 in magnitude (neighbours and sides 0);  1 neighbours < min_neighbours;
+ *     5 require_enclosed is set and sides != 63;  4 degenerate window;  0 otherwise.
+ *     A non-zero status zeroes every double and still reports neighbours and sides.
+ *   Determinism: no float atomics; the members are visited in the order of the POI index (cells of a uniform grid, a cell's POIs
+ *     in ascending index) and every fp64 sum is reduced in a fixed order: two calls on the same input return the same bytes.
+ * SIFT3D_ERR_ARG (checked before any device call): m < 0 or nq < 0, radius outside 1..4095, min_neighbours outside 4..1048576,
+ * weighting or require_enclosed outside 0..1, a non-zero reserved word, NULL out or queries3 with nq > 0, NULL points3 or disp3 with
+ * m > 0.  SIFT3D_ERR_NO_DEVICE after that check when no GPU is visible: there is no CPU fallback.  nq = 0 succeeds; m = 0 with
+ * nq > 0 succeeds with status 1 at every query whose coordinates are in range.  o may be NULL (defaults).  on_device != 0: points3,
+ * disp3, valid and queries3 are device pointers on `device`, ordered behind the legacy default stream; out is host memory, filled
+ * by one copy at the end.  *seconds (may be NULL): device time of the call (HIP events; the uploads of host inputs excluded).
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct sift3d_field_options {
+	int radius;            /* window half width in voxels (Chebyshev), 1..4095, default 16 */
+	int min_neighbours;    /* 4..1048576, default 10 */
+	int weighting;         /* 1 (default): tensor biweight; 0: uniform */
+	int require_enclosed;  /* 1 (default): status 5 unless the query has neighbours on both sides of every axis */
+	int reserved[4];       /* must be 0 */
+} sift3d_field_options;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_field_options) == 32, "sift3d_field_options must be 32 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_field_options, min_neighbours) == 4 && offsetof(sift3d_field_options, weighting) == 8 &&
+                     offsetof(sift3d_field_options, require_enclosed) == 12 && offsetof(sift3d_field_options, reserved) == 16,
+                     "sift3d_field_options field offsets");
+
+typedef struct sift3d_field_result {
+	double disp[3];        /* the field at the query (the plane's constant term) */
+	double G[9];           /* its gradient there, row-major: rows u v w, columns x y z */
+	double rms;            /* weighted residual of the fit */
+	double wsum;           /* W, the sum of the weights */
+	int neighbours;        /* members with weight > 0 */
+	int sides;             /* bit 2a: a member with d_a <= 0, bit 2a + 1: one with d_a >= 0 */
+	int status;            /* the table above */
+	int reserved;          /* 0 */
+} sift3d_field_result;
+SIFT3D_STATIC_ASSERT(sizeof(sift3d_field_result) == 128, "sift3d_field_result must be 128 bytes");
+SIFT3D_STATIC_ASSERT(offsetof(sift3d_field_result, G) == 24 && offsetof(sift3d_field_result, rms) == 96 &&
+                     offsetof(sift3d_field_result, wsum) == 104 && offsetof(sift3d_field_result, neighbours) == 112 &&
+                     offsetof(sift3d_field_result, sides) == 116 && offsetof(sift3d_field_result, status) == 120 &&
+                     offsetof(sift3d_field_result, reserved) == 124, "sift3d_field_result field offsets");
+
+/* the defaults above; needs no GPU */
+void sift3d_default_field_options(sift3d_field_options *o);
+/* m POIs (x, y, z int triples), their displacements (m * 3) and validity bytes (m, or NULL); nq queries (x, y, z doubles); out: nq
+ * records */
+int sift3d_field_eval(const int *points3, const double *disp3, const unsigned char *valid, int m, const double *queries3, int nq,
+                      const sift3d_field_options *o, int on_device, int device, sift3d_field_result *out, double *seconds);
+/* host only, no GPU: the positions the POIs moved to, x = (double)p + u per component -- the queries of the next load step.  The
+ * result is non-finite where u is, and such a query gets status 2.  SIFT3D_ERR_ARG: m < 0, or a NULL pointer with m > 0. */
+int sift3d_field_queries_from_displacements(const int *points3, const double *disp3, int m, double *queries3);
+/* host only: row i of disp3 = res[i].disp, of grad9 = res[i].G, valid[i] = (res[i].status == 0); grad9 and valid may be NULL (not
+ * wanted).  SIFT3D_ERR_ARG: n < 0, or NULL res / disp3 with n > 0. */
+int sift3d_field_unpack(const sift3d_field_result *res, int n, double *disp3, double *grad9, unsigned char *valid);
+/* host only: step A's result at its POIs (dispA3, gradA9 or NULL, validA or NULL: all valid) and step B's field evaluated where those
+ * POIs moved to (atB) -> the total in step A's frame: disp = u_A + u_B and, with gradA9, grad = (G_A + G_B) + G_B G_A (from
+ * F = F_B F_A with F = I + G), an entry of the product formed as (a * b + c * d) + e * f.  valid[i] = (validA is NULL or validA[i] != 0)
+ * and atB[i].status == 0; the rows of an invalid POI are zero.  grad9 and valid may be NULL (not wanted).  SIFT3D_ERR_ARG: m < 0,
+ * NULL dispA3 / atB / disp3 with m > 0, or a non-NULL grad9 with a NULL gradA9. */
+int sift3d_compose_displacements(const double *dispA3, const double *gradA9, const unsigned char *validA, const sift3d_field_result *atB,
+                                 int m, double *disp3, double *grad9, unsigned char *valid);
+/* host only: row i of init12 (m * 12) becomes (u, G00, G01, G02, v, G10, G11, G12, w, G20, G21, G22) of row i of disp3 and grad9 (NULL:
+ * a zero gradient): the start of sift3d_icgn from a measured field.  only_valid != 0: only the rows whose valid byte is set are
+ * written (valid NULL: all) and the others stay as they are; only_valid == 0: every row is written.  *count (may be NULL): rows
+ * written.  SIFT3D_ERR_ARG: m < 0, or NULL disp3 / init12 with m > 0. */
+int sift3d_icgn_init_from_field(const double *disp3, const double *grad9, const unsigned char *valid, int m, int only_valid, double *init12,
+                                int *count);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Subset screening: the step in front of IC-GN (no reference counterpart: the SSSIG rule of DIC / DVC codes, Pan et al. 2008,
  * Var(u) ~ 2 sigma_noise^2 / SSSIG_x).  Per POI it forms the texture sums of the subset -- the cube of voxels IC-GN would match -- at
  * growing radius and reports the smallest radius at which the sum of squared intensity gradients reaches a threshold, or that no
