@@ -64,6 +64,9 @@ SYMBOLS = [
     "sift3d_default_subset_options", "sift3d_subset_quality", "sift3d_subset_group_by_radius",
     # masked IC-GN: subsets limited to a voxel mask of the reference, and the mask of a grey level
     "sift3d_icgn_masked", "sift3d_mask_from_level",
+    # several bodies: connected-component labels of a mask, and the three window calls limited to a POI's own body
+    "sift3d_mask_label", "sift3d_labels_at_points", "sift3d_test_label_tile", "sift3d_strain_labelled",
+    "sift3d_validate_displacements_labelled", "sift3d_field_eval_labelled",
     "sift3d_device_count", "sift3d_error_string", "sift3d_last_error",
     # typed input: 8 / 16-bit integer voxels uploaded at their own width and widened on the GPU
     "sift3d_dtype_bytes", "sift3d_create_typed", "sift3d_volume_to_device", "sift3d_test_ingest_launch",
@@ -342,6 +345,16 @@ def lib():
                                          C.c_void_p, C.POINTER(C.c_double)]
         L.sift3d_mask_from_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_int,
                                              C.POINTER(C.c_double)]
+        L.sift3d_mask_label.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, _ip, C.c_int, C.c_int,
+                                        C.POINTER(C.c_double)]
+        L.sift3d_labels_at_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        L.sift3d_test_label_tile.argtypes = [_ip]
+        L.sift3d_strain_labelled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(StrainOptions), C.c_int, C.c_int,
+                                             C.c_void_p, C.POINTER(C.c_double)]
+        L.sift3d_validate_displacements_labelled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                             C.POINTER(ValidateOptions), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+        L.sift3d_field_eval_labelled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                 C.POINTER(FieldOptions), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
         L.sift3d_validate_stage_capacity.argtypes = [_ip]
         L.sift3d_default_field_options.argtypes = [C.POINTER(FieldOptions)]
         L.sift3d_default_field_options.restype = None
@@ -930,6 +943,63 @@ def mask_from_level(vol, level, device=0, with_seconds=False):
     return (out, sec.value) if with_seconds else out
 
 
+def label_tile():
+    """sift3d_test_label_tile (test hook): the extents (tx, ty, tz) of the tile whose union-find mask_label runs in LDS.  Needs no GPU."""
+    t = (C.c_int * 3)()
+    _check(lib().sift3d_test_label_tile(t))
+    return tuple(t)
+
+
+def mask_label(mask, connectivity=6, min_voxels=1, device=0, with_seconds=False):
+    """sift3d_mask_label: the connected components of a mask, an (nz, ny, nx) uint8 (or bool) numpy array or a contiguous uint8 device
+    tensor; any non-zero byte is "in".  connectivity: 6 (faces) or 26 (faces, edges and corners).  Returns labels, an int32 array / tensor
+    of the same shape and kind -- 0 outside the mask and in components of fewer than min_voxels voxels, else 1..count in ascending
+    order of a component's lowest voxel (scipy.ndimage.label's numbering) -- and count (with_seconds: and the device seconds)."""
+    on_dev = _is_dev(mask)
+    if on_dev:
+        import torch
+
+        if str(mask.dtype) not in ("torch.uint8", "torch.bool") or not mask.is_contiguous() or mask.dim() != 3:
+            raise ValueError("mask: a contiguous uint8 (nz, ny, nx) device tensor is needed")
+        v = mask
+        vp = C.c_void_p(v.data_ptr())
+        out = torch.empty(v.shape, dtype=torch.int32, device=v.device)
+        op = C.c_void_p(out.data_ptr())
+        device = v.device.index if v.device.index is not None else device
+    else:
+        v = np.asarray(mask)
+        if v.ndim != 3 or v.dtype not in (np.uint8, np.bool_):
+            raise ValueError("mask: a uint8 or bool (nz, ny, nx) array is needed")
+        v = np.ascontiguousarray(v).view(np.uint8)
+        vp = _p(v)
+        out = np.empty(v.shape, np.int32)
+        op = _p(out)
+    sec, count = C.c_double(0), C.c_int(0)
+    _check(lib().sift3d_mask_label(vp, *tuple(v.shape)[::-1], int(connectivity), int(min_voxels), op, C.byref(count), int(on_dev), int(device),
+                                   C.byref(sec)))
+    return (out, count.value, sec.value) if with_seconds else (out, count.value)
+
+
+def labels_at(labels, points, device=0):
+    """sift3d_labels_at_points: the label (m,) int32 at each point ((m, 3) int32 x, y, z) of labels, an (nz, ny, nx) int32 numpy array or
+    contiguous int32 device tensor (what mask_label returns); 0 for a point outside the volume.  With a host array it needs no GPU."""
+    on_dev = _is_dev(labels)
+    if on_dev:
+        if str(labels.dtype) != "torch.int32" or not labels.is_contiguous() or labels.dim() != 3:
+            raise ValueError("labels: a contiguous int32 (nz, ny, nx) device tensor is needed")
+        lab, lp = labels, C.c_void_p(labels.data_ptr())
+        device = labels.device.index if labels.device.index is not None else device
+    else:
+        lab = np.ascontiguousarray(labels, np.int32)
+        if lab.ndim != 3:
+            raise ValueError("labels: an (nz, ny, nx) volume is needed")
+        lp = _p(lab)
+    qp, m, q = _table(points, np.int32, 3, labels)
+    out = np.zeros(max(m, 1), np.int32)
+    _check(lib().sift3d_labels_at_points(lp, *tuple(lab.shape)[::-1], qp, m, _p(out), int(on_dev), int(device)))
+    return out[:m].copy()
+
+
 SEARCH_OPTIONS = ("subset_radius", "search_radius")
 
 
@@ -1016,12 +1086,13 @@ def strain_input_from_icgn2(res, zncc_min=0.0, accept_unconverged=False):
     return disp[:m].copy(), valid[:m].copy()
 
 
-def strain(points, disp, valid=None, device=0, **opts):
+def strain(points, disp, valid=None, device=0, label=None, **opts):
     """sift3d_strain: a plane fitted to the displacements ((m, 3) float64 u, v, w) of the POIs ((m, 3) int32 x, y, z) within `radius`
     voxels (Chebyshev) of each POI, and the strain of the fitted gradient.  valid: (m,) bytes or None (all valid).  points / disp /
     valid: numpy arrays or contiguous device tensors, all of the same kind.  Options: radius, min_neighbours, measure (0
-    Green-Lagrange, 1 infinitesimal).  Returns disp (m, 3), G (m, 3, 3) (rows u, v, w; columns x, y, z), E (m, 6) (xx yy zz xy yz zx),
-    principal (m, 3), equivalent, rms, neighbours, status (m,) and the device seconds."""
+    Green-Lagrange, 1 infinitesimal).  label: None, or (m,) int32 body labels (sift3d_strain_labelled: a POI's neighbours are those of
+    its own label, which is > 0; what labels_at returns).  Returns disp (m, 3), G (m, 3, 3) (rows u, v, w; columns x, y, z), E (m, 6)
+    (xx yy zz xy yz zx), principal (m, 3), equivalent, rms, neighbours, status (m,) and the device seconds."""
     o = _options(StrainOptions, "sift3d_default_strain_options", STRAIN_OPTIONS, "strain", opts)
     dev = [_is_dev(a) for a in (points, disp, valid) if a is not None]
     if any(dev) != all(dev):
@@ -1030,11 +1101,15 @@ def strain(points, disp, valid=None, device=0, **opts):
     up, mu, u = _table(disp, np.float64, 3, points)
     ok = None if valid is None else (valid.ne(0) if dev[0] else np.asarray(valid) != 0)
     vp, mv, ok = _table(ok, np.uint8, 0, points)
-    if mu != m or (ok is not None and mv != m):
-        raise ValueError("disp, valid: one row per point")
+    lp, ml, lab = _table(label, np.int32, 0, points)
+    if mu != m or (ok is not None and mv != m) or (lab is not None and ml != m):
+        raise ValueError("disp, valid, label: one row per point")
     out = np.zeros(max(m, 1), STRAIN_DTYPE)
     sec = C.c_double(0)
-    _check(lib().sift3d_strain(qp, up, vp, m, C.byref(o), int(dev[0]), int(device), _p(out), C.byref(sec)))
+    if lab is None:
+        _check(lib().sift3d_strain(qp, up, vp, m, C.byref(o), int(dev[0]), int(device), _p(out), C.byref(sec)))
+    else:
+        _check(lib().sift3d_strain_labelled(qp, up, vp, lp, m, C.byref(o), int(dev[0]), int(device), _p(out), C.byref(sec)))
     d = _fields(out, m, ("disp", "G", "E", "principal", "equivalent", "rms", "neighbours", "status"))
     d["G"] = d["G"].reshape(-1, 3, 3)
     d["seconds"] = sec.value
@@ -1079,12 +1154,13 @@ def validate_input_from_icgn(res, zncc_min=0.0, accept_unconverged=False):
     return disp[:m].copy(), grad[:m].copy(), valid[:m].copy()
 
 
-def validate(points, disp, grad=None, valid=None, device=0, **opts):
+def validate(points, disp, grad=None, valid=None, device=0, label=None, **opts):
     """sift3d_validate_displacements: the normalised median test of the displacements ((m, 3) float64 u, v, w) of the POIs ((m, 3) int32
     x, y, z) against the POIs within `radius` voxels (Chebyshev) of each.  grad: (m, 9) float64 gradients of the POIs (rows u, v, w;
     columns x, y, z) that carry a neighbour's value to the tested POI, or None; valid: (m,) bytes or None (all valid).  points / disp /
     grad / valid: numpy arrays or contiguous device tensors, all of the same kind.  Options: radius, min_neighbours, passes,
-    threshold, eps.  Returns median (m, 3), mad (m, 3), score, neighbours, status, flagged, pass (m,), the records themselves as
+    threshold, eps.  label: None, or (m,) int32 body labels (sift3d_validate_displacements_labelled: a POI's neighbours are those of its
+    own label, which is > 0).  Returns median (m, 3), mad (m, 3), score, neighbours, status, flagged, pass (m,), the records themselves as
     `records` (VALIDATE_DTYPE: what validate_keep and icgn_init_from_validation take) and the device seconds."""
     o = _options(ValidateOptions, "sift3d_default_validate_options", VALIDATE_OPTIONS, "validate", opts)
     dev = [_is_dev(a) for a in (points, disp, grad, valid) if a is not None]
@@ -1095,11 +1171,16 @@ def validate(points, disp, grad=None, valid=None, device=0, **opts):
     gp, mg, gr = _table(grad, np.float64, 9, points)
     ok = None if valid is None else (valid.ne(0) if dev[0] else np.asarray(valid) != 0)
     vp, mv, ok = _table(ok, np.uint8, 0, points)
-    if mu != m or (gr is not None and mg != m) or (ok is not None and mv != m):
-        raise ValueError("disp, grad, valid: one row per point")
+    lp, ml, lab = _table(label, np.int32, 0, points)
+    if mu != m or (gr is not None and mg != m) or (ok is not None and mv != m) or (lab is not None and ml != m):
+        raise ValueError("disp, grad, valid, label: one row per point")
     out = np.zeros(max(m, 1), VALIDATE_DTYPE)
     sec = C.c_double(0)
-    _check(lib().sift3d_validate_displacements(qp, up, gp, vp, m, C.byref(o), int(dev[0]), int(device), _p(out), C.byref(sec)))
+    if lab is None:
+        _check(lib().sift3d_validate_displacements(qp, up, gp, vp, m, C.byref(o), int(dev[0]), int(device), _p(out), C.byref(sec)))
+    else:
+        _check(lib().sift3d_validate_displacements_labelled(qp, up, gp, vp, lp, m, C.byref(o), int(dev[0]), int(device), _p(out),
+                                                            C.byref(sec)))
     d = _fields(out, m, VALIDATE_FIELDS)
     d["records"] = out[:m].copy()
     d["seconds"] = sec.value
@@ -1155,11 +1236,13 @@ def default_field_options():
     return {k: getattr(o, k) for k in FIELD_OPTIONS}
 
 
-def field_eval(points, disp, valid, queries, device=0, **opts):
+def field_eval(points, disp, valid, queries, device=0, label=None, query_label=None, **opts):
     """sift3d_field_eval: the displacement field of the POIs ((m, 3) int32 x, y, z with displacements (m, 3) float64 and validity bytes
     (m,) or None) at the real-valued positions queries ((nq, 3) float64): a plane fitted to the POIs within `radius` voxels (Chebyshev)
     of each query, weighted by the tensor biweight (weighting 1) or uniformly (0).  points / disp / valid / queries: numpy arrays or
-    contiguous device tensors, all of the same kind.  Options: radius, min_neighbours, weighting, require_enclosed.  Returns disp
+    contiguous device tensors, all of the same kind.  Options: radius, min_neighbours, weighting, require_enclosed.  label and
+    query_label: both None, or the (m,) and (nq,) int32 body labels of the POIs and of the queries (sift3d_field_eval_labelled: a query's
+    members are the POIs of its label, which is > 0).  Returns disp
     (nq, 3), G (nq, 3, 3) (rows u, v, w; columns x, y, z), rms, wsum, neighbours, sides, status (nq,), the records themselves as
     `records` (FIELD_DTYPE: what field_unpack and compose_displacements take) and the device seconds."""
     o = _options(FieldOptions, "sift3d_default_field_options", FIELD_OPTIONS, "field", opts)
@@ -1173,9 +1256,18 @@ def field_eval(points, disp, valid, queries, device=0, **opts):
     xp, nq, x = _table(queries, np.float64, 3, points)
     if mu != m or (ok is not None and mv != m):
         raise ValueError("disp, valid: one row per point")
+    if (label is None) != (query_label is None):
+        raise ValueError("label and query_label: both or neither")
+    lp, ml, lab = _table(label, np.int32, 0, points)
+    kp, nk, qlab = _table(query_label, np.int32, 0, points)
+    if lab is not None and (ml != m or nk != nq):
+        raise ValueError("label: one per point; query_label: one per query")
     out = np.zeros(max(nq, 1), FIELD_DTYPE)
     sec = C.c_double(0)
-    _check(lib().sift3d_field_eval(qp, up, vp, m, xp, nq, C.byref(o), int(dev[0]), int(device), _p(out), C.byref(sec)))
+    if lab is None:
+        _check(lib().sift3d_field_eval(qp, up, vp, m, xp, nq, C.byref(o), int(dev[0]), int(device), _p(out), C.byref(sec)))
+    else:
+        _check(lib().sift3d_field_eval_labelled(qp, up, vp, lp, m, xp, kp, nq, C.byref(o), int(dev[0]), int(device), _p(out), C.byref(sec)))
     d = _fields(out, nq, FIELD_FIELDS)
     d["G"] = d["G"].reshape(-1, 3, 3)
     d["records"] = out[:nq].copy()

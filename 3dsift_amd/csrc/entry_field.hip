@@ -107,11 +107,15 @@ extern "C" int sift3d_icgn_init_from_field(const double *disp3, const double *gr
 	return SIFT3D_OK;
 }
 
-extern "C" int sift3d_field_eval(const int *points3, const double *disp3, const unsigned char *valid, int m, const double *queries3, int nq,
-                                 const sift3d_field_options *o, int on_device, int device, sift3d_field_result *out, double *seconds) {
+namespace {
+// both entries; labelled: label holds m labels, query_label nq, and a query's members are the POIs of its label
+int field_call(const char *name, const int *points3, const double *disp3, const unsigned char *valid, const int *label, int m,
+               const double *queries3, const int *query_label, bool labelled, int nq, const sift3d_field_options *o, int on_device, int device,
+               sift3d_field_result *out, double *seconds) {
 	sift3d_field_options v;
-	if (m < 0 || nq < 0 || (nq > 0 && (!out || !queries3)) || (m > 0 && (!points3 || !disp3)) || !take_options(o, v)) {
-		set_last_error("sift3d_field_eval: bad argument");
+	if (m < 0 || nq < 0 || (nq > 0 && (!out || !queries3)) || (m > 0 && (!points3 || !disp3)) || (labelled && (!label || (nq > 0 && !query_label))) ||
+	    !take_options(o, v)) {
+		set_last_error(std::string(name) + ": bad argument");
 		return SIFT3D_ERR_ARG;
 	}
 	if (seconds) *seconds = 0;
@@ -124,10 +128,11 @@ extern "C" int sift3d_field_eval(const int *points3, const double *disp3, const 
 	hipStream_t st = D.stream;
 	CallTemps T;
 	// block a: [results | the index's pieces (m = 0: the two cell starts of an empty one-cell index) | (host inputs) points | disp | valid |
-	// queries]
+	// queries | labels | query labels]
 	const size_t M = (size_t)m, Q = (size_t)nq, res_bytes = sizeof(sift3d_field_result) * Q;
 	const size_t b_pts = on_device ? 0 : sizeof(int) * 3 * M, b_disp = on_device ? 0 : sizeof(double) * 3 * M, b_valid = on_device || !valid ? 0 : M;
 	const size_t b_qry = on_device ? 0 : sizeof(double) * 3 * Q;
+	const size_t b_label = on_device || !labelled ? 0 : sizeof(int) * M, b_qlabel = on_device || !labelled ? 0 : sizeof(int) * Q;
 	Layout L;
 	L.take(res_bytes);
 	PoiGridPlan G;
@@ -137,9 +142,10 @@ extern "C" int sift3d_field_eval(const int *points3, const double *disp3, const 
 	else
 		o_empty = L.take(sizeof(int) * 2);
 	const size_t o_pts = L.take(b_pts), o_disp = L.take(b_disp), o_valid = L.take(b_valid), o_qry = L.take(b_qry);
+	const size_t o_label = L.take(b_label), o_qlabel = L.take(b_qlabel);
 	S3D_HIP(hipMalloc(&T.a, L.end));
 	char *A = T.a;
-	const int *d_pts = points3;
+	const int *d_pts = points3, *d_label = labelled ? label : nullptr, *d_qlabel = labelled ? query_label : nullptr;
 	const double *d_disp = disp3, *d_qry = queries3;
 	const unsigned char *d_valid = valid;
 	if (on_device && (rc = D.after_legacy_stream())) return rc;
@@ -147,6 +153,8 @@ extern "C" int sift3d_field_eval(const int *points3, const double *disp3, const 
 	S3D_HIP_ST(st, upload(d_disp, A, o_disp, b_disp, st));
 	S3D_HIP_ST(st, upload(d_valid, A, o_valid, b_valid, st));
 	S3D_HIP_ST(st, upload(d_qry, A, o_qry, b_qry, st));
+	S3D_HIP_ST(st, upload(d_label, A, o_label, b_label, st));
+	S3D_HIP_ST(st, upload(d_qlabel, A, o_qlabel, b_qlabel, st));
 	S3D_HIP_ST(st, hipEventRecord(D.e0, st));
 	PoiIndex ix;
 	if (m > 0) {
@@ -156,10 +164,23 @@ extern "C" int sift3d_field_eval(const int *points3, const double *disp3, const 
 		S3D_HIP_ST(st, hipMemsetAsync(A + o_empty, 0, sizeof(int) * 2, st));
 		ix = PoiIndex{PoiGrid{0, 0, 0, v.radius + 1, 1, 1, 1}, 1, nullptr, reinterpret_cast<const int *>(A + o_empty), PoiSorted{}};
 	}
-	launch_field_eval(d_qry, nq, d_disp, ix, v.radius, v.min_neighbours, v.weighting, v.require_enclosed,
+	launch_field_eval(d_qry, nq, d_disp, d_label, d_qlabel, ix, v.radius, v.min_neighbours, v.weighting, v.require_enclosed,
 	                  reinterpret_cast<sift3d_field_result *>(A), st);
 	S3D_HIP_ST(st, hipGetLastError());
 	S3D_HIP_ST(st, hipMemcpyAsync(out, A, res_bytes, hipMemcpyDeviceToHost, st));
 	S3D_HIP_ST(st, hipEventRecord(D.e1, st));
 	return D.finish(seconds);
+}
+}  // namespace
+
+extern "C" int sift3d_field_eval(const int *points3, const double *disp3, const unsigned char *valid, int m, const double *queries3, int nq,
+                                 const sift3d_field_options *o, int on_device, int device, sift3d_field_result *out, double *seconds) {
+	return field_call("sift3d_field_eval", points3, disp3, valid, nullptr, m, queries3, nullptr, false, nq, o, on_device, device, out, seconds);
+}
+
+extern "C" int sift3d_field_eval_labelled(const int *points3, const double *disp3, const unsigned char *valid, const int *label, int m,
+                                          const double *queries3, const int *query_label, int nq, const sift3d_field_options *o, int on_device,
+                                          int device, sift3d_field_result *out, double *seconds) {
+	return field_call("sift3d_field_eval_labelled", points3, disp3, valid, label, m, queries3, query_label, true, nq, o, on_device, device, out,
+	                  seconds);
 }

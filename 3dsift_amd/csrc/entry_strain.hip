@@ -52,11 +52,13 @@ extern "C" int sift3d_strain_input_from_icgn(const sift3d_icgn_result *res, int 
 	return SIFT3D_OK;
 }
 
-extern "C" int sift3d_strain(const int *points3, const double *disp3, const unsigned char *valid, int m, const sift3d_strain_options *o,
-                             int on_device, int device, sift3d_strain_result *out, double *seconds) {
+namespace {
+// both entries; labelled: label holds m labels and limits a POI's neighbours to its own body
+int strain_call(const char *name, const int *points3, const double *disp3, const unsigned char *valid, const int *label, bool labelled, int m,
+                const sift3d_strain_options *o, int on_device, int device, sift3d_strain_result *out, double *seconds) {
 	int radius, min_nb, measure;
-	if (m < 0 || !out || (m > 0 && (!points3 || !disp3)) || !take_options(o, radius, min_nb, measure)) {
-		set_last_error("sift3d_strain: bad argument");
+	if (m < 0 || !out || (m > 0 && (!points3 || !disp3)) || (labelled && !label) || !take_options(o, radius, min_nb, measure)) {
+		set_last_error(std::string(name) + ": bad argument");
 		return SIFT3D_ERR_ARG;
 	}
 	if (seconds) *seconds = 0;
@@ -68,29 +70,42 @@ extern "C" int sift3d_strain(const int *points3, const double *disp3, const unsi
 	if ((rc = D.ensure(0, 0))) return rc;
 	hipStream_t st = D.stream;
 	CallTemps T;
-	// block a: [results | the index's pieces | (host inputs) points | disp | valid]
+	// block a: [results | the index's pieces | (host inputs) points | disp | valid | labels]
 	const size_t M = (size_t)m, res_bytes = sizeof(sift3d_strain_result) * M;
 	const size_t b_pts = on_device ? 0 : sizeof(int) * 3 * M, b_disp = on_device ? 0 : sizeof(double) * 3 * M, b_valid = on_device || !valid ? 0 : M;
+	const size_t b_label = on_device || !labelled ? 0 : sizeof(int) * M;
 	Layout L;
 	L.take(res_bytes);
 	PoiGridPlan G;
 	G.take(L, m);
-	const size_t o_pts = L.take(b_pts), o_disp = L.take(b_disp), o_valid = L.take(b_valid);
+	const size_t o_pts = L.take(b_pts), o_disp = L.take(b_disp), o_valid = L.take(b_valid), o_label = L.take(b_label);
 	S3D_HIP(hipMalloc(&T.a, L.end));
 	char *A = T.a;
-	const int *d_pts = points3;
+	const int *d_pts = points3, *d_label = labelled ? label : nullptr;
 	const double *d_disp = disp3;
 	const unsigned char *d_valid = valid;
 	if (on_device && (rc = D.after_legacy_stream())) return rc;
 	S3D_HIP_ST(st, upload(d_pts, A, o_pts, b_pts, st));
 	S3D_HIP_ST(st, upload(d_disp, A, o_disp, b_disp, st));
 	S3D_HIP_ST(st, upload(d_valid, A, o_valid, b_valid, st));
+	S3D_HIP_ST(st, upload(d_label, A, o_label, b_label, st));
 	S3D_HIP_ST(st, hipEventRecord(D.e0, st));
 	PoiIndex ix;
 	if ((rc = poi_grid_build(G, A, d_pts, d_disp, d_valid, m, radius, T, st, ix))) return rc;
-	launch_strain_fit(d_pts, d_disp, m, ix, radius, min_nb, measure, reinterpret_cast<sift3d_strain_result *>(A), st);
+	launch_strain_fit(d_pts, d_disp, d_label, m, ix, radius, min_nb, measure, reinterpret_cast<sift3d_strain_result *>(A), st);
 	S3D_HIP_ST(st, hipGetLastError());
 	S3D_HIP_ST(st, hipMemcpyAsync(out, A, res_bytes, hipMemcpyDeviceToHost, st));
 	S3D_HIP_ST(st, hipEventRecord(D.e1, st));
 	return D.finish(seconds);
+}
+}  // namespace
+
+extern "C" int sift3d_strain(const int *points3, const double *disp3, const unsigned char *valid, int m, const sift3d_strain_options *o,
+                             int on_device, int device, sift3d_strain_result *out, double *seconds) {
+	return strain_call("sift3d_strain", points3, disp3, valid, nullptr, false, m, o, on_device, device, out, seconds);
+}
+
+extern "C" int sift3d_strain_labelled(const int *points3, const double *disp3, const unsigned char *valid, const int *label, int m,
+                                      const sift3d_strain_options *o, int on_device, int device, sift3d_strain_result *out, double *seconds) {
+	return strain_call("sift3d_strain_labelled", points3, disp3, valid, label, true, m, o, on_device, device, out, seconds);
 }

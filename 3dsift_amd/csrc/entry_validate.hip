@@ -98,13 +98,15 @@ extern "C" int sift3d_icgn_init_from_validation(const sift3d_validate_result *va
 	return SIFT3D_OK;
 }
 
-extern "C" int sift3d_validate_displacements(const int *points3, const double *disp3, const double *grad9, const unsigned char *valid, int m,
-                                             const sift3d_validate_options *o, int on_device, int device, sift3d_validate_result *out,
-                                             double *seconds) {
+namespace {
+// both entries; labelled: label holds m labels and limits a POI's neighbours to its own body
+int validate_call(const char *name, const int *points3, const double *disp3, const double *grad9, const unsigned char *valid, const int *label,
+                  bool labelled, int m, const sift3d_validate_options *o, int on_device, int device, sift3d_validate_result *out,
+                  double *seconds) {
 	ValidateParams P;
 	int passes;
-	if (m < 0 || !out || (m > 0 && (!points3 || !disp3)) || !take_options(o, P, passes)) {
-		set_last_error("sift3d_validate_displacements: bad argument");
+	if (m < 0 || !out || (m > 0 && (!points3 || !disp3)) || (labelled && !label) || !take_options(o, P, passes)) {
+		set_last_error(std::string(name) + ": bad argument");
 		return SIFT3D_ERR_ARG;
 	}
 	if (seconds) *seconds = 0;
@@ -116,19 +118,21 @@ extern "C" int sift3d_validate_displacements(const int *points3, const double *d
 	if ((rc = D.ensure(0, 0))) return rc;
 	hipStream_t st = D.stream;
 	CallTemps T;
-	// block a: [results | the index's pieces | pass of a flag | folded valid bytes | flags, twice | (host inputs) points | disp | grad | valid]
+	// block a: [results | the index's pieces | pass of a flag | folded valid bytes | flags, twice | (host inputs) points | disp | grad | valid |
+	// labels]
 	const size_t M = (size_t)m, wb = al256(M), res_bytes = sizeof(sift3d_validate_result) * M;
 	const size_t b_pts = on_device ? 0 : sizeof(int) * 3 * M, b_disp = on_device ? 0 : sizeof(double) * 3 * M;
 	const size_t b_grad = on_device || !grad9 ? 0 : sizeof(double) * 9 * M, b_valid = on_device || !valid ? 0 : M;
+	const size_t b_label = on_device || !labelled ? 0 : sizeof(int) * M;
 	Layout L;
 	L.take(res_bytes);
 	PoiGridPlan G;
 	G.take(L, m);
 	const size_t o_pass = L.take(sizeof(int) * M), o_fold = L.take(wb), o_flags = L.take(2 * wb);
-	const size_t o_pts = L.take(b_pts), o_disp = L.take(b_disp), o_grad = L.take(b_grad), o_valid = L.take(b_valid);
+	const size_t o_pts = L.take(b_pts), o_disp = L.take(b_disp), o_grad = L.take(b_grad), o_valid = L.take(b_valid), o_label = L.take(b_label);
 	S3D_HIP(hipMalloc(&T.a, L.end));
 	char *A = T.a;
-	const int *d_pts = points3;
+	const int *d_pts = points3, *d_label = labelled ? label : nullptr;
 	const double *d_disp = disp3, *d_grad = grad9;
 	const unsigned char *d_valid = valid;
 	if (on_device && (rc = D.after_legacy_stream())) return rc;
@@ -136,6 +140,7 @@ extern "C" int sift3d_validate_displacements(const int *points3, const double *d
 	S3D_HIP_ST(st, upload(d_disp, A, o_disp, b_disp, st));
 	S3D_HIP_ST(st, upload(d_grad, A, o_grad, b_grad, st));
 	S3D_HIP_ST(st, upload(d_valid, A, o_valid, b_valid, st));
+	S3D_HIP_ST(st, upload(d_label, A, o_label, b_label, st));
 	int *d_pass = reinterpret_cast<int *>(A + o_pass);
 	unsigned char *d_fold = reinterpret_cast<unsigned char *>(A + o_fold);
 	unsigned char *d_flags[2] = {reinterpret_cast<unsigned char *>(A + o_flags), reinterpret_cast<unsigned char *>(A + o_flags + wb)};
@@ -147,10 +152,25 @@ extern "C" int sift3d_validate_displacements(const int *points3, const double *d
 	if ((rc = poi_grid_build(G, A, d_pts, d_disp, d_fold, m, P.radius, T, st, ix))) return rc;
 	sift3d_validate_result *d_out = reinterpret_cast<sift3d_validate_result *>(A);
 	// pass p reads the flags of pass p - 1 and writes its own into the other buffer; the report reads the last pass's
-	for (int p = 1; p <= passes; p++) launch_validate_test(d_pts, d_disp, d_grad, m, ix, P, p, d_flags[(p - 1) & 1], d_flags[p & 1], d_pass, d_out, st);
-	launch_validate_test(d_pts, d_disp, d_grad, m, ix, P, 0, d_flags[passes & 1], nullptr, d_pass, d_out, st);
+	for (int p = 1; p <= passes; p++)
+		launch_validate_test(d_pts, d_disp, d_grad, d_label, m, ix, P, p, d_flags[(p - 1) & 1], d_flags[p & 1], d_pass, d_out, st);
+	launch_validate_test(d_pts, d_disp, d_grad, d_label, m, ix, P, 0, d_flags[passes & 1], nullptr, d_pass, d_out, st);
 	S3D_HIP_ST(st, hipGetLastError());
 	S3D_HIP_ST(st, hipMemcpyAsync(out, A, res_bytes, hipMemcpyDeviceToHost, st));
 	S3D_HIP_ST(st, hipEventRecord(D.e1, st));
 	return D.finish(seconds);
+}
+}  // namespace
+
+extern "C" int sift3d_validate_displacements(const int *points3, const double *disp3, const double *grad9, const unsigned char *valid, int m,
+                                             const sift3d_validate_options *o, int on_device, int device, sift3d_validate_result *out,
+                                             double *seconds) {
+	return validate_call("sift3d_validate_displacements", points3, disp3, grad9, valid, nullptr, false, m, o, on_device, device, out, seconds);
+}
+
+extern "C" int sift3d_validate_displacements_labelled(const int *points3, const double *disp3, const double *grad9, const unsigned char *valid,
+                                                      const int *label, int m, const sift3d_validate_options *o, int on_device, int device,
+                                                      sift3d_validate_result *out, double *seconds) {
+	return validate_call("sift3d_validate_displacements_labelled", points3, disp3, grad9, valid, label, true, m, o, on_device, device, out,
+	                     seconds);
 }

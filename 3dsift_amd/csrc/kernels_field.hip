@@ -45,8 +45,11 @@ __device__ inline void write_failed(sift3d_field_result *o, int n, int sides, in
 	o->reserved = 0;
 }
 
-template <bool Weighted>
-__global__ __launch_bounds__(kThreads) void k_field_eval(const double *__restrict__ queries, int nq, const double *__restrict__ disp, PoiGrid g,
+// Labelled (sift3d_field_eval_labelled): a member also has the query's label, which is positive, and the lanes share out the entries of
+// that label (walk_matching, poi_window.h); the plain instantiations read no label and walk as they always did
+template <bool Weighted, bool Labelled>
+__global__ __launch_bounds__(kThreads) void k_field_eval(const double *__restrict__ queries, int nq, const double *__restrict__ disp,
+                                                        const int *__restrict__ label, const int *__restrict__ qlabel, PoiGrid g,
                                                         const int *__restrict__ start, int ncells, PoiSorted S, int radius, int min_nb,
                                                         int enclosed, sift3d_field_result *__restrict__ out) {
 	const int lane = threadIdx.x & 63;
@@ -56,6 +59,14 @@ __global__ __launch_bounds__(kThreads) void k_field_eval(const double *__restric
 		if (!(query_ok(x) && query_ok(y) && query_ok(z))) {
 			if (lane == 0) write_failed(out + i, 0, 0, 2);
 			continue;
+		}
+		int own = 0;
+		if constexpr (Labelled) {
+			own = qlabel[i];
+			if (own <= 0) {
+				if (lane == 0) write_failed(out + i, 0, 0, 1);
+				continue;
+			}
 		}
 		const PoiWindow<true> W(g, start, ncells, (int)floor(x), (int)floor(y), (int)floor(z), radius + 1);
 		const int total = W.total;
@@ -74,10 +85,17 @@ __global__ __launch_bounds__(kThreads) void k_field_eval(const double *__restric
 			}
 		};
 
+		// f(j) for the lane's share of the window's entries: every 64th of them, or (labelled) every 64th of those of the query's label
+		auto walk = [&](auto f) {
+			if constexpr (Labelled)
+				walk_matching(W, lane, [&](int j) { return label[S.idx[j]] == own; }, f);
+			else
+				for (int t = lane; t < total; t += 64) f(W.entry(t));
+		};
+
 		// walk 1: the count, the lowest index and the sides among the counted members
 		int n = 0, first = 0x7fffffff, sides = 0;
-		for (int t = lane; t < total; t += 64) {
-			const int j = W.entry(t);
+		walk([&](int j) {
 			double d[3];
 			if (weigh(j, d) > 0.0) {
 				n++;
@@ -85,7 +103,7 @@ __global__ __launch_bounds__(kThreads) void k_field_eval(const double *__restric
 #pragma unroll
 				for (int a = 0; a < 3; a++) sides |= (d[a] <= 0.0 ? 1 << (2 * a) : 0) | (d[a] >= 0.0 ? 2 << (2 * a) : 0);
 			}
-		}
+		});
 		n = wave_isum(n);
 		first = wave_min(first);
 		sides = wave_or(sides);
@@ -101,11 +119,10 @@ __global__ __launch_bounds__(kThreads) void k_field_eval(const double *__restric
 
 		// walk 2: W = sum w, S1 = sum w d, S2 = sum w d d^T, U = sum w (u - u0), P[c][a] = sum w (u_c - u0_c) d_a
 		double sw = 0, s1[3] = {0, 0, 0}, s2[6] = {0, 0, 0, 0, 0, 0}, U[3] = {0, 0, 0}, P[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-		for (int t = lane; t < total; t += 64) {
-			const int j = W.entry(t);
+		walk([&](int j) {
 			double d[3];
 			const double w = weigh(j, d);
-			if (!(w > 0.0)) continue;
+			if (!(w > 0.0)) return;
 			const double wd[3] = {w * d[0], w * d[1], w * d[2]};
 			const double wa[3] = {w * (S.u[j] - u0[0]), w * (S.v[j] - u0[1]), w * (S.w[j] - u0[2])};
 			sw += w;
@@ -118,7 +135,7 @@ __global__ __launch_bounds__(kThreads) void k_field_eval(const double *__restric
 			}
 			s2[0] += wd[0] * d[0]; s2[1] += wd[0] * d[1]; s2[2] += wd[0] * d[2];
 			s2[3] += wd[1] * d[1]; s2[4] += wd[1] * d[2]; s2[5] += wd[2] * d[2];
-		}
+		});
 		sw = wave_sum(sw);
 #pragma unroll
 		for (int c = 0; c < 3; c++) {
@@ -159,11 +176,10 @@ __global__ __launch_bounds__(kThreads) void k_field_eval(const double *__restric
 
 		// walk 3: the weighted residual of the fitted plane
 		double rs = 0;
-		for (int t = lane; t < total; t += 64) {
-			const int j = W.entry(t);
+		walk([&](int j) {
 			double d[3];
 			const double w = weigh(j, d);
-			if (!(w > 0.0)) continue;
+			if (!(w > 0.0)) return;
 			const double uj[3] = {S.u[j], S.v[j], S.w[j]};
 			double ee = 0;
 #pragma unroll
@@ -172,7 +188,7 @@ __global__ __launch_bounds__(kThreads) void k_field_eval(const double *__restric
 				ee += e * e;
 			}
 			rs += w * ee;
-		}
+		});
 		rs = wave_sum(rs);
 
 		if (lane == 0) {
@@ -193,18 +209,27 @@ __global__ __launch_bounds__(kThreads) void k_field_eval(const double *__restric
 	}
 }
 
+template <bool Weighted, bool Labelled>
+void launch_one(dim3 grid, const double *d_queries, int nq, const double *d_disp, const int *d_label, const int *d_qlabel, const PoiIndex &ix,
+                int radius, int min_nb, int enclosed, sift3d_field_result *d_out, hipStream_t st) {
+	hipLaunchKernelGGL((k_field_eval<Weighted, Labelled>), grid, dim3(kThreads), 0, st, d_queries, nq, d_disp, d_label, d_qlabel, ix.g, ix.start,
+	                   ix.ncells, ix.S, radius, min_nb, enclosed, d_out);
+}
 }  // namespace
 
-void launch_field_eval(const double *d_queries, int nq, const double *d_disp, const PoiIndex &ix, int radius, int min_nb, int weighting,
-                       int enclosed, sift3d_field_result *d_out, hipStream_t st) {
+void launch_field_eval(const double *d_queries, int nq, const double *d_disp, const int *d_label, const int *d_qlabel, const PoiIndex &ix,
+                       int radius, int min_nb, int weighting, int enclosed, sift3d_field_result *d_out, hipStream_t st) {
 	const size_t want = ((size_t)nq + kWaves - 1) / kWaves;
 	const dim3 grid((unsigned)(want < (size_t)kMaxBlocks ? want : (size_t)kMaxBlocks));
-	if (weighting)
-		hipLaunchKernelGGL(k_field_eval<true>, grid, dim3(kThreads), 0, st, d_queries, nq, d_disp, ix.g, ix.start, ix.ncells, ix.S, radius, min_nb,
-		                   enclosed, d_out);
+	const bool labelled = d_qlabel != nullptr;
+	if (weighting && labelled)
+		launch_one<true, true>(grid, d_queries, nq, d_disp, d_label, d_qlabel, ix, radius, min_nb, enclosed, d_out, st);
+	else if (weighting)
+		launch_one<true, false>(grid, d_queries, nq, d_disp, d_label, d_qlabel, ix, radius, min_nb, enclosed, d_out, st);
+	else if (labelled)
+		launch_one<false, true>(grid, d_queries, nq, d_disp, d_label, d_qlabel, ix, radius, min_nb, enclosed, d_out, st);
 	else
-		hipLaunchKernelGGL(k_field_eval<false>, grid, dim3(kThreads), 0, st, d_queries, nq, d_disp, ix.g, ix.start, ix.ncells, ix.S, radius, min_nb,
-		                   enclosed, d_out);
+		launch_one<false, false>(grid, d_queries, nq, d_disp, d_label, d_qlabel, ix, radius, min_nb, enclosed, d_out, st);
 }
 
 }  // namespace s3d

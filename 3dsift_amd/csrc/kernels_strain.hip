@@ -49,9 +49,13 @@ __device__ inline void write_failed(sift3d_strain_result *o, int n, int status) 
 	o->status = status;
 }
 
-__global__ __launch_bounds__(kThreads) void k_strain_fit(const int *__restrict__ pts, const double *__restrict__ disp, int m, PoiGrid g,
-                                                        const int *__restrict__ start, int ncells, PoiSorted S, int radius, int min_nb,
-                                                        int measure, sift3d_strain_result *__restrict__ out) {
+// Labelled (sift3d_strain_labelled): a neighbour also has the POI's own label, which is positive, and the lanes share out the entries
+// of that label (walk_matching, poi_window.h); the plain instantiation reads no label and walks as it always did
+template <bool Labelled>
+__global__ __launch_bounds__(kThreads) void k_strain_fit(const int *__restrict__ pts, const double *__restrict__ disp,
+                                                        const int *__restrict__ label, int m, PoiGrid g, const int *__restrict__ start,
+                                                        int ncells, PoiSorted S, int radius, int min_nb, int measure,
+                                                        sift3d_strain_result *__restrict__ out) {
 	const int lane = threadIdx.x & 63;
 	const int i = blockIdx.x * kWaves + (threadIdx.x >> 6);
 	if (i >= m) return;
@@ -60,19 +64,33 @@ __global__ __launch_bounds__(kThreads) void k_strain_fit(const int *__restrict__
 		if (lane == 0) write_failed(out + i, 0, 2);
 		return;
 	}
+	int own = 0;
+	if constexpr (Labelled) {
+		own = label[i];
+		if (own <= 0) {
+			if (lane == 0) write_failed(out + i, 0, 1);
+			return;
+		}
+	}
 	const PoiWindow<false> W(g, start, ncells, x, y, z, radius);
 	const int total = W.total;
 	auto inside = [&](int j) { return abs(S.x[j] - x) <= radius && abs(S.y[j] - y) <= radius && abs(S.z[j] - z) <= radius; };
+	// f(j) for the lane's share of the window's entries: every 64th of them, or (labelled) every 64th of those of the POI's label
+	auto walk = [&](auto f) {
+		if constexpr (Labelled)
+			walk_matching(W, lane, [&](int j) { return label[S.idx[j]] == own; }, f);
+		else
+			for (int t = lane; t < total; t += 64) f(W.entry(t));
+	};
 
 	// walk 1: the neighbour count and the lowest index among them
 	int n = 0, first = 0x7fffffff;
-	for (int t = lane; t < total; t += 64) {
-		const int j = W.entry(t);
+	walk([&](int j) {
 		if (inside(j)) {
 			n++;
 			first = min(first, S.idx[j]);
 		}
-	}
+	});
 	n = wave_isum(n);
 	first = wave_min(first);
 	if (n < min_nb) {
@@ -83,9 +101,8 @@ __global__ __launch_bounds__(kThreads) void k_strain_fit(const int *__restrict__
 
 	// walk 2: S1 = sum d, S2 = sum d d^T, U = sum (u - u0), P[c][a] = sum (u_c - u0_c) d_a
 	double s1[3] = {0, 0, 0}, s2[6] = {0, 0, 0, 0, 0, 0}, U[3] = {0, 0, 0}, P[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-	for (int t = lane; t < total; t += 64) {
-		const int j = W.entry(t);
-		if (!inside(j)) continue;
+	walk([&](int j) {
+		if (!inside(j)) return;
 		const double d[3] = {(double)(S.x[j] - x), (double)(S.y[j] - y), (double)(S.z[j] - z)};
 		const double a[3] = {S.u[j] - u0[0], S.v[j] - u0[1], S.w[j] - u0[2]};
 #pragma unroll
@@ -97,7 +114,7 @@ __global__ __launch_bounds__(kThreads) void k_strain_fit(const int *__restrict__
 		}
 		s2[0] += d[0] * d[0]; s2[1] += d[0] * d[1]; s2[2] += d[0] * d[2];
 		s2[3] += d[1] * d[1]; s2[4] += d[1] * d[2]; s2[5] += d[2] * d[2];
-	}
+	});
 #pragma unroll
 	for (int c = 0; c < 3; c++) {
 		s1[c] = wave_sum(s1[c]);
@@ -138,9 +155,8 @@ __global__ __launch_bounds__(kThreads) void k_strain_fit(const int *__restrict__
 
 	// walk 3: the residual of the fitted plane
 	double rs = 0;
-	for (int t = lane; t < total; t += 64) {
-		const int j = W.entry(t);
-		if (!inside(j)) continue;
+	walk([&](int j) {
+		if (!inside(j)) return;
 		const double d[3] = {(double)(S.x[j] - x), (double)(S.y[j] - y), (double)(S.z[j] - z)};
 		const double uj[3] = {S.u[j], S.v[j], S.w[j]};
 #pragma unroll
@@ -148,7 +164,7 @@ __global__ __launch_bounds__(kThreads) void k_strain_fit(const int *__restrict__
 			const double e = (uj[c] - dsp[c]) - ((G[c][0] * d[0] + G[c][1] * d[1]) + G[c][2] * d[2]);
 			rs += e * e;
 		}
-	}
+	});
 	rs = wave_sum(rs);
 
 	// E of the chosen measure (xx yy zz xy yz zx), its eigenvalues and the equivalent strain
@@ -195,10 +211,15 @@ __global__ __launch_bounds__(kThreads) void k_strain_fit(const int *__restrict__
 int blocks_for(size_t n, int per) { return (int)((n + per - 1) / per); }
 }  // namespace
 
-void launch_strain_fit(const int *d_pts, const double *d_disp, int m, const PoiIndex &ix, int radius, int min_nb, int measure,
-                       sift3d_strain_result *d_out, hipStream_t st) {
-	hipLaunchKernelGGL(k_strain_fit, dim3(blocks_for(m, kWaves)), dim3(kThreads), 0, st, d_pts, d_disp, m, ix.g, ix.start, ix.ncells, ix.S, radius,
-	                   min_nb, measure, d_out);
+void launch_strain_fit(const int *d_pts, const double *d_disp, const int *d_label, int m, const PoiIndex &ix, int radius, int min_nb,
+                       int measure, sift3d_strain_result *d_out, hipStream_t st) {
+	const dim3 grid(blocks_for(m, kWaves)), block(kThreads);
+	if (d_label)
+		hipLaunchKernelGGL(k_strain_fit<true>, grid, block, 0, st, d_pts, d_disp, d_label, m, ix.g, ix.start, ix.ncells, ix.S, radius, min_nb,
+		                   measure, d_out);
+	else
+		hipLaunchKernelGGL(k_strain_fit<false>, grid, block, 0, st, d_pts, d_disp, d_label, m, ix.g, ix.start, ix.ncells, ix.S, radius, min_nb,
+		                   measure, d_out);
 }
 
 }  // namespace s3d

@@ -157,9 +157,12 @@ __device__ inline void write_record(sift3d_validate_result *o, const double *med
 	o->pass = pass;
 }
 
+// Labelled (the labelled test): a neighbour also has the POI's own label, which is positive; the plain instantiation reads no label
+template <bool Labelled>
 __global__ __launch_bounds__(64) void k_validate_test(const int *__restrict__ pts, const double *__restrict__ disp, const double *__restrict__ grad,
-                                                      const int *__restrict__ cell, int m, PoiGrid g, const int *__restrict__ start, int ncells,
-                                                      PoiSorted S, ValidateParams P, int pass, const unsigned char *__restrict__ fin,
+                                                      const int *__restrict__ label, const int *__restrict__ cell, int m, PoiGrid g,
+                                                      const int *__restrict__ start, int ncells, PoiSorted S, ValidateParams P, int pass,
+                                                      const unsigned char *__restrict__ fin,
                                                       unsigned char *__restrict__ fout, int *__restrict__ pass_of,
                                                       sift3d_validate_result *__restrict__ out) {
 	__shared__ u64 keys[kCap];
@@ -184,10 +187,14 @@ __global__ __launch_bounds__(64) void k_validate_test(const int *__restrict__ pt
 	const int radius = P.radius;
 	const PoiWindow<true> W(g, start, ncells, x, y, z, radius);
 	const int total = W.total;
-	// a neighbour of this launch: inside the window, not the POI itself, not flagged by the pass before
+	int own = 0;
+	if constexpr (Labelled) own = label[i];
+	// a neighbour of this launch: inside the window, not the POI itself, not flagged by the pass before (and of the POI's body)
 	auto keep = [&](int j) {
 		if (!(abs(S.x[j] - x) <= radius && abs(S.y[j] - y) <= radius && abs(S.z[j] - z) <= radius)) return false;
 		const int id = S.idx[j];
+		if constexpr (Labelled)
+			if (own <= 0 || label[id] != own) return false;
 		return id != i && !fin[id];
 	};
 	// neighbour j's estimate of component c at the POI
@@ -291,10 +298,15 @@ void launch_validate_fold(const double *d_grad, const unsigned char *d_valid, in
 	hipLaunchKernelGGL(k_validate_fold, dim3(blocks_for(m, kFoldThreads)), dim3(kFoldThreads), 0, st, d_grad, d_valid, m, d_fold);
 }
 
-void launch_validate_test(const int *d_pts, const double *d_disp, const double *d_grad, int m, const PoiIndex &ix, ValidateParams P, int pass,
-                          const unsigned char *d_fin, unsigned char *d_fout, int *d_pass, sift3d_validate_result *d_out, hipStream_t st) {
-	hipLaunchKernelGGL(k_validate_test, dim3(m), dim3(64), 0, st, d_pts, d_disp, d_grad, ix.cell, m, ix.g, ix.start, ix.ncells, ix.S, P, pass, d_fin,
-	                   d_fout, d_pass, d_out);
+void launch_validate_test(const int *d_pts, const double *d_disp, const double *d_grad, const int *d_label, int m, const PoiIndex &ix,
+                          ValidateParams P, int pass, const unsigned char *d_fin, unsigned char *d_fout, int *d_pass,
+                          sift3d_validate_result *d_out, hipStream_t st) {
+	if (d_label)
+		hipLaunchKernelGGL(k_validate_test<true>, dim3(m), dim3(64), 0, st, d_pts, d_disp, d_grad, d_label, ix.cell, m, ix.g, ix.start, ix.ncells,
+		                   ix.S, P, pass, d_fin, d_fout, d_pass, d_out);
+	else
+		hipLaunchKernelGGL(k_validate_test<false>, dim3(m), dim3(64), 0, st, d_pts, d_disp, d_grad, d_label, ix.cell, m, ix.g, ix.start, ix.ncells,
+		                   ix.S, P, pass, d_fin, d_fout, d_pass, d_out);
 }
 
 }  // namespace s3d

@@ -61,4 +61,56 @@ private:
 	}
 };
 
+// the lane that holds the k-th set bit of b (k from 0; k below the number of set bits)
+__device__ inline int kth_set_bit(unsigned long long b, int k) {
+	int pos = 0;
+#pragma unroll
+	for (int w = 32; w > 0; w >>= 1) {
+		const int c = __popcll((b >> pos) & ((1ull << w) - 1ull));
+		if (k >= c) {
+			k -= c;
+			pos += w;
+		}
+	}
+	return pos;
+}
+
+// The walk of the labelled kernels: f(j) for the entries j of the window that match (the centre's label), lane l taking the l-th,
+// (l + 64)-th, ... of the MATCHING entries in the window's order -- the share it has in the plain walk (t = lane, lane + 64, ...)
+// when every entry matches, and one that the entries of other labels, present or not, do not move: a lane's partial sums, and so the
+// bytes of a record, depend on the POIs of its own label only.  Matches are drawn from each 64 entries by ballot and handed to the
+// lanes by shuffle; up to 63 wait in `hold` (lane l: the l-th waiting one) for the next batch.  Called by all 64 lanes.
+template <bool Pinned, class Match, class F>
+__device__ inline void walk_matching(const PoiWindow<Pinned> &W, int lane, Match match, F f) {
+	const int total = W.total;
+	int hold = 0, nhold = 0;
+	for (int t0 = 0; t0 < total; t0 += 64) {
+		const int t = t0 + lane;
+		int j = 0;
+		bool m = false;
+		if (t < total) {
+			j = W.entry(t);
+			m = match(j);
+		}
+		const unsigned long long b = __ballot(m);
+		if (nhold == 0 && b == ~0ull) {  // 64 matches and nobody waits: the batch is what the lanes hold
+			f(j);
+			continue;
+		}
+		const int cnt = __popcll(b);
+		const int want = lane - nhold;  // the new match that completes a batch in this lane
+		const int j1 = __shfl(j, kth_set_bit(b, want > 0 ? want : 0));
+		if (nhold + cnt >= 64) {
+			const int j2 = __shfl(j, kth_set_bit(b, min(64 - nhold + lane, 63)));  // the matches behind the batch wait
+			f(lane < nhold ? hold : j1);
+			hold = j2;
+			nhold += cnt - 64;
+		} else {
+			if (want >= 0 && want < cnt) hold = j1;
+			nhold += cnt;
+		}
+	}
+	if (lane < nhold) f(hold);
+}
+
 }  // namespace s3d

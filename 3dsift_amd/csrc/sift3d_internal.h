@@ -367,6 +367,17 @@ void launch_mask_active(const unsigned char *d_mask, int nx, int ny, int nz, uns
 // d_mask[i] = 1 where (double)d_vol[i] >= level, else 0
 void launch_mask_threshold(const float *d_vol, size_t n, double level, unsigned char *d_mask, hipStream_t st);
 
+// ---- kernels_label.hip: connected components of a byte mask (sift3d_mask_label, sift3d_labels_at_points) ---------------------------
+constexpr int kLabelTX = 32, kLabelTY = 8, kLabelTZ = 8;  // the tile of the LDS union-find (sift3d_test_label_tile)
+constexpr int kLabelChunk = 2048;                        // voxels per entry of the renumbering's sums
+inline size_t label_chunks(size_t n) { return (n + kLabelChunk - 1) / kLabelChunk; }
+// d_labels (n ints): the labels of d_mask's components of at least min_voxels voxels, *d_count their number; d_aux: n ints,
+// d_sums: label_chunks(n) ints.  n = nx ny nz < 2^31, connectivity 6 or 26.
+void launch_mask_label(const unsigned char *d_mask, int nx, int ny, int nz, int connectivity, int min_voxels, int *d_labels, int *d_aux,
+                       int *d_sums, int *d_count, hipStream_t st);
+// d_out[i] = the label at voxel d_pts[i], 0 outside the volume
+void launch_labels_at(const int *d_labels, int nx, int ny, int nz, const int *d_pts, int m, int *d_out, hipStream_t st);
+
 // ---- kernels_icgn2.hip: second-order IC-GN (sift3d_icgn2, include/sift3d_hip.h) --------------------------------------------------
 size_t icgn2_state_bytes();  // per-POI scratch record of the prepare kernel
 // as launch_icgn, with m * 30 doubles in d_init and m * icgn2_state_bytes() in d_state
@@ -397,13 +408,15 @@ void launch_subset_quality(IcgnVol R, const int *d_pts, int m, SubsetParams P, s
 struct PoiIndex;
 
 // ---- kernels_strain.hip: strain fields from the POIs' displacements (sift3d_strain, include/sift3d_hip.h) ------------------------
-void launch_strain_fit(const int *d_pts, const double *d_disp, int m, const PoiIndex &ix, int radius, int min_nb, int measure,
-                       sift3d_strain_result *d_out, hipStream_t st);
+// d_label: null (sift3d_strain), or m labels (sift3d_strain_labelled: the neighbours are those of the POI's own positive label)
+void launch_strain_fit(const int *d_pts, const double *d_disp, const int *d_label, int m, const PoiIndex &ix, int radius, int min_nb,
+                       int measure, sift3d_strain_result *d_out, hipStream_t st);
 
 // ---- kernels_field.hip: the displacement field at real-valued queries (sift3d_field_eval, include/sift3d_hip.h) --------------------
-// ix: the index built with radius + 1; d_out: nq records
-void launch_field_eval(const double *d_queries, int nq, const double *d_disp, const PoiIndex &ix, int radius, int min_nb, int weighting,
-                       int enclosed, sift3d_field_result *d_out, hipStream_t st);
+// ix: the index built with radius + 1; d_out: nq records; d_label, d_qlabel: both null (sift3d_field_eval), or the labels of the m POIs
+// and of the nq queries (sift3d_field_eval_labelled)
+void launch_field_eval(const double *d_queries, int nq, const double *d_disp, const int *d_label, const int *d_qlabel, const PoiIndex &ix,
+                       int radius, int min_nb, int weighting, int enclosed, sift3d_field_result *d_out, hipStream_t st);
 
 // ---- kernels_validate.hip: the normalised median test of the displacements (sift3d_validate_displacements, include/sift3d_hip.h) --
 // It runs on an index built with d_fold as the valid bytes.
@@ -415,9 +428,10 @@ int validate_stage_capacity();  // neighbour counts up to this are selected in L
 // d_fold[i] = (d_valid null or d_valid[i]) and, with d_grad, nine finite gradients
 void launch_validate_fold(const double *d_grad, const unsigned char *d_valid, int m, unsigned char *d_fold, hipStream_t st);
 // pass > 0: one pass of the test -- reads the flags d_fin, writes d_fout (m bytes each) and the pass number of a new flag into d_pass;
-// pass 0: the report from the final flags d_fin and d_pass into d_out
-void launch_validate_test(const int *d_pts, const double *d_disp, const double *d_grad, int m, const PoiIndex &ix, ValidateParams P, int pass,
-                          const unsigned char *d_fin, unsigned char *d_fout, int *d_pass, sift3d_validate_result *d_out, hipStream_t st);
+// pass 0: the report from the final flags d_fin and d_pass into d_out.  d_label: null, or m labels (the labelled test)
+void launch_validate_test(const int *d_pts, const double *d_disp, const double *d_grad, const int *d_label, int m, const PoiIndex &ix,
+                          ValidateParams P, int pass, const unsigned char *d_fin, unsigned char *d_fout, int *d_pass,
+                          sift3d_validate_result *d_out, hipStream_t st);
 
 // ---- kernels_match_guided.hip: the matcher inside a spatial gate (sift3d_match_guided, include/sift3d_hip.h) -----------------------
 // d_xyz: n fp32 positions -> what poi_grid_build indexes: d_pts their floors (3 n ints; a position no gate holds gets a floor the index

@@ -339,5 +339,38 @@ SIFT_LIBRARY_API std::vector<FieldResult> ComposeDisplacements(const std::vector
 // (I + G) q + b - q = u, status 0 where the field's status is 0; status 1 (no start) elsewhere
 SIFT_LIBRARY_API std::vector<AffineFit> SeedsFromField(const std::vector<Cvec> &points, const std::vector<FieldResult> &field);
 
+// ---- several bodies: labels (include/sift3d_hip.h, sift3d_mask_label and the labelled window calls) ---------------------------------
+// labels (nx x ny x nz ints, host memory, x fastest): 0 where mask is 0, else the number 1..*count of the voxel's connected component
+// (connectivity 6: faces; 26: faces, edges and corners), numbered in ascending order of a component's lowest voxel; a component of fewer
+// than min_voxels voxels gets 0 and is not counted.  false: the call failed (message on stderr).  seconds (may be null): device time.
+// The mask of body L for RefineDisplacementsMasked is labels == L.
+SIFT_LIBRARY_API bool LabelMask(const unsigned char *mask, int nx, int ny, int nz, int connectivity, int min_voxels, int *labels, int *count,
+                                double *seconds = nullptr);
+// the label at each point (0 for a point outside the volume); host only.  Empty when a coordinate is not integral
+SIFT_LIBRARY_API std::vector<int> LabelsAt(const int *labels, int nx, int ny, int nz, const std::vector<Cvec> &points);
+// ComputeStrains, ValidateDisplacements and EvaluateField limited to a point's own body: a point is a neighbour of another only where
+// both have the same label > 0 (labels: one per point, what LabelsAt returns); a point or query whose label is <= 0 gets status 1 with no
+// neighbours.  keep (may be null): as for ComputeStrains with keep.  query_labels: one per query
+SIFT_LIBRARY_API std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp,
+                                                          const std::vector<int> &labels, const std::vector<unsigned char> *keep = nullptr,
+                                                          const StrainOptions &o = StrainOptions(), double zncc_min = 0,
+                                                          bool accept_unconverged = false);
+SIFT_LIBRARY_API std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp,
+                                                          const std::vector<int> &labels, const std::vector<unsigned char> *keep = nullptr,
+                                                          const StrainOptions &o = StrainOptions(), double zncc_min = 0,
+                                                          bool accept_unconverged = false);
+SIFT_LIBRARY_API std::vector<ValidationResult> ValidateDisplacements(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp,
+                                                                     const std::vector<int> &labels,
+                                                                     const ValidationOptions &o = ValidationOptions(), double zncc_min = 0,
+                                                                     bool accept_unconverged = false, bool use_gradients = true);
+SIFT_LIBRARY_API std::vector<ValidationResult> ValidateDisplacements(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp,
+                                                                     const std::vector<int> &labels,
+                                                                     const ValidationOptions &o = ValidationOptions(), double zncc_min = 0,
+                                                                     bool accept_unconverged = false, bool use_gradients = true);
+SIFT_LIBRARY_API std::vector<FieldResult> EvaluateField(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp,
+                                                        const std::vector<int> &labels, const std::vector<double> &queries3,
+                                                        const std::vector<int> &query_labels, const FieldOptions &o = FieldOptions(),
+                                                        double zncc_min = 0, bool accept_unconverged = false);
+
 }  // namespace CPUSIFT
 #endif

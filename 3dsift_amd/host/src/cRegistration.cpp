@@ -1,6 +1,7 @@
 // cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine / PredictPositions / GuidedMatch / SearchDisplacements / RefineDisplacements / RefineDisplacementsMasked / MaskFromLevel / ValidateDisplacements /
 // ComputeStrains over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_predict_positions / sift3d_match_guided / sift3d_zncc_search / sift3d_icgn / sift3d_icgn_bspline / sift3d_icgn_masked /
-// sift3d_mask_from_level / sift3d_validate_displacements / sift3d_strain, and
+// sift3d_mask_from_level / sift3d_validate_displacements / sift3d_strain, CPUSIFT::LabelMask / LabelsAt and the labelled overloads over
+// sift3d_mask_label / sift3d_labels_at_points / sift3d_*_labelled, and
 // CPUSIFT::PrefilterBSpline over sift3d_bspline_prefilter (include/sift3d_hip.h).
 #include "../Include/cRegistration.h"
 
@@ -452,10 +453,43 @@ std::vector<IcgnResult> RefineDisplacementsMasked(const float *ref, int nx, int 
 	return res;
 }
 
-// the strain call behind both ComputeStrains overloads: rc is what the input conversion returned
+// true when labels is null (no labels) or holds one label per item; a message on stderr otherwise
+static bool labels_fit(const char *who, const char *what, const std::vector<int> *labels, size_t m) {
+	if (!labels || labels->size() == m) return true;
+	fprintf(stderr, "[3dsift_amd] %s: %zu labels for %zu %s\n", who, labels->size(), m, what);
+	return false;
+}
+// the pointer the C entry takes: never null, also for no items
+static const int *label_data(const std::vector<int> &labels) {
+	static const int none = 0;
+	return labels.empty() ? &none : labels.data();
+}
+
+bool LabelMask(const unsigned char *mask, int nx, int ny, int nz, int connectivity, int min_voxels, int *labels, int *count, double *seconds) {
+	const int rc = sift3d_mask_label(mask, nx, ny, nz, connectivity, min_voxels, labels, count, 0, GetDevice(), seconds);
+	if (rc != SIFT3D_OK) fprintf(stderr, "[3dsift_amd] LabelMask: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+	return rc == SIFT3D_OK;
+}
+
+std::vector<int> LabelsAt(const int *labels, int nx, int ny, int nz, const std::vector<Cvec> &points) {
+	const size_t m = points.size();
+	std::vector<int> q, out(m ? m : 1, 0);
+	if (!int_triples("LabelsAt", "point", points, q)) return std::vector<int>();
+	const int rc = sift3d_labels_at_points(labels, nx, ny, nz, q.data(), (int)m, out.data(), 0, GetDevice());
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] LabelsAt: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return std::vector<int>();
+	}
+	out.resize(m);
+	return out;
+}
+
+// the strain call behind the ComputeStrains overloads: rc is what the input conversion returned; labels null: the unlabelled call
 static std::vector<StrainResult> strains_of(const std::vector<int> &q, size_t m, int rc, const std::vector<double> &u,
-                                            const std::vector<unsigned char> &valid, const StrainOptions &opts) {
+                                            const std::vector<unsigned char> &valid, const StrainOptions &opts,
+                                            const std::vector<int> *labels = nullptr) {
 	std::vector<StrainResult> res(m);
+	if (!labels_fit("ComputeStrains", "points", labels, m)) return res;
 	sift3d_strain_options o;
 	sift3d_default_strain_options(&o);
 	o.radius = opts.radius;
@@ -463,7 +497,10 @@ static std::vector<StrainResult> strains_of(const std::vector<int> &q, size_t m,
 	o.measure = opts.measure;
 	std::vector<sift3d_strain_result> r(m ? m : 1);
 	double sec = 0;
-	if (rc == SIFT3D_OK) rc = sift3d_strain(q.data(), u.data(), valid.data(), (int)m, &o, 0, GetDevice(), r.data(), &sec);
+	if (rc == SIFT3D_OK && labels)
+		rc = sift3d_strain_labelled(q.data(), u.data(), valid.data(), label_data(*labels), (int)m, &o, 0, GetDevice(), r.data(), &sec);
+	else if (rc == SIFT3D_OK)
+		rc = sift3d_strain(q.data(), u.data(), valid.data(), (int)m, &o, 0, GetDevice(), r.data(), &sec);
 	if (rc != SIFT3D_OK) {
 		fprintf(stderr, "[3dsift_amd] ComputeStrains: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
 		return res;
@@ -508,7 +545,7 @@ static bool apply_keep(const std::vector<unsigned char> *keep, size_t m, std::ve
 
 static std::vector<StrainResult> strains_first(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp,
                                                const std::vector<unsigned char> *keep, const StrainOptions &opts, double zncc_min,
-                                               bool accept_unconverged) {
+                                               bool accept_unconverged, const std::vector<int> *labels = nullptr) {
 	const size_t m = points.size();
 	std::vector<StrainResult> res(m);
 	std::vector<int> q;
@@ -522,7 +559,7 @@ static std::vector<StrainResult> strains_first(const std::vector<Cvec> &points, 
 	std::vector<unsigned char> valid(m ? m : 1);
 	const int rc = sift3d_strain_input_from_icgn(ic.data(), (int)m, zncc_min, accept_unconverged ? 1 : 0, u.data(), valid.data());
 	if (!apply_keep(keep, m, valid)) return res;
-	return strains_of(q, m, rc, u, valid, opts);
+	return strains_of(q, m, rc, u, valid, opts, labels);
 }
 
 std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const StrainOptions &opts, double zncc_min,
@@ -532,6 +569,11 @@ std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const 
 std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const std::vector<unsigned char> &keep,
                                          const StrainOptions &opts, double zncc_min, bool accept_unconverged) {
 	return strains_first(points, disp, &keep, opts, zncc_min, accept_unconverged);
+}
+std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const std::vector<int> &labels,
+                                         const std::vector<unsigned char> *keep, const StrainOptions &opts, double zncc_min,
+                                         bool accept_unconverged) {
+	return strains_first(points, disp, keep, opts, zncc_min, accept_unconverged, &labels);
 }
 
 Cvec Icgn2Result::Displacement() const { return Cvec((float)p[0], (float)p[10], (float)p[20]); }
@@ -590,7 +632,7 @@ std::vector<Icgn2Result> RefineDisplacementsSecondOrder(const float *ref, int nx
 
 static std::vector<StrainResult> strains_second(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp,
                                                 const std::vector<unsigned char> *keep, const StrainOptions &opts, double zncc_min,
-                                                bool accept_unconverged) {
+                                                bool accept_unconverged, const std::vector<int> *labels = nullptr) {
 	const size_t m = points.size();
 	std::vector<int> q;
 	if (!int_triples("ComputeStrains", "point", points, q)) return std::vector<StrainResult>(m);
@@ -603,7 +645,7 @@ static std::vector<StrainResult> strains_second(const std::vector<Cvec> &points,
 	std::vector<unsigned char> valid(m ? m : 1);
 	const int rc = sift3d_strain_input_from_icgn2(ic.data(), (int)m, zncc_min, accept_unconverged ? 1 : 0, u.data(), valid.data());
 	if (!apply_keep(keep, m, valid)) return std::vector<StrainResult>(m);
-	return strains_of(q, m, rc, u, valid, opts);
+	return strains_of(q, m, rc, u, valid, opts, labels);
 }
 
 std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp, const StrainOptions &opts,
@@ -614,12 +656,18 @@ std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const 
                                          const StrainOptions &opts, double zncc_min, bool accept_unconverged) {
 	return strains_second(points, disp, &keep, opts, zncc_min, accept_unconverged);
 }
+std::vector<StrainResult> ComputeStrains(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp, const std::vector<int> &labels,
+                                         const std::vector<unsigned char> *keep, const StrainOptions &opts, double zncc_min,
+                                         bool accept_unconverged) {
+	return strains_second(points, disp, keep, opts, zncc_min, accept_unconverged, &labels);
+}
 
-// the validation call behind both ValidateDisplacements overloads: rc is what the input conversion returned
+// the validation call behind the ValidateDisplacements overloads: rc is what the input conversion returned; labels null: the unlabelled call
 static std::vector<ValidationResult> validation_of(const std::vector<int> &q, size_t m, int rc, const std::vector<double> &u,
                                                    const std::vector<double> &g, bool use_gradients, const std::vector<unsigned char> &valid,
-                                                   const ValidationOptions &opts) {
+                                                   const ValidationOptions &opts, const std::vector<int> *labels) {
 	std::vector<ValidationResult> res(m);
+	if (!labels_fit("ValidateDisplacements", "points", labels, m)) return res;
 	sift3d_validate_options o;
 	sift3d_default_validate_options(&o);
 	o.radius = opts.radius;
@@ -629,7 +677,10 @@ static std::vector<ValidationResult> validation_of(const std::vector<int> &q, si
 	o.eps = opts.eps;
 	std::vector<sift3d_validate_result> r(m ? m : 1);
 	double sec = 0;
-	if (rc == SIFT3D_OK)
+	if (rc == SIFT3D_OK && labels)
+		rc = sift3d_validate_displacements_labelled(q.data(), u.data(), use_gradients ? g.data() : nullptr, valid.data(), label_data(*labels), (int)m,
+		                                            &o, 0, GetDevice(), r.data(), &sec);
+	else if (rc == SIFT3D_OK)
 		rc = sift3d_validate_displacements(q.data(), u.data(), use_gradients ? g.data() : nullptr, valid.data(), (int)m, &o, 0, GetDevice(), r.data(),
 		                                   &sec);
 	if (rc != SIFT3D_OK) {
@@ -651,7 +702,8 @@ static std::vector<ValidationResult> validation_of(const std::vector<int> &q, si
 
 template <class CRecord, class Result, class Convert>
 static std::vector<ValidationResult> validate_results(const std::vector<Cvec> &points, const std::vector<Result> &disp, const ValidationOptions &opts,
-                                                      double zncc_min, bool accept_unconverged, bool use_gradients, Convert convert) {
+                                                      double zncc_min, bool accept_unconverged, bool use_gradients, Convert convert,
+                                                      const std::vector<int> *labels = nullptr) {
 	const size_t m = points.size();
 	std::vector<int> q;
 	if (!int_triples("ValidateDisplacements", "point", points, q)) return std::vector<ValidationResult>(m);
@@ -663,7 +715,7 @@ static std::vector<ValidationResult> validate_results(const std::vector<Cvec> &p
 	std::vector<double> u(3 * (m ? m : 1)), g(9 * (m ? m : 1));
 	std::vector<unsigned char> valid(m ? m : 1);
 	const int rc = convert(ic.data(), (int)m, zncc_min, accept_unconverged ? 1 : 0, u.data(), g.data(), valid.data());
-	return validation_of(q, m, rc, u, g, use_gradients, valid, opts);
+	return validation_of(q, m, rc, u, g, use_gradients, valid, opts, labels);
 }
 
 std::vector<ValidationResult> ValidateDisplacements(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const ValidationOptions &opts,
@@ -673,6 +725,16 @@ std::vector<ValidationResult> ValidateDisplacements(const std::vector<Cvec> &poi
 std::vector<ValidationResult> ValidateDisplacements(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp, const ValidationOptions &opts,
                                                     double zncc_min, bool accept_unconverged, bool use_gradients) {
 	return validate_results<sift3d_icgn2_result>(points, disp, opts, zncc_min, accept_unconverged, use_gradients, sift3d_validate_input_from_icgn2);
+}
+std::vector<ValidationResult> ValidateDisplacements(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const std::vector<int> &labels,
+                                                    const ValidationOptions &opts, double zncc_min, bool accept_unconverged, bool use_gradients) {
+	return validate_results<sift3d_icgn_result>(points, disp, opts, zncc_min, accept_unconverged, use_gradients, sift3d_validate_input_from_icgn,
+	                                            &labels);
+}
+std::vector<ValidationResult> ValidateDisplacements(const std::vector<Cvec> &points, const std::vector<Icgn2Result> &disp, const std::vector<int> &labels,
+                                                    const ValidationOptions &opts, double zncc_min, bool accept_unconverged, bool use_gradients) {
+	return validate_results<sift3d_icgn2_result>(points, disp, opts, zncc_min, accept_unconverged, use_gradients, sift3d_validate_input_from_icgn2,
+	                                             &labels);
 }
 
 // the C records of the shell's validation results
@@ -745,12 +807,15 @@ static std::vector<sift3d_field_result> c_field(const std::vector<FieldResult> &
 	return r;
 }
 
-std::vector<FieldResult> EvaluateField(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const std::vector<double> &queries3,
-                                       const FieldOptions &opts, double zncc_min, bool accept_unconverged) {
+// the call behind the EvaluateField overloads; labels and query_labels both null: the unlabelled call
+static std::vector<FieldResult> field_of(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const std::vector<int> *labels,
+                                         const std::vector<double> &queries3, const std::vector<int> *query_labels, const FieldOptions &opts,
+                                         double zncc_min, bool accept_unconverged) {
 	const size_t m = points.size(), nq = queries3.size() / 3;
 	std::vector<FieldResult> res(nq);
 	std::vector<int> q;
 	if (!int_triples("EvaluateField", "point", points, q)) return res;
+	if (!labels_fit("EvaluateField", "points", labels, m) || !labels_fit("EvaluateField", "queries", query_labels, nq)) return res;
 	if (disp.size() != m || queries3.size() != 3 * nq) {
 		fprintf(stderr, "[3dsift_amd] EvaluateField: %zu displacements for %zu points, %zu query coordinates\n", disp.size(), m, queries3.size());
 		return res;
@@ -767,7 +832,11 @@ std::vector<FieldResult> EvaluateField(const std::vector<Cvec> &points, const st
 	o.require_enclosed = opts.require_enclosed ? 1 : 0;
 	std::vector<sift3d_field_result> r(nq ? nq : 1);
 	double sec = 0;
-	if (rc == SIFT3D_OK) rc = sift3d_field_eval(q.data(), u.data(), valid.data(), (int)m, queries3.data(), (int)nq, &o, 0, GetDevice(), r.data(), &sec);
+	if (rc == SIFT3D_OK && labels)
+		rc = sift3d_field_eval_labelled(q.data(), u.data(), valid.data(), label_data(*labels), (int)m, queries3.data(), label_data(*query_labels),
+		                                (int)nq, &o, 0, GetDevice(), r.data(), &sec);
+	else if (rc == SIFT3D_OK)
+		rc = sift3d_field_eval(q.data(), u.data(), valid.data(), (int)m, queries3.data(), (int)nq, &o, 0, GetDevice(), r.data(), &sec);
 	if (rc != SIFT3D_OK) {
 		fprintf(stderr, "[3dsift_amd] EvaluateField: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
 		return res;
@@ -783,6 +852,16 @@ std::vector<FieldResult> EvaluateField(const std::vector<Cvec> &points, const st
 		res[i].seconds = sec;
 	}
 	return res;
+}
+
+std::vector<FieldResult> EvaluateField(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const std::vector<double> &queries3,
+                                       const FieldOptions &opts, double zncc_min, bool accept_unconverged) {
+	return field_of(points, disp, nullptr, queries3, nullptr, opts, zncc_min, accept_unconverged);
+}
+std::vector<FieldResult> EvaluateField(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const std::vector<int> &labels,
+                                       const std::vector<double> &queries3, const std::vector<int> &query_labels, const FieldOptions &opts,
+                                       double zncc_min, bool accept_unconverged) {
+	return field_of(points, disp, &labels, queries3, &query_labels, opts, zncc_min, accept_unconverged);
 }
 
 std::vector<FieldResult> EvaluateField(const std::vector<Cvec> &points, const std::vector<IcgnResult> &disp, const std::vector<Cvec> &pointsA,

@@ -1232,6 +1232,59 @@ int sift3d_icgn_masked(const float *ref, int rnx, int rny, int rnz, const float 
 int sift3d_mask_from_level(const float *vol, int nx, int ny, int nz, double level, unsigned char *mask, int on_device, int device,
                            double *seconds);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Several bodies: connected-component labels of a mask, and the three window calls limited to a POI's own body (no reference
+ * counterpart: what DVC codes for granular specimens do).  sift3d_strain, sift3d_validate_displacements and sift3d_field_eval take
+ * every contributing POI of the window as a neighbour, whichever body it lies in: across a contact between two bodies that move
+ * differently the plane fit reports a strain that is not there, the median test flags the correct vectors of the smaller body, and
+ * the field is a blend of two motions.  The labels say which body a voxel and a POI belong to.
+ *
+ * sift3d_mask_label: the components of a byte mask (tests/label_ref.py restates it in NumPy).
+ *   Layout [z][y][x], x fastest, as every volume here; any non-zero mask byte is "in".  labels[i] = 0 where mask[i] is 0.
+ *   A component is a maximal set of in-voxels connected through faces (connectivity 6) or through faces, edges and corners (26).
+ *   The kept components -- those of at least min_voxels voxels -- are numbered 1..*count in ascending order of their lowest linear
+ *   voxel index (z * ny + y) * nx + x (scipy.ndimage.label's numbering); a voxel of a smaller component gets 0 and the component is
+ *   neither counted nor numbered.
+ *   Determinism: the output is a function of the input alone (integer atomics only): two calls return the same bytes.
+ *   SIFT3D_ERR_ARG (checked before any device call): NULL mask, labels or count, a dimension < 1, nx * ny * nz >= 2^31 (linear
+ *   indices are int), a connectivity other than 6 or 26, min_voxels < 1.  SIFT3D_ERR_NO_DEVICE after that check when no GPU is
+ *   visible: there is no CPU fallback.  on_device != 0: mask and labels are device pointers on `device`, ordered behind the legacy
+ *   default stream; otherwise both are host memory.  count is host memory either way.  *seconds (may be NULL): device time of the
+ *   kernels (the copies excluded).
+ *   Device memory: beside labels the call keeps 4 bytes per voxel and 4 bytes per 2048 voxels, and with host pointers 5 more bytes per
+ *   voxel (the mask and the labels), in a block that grows with the largest call so far (a quarter of head room) and stays allocated
+ *   for later calls.
+ *
+ * sift3d_labels_at_points: poi_label[i] = labels at voxel points3[i] (x, y, z), or 0 when that voxel lies outside the volume.
+ *   on_device == 0: a host loop, no GPU needed.  on_device != 0: labels and points3 are device pointers on `device`, ordered behind
+ *   the legacy default stream; poi_label is host memory either way, filled by one kernel and one copy.  SIFT3D_ERR_ARG: NULL labels,
+ *   a dimension < 1, nx * ny * nz >= 2^31, m < 0, NULL points3 or poi_label with m > 0.
+ *
+ * The labelled window calls: sift3d_strain, sift3d_validate_displacements and sift3d_field_eval with one sentence added to each
+ * contract.  POI j is a neighbour (strain, validation) or a member (field) of centre i only if it is one under the unlabelled rule
+ * and label[j] == label[i] and that label is > 0; for a field query k, query_label[k] takes the place of label[i].  A centre or query
+ * whose label is <= 0 has no neighbours: status 1 with neighbours 0 (and sides 0); the coordinate test, status 2, still comes first.
+ * u0, "the neighbour with the lowest index", is taken among the neighbours so defined.  Everything else stands word for word: which
+ * POIs contribute, hole filling (status 3), the passes of the median test, require_enclosed, the pivot rule, determinism.  With all
+ * labels equal and positive a call returns the bytes of the unlabelled call.  A POI's record does not depend on the POIs of other
+ * labels: the lanes of a wave share out the entries of the centre's label alone, so the other POIs' displacements, finite or not,
+ * do not move a single fp64 sum -- as long as the bounding box of the contributing POIs, which places the cell grid and with it the
+ * order of a window's entries, stays where it is (a validation record, which sums nothing, is independent without that).  label: m ints; query_label: nq ints; device pointers when on_device != 0.  SIFT3D_ERR_ARG: the unlabelled call's rules
+ * with these, a NULL label, a NULL query_label with nq > 0.  A per-body mask for sift3d_icgn_masked is labels == L.
+ * ------------------------------------------------------------------------------------------------------------ */
+int sift3d_mask_label(const unsigned char *mask, int nx, int ny, int nz, int connectivity /* 6 or 26 */, int min_voxels /* >= 1 */,
+                      int *labels /* nx*ny*nz */, int *count, int on_device, int device, double *seconds);
+int sift3d_labels_at_points(const int *labels, int nx, int ny, int nz, const int *points3, int m, int *poi_label /* m, host */, int on_device,
+                            int device);
+int sift3d_strain_labelled(const int *points3, const double *disp3, const unsigned char *valid, const int *label /* m */, int m,
+                           const sift3d_strain_options *o, int on_device, int device, sift3d_strain_result *out, double *seconds);
+int sift3d_validate_displacements_labelled(const int *points3, const double *disp3, const double *grad9, const unsigned char *valid,
+                                           const int *label /* m */, int m, const sift3d_validate_options *o, int on_device, int device,
+                                           sift3d_validate_result *out, double *seconds);
+int sift3d_field_eval_labelled(const int *points3, const double *disp3, const unsigned char *valid, const int *label /* m */, int m,
+                               const double *queries3, const int *query_label /* nq */, int nq, const sift3d_field_options *o, int on_device,
+                               int device, sift3d_field_result *out, double *seconds);
+
 /* Test hooks, rare-path counters and the unit-level debug entry points live in include/sift3d_hip_test.h: this header is the
  * product boundary only. */
 const char *sift3d_error_string(int code);

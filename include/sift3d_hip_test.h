@@ -89,6 +89,10 @@ int sift3d_validate_stage_capacity(int *n);
  * piece per lane, as many workgroups as pieces) and the most k_absmax_t is launched with (grid-stride beyond).  Host only, no GPU. */
 int sift3d_test_ingest_launch(int dtype, int *block, int *piece_elems, int *ingest_max_blocks, int *absmax_max_blocks);
 
+/* the extents (x, y, z) of the tile whose union-find sift3d_mask_label runs in LDS (csrc/kernels_label.hip; 32 x 8 x 8), so that tests
+ * can put contacts on the seams between tiles, which a second kernel merges.  Host only, no GPU. */
+int sift3d_test_label_tile(int t[3]);
+
 #ifdef __cplusplus
 }
 #endif
