@@ -9,8 +9,8 @@
 // depends on it, so instead of an atomic append + sort the scan is made order-preserving.  One launch
 // of each kernel covers the THREE keypoint levels of an octave:
 //   k_mark : block = (level, z, kRows rows) -- a contiguous range in scan order; lanes run along x (coalesced, no
-//            index divisions); voxels above the peak threshold are queued per wave and their eight neighbours gathered 64
-//            candidates at a time; each wave stores the 64-bit ballots of its rows, each block its hit count
+//            index divisions); voxels above the peak threshold that are strict extrema among their four in-plane neighbours
+//            are queued per wave and their other four neighbours gathered 64 candidates at a time; each wave stores the 64-bit ballots of its rows, each block its hit count
 //   k_lazy_next : the last Gaussian level of an octave is not built; the candidates of the last keypoint level that passed seven
 //            tests are parked by k_mark and get the missing neighbour value here (one workgroup per candidate)
 //   k_scan : one workgroup turns the block counts into exclusive offsets on top of the running total
@@ -27,33 +27,23 @@
 
 namespace s3d {
 
-#ifndef S3D_DET_ROWS
-#define S3D_DET_ROWS 32  /* rows per block: 32 measured best (detect 0.93 -> 0.84 ms at 512^3; 64: 1.01) */
-#endif
-#ifndef S3D_DET_QUEUE
-#define S3D_DET_QUEUE 640  /* 640: the queue is drained after a batch of 8 ballot words; 128: after every word (1.06 vs 0.99 ms detection) */
-#endif
 // development diagnostics, timing only (wrong results; never set in the product build): 1 no neighbour gathers, 2 nothing is queued
 #ifndef S3D_DETDIAG
 #define S3D_DETDIAG 0
 #endif
-#ifndef S3D_DET_LEAN
-#define S3D_DET_LEAN 1
-#endif
-#ifndef S3D_DET_XPRE
-#define S3D_DET_XPRE 0  /* generic row loop, 1: the two x neighbours are read with the centre values (two more coalesced loads per word) and tested before a voxel is queued -- no gain on the blob volumes (noise makes two voxels out of three x extrema) */
-#endif
-constexpr int kRows = S3D_DET_ROWS;   // rows per block
+constexpr int kRows = 32;  // rows per block: 32 measured best (detect 0.93 -> 0.84 ms at 512^3; 64: 1.01)
 constexpr int kThreads = 256;
 
 // masks layout: word index = ((lvl * nz + z) * ny + y) * wpr + xw, wpr = ceil(nx / 64): scan order
 //
-// Two-phase per wave: (1) stream the centre values, kBatch ballot words per pass, and push the voxels that pass the peak
-// threshold (a few per cent) into a wave-private LDS queue by ballot rank; (2) whenever 64 candidates are queued, all 64
-// lanes fetch the 8 neighbours of one candidate each and OR their verdict into the wave's LDS copy of the mask words.
-// A per-word `if (candidate) { 8 loads }` issues those 8 load instructions for nearly every word (some lane usually is a
+// Two-phase per wave: (1) stream the rows, kBatch ballot words per pass, and push the voxels that pass the peak threshold
+// and the in-plane tests (a few per cent) into a wave-private LDS queue by ballot rank; (2) whenever 64 candidates are queued,
+// all 64 lanes fetch the remaining neighbours of one candidate each and OR their verdict into the wave's LDS copy of the mask
+// words.  A per-word `if (candidate) { loads }` issues those load instructions for nearly every word (some lane usually is a
 // candidate) and the compiler drains them at each join: one memory round trip per word.
-constexpr int kQueue = S3D_DET_QUEUE;  // >= 63 left over + the lanes pushed before the next drain (one word: 64, a whole batch: 512)
+// kQueue: >= 63 left over + the lanes pushed before the next drain (a whole batch: 512).  640: the queue is drained after a batch of 8 ballot
+// words; 128, drained after every word, measured slower (1.06 vs 0.99 ms detection)
+constexpr int kQueue = 640;
 __global__ void __launch_bounds__(kThreads) k_mark(DetectLevels L, int nx, int ny, ZRange zr, int nyb, float peak_thresh,
                                                    unsigned long long *__restrict__ masks, unsigned *__restrict__ block_counts,
                                                    unsigned *__restrict__ prov, unsigned *__restrict__ prov_count, unsigned prov_cap,
@@ -90,7 +80,6 @@ __global__ void __launch_bounds__(kThreads) k_mark(DetectLevels L, int nx, int n
 	const unsigned long long lt = (1ull << lane) - 1ull;
 	const size_t plane0 = sz * (size_t)z + sy * (size_t)y0;
 	int qn = 0;  // wave-uniform
-	const bool lean = S3D_DET_LEAN != 0;  // the lean row loop (below); S3D_DET_LEAN=0 builds keep the generic one for A/B runs
 	// evaluate `n` queued candidates starting at entry `first` (n <= 64)
 	auto evaluate = [&](int first, int n, int seg0) {
 		if (S3D_DETDIAG & 1) {  // no gathers: the queue entry alone decides (keeps the queue traffic alive)
@@ -114,16 +103,13 @@ __global__ void __launch_bounds__(kThreads) k_mark(DetectLevels L, int nx, int n
 		const size_t ic = act ? i : sz * (size_t)z + sy + 1;
 		// elided first / last DoG level: formed from the two Gaussian levels like Sub does (block-uniform choice)
 		const float n0 = lazy_prev ? (L.prev0_hi[ic] - L.prev0_lo[ic]) * (-1.0f) : prev[ic];
-		// lean row loop: the four in-plane neighbours were tested in registers (bit 16 of the entry: the voxel is a strict MAXIMUM among
+		// the row loop tested the four in-plane neighbours in registers (bit 16 of the entry: the voxel is a strict MAXIMUM among
 		// them, else a strict minimum); only the neighbours in z and in scale are gathered
-		const bool pre = lean;  // kernel-uniform
 		const bool dmax = (id >> 16) & 1u;
-		float n1 = 0.f, n2 = 0.f, n3 = 0.f, n4 = 0.f;
-		if (!pre) { n1 = cur[ic - 1]; n2 = cur[ic + 1]; n3 = cur[ic + sy]; n4 = cur[ic - sy]; }
 		const float n5 = cur[ic + sz], n6 = cur[ic - sz];
 		if (lazy_g) {  // block-uniform
-			const bool mn7 = pre ? (!dmax && v < n0 && v < n5 && v < n6) : (v < n0 && v < n1 && v < n2 && v < n3 && v < n4 && v < n5 && v < n6);
-			const bool mx7 = pre ? (dmax && v > n0 && v > n5 && v > n6) : (v > n0 && v > n1 && v > n2 && v > n3 && v > n4 && v > n5 && v > n6);
+			const bool mn7 = !dmax && v < n0 && v < n5 && v < n6;
+			const bool mx7 = dmax && v > n0 && v > n5 && v > n6;
 			// one counter increment per wave (a single word takes ~90 atomics per microsecond: one per candidate cost 0.45 ms)
 			const bool park = act && (mn7 || mx7);
 			const unsigned long long pm = __ballot(park);
@@ -140,8 +126,8 @@ __global__ void __launch_bounds__(kThreads) k_mark(DetectLevels L, int nx, int n
 			return;
 		}
 		const float n7 = lazy_next ? (L.nextl_hi[ic] - L.nextl_lo[ic]) * (-1.0f) : next[ic];
-		const bool mn = pre ? (!dmax && v < n0 && v < n5 && v < n6 && v < n7) : (v < n0 && v < n1 && v < n2 && v < n3 && v < n4 && v < n5 && v < n6 && v < n7);
-		const bool mx = pre ? (dmax && v > n0 && v > n5 && v > n6 && v > n7) : (v > n0 && v > n1 && v > n2 && v > n3 && v > n4 && v > n5 && v > n6 && v > n7);
+		const bool mn = !dmax && v < n0 && v < n5 && v < n6 && v < n7;
+		const bool mx = dmax && v > n0 && v > n5 && v > n6 && v > n7;
 		if (act && (mn || mx)) atomicOr(&mloc[rr * segw + xw], 1ull << bit);
 	};
 	unsigned cnt = 0;
@@ -158,7 +144,7 @@ __global__ void __launch_bounds__(kThreads) k_mark(DetectLevels L, int nx, int n
 		// below (8 + 2 rows read for 8).  With the threshold alone 10 % of the voxels of the blob volumes were queued and their eight
 		// gathers (64 different cache lines per instruction) cost 0.19 of the remaining 0.48 ms; now two candidates out of five
 		// survive (noise: a voxel is an extremum of five with probability 2/5) and four neighbours are left to gather.
-		if (lean && z_in) {
+		if (z_in) {
 			// rows of this wave with 1 <= y <= ny-2 (a contiguous range; the rows above and below it exist)
 			const int ry_a = max(r_lo, 1 - y0), ry_b = min(r_hi, ny - 1 - y0);
 			const int nws = seg1 - seg0;
@@ -225,47 +211,6 @@ __global__ void __launch_bounds__(kThreads) k_mark(DetectLevels L, int nx, int n
 #pragma unroll
 					for (int bb = 0; bb < kBatch; bb++) { up[bb] = mid[bb]; mid[bb] = dn[bb]; }
 					emid = edn;
-				}
-			}
-		}
-		for (int ry = r_lo; !lean && ry < r_hi; ry++) {
-			const int y = y0 + ry;
-			const bool y_in = z_in && y >= 1 && y <= ny - 2;
-			const size_t rowbase = sy * (size_t)y + sz * (size_t)z;
-			for (int xw0 = seg0; xw0 < seg1; xw0 += kBatch) {
-				float val[kBatch], vxm[kBatch], vxp[kBatch];
-				bool in[kBatch];
-#pragma unroll
-				for (int bb = 0; bb < kBatch; bb++) {
-					const int x = (xw0 + bb) * 64 + lane;
-					in[bb] = y_in && xw0 + bb < seg1 && x >= 1 && x <= nx - 2;
-					const float *a = cur + (in[bb] ? rowbase + (size_t)x : sz * (size_t)z + 1);  // unconditional loads, clamped address
-					val[bb] = a[0];
-					if (S3D_DET_XPRE) { vxm[bb] = a[-1]; vxp[bb] = a[1]; }
-				}
-#pragma unroll
-				for (int bb = 0; bb < kBatch; bb++) {
-					const float v = val[bb];
-					// r03: the gathers of the queued voxels (8 x 64 different cache lines per 64 candidates, 10 % of the voxels of the blob
-					// volumes pass the peak threshold) kept the texture addresser busy for the whole kernel (TA_BUSY = kernel time, 438 M cache
-					// accesses per 512^3); a voxel that is not a strict extremum among its two x neighbours cannot pass the full test
-					const bool xext = !S3D_DET_XPRE || (((int)(v > vxm[bb]) & (int)(v > vxp[bb])) | ((int)(v < vxm[bb]) & (int)(v < vxp[bb]))) != 0;
-					const bool c = in[bb] && (v > thr || v < -thr) && xext && !((S3D_DETDIAG & 2) && v != 12345.678f);
-					const unsigned long long m = __ballot(c);
-					if (c) {
-						const int pos = qn + (int)__popcll(m & lt);
-						q[pos] = make_uint2(__float_as_uint(v), (unsigned)(((ry - r_lo) << 12) | ((xw0 + bb - seg0) << 6) | lane));
-					}
-					qn += (int)__popcll(m);
-					if (kQueue < 63 + kBatch * 64 && qn >= 64) {  // small queue: drain after every word
-						qn -= 64;
-						evaluate(qn, 64, seg0);
-					}
-				}
-				// drain full waves of candidates (entries are consumed from the END so the front stays in place)
-				while (qn >= 64) {
-					qn -= 64;
-					evaluate(qn, 64, seg0);
 				}
 			}
 		}

@@ -6,9 +6,10 @@
 // the lower j, both start at FLT_MIN), reported as d = 2 - 2*dot.  The reference accumulates fp32
 // products in fp64; an fp32 MFMA chain cannot reproduce that bit-for-bit, so the work is split:
 //   k_scores_topk2: S = A * B^T with v_mfma_f32_32x32x2_f32 (exact fp32 fma chain), fused running
-//                   top-K per row ordered by (score desc, j asc) -- candidate SELECTION only.  (r03: the second form of the kernel,
-//                   A straight into registers / B by LDS-DMA / three workgroups per CU; k_scores_top4<DMA> is the r02 form, kept for
-//                   A/B builds -DS3D_MATCH_V2=0, k_scores_top4<false> the register-staged one for matrices of 4 GB and more)
+//                   top-K per row ordered by (score desc, j asc) -- candidate SELECTION only.  A goes straight into registers, B by
+//                   LDS-DMA, three workgroups per CU; both are addressed with 32-bit byte offsets
+//   k_scores_top4 : the same selection with both matrices staged through registers and 64-bit addresses, two workgroups per CU:
+//                   for matrices of 4 GB and more
 //   k_rescore     : the 4 candidates of each row are re-scored exactly like the reference
 //                   (fp32 product, fp64 accumulate, k ascending) and the reference's update rule is
 //                   replayed over them in ascending j -- bit-identical d1, d2, i1, i2 as long as the
@@ -34,10 +35,10 @@ namespace s3d {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef S3D_MATCH_TOPK
-#define S3D_MATCH_TOPK 6  /* candidates kept per row by the fp32 selection (r02, two similar 512^3 volumes, one full pass: 4 -> 3.6 ms because ~10 % of the rows fail the guard and are re-done exactly, 6 -> 2.6 ms, 8 -> 2.9 ms) */
-#endif
-constexpr int KD = kDesc, TOPK = S3D_MATCH_TOPK;
+// candidates kept per row by the fp32 selection (r02, two similar 512^3 volumes, one full pass: 4 -> 3.6 ms because ~10 % of the rows
+// fail the guard and are re-done exactly, 6 -> 2.6 ms, 8 -> 2.9 ms)
+constexpr int TOPK = 6;
+constexpr int KD = kDesc;
 // score kernel tiling: a 256-thread workgroup owns 128 rows x 128 columns per tile; wave w owns rows 32w..32w+31 across all
 // 128 columns (four 32x32 accumulators), so every row's running top-4 belongs to exactly one wave and lives in registers
 constexpr int BM = 128, BN = 128, BK = 32, PITCH = BK + 4;  // +16 B: the 16-B reads of 8 consecutive rows hit distinct banks
@@ -77,26 +78,12 @@ __device__ __forceinline__ void topk_bubble(float (&bs)[TOPK], int (&bj)[TOPK], 
 	}
 }
 
-// S = A * B^T on v_mfma_f32_32x32x2_f32 with a fused running top-4 per row.  grid = (row blocks, column splits); each
-// workgroup streams the tiles of its column range, double-buffered through LDS.  An MFMA step multiplies two k indices:
+// The register-staged score kernel (matrices of 4 GB and more).  S = A * B^T on v_mfma_f32_32x32x2_f32 with a fused running top-K
+// per row.  Each workgroup streams the tiles of its share, double-buffered through LDS: the 32-wide k chunks of both matrices are
+// loaded into registers and stored into padded row-major tiles.  An MFMA step multiplies two k indices:
 // lanes 0-31 feed k = s, lanes 32-63 feed k = s + 16 of the 32-wide chunk, so a lane's operands for four consecutive steps
 // are four consecutive floats of a plain row-major LDS tile (one ds_read_b128).  The summation order over k is free here:
 // the scores only SELECT candidates, k_rescore recomputes them exactly.
-// LDS-DMA: lane l's 16 bytes at base + voff land at lds_dst + 16*l (global_load_lds_dwordx4).  M0 carries the wave-uniform LDS byte
-// address (restored).  Counted by vmcnt like any load.
-__device__ __forceinline__ void x_dma16(const float *base, unsigned voff, unsigned lds_dst) {
-	unsigned keep;
-	asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-	             : "=&s"(keep) : "v"(voff), "s"(base), "s"(lds_dst) : "memory");
-}
-
-// DMA = true (every byte offset into A and B fits 32 bits): the 32-wide k chunks travel global -> LDS by LDS-DMA instead of through
-// registers (no staging registers, no ds_write, no VALU).  A wave's instruction fills 8 rows x 128 B contiguously, so the rows are
-// NOT padded; instead the 16-byte piece g of tile row r is stored at slot g ^ ((r >> 1) & 7) -- the lane that owns slot c of row r
-// simply requests piece c ^ ((r >> 1) & 7) -- which makes the ds_read_b128 fragment reads of 16 consecutive rows hit the 16
-// distinct 4-bank groups (also in the lane groups the hardware serves a b128 read in).  Rows / columns past the end request row 0:
-// their scores are never looked at.
-template <bool DMA>
 __global__ void __launch_bounds__(256, 2) k_scores_top4(const float *__restrict__ A, const int *__restrict__ row_ids, int nrows,
                                                         const float *__restrict__ B, int m, int slots,
                                                         Cand *__restrict__ part /*[nrows][slots][TOPK]*/) {
@@ -132,17 +119,6 @@ __global__ void __launch_bounds__(256, 2) k_scores_top4(const float *__restrict_
 		const int r = row0 + srow + 32 * p;
 		Ap[p] = r < nrows ? A + (size_t)(row_ids ? row_ids[r] : r) * KD + spiece : nullptr;
 	}
-	// DMA staging: byte offset of this lane's piece of tile row srow + 32 p (k = 0) and the LDS address of the wave's 8-row slab
-	const unsigned swz = (unsigned)((tid & 7) ^ ((srow >> 1) & 7)) * 16u;  // (row + 32 p) >> 1 has the same low three bits
-	unsigned aoff[4];
-#pragma unroll
-	for (int p = 0; p < 4; p++) {
-		const int r = row0 + srow + 32 * p;
-		aoff[p] = (unsigned)(r < nrows ? (row_ids ? row_ids[r] : r) : (row_ids ? row_ids[0] : 0)) * (unsigned)(KD * 4) + swz;
-	}
-	const unsigned lds_a = (unsigned)(unsigned long long)&As[0][0], lds_b = (unsigned)(unsigned long long)&Bs[0][0];
-	const unsigned slab = (unsigned)__builtin_amdgcn_readfirstlane(wid) * (8u * 32u * 4u);  // this wave's rows 8 wid .. 8 wid + 7 of a 32-row pass
-	const unsigned fswz = (unsigned)((li >> 1) & 7);  // fragment reads: tile rows wid*32 + li and li + 32 nb share (row >> 1) & 7
 	float bs[TOPK];
 	int bj[TOPK];
 #pragma unroll
@@ -178,55 +154,30 @@ __global__ void __launch_bounds__(256, 2) k_scores_top4(const float *__restrict_
 				*reinterpret_cast<f32x4 *>(&Bs[buf][(srow + 32 * p) * PITCH + spiece]) = pb[p];
 			}
 		};
-		unsigned boff[4];
-#pragma unroll
-		for (int p = 0; p < 4; p++) {
-			const int c = col0 + srow + 32 * p;
-			boff[p] = (unsigned)(c < m ? c : 0) * (unsigned)(KD * 4) + swz;
-		}
-		auto dma = [&](int buf, int k0) {  // chunk k0 .. k0 + 31 of both tiles -> buffer buf
-#pragma unroll
-			for (int p = 0; p < 4; p++) {
-				x_dma16(A, aoff[p] + (unsigned)(k0 * 4), lds_a + (unsigned)(buf * BM * PITCH * 4) + (unsigned)(p * 32 * 32 * 4) + slab);
-				x_dma16(B, boff[p] + (unsigned)(k0 * 4), lds_b + (unsigned)(buf * BN * PITCH * 4) + (unsigned)(p * 32 * 32 * 4) + slab);
-			}
-		};
 		constexpr int NCH = KD / BK;
-		if (DMA) {
-			__syncthreads();  // every wave is done with both buffers (and the score tile) of the previous tile
-			dma(0, 0);
-			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-			__syncthreads();
-		} else {
-			fetch(0);
-			__syncthreads();  // every wave is done with both buffers of the previous tile
-			stash(0);
-			__syncthreads();
-		}
+		fetch(0);
+		__syncthreads();  // every wave is done with both buffers of the previous tile
+		stash(0);
+		__syncthreads();
 		for (int ch = 0; ch < NCH; ch++) {
 			const int buf = ch & 1;
-			if (ch + 1 < NCH) {  // in flight during the MFMAs of this chunk (the other buffer was last read in chunk ch-1, a barrier ago)
-				if (DMA) dma(buf ^ 1, (ch + 1) * BK);
-				else fetch((ch + 1) * BK);
-			}
-			constexpr int RP = DMA ? 32 : PITCH;  // row pitch of the staged tiles
-			const float *ar = &As[buf][(wid * 32 + li) * RP];
-			const float *br = &Bs[buf][li * RP];
+			if (ch + 1 < NCH) fetch((ch + 1) * BK);  // in flight during the MFMAs of this chunk (the other buffer was last read in chunk ch-1, a barrier ago)
+			const float *ar = &As[buf][(wid * 32 + li) * PITCH];
+			const float *br = &Bs[buf][li * PITCH];
 #pragma unroll
 			for (int q = 0; q < 4; q++) {
-				const int po = DMA ? (int)((((unsigned)lh << 2 | (unsigned)q) ^ fswz) * 4u) : lh * 16 + 4 * q;  // piece lh*4 + q of the row
+				const int po = lh * 16 + 4 * q;  // piece lh*4 + q of the row
 				const f32x4 a4 = *reinterpret_cast<const f32x4 *>(ar + po);
 				f32x4 b4[4];
 #pragma unroll
-				for (int nb = 0; nb < 4; nb++) b4[nb] = *reinterpret_cast<const f32x4 *>(br + nb * 32 * RP + po);
+				for (int nb = 0; nb < 4; nb++) b4[nb] = *reinterpret_cast<const f32x4 *>(br + nb * 32 * PITCH + po);
 #pragma unroll
 				for (int e = 0; e < 4; e++)
 #pragma unroll
 					for (int nb = 0; nb < 4; nb++) acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[e], b4[nb][e], acc[nb], 0, 0, 0);
 			}
 			if (ch + 1 < NCH) {
-				if (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-				else stash(buf ^ 1);
+				stash(buf ^ 1);
 				__syncthreads();
 			}
 		}
@@ -271,14 +222,18 @@ __global__ void __launch_bounds__(256, 2) k_scores_top4(const float *__restrict_
 	}  // next row block of this workgroup's share
 }
 
-// ---- r03: the score kernel, second form (S3D_MATCH_V2; the DMA form above stays for A/B builds, the register-staged one for >= 4 GB) ----
-// What is different:
+// ---- the score kernel of matrices below 4 GB: every byte offset into A and B fits 32 bits (r03; it replaced a form that sent both
+// matrices through LDS, by LDS-DMA, at two workgroups per CU).  What is different from k_scores_top4:
 //   * A never touches the LDS.  A wave's 32 rows are read by nobody else: lane (li, lh) loads the 16 floats k0 + 16 lh .. + 15 of
 //     its row straight into registers (two lanes use one 128-byte line completely).  Piece q of the NEXT chunk is requested into
 //     the same four registers right behind the sixteen MFMAs that consumed it, by an untracked load; each MFMA group waits for its
 //     piece with a COUNTED s_waitcnt (vmcnt retires in order; the eight younger operations -- three A pieces, the four DMA
 //     instructions of the chunk, one refreshed piece -- stay in flight).  Only the B chunks travel by LDS-DMA: 33 KB instead of
-//     73 KB of LDS per workgroup -> THREE workgroups per CU, half the LDS-DMA traffic.
+//     73 KB of LDS per workgroup -> THREE workgroups per CU.  A wave's DMA instruction fills 8 rows x 128 B contiguously, so the rows
+//     are NOT padded; instead the 16-byte piece g of tile row r is stored at slot g ^ ((r >> 1) & 7) -- the lane that owns slot c of
+//     row r simply requests piece c ^ ((r >> 1) & 7) -- which makes the ds_read_b128 fragment reads of 16 consecutive rows hit the 16
+//     distinct 4-bank groups (also in the lane groups the hardware serves a b128 read in).  Columns past the end request row 0: their
+//     scores are never looked at.
 //   * every chunk issues exactly four DMA instructions: the last chunk of a tile requests the first chunk of the NEXT tile into the
 //     free stage, so it lands during the selection and a tile costs one barrier more than its 24 chunks.
 //   * the selection does not run the insert in lock step.  Each lane compares its 16 scores of a quarter band with its list's last
@@ -290,22 +245,23 @@ __global__ void __launch_bounds__(256, 2) k_scores_top4(const float *__restrict_
 //     half: the same code with two of the four accumulators.
 // Lists are per (row, lane half): lane (li, lh) scans the columns 16 lh .. 16 lh + 15 of each 32-column block, in ascending column
 // order over the tiles, with the reference's strict '>' rule; the halves are merged at the end (order independent).
-#ifndef S3D_MATCH_V2
-#define S3D_MATCH_V2 1
-#endif
-#ifndef S3D_MATCH_V2_OCC
-#define S3D_MATCH_V2_OCC 3
-#endif
 constexpr int SP2 = 33;  // pitch of a 32-column score block
 // development diagnostics, timing only (wrong results by construction; never set in the product build): 1 no selection, 2 no B DMA,
 // 4 no A refresh loads, 8 no barriers inside the chunk loop
 #ifndef S3D_XDIAG
 #define S3D_XDIAG 0
 #endif
+// LDS-DMA: lane l's 16 bytes at base + voff land at lds_dst + 16*l (global_load_lds_dwordx4).  M0 carries the wave-uniform LDS byte
+// address (restored).  Counted by vmcnt like any load.
+__device__ __forceinline__ void x_dma16(const float *base, unsigned voff, unsigned lds_dst) {
+	unsigned keep;
+	asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+	             : "=&s"(keep) : "v"(voff), "s"(base), "s"(lds_dst) : "memory");
+}
 template <int N>
 __device__ __forceinline__ void x_wait_piece(f32x4 &piece) { asm volatile("s_waitcnt vmcnt(%1)" : "+v"(piece) : "n"(N) : "memory"); }
 
-__global__ void __launch_bounds__(256, S3D_MATCH_V2_OCC) k_scores_topk2(const float *__restrict__ A, const int *__restrict__ row_ids, int nrows,
+__global__ void __launch_bounds__(256, 3) k_scores_topk2(const float *__restrict__ A, const int *__restrict__ row_ids, int nrows,
                                                                       const float *__restrict__ B, int m, int slots,
                                                                       Cand *__restrict__ part /*[nrows][slots][TOPK]*/) {
 	constexpr int kStage = BN * BK;  // floats per B stage; stage 1 is followed by the tail of the score blocks (4 waves x 32 x 33 floats)
@@ -670,24 +626,22 @@ __global__ void __launch_bounds__(256) k_exact_rows(const float *__restrict__ A,
 int match_rows_device(const float *d_a, const int *d_row_ids, int nrows, const float *d_b, int m, int *d_cand, void *d_part,
                       float *d_gd, float *d_sd, int *d_gi, int *d_si, const MatchGuard &g, hipStream_t st) {
 	if (nrows <= 0) return SIFT3D_OK;
-	// as many workgroups as fit ONE residency round (two per CU), each with an equal share of the (row block, column tile) pairs;
-	// at most kMaxSplits - 1 workgroups per row block (plus the one that straddles its start)
+	// as many workgroups as fit ONE residency round (the kernel's workgroups per CU), each with an equal share of the (row block,
+	// column unit) pairs; at most kMaxSplits - 1 workgroups per row block (plus the one that straddles its start)
 	const int rb = (nrows + BM - 1) / BM, ntiles = (m + BN - 1) / BN;
-	const bool v2 = S3D_MATCH_V2 && g.small_offsets;
-	const int per_cu = v2 ? S3D_MATCH_V2_OCC : 2;
-	const int nunits = v2 ? 2 * ntiles : ntiles;  // the second form deals half tiles
+	const bool dma = g.small_offsets;  // k_scores_topk2: three workgroups per CU, dealt in half tiles
+	const int per_cu = dma ? 3 : 2;
+	const int nunits = dma ? 2 * ntiles : ntiles;
 	const long long total = (long long)rb * nunits;
 	const int nwg = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(per_cu * 256, total), (long long)(kMaxSplits - 1) * rb));
 	// workgroups that can touch one row block: those starting inside it plus the one running into it
 	const int slots = std::min(kMaxSplits, (int)(((long long)nunits * nwg + total - 1) / total) + 1);
-	// (the DMA form addresses A and B with 32-bit byte offsets; row_ids index the caller's whole A, whose size is not known here:
+	// (k_scores_topk2 addresses A and B with 32-bit byte offsets; row_ids index the caller's whole A, whose size is not known here:
 	// the caller says whether both matrices stay below 4 GB)
-	if (v2)
+	if (dma)
 		hipLaunchKernelGGL(k_scores_topk2, dim3(nwg), dim3(256), 0, st, d_a, d_row_ids, nrows, d_b, m, slots, (Cand *)d_part);
-	else if (g.small_offsets)
-		hipLaunchKernelGGL(k_scores_top4<true>, dim3(nwg), dim3(256), 0, st, d_a, d_row_ids, nrows, d_b, m, slots, (Cand *)d_part);
 	else
-		hipLaunchKernelGGL(k_scores_top4<false>, dim3(nwg), dim3(256), 0, st, d_a, d_row_ids, nrows, d_b, m, slots, (Cand *)d_part);
+		hipLaunchKernelGGL(k_scores_top4, dim3(nwg), dim3(256), 0, st, d_a, d_row_ids, nrows, d_b, m, slots, (Cand *)d_part);
 	hipLaunchKernelGGL(k_merge_top4, dim3((nrows + 31) / 32), dim3(256), 0, st, (const Cand *)d_part, nrows, slots, d_cand, g.s4, nunits, nwg, g.redo);
 	hipLaunchKernelGGL(k_rescore, dim3((nrows + kRsWaves * kRowsPerWave - 1) / (kRsWaves * kRowsPerWave)), dim3(64 * kRsWaves), 0, st, d_a, d_row_ids, nrows, d_b, d_cand, d_gd, d_sd, d_gi, d_si,
 	                   g.s4, g.a_n2, g.b_n2max, g.redo);
@@ -695,169 +649,15 @@ int match_rows_device(const float *d_a, const int *d_row_ids, int nrows, const f
 	return SIFT3D_OK;
 }
 
-}  // namespace s3d
-
-// ---------------------------------------------------------------------------------------------
-// C-ABI: muBruteMatcher::bijectMatchBase (Src/cMatcher.cc:146-215).  The O(N*M*768) passes run on
-// the device; the O(N) bookkeeping (ratio filter, countMatched, toMask, bijectFilter, toCvec) is
-// replayed on the host exactly as written in the reference, including its sign-flip quirks (match_host.h).
-// ---------------------------------------------------------------------------------------------
-#include <algorithm>
-#include <vector>
-
-using namespace s3d;
-
-// Per-device matcher state (call_state.h; r03: a call used to do 3-5 hipMalloc / hipFree and ran on the null stream).  d holds
-// everything but the descriptor matrices, h the results of a pass (+ the coordinates of device-resident inputs).
-#include <chrono>
-
-#include "call_state.h"
-#include "match_host.h"
-
-namespace {
-struct MatchState : CallState {
-	DevBlock ab;  // device copies of host-resident descriptor matrices
-};
-MatchState g_match[kMaxDev];
-thread_local double t_match_dev = 0.0, t_match_wall = 0.0;
-thread_local int t_match_redo_rows = 0;  // rows re-scored exactly by the calling thread's last call (sift3d_debug_counters)
-}  // namespace
-
-namespace s3d { int match_redo_rows() { return t_match_redo_rows; } }
-
-// First use of the matcher on a device, ahead of time (muBruteMatcher's constructor, sift3d_create): the translation unit's code object is
-// loaded (HIP loads it at the first launch of one of its kernels: the first pass of a process took 2.48 ms instead of 1.70), the
-// stream and the events exist.  Never fails loudly: a device that cannot be prepared fails in sift3d_match.
-namespace s3d {
+// what the C-ABI (entry_match.hip) needs of this file besides match_rows_device: the sizes of its scratch for `rows` rows ...
+size_t match_cand_bytes(size_t rows) { return sizeof(int) * TOPK * rows; }
+size_t match_part_bytes(size_t rows) { return sizeof(Cand) * TOPK * kMaxSplits * rows; }
+// ... the row norms of both matrices for the guard (d_nmax[0]: A's maximum, [1]: B's; zeroed by the caller) ...
+void launch_row_norm2(const float *d_a, int n, float *d_an2, const float *d_b, int m, float *d_bn2, unsigned *d_nmax, hipStream_t st) {
+	if (n + m > 0) hipLaunchKernelGGL(k_row_norm2, dim3((n + 15) / 16 + (m + 15) / 16), dim3(256), 0, st, d_a, n, d_an2, d_b, m, d_bn2, d_nmax);
+}
+// ... and the code object loaded ahead of the first call (HIP loads it at the first launch of one of its kernels: the first pass of a
+// process took 2.48 ms instead of 1.70)
 void preload_match_kernels() { hipFuncAttributes a; (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_scores_topk2)); }
-}
-extern "C" int sift3d_match_warmup(int device) {
-	int rc = pick_device(device);
-	if (rc) return rc;
-	s3d::preload_match_kernels();
-	MatchState &S = g_match[device];
-	std::lock_guard<std::mutex> lock(S.mu);
-	return S.ensure(0, 0);  // (stream and events; the scratch is sized by the first call)
-}
 
-extern "C" int sift3d_match_times(double *device_seconds, double *wall_seconds) {
-	if (device_seconds) *device_seconds = t_match_dev;
-	if (wall_seconds) *wall_seconds = t_match_wall;
-	return SIFT3D_OK;
-}
-
-extern "C" int sift3d_match(const float *ref_desc, const float *ref_xyz, int n, const float *tar_desc, const float *tar_xyz, int m,
-                            double thresHold, int mode, int on_device, int device, int *gIdx, int *sIdx, float *gDist,
-                            float *sDist, float *pairs6, int *npairs, double *seconds) {
-	const auto wall0 = std::chrono::steady_clock::now();
-	if (n < 0 || m < 0 || mode < 1 || mode > 3 || (n > 0 && (!ref_desc || !ref_xyz)) || (m > 0 && (!tar_desc || !tar_xyz))) {
-		set_last_error("sift3d_match: bad argument");
-		return SIFT3D_ERR_ARG;
-	}
-	int rc = pick_device(device);
-	if (rc) return rc;
-	if (npairs) *npairs = 0;
-	if (seconds) *seconds = 0;
-	t_match_dev = t_match_wall = 0.0;
-
-	MatchState &S = g_match[device];
-	std::lock_guard<std::mutex> lock(S.mu);
-	const size_t nn = (size_t)std::max(n, 1), mm = (size_t)std::max(m, 1), big = std::max(nn, mm);
-	// device scratch layout (256-B aligned pieces): results [gd | sd | gi | si] of a pass (ONE D2H copy), then the working arrays
-	// pinned host: [results | redo count | coordinates (device inputs)]
-	Layout L, H;
-	const size_t o_res = L.take(4 * 4 * big), o_cand = L.take(4 * (size_t)TOPK * big), o_rows = L.take(4 * big), o_redo = L.take(4 * (big + 1));
-	const size_t o_s4 = L.take(4 * big), o_an2 = L.take(4 * nn), o_bn2 = L.take(4 * mm), o_nmax = L.take(2 * sizeof(unsigned));
-	const size_t o_part = L.take(sizeof(Cand) * TOPK * kMaxSplits * big);
-	const size_t h_res = H.take(4 * 4 * big), h_redo_at = H.take(sizeof(int)), h_xyz = H.take(on_device ? 4 * 3 * (nn + mm) : 0);
-	if ((rc = S.ensure(L.end, H.end))) return rc;
-	hipStream_t st = S.stream;
-	if (!on_device && (rc = S.ab.reserve(sizeof(float) * kDesc * (nn + mm), st))) return rc;
-
-	std::vector<float> gd(n, 0.f), sd(n, 0.f), gd2(m, 0.f), sd2(m, 0.f);
-	std::vector<int> gi(n, -1), si(n, -1), gi2(m, -1), si2(m, -1);
-	const float *rx = ref_xyz, *tx = tar_xyz;
-	int redo_rows = 0;
-	float *d_a, *d_b;
-	if (on_device) {
-		if ((rc = S.after_legacy_stream())) return rc;
-		d_a = const_cast<float *>(ref_desc); d_b = const_cast<float *>(tar_desc);
-		float *hx = reinterpret_cast<float *>(S.h.p + h_xyz), *hy = hx + 3 * nn;
-		if (n) S3D_HIP_ST(st, hipMemcpyAsync(hx, ref_xyz, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, st));
-		if (m) S3D_HIP_ST(st, hipMemcpyAsync(hy, tar_xyz, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, st));
-		rx = hx; tx = hy;  // read after the first synchronisation below
-	} else {
-		d_a = reinterpret_cast<float *>(S.ab.p); d_b = d_a + (size_t)kDesc * nn;
-		if (n) S3D_HIP_ST(st, hipMemcpyAsync(d_a, ref_desc, sizeof(float) * kDesc * n, hipMemcpyHostToDevice, st));
-		if (m) S3D_HIP_ST(st, hipMemcpyAsync(d_b, tar_desc, sizeof(float) * kDesc * m, hipMemcpyHostToDevice, st));
-	}
-	{
-		char *D = S.d.p;
-		float *d_gd = reinterpret_cast<float *>(D + o_res), *d_sd = d_gd + big;
-		int *d_gi = reinterpret_cast<int *>(d_sd + big), *d_si = d_gi + big;
-		int *d_cand = reinterpret_cast<int *>(D + o_cand), *d_rows = reinterpret_cast<int *>(D + o_rows), *d_redo = reinterpret_cast<int *>(D + o_redo);
-		float *d_s4 = reinterpret_cast<float *>(D + o_s4), *d_an2 = reinterpret_cast<float *>(D + o_an2), *d_bn2 = reinterpret_cast<float *>(D + o_bn2);
-		unsigned *d_nmax = reinterpret_cast<unsigned *>(D + o_nmax);
-		void *d_part = D + o_part;
-		float *h_gd = reinterpret_cast<float *>(S.h.p + h_res), *h_sd = h_gd + big;
-		int *h_gi = reinterpret_cast<int *>(h_sd + big), *h_si = h_gi + big;
-		int *h_redo = reinterpret_cast<int *>(S.h.p + h_redo_at);
-
-		S3D_HIP_ST(st, hipEventRecord(S.e0, st));
-		S3D_HIP_ST(st, hipMemsetAsync(d_nmax, 0, 2 * sizeof(unsigned), st));
-		if (n + m > 0) hipLaunchKernelGGL(k_row_norm2, dim3((n + 15) / 16 + (m + 15) / 16), dim3(256), 0, st, d_a, n, d_an2, d_b, m, d_bn2, d_nmax);
-		// matrices of 4 GB and more take the register-staged form (SIFT3D_HOOK_MATCH_NODMA forces it on any size, for the tests)
-		const bool small = !hook(SIFT3D_HOOK_MATCH_NODMA) && (size_t)std::max(n, m) * KD * sizeof(float) < ((size_t)1 << 32);
-		const MatchGuard g_fwd{d_s4, d_an2, d_nmax + 1, d_redo, small}, g_rev{d_s4, d_bn2, d_nmax, d_redo, small};
-
-		// ---- ref -> tar ----
-		if (n > 0 && m > 0) {
-			match_rows_device(d_a, nullptr, n, d_b, m, d_cand, d_part, d_gd, d_sd, d_gi, d_si, g_fwd, st);
-			S3D_HIP_ST(st, hipMemcpyAsync(h_gd, d_gd, 4 * 4 * big, hipMemcpyDeviceToHost, st));
-			S3D_HIP_ST(st, hipMemcpyAsync(h_redo, d_redo, sizeof(int), hipMemcpyDeviceToHost, st));
-			S3D_HIP_ST(st, hipEventRecord(S.e1, st));  // device time ends with the last device operation of the call (recorded again behind a reverse pass)
-			S3D_HIP_ST(st, hipStreamSynchronize(st));
-			memcpy(gd.data(), h_gd, sizeof(float) * n); memcpy(sd.data(), h_sd, sizeof(float) * n);
-			memcpy(gi.data(), h_gi, sizeof(int) * n); memcpy(si.data(), h_si, sizeof(int) * n);
-			redo_rows += h_redo[0];
-		} else {
-			S3D_HIP_ST(st, hipEventRecord(S.e1, st));
-			S3D_HIP_ST(st, hipStreamSynchronize(st));
-			// no targets: every dot loop is empty -> d = 2 - 2*FLT_MIN, idx -1
-			for (int i = 0; i < n; i++) { gd[i] = sd[i] = (float)(2 - 2 * (double)FLT_MIN); }
-		}
-		match_ratio_filter(gi, gd, sd, thresHold);
-
-		if (mode != 1) {
-			std::vector<int> cnt;
-			const std::vector<int> rows = match_mask_rows(gi, m, mode, cnt);
-			// ---- tar -> ref over the masked targets only (masked-out rows keep gIdx2 = -1) ----
-			if (!rows.empty() && n > 0) {
-				S3D_HIP_ST(st, hipMemcpyAsync(d_rows, rows.data(), sizeof(int) * rows.size(), hipMemcpyHostToDevice, st));
-				match_rows_device(d_b, d_rows, (int)rows.size(), d_a, n, d_cand, d_part, d_gd, d_sd, d_gi, d_si, g_rev, st);
-				S3D_HIP_ST(st, hipMemcpyAsync(h_gd, d_gd, 4 * 4 * big, hipMemcpyDeviceToHost, st));
-				S3D_HIP_ST(st, hipMemcpyAsync(h_redo, d_redo, sizeof(int), hipMemcpyDeviceToHost, st));
-				S3D_HIP_ST(st, hipEventRecord(S.e1, st));
-				S3D_HIP_ST(st, hipStreamSynchronize(st));
-				for (int j : rows) { gd2[j] = h_gd[j]; sd2[j] = h_sd[j]; gi2[j] = h_gi[j]; si2[j] = h_si[j]; }
-				redo_rows += h_redo[0];
-			}
-			match_ratio_filter(gi2, gd2, sd2, thresHold);
-			match_biject(gi, cnt, gi2);
-		}
-		if ((rc = S.finish(&t_match_dev))) return rc;
-		if (seconds) *seconds = t_match_dev;
-
-		const int np = match_to_cvec(gi, rx, tx, pairs6);
-		if (npairs) *npairs = np;
-		for (int i = 0; i < n; i++) {
-			if (gIdx) gIdx[i] = gi[i];
-			if (sIdx) sIdx[i] = si[i];
-			if (gDist) gDist[i] = gd[i];
-			if (sDist) sDist[i] = sd[i];
-		}
-	}
-	t_match_redo_rows = redo_rows;
-	t_match_wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
-	return SIFT3D_OK;
-}
+}  // namespace s3d

@@ -189,9 +189,6 @@ __device__ int finish_orientation(DevKp &kp, const float T6[6], const float w3[3
 
 // LDS tiles of the orientation window: the default radius (3 * 1.5 * scale <= 11.43 voxels) gives <= 25 voxels per side,
 // + 2 for the central differences; larger windows (non-default sigma) take the global-load path
-#ifndef S3D_ORI_UN
-#define S3D_ORI_UN 2  /* window voxels per lane and pass of the box scan (the list path runs one slot of 64 entries per pass) */
-#endif
 constexpr int kTileW = 28, kTileH = 27;
 constexpr int kTilePc = ((kTileW / 4) * kTileH + 63) / 64;  // 16-byte pieces of a tile plane per lane (3)
 typedef float f4o __attribute__((ext_vector_type(4), aligned(4)));  // 16-byte global piece at dword alignment
@@ -407,7 +404,7 @@ __global__ void __launch_bounds__(256) k_orient(DevKp *__restrict__ kps, int *__
 				const int dz = z - czi;
 				// box scan: kUn voxels per pass, all LDS reads (weights included) issued before the first use; inactive voxels read
 				// valid addresses and are masked
-				constexpr int kUn = S3D_ORI_UN;
+				constexpr int kUn = 2;  // window voxels per lane and pass of the box scan (the list path runs one slot of 64 entries per pass)
 #ifdef S3D_ODIAG
 				if (S3D_ODIAG & 1) { } else  // timing only: no window arithmetic
 #endif

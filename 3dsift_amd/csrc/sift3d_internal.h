@@ -306,15 +306,18 @@ void launch_finalize(const DevKp *kps, const unsigned *d_count, unsigned cap, in
 // ---- kernels_match.hip ---------------------------------------------------------------------
 // best / second-best dot of every listed row of A against all m rows of B (calMatches);
 // d_row_ids == nullptr means rows 0..nrows-1; outputs are indexed by the ORIGINAL row id.
-// d_part: scratch for the per-column-split partial top-4 lists, 8 B * 4 * 16 * nrows
+// d_part: scratch for the per-column-split partial top-K lists
 // near-tie guard scratch (see kernels_match.hip): s4[nrows], squared norms of the A rows (indexed by ORIGINAL row id), the maximal
 // squared norm of the B rows (bits), redo list [1 + nrows]
 struct MatchGuard {
 	float *s4; const float *a_n2; const unsigned *b_n2max; int *redo;
-	bool small_offsets = false;  // both descriptor matrices are smaller than 4 GB: k_scores_top4 may stage them by LDS-DMA (32-bit offsets)
+	bool small_offsets = false;  // both descriptor matrices are smaller than 4 GB: k_scores_topk2 (32-bit byte offsets, B by LDS-DMA); else k_scores_top4
 };
-int match_rows_device(const float *d_a, const int *d_row_ids, int nrows, const float *d_b, int m, int *d_cand /*nrows*4*/,
-                      void *d_part, float *d_gd, float *d_sd, int *d_gi, int *d_si, const MatchGuard &g, hipStream_t st);
+int match_rows_device(const float *d_a, const int *d_row_ids, int nrows, const float *d_b, int m, int *d_cand /*match_cand_bytes(nrows)*/,
+                      void *d_part /*match_part_bytes(nrows)*/, float *d_gd, float *d_sd, int *d_gi, int *d_si, const MatchGuard &g, hipStream_t st);
+size_t match_cand_bytes(size_t rows), match_part_bytes(size_t rows);
+// squared row norms of both matrices and their maxima (MatchGuard::a_n2 / b_n2max); d_nmax[0]: A's, [1]: B's, zeroed by the caller
+void launch_row_norm2(const float *d_a, int n, float *d_an2, const float *d_b, int m, float *d_bn2, unsigned *d_nmax, hipStream_t st);
 int match_redo_rows();  // rows the last sift3d_match re-scored exactly (near-tie guard)
 void launch_describe_overflow(const DevKp *kps, unsigned k, const LevelRef *d_levels, const WinLut *d_luts, const float *d_lutpool, float *d_desc,
                               hipStream_t st);  // one-keypoint entry: a window whose |g|^2 overflows (kernels_desc.hip)

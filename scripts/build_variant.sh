@@ -1,18 +1,17 @@
 #!/bin/bash
 # build a kernel-variant library for A/B timing:
 #   scripts/build_variant.sh NAME "-DS3D_...=..." [source=kernels_march]   ->  variants/libsift3d_hip_NAME.so
+# One source is rebuilt with the extra macros; every other object is the default build's.  Sources and flags are the Makefile's.
+# (the development switches -- -DS3D_DEV_SWITCHES: environment overrides of tuning values and hooks -- live in entry_test.hip)
 set -e
 cd "$(dirname "$0")/.."
 name=$1; extra=$2; src=${3:-kernels_march}
-# (the development switches -- -DS3D_DEV_SWITCHES: environment overrides of tuning values and hooks -- live in entry_test.hip)
-B=build/variants/$name   # under csrc/build: git-ignored and .gpurunignore'd (only the linked .so under variants/ travels)
-mkdir -p variants 3dsift_amd/csrc/$B
-cd 3dsift_amd/csrc
-for f in context tables entry_free entry_slab entry_test staging sharded kernels_pyramid kernels_march kernels_small kernels_detect kernels_orient kernels_desc kernels_match; do
-  [ "$f" != "$src" ] && [ -f build/$f.o ] && cp -u build/$f.o $B/$f.o
-done
-FL="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function -Wno-unused-value"
-{ [ "$src" = kernels_march ] || [ "$src" = kernels_small ] || [ "$src" = kernels_desc ] || [ "$src" = kernels_orient ]; } && FL="$FL -fno-slp-vectorize"
-/opt/rocm/bin/hipcc $extra $FL -c $src.hip -o $B/$src.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../variants/libsift3d_hip_$name.so $B/*.o
+csrc=3dsift_amd/csrc
+B=build/variants/$name   # under csrc/build: git-ignored
+[ -f $csrc/$src.hip ] || { echo "no such source: $csrc/$src.hip" >&2; exit 1; }
+make -C $csrc -j8   # the default objects, up to date and built without the extra macros
+mkdir -p variants $csrc/$B
+cp -u $csrc/build/*.o $csrc/$B/
+rm -f $csrc/$B/$src.o   # the only object make finds missing: the one built with EXTRA
+make -C $csrc -j8 BUILD=$B OUT="$PWD/variants/libsift3d_hip_$name.so" EXTRA="$extra"
 echo built variants/libsift3d_hip_$name.so

@@ -3,8 +3,7 @@ dealing regime, hostile descriptor values, chosen reverse-pass subsets -- agains
 bit, in modes 1, 2 and 3.  tests/test_match_cpu.py shows on the CPU what each case is (planted columns, margins, dealing regime).
 
 Every case runs under two forms of the score kernel: the default (k_scores_topk2) and, with the hook match_nodma, the
-register-staged k_scores_top4<false> that serves matrices of 4 GB and more.  The third form, k_scores_top4<true>, exists only in
--DS3D_MATCH_V2=0 builds and is not run here; it shares its selection with k_scores_top4<false>.
+register-staged k_scores_top4 that serves matrices of 4 GB and more.  There is no other form.
 
 On the planted cases the candidate selection must give the answer by itself (exact_rows == 0: the CPU module proves that the guard
 has no reason to fire); on the tie cases the guard must fire.  No comparison here has a tolerance."""
