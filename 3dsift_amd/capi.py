@@ -42,6 +42,8 @@ SYMBOLS = [
     "sift3d_default_ransac_options", "sift3d_fit_affine", "sift3d_fit_affine_local",
     # RANSAC rigid / similarity fits of the same pairs, and the rotation a fit holds
     "sift3d_fit_rigid", "sift3d_fit_rigid_local", "sift3d_fit_rotation",
+    # one rigid / similarity fit per body of a labelled specimen, and IC-GN with every POI limited to its own body
+    "sift3d_fit_rigid_bodies", "sift3d_labels_at_positions", "sift3d_icgn_init_from_body_fits", "sift3d_icgn_labelled",
     # guided matching: best and second best within a spatial gate around the position a fit predicts
     "sift3d_predict_positions", "sift3d_match_guided",
     # IC-GN displacement refinement (digital volume correlation)
@@ -302,6 +304,14 @@ def lib():
         L.sift3d_fit_rigid_local.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(RansacOptions),
                                              C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         L.sift3d_fit_rotation.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sift3d_fit_rigid_bodies.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(RansacOptions), C.c_int, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        L.sift3d_labels_at_positions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                 C.c_int]
+        L.sift3d_icgn_init_from_body_fits.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.sift3d_icgn_labelled.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_int, C.c_void_p, C.POINTER(IcgnOptions), C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         L.sift3d_predict_positions.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.sift3d_match_guided.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_double,
                                           C.c_int, C.c_int, C.c_int, _ip, _ip, _fp, _fp, _ip, _fp, _ip, C.POINTER(C.c_double)]
@@ -718,6 +728,29 @@ def fit_rigid_local(pairs, points, k=16, radius=0.0, model="rigid", device=0, **
     return _fit_local(pairs, points, k, radius, model, device, opts)
 
 
+def fit_rigid_bodies(pairs, pair_label, count, model="rigid", device=0, **opts):
+    """sift3d_fit_rigid_bodies: one RANSAC rigid or similarity fit per body.  pairs: (n, 6) float32 as for fit_rigid; pair_label: (n,)
+    int32, the body 1..count of each pair (labels_at_positions on pairs gives it; any other value: no body), a numpy array or, where
+    pairs is a device tensor, an int32 device tensor.  iterations 0 means 256.  Returns fit_rigid_local's fields with a leading body
+    axis (A, hyp: (count, 3, 4); status, counts, rms: (count,); row L - 1 is body L), mask (bool [n]: pair i is an inlier of its own
+    body's fit) and the device seconds."""
+    o = _ransac_options(opts)
+    pp, n, keep, on_dev = _rows(pairs, 6, "pairs")
+    lp, nl, lab = _table(pair_label, np.int32, 0, pairs)
+    if lab is None or nl != n:
+        raise ValueError("pair_label: one label per pair")
+    count = int(count)
+    out = np.zeros(max(count, 1), FIT_DTYPE)
+    mask = np.zeros(max(n, 1), np.uint8)
+    sec = C.c_double(0)
+    _check(lib().sift3d_fit_rigid_bodies(pp, n, lp, count, _model_code(model), C.byref(o), on_dev, int(device), _p(out), _p(mask),
+                                         C.byref(sec)))
+    d = _fit_dict(out, max(count, 0))
+    d["mask"] = mask[:n].astype(bool)
+    d["seconds"] = sec.value
+    return d
+
+
 def fit_rotation(fits):
     """sift3d_fit_rotation (needs no GPU): the rotation each fit holds, from the dict fit_rigid / fit_rigid_local returns (A (3, 4) or
     (m, 3, 4), status).  Returns quat ((m, 4): w, x, y, z with w >= 0), scale (m,) and angle_deg (m,) -- without the leading axis for
@@ -810,6 +843,23 @@ def icgn_init_from_fits(fits, points):
     return out[:len(A)].copy()
 
 
+def icgn_init_from_body_fits(fits, poi_label, points):
+    """sift3d_icgn_init_from_body_fits (needs no GPU): (m, 12) float64 initial parameters from the dict fit_rigid_bodies returns (A
+    (count, 3, 4), status), the body of each point (poi_label (m,) int32: labels_at's output) and the integer points ((m, 3) x, y, z):
+    row i is icgn_init_from_fits' for the fit of body poi_label[i]; a point of no body and a failed fit give a NaN row"""
+    A = np.asarray(fits["A"], np.float64).reshape(-1, 12)
+    f = np.zeros(max(len(A), 1), FIT_DTYPE)
+    f["A"][:len(A)] = A
+    f["status"][:len(A)] = np.asarray(fits["status"])
+    q = np.ascontiguousarray(points, np.int32).reshape(-1, 3)
+    lab = np.ascontiguousarray(poi_label, np.int32).reshape(-1)
+    if len(q) != len(lab):
+        raise ValueError("one label per point")
+    out = np.zeros((max(len(q), 1), 12), np.float64)
+    _check(lib().sift3d_icgn_init_from_body_fits(_p(f), len(A), _p(lab), _p(q), len(q), _p(out)))
+    return out[:len(q)].copy()
+
+
 def icgn(ref, tar, points, init=None, device=0, **opts):
     """sift3d_icgn: IC-GN refinement of the displacement at each point ((m, 3) int32 x, y, z of ref) from ref to tar.  ref / tar:
     (nz, ny, nx) float32 numpy arrays or contiguous float32 device tensors, both of the same kind; init: (m, 12) float64 or None (zero).
@@ -819,10 +869,11 @@ def icgn(ref, tar, points, init=None, device=0, **opts):
     return _icgn(1, "sift3d_icgn", ref, tar, points, init, device, opts, None)
 
 
-def _icgn(order, entry, ref, tar, points, init, device, opts, coefficients, mask=None, min_fraction=0.0):
-    """the call behind icgn, icgn_bspline, icgn_masked (order 1) and icgn2 (order 2); entry: the exported function's name;
-    coefficients None: the entry has no tar_is_coefficients argument; mask: icgn_masked's, with its min_fraction (the entry then takes
-    the mask behind the volumes, min_fraction behind the options and the active counts behind the records)"""
+def _icgn(order, entry, ref, tar, points, init, device, opts, coefficients, mask=None, min_fraction=0.0, labels=None):
+    """the call behind icgn, icgn_bspline, icgn_masked, icgn_labelled (order 1) and icgn2 (order 2); entry: the exported function's
+    name; coefficients None: the entry has no tar_is_coefficients argument; mask: icgn_masked's, with its min_fraction (the entry then
+    takes the mask behind the volumes, min_fraction behind the options and the active counts behind the records); labels:
+    icgn_labelled's, in the mask's place (the entry also takes the POI labels behind the active counts)"""
     width, dtype = {1: (12, ICGN_DTYPE), 2: (30, ICGN2_DTYPE)}[order]
     o = _icgn_options(opts)
     (rp, tp), (rdim, tdim), on_dev, keep = _volume_pair(ref, tar)
@@ -838,10 +889,16 @@ def _icgn(order, entry, ref, tar, points, init, device, opts, coefficients, mask
         active = np.zeros(max(m, 1), np.int32)
         mptr, mkeep = _mask(mask, keep[0].shape, on_dev)  # (mkeep: the array behind the pointer lives until the call returns)
         mp, mf, ap = (mptr,), (float(min_fraction),), (_p(active),)
+    if labels is not None:
+        active, poi_label = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.int32)
+        mptr, mkeep = _label_volume(labels, keep[0].shape, on_dev)
+        mp, mf, ap = (mptr,), (float(min_fraction),), (_p(active), _p(poi_label))
     _check(getattr(lib(), entry)(rp, *rdim, tp, *tdim, *mp, qp, m, ip, C.byref(o), *mf, *coef, on_dev, int(device), _p(out), *ap, C.byref(sec)))
     d = _fields(out, m, ("p", "zncc", "last_step", "iterations", "status"))
-    if mask is not None:
+    if mask is not None or labels is not None:
         d["active"] = active[:m].copy()
+    if labels is not None:
+        d["label"] = poi_label[:m].copy()
     e = d["p"].reshape(-1, 3, width // 3)
     d["displacement"] = e[:, :, 0].copy()
     d["gradient"] = e[:, :, 1:4].copy()
@@ -923,6 +980,29 @@ def icgn_masked(ref, tar, mask, points, init=None, min_fraction=0.0, tar_is_coef
     return _icgn(1, "sift3d_icgn_masked", ref, tar, points, init, device, opts, bool(tar_is_coefficients), mask, min_fraction)
 
 
+def _label_volume(a, shape, on_dev):
+    """(pointer, keep-alive) of an int32 label volume of `shape` that lies where the volumes lie"""
+    if on_dev:
+        if not _is_dev(a) or str(a.dtype) != "torch.int32" or not a.is_contiguous() or tuple(a.shape) != tuple(shape):
+            raise ValueError(f"labels: a contiguous int32 device tensor of shape {tuple(shape)} is needed")
+        return C.c_void_p(a.data_ptr()), a
+    if _is_dev(a):
+        raise ValueError("labels must lie where ref and tar lie")
+    h = np.ascontiguousarray(a, np.int32)
+    if h.shape != tuple(shape):
+        raise ValueError(f"labels: an int32 array of shape {tuple(shape)} is needed")
+    return _p(h), h
+
+
+def icgn_labelled(ref, tar, labels, points, init=None, min_fraction=0.0, tar_is_coefficients=False, device=0, **opts):
+    """sift3d_icgn_labelled: every point correlated over its own body, in one call: point i is treated as icgn_masked treats it under
+    the mask labels == labels[point i].  labels: an (nz, ny, nx) int32 numpy array (what mask_label returns; any positive int is a
+    label), or a contiguous int32 device tensor where ref and tar are device tensors.  A point on a voxel whose label is <= 0 returns
+    status 7.  Options and the other arguments: icgn_masked's.  Returns what icgn_masked returns and label (m,) int32, the label under
+    each point (0 outside ref)."""
+    return _icgn(1, "sift3d_icgn_labelled", ref, tar, points, init, device, opts, bool(tar_is_coefficients), None, min_fraction, labels)
+
+
 def mask_from_level(vol, level, device=0, with_seconds=False):
     """sift3d_mask_from_level: the uint8 mask icgn_masked takes, 1 where float64(vol) >= level (subset_quality's rule for `material`; a
     NaN voxel is 0), else 0.  vol: an (nz, ny, nx) float32 numpy array or a contiguous float32 device tensor; returns an array / a
@@ -998,6 +1078,35 @@ def labels_at(labels, points, device=0):
     out = np.zeros(max(m, 1), np.int32)
     _check(lib().sift3d_labels_at_points(lp, *tuple(lab.shape)[::-1], qp, m, _p(out), int(on_dev), int(device)))
     return out[:m].copy()
+
+
+def labels_at_positions(labels, xyz, device=0):
+    """sift3d_labels_at_positions: the label (n,) int32 at the voxel nearest to each fp32 position of xyz -- (n, 3) x, y, z, or the
+    (n, 6) pairs of the fits, whose reference positions are then used -- 0 for a position outside the volume (closer than half a
+    voxel to the first or last voxel counts as inside).  labels: an (nz, ny, nx) int32 numpy array, or a contiguous int32 device tensor
+    with xyz a float32 device tensor.  With host arrays it needs no GPU."""
+    on_dev = _is_dev(labels)
+    if on_dev != _is_dev(xyz):
+        raise ValueError("labels and xyz must both be numpy arrays or both device tensors")
+    if on_dev:
+        if str(labels.dtype) != "torch.int32" or not labels.is_contiguous() or labels.dim() != 3:
+            raise ValueError("labels: a contiguous int32 (nz, ny, nx) device tensor is needed")
+        if str(xyz.dtype) != "torch.float32" or not xyz.is_contiguous() or xyz.dim() != 2 or xyz.shape[1] not in (3, 6):
+            raise ValueError("xyz: a contiguous float32 (n, 3) or (n, 6) device tensor is needed")
+        lab, lp, pos, xp = labels, C.c_void_p(labels.data_ptr()), xyz, C.c_void_p(xyz.data_ptr())
+        device = labels.device.index if labels.device.index is not None else device
+    else:
+        lab = np.ascontiguousarray(labels, np.int32)
+        if lab.ndim != 3:
+            raise ValueError("labels: an (nz, ny, nx) volume is needed")
+        pos = np.ascontiguousarray(xyz, np.float32)
+        if pos.ndim != 2 or pos.shape[1] not in (3, 6):
+            raise ValueError("xyz: an (n, 3) or (n, 6) array is needed")
+        lp, xp = _p(lab), _p(pos)
+    n, stride = int(pos.shape[0]), int(pos.shape[1])
+    out = np.zeros(max(n, 1), np.int32)
+    _check(lib().sift3d_labels_at_positions(lp, *tuple(lab.shape)[::-1], xp, stride, n, _p(out), int(on_dev), int(device)))
+    return out[:n].copy()
 
 
 SEARCH_OPTIONS = ("subset_radius", "search_radius")

@@ -1,5 +1,5 @@
 // call_state.h -- what the one-shot entry points share (sift3d_match, sift3d_match_guided, sift3d_fit_affine[_local], sift3d_icgn[_bspline],
-// sift3d_icgn2, sift3d_icgn_masked, sift3d_mask_from_level, sift3d_zncc_search, sift3d_strain, sift3d_validate_displacements, sift3d_field_eval, sift3d_bspline_prefilter, sift3d_subset_quality): the per-device call state, its grow-only blocks, the
+// sift3d_icgn2, sift3d_icgn_masked, sift3d_icgn_labelled, sift3d_fit_rigid[_local], sift3d_fit_rigid_bodies, sift3d_mask_from_level, sift3d_zncc_search, sift3d_strain, sift3d_validate_displacements, sift3d_field_eval, sift3d_bspline_prefilter, sift3d_subset_quality): the per-device call state, its grow-only blocks, the
 // scratch layout, the staging of a volume pair, the device pick and the stream-aware check macro.  Every family keeps an array of
 // states of its own (its own stream and mutex per device).
 #pragma once

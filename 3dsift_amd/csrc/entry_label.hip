@@ -1,4 +1,4 @@
-// entry_label.hip -- C-ABI of the connected-component labels (include/sift3d_hip.h: sift3d_mask_label, sift3d_labels_at_points;
+// entry_label.hip -- C-ABI of the connected-component labels (include/sift3d_hip.h: sift3d_mask_label, sift3d_labels_at_points, sift3d_labels_at_positions;
 // include/sift3d_hip_test.h: sift3d_test_label_tile).  No reference counterpart.  Kernels: kernels_label.hip.  One-shot entries: call
 // state, timing and the order of the checks as DESIGN 4.10 (call_state.h).
 #include "call_state.h"
@@ -90,6 +90,36 @@ extern "C" int sift3d_labels_at_points(const int *labels, int nx, int ny, int nz
 	launch_labels_at(labels, nx, ny, nz, points3, m, d_out, st);
 	S3D_HIP_ST(st, hipGetLastError());
 	S3D_HIP_ST(st, hipMemcpyAsync(poi_label, d_out, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, st));
+	S3D_HIP_ST(st, hipEventRecord(S.e1, st));
+	return S.finish(nullptr);
+}
+
+extern "C" int sift3d_labels_at_positions(const int *labels, int nx, int ny, int nz, const float *xyz, int stride, int n, int *out_label,
+                                          int on_device, int device) {
+	if (!labels || !dims_fit_int(nx, ny, nz) || n < 0 || stride < 3 || (n > 0 && (!xyz || !out_label))) {
+		set_last_error("sift3d_labels_at_positions: bad argument");
+		return SIFT3D_ERR_ARG;
+	}
+	if (!on_device) {
+		for (int i = 0; i < n; i++) {
+			const float *p = xyz + (size_t)i * stride;
+			out_label[i] = label_at_position(labels, nx, ny, nz, p[0], p[1], p[2]);
+		}
+		return SIFT3D_OK;
+	}
+	int rc = pick_device(device);
+	if (rc) return rc;
+	if (n == 0) return SIFT3D_OK;
+	CallState &S = g_labels_at[device];
+	std::lock_guard<std::mutex> lock(S.mu);
+	if ((rc = S.ensure(sizeof(int) * (size_t)n, 0))) return rc;
+	hipStream_t st = S.stream;
+	if ((rc = S.after_legacy_stream())) return rc;
+	int *d_out = reinterpret_cast<int *>(S.d.p);
+	S3D_HIP_ST(st, hipEventRecord(S.e0, st));
+	launch_labels_at_positions(labels, nx, ny, nz, xyz, stride, n, d_out, st);
+	S3D_HIP_ST(st, hipGetLastError());
+	S3D_HIP_ST(st, hipMemcpyAsync(out_label, d_out, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
 	S3D_HIP_ST(st, hipEventRecord(S.e1, st));
 	return S.finish(nullptr);
 }

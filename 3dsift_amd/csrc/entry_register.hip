@@ -1,11 +1,13 @@
 // entry_register.hip -- C-ABI of the RANSAC fits (include/sift3d_hip.h: sift3d_fit_affine[_local], sift3d_fit_rigid[_local],
-// sift3d_fit_rotation).  The affine and the rigid / similarity entries share one body each: they differ in the kernels launched
+// sift3d_fit_rigid_bodies, sift3d_fit_rotation).  The affine and the rigid / similarity entries share one body each: they differ in the kernels launched
 // and in the candidates a fit needs (4 and 3).
 // No reference counterpart.  Call state, scratch layout, timing and the order of the checks: DESIGN 4.10 (call_state.h).
 #include "call_state.h"
 
 #include <math.h>
 #include <string.h>
+
+#include <vector>
 
 using namespace s3d;
 
@@ -179,6 +181,77 @@ extern "C" int sift3d_fit_rigid_local(const float *pairs6, int n, const float *p
 	}
 	return fit_local("sift3d_fit_rigid_local: bad argument", model, pairs6, n, points3, m, k, radius, o, on_device, device, out,
 	                 neighbours, seconds);
+}
+
+// One fit per body.  The pairs are segmented by label on the host: a stable counting sort (two passes over the labels, which are
+// copied down first when they lie on the device) gives the list of pair indices grouped by body in ascending order, whatever the
+// size of a body -- one body may hold every pair -- and the list and the count + 1 segment bounds go up in one copy each.
+extern "C" int sift3d_fit_rigid_bodies(const float *pairs6, int n, const int *pair_label, int count, int model, const sift3d_ransac_options *o,
+                                       int on_device, int device, sift3d_affine_fit *out, unsigned char *inlier_mask, double *seconds) {
+	int H, refine;
+	double tau2, min_det;
+	uint32_t s;
+	if (n < 0 || count < 0 || (model != 0 && model != 1) || (n > 0 && (!pairs6 || !pair_label)) || (count > 0 && !out) ||
+	    !take_options(o, true, H, tau2, min_det, refine, s)) {
+		set_last_error("sift3d_fit_rigid_bodies: bad argument");
+		return SIFT3D_ERR_ARG;
+	}
+	if (seconds) *seconds = 0;
+	int rc = pick_device(device);
+	if (rc) return rc;
+	if (n == 0 || count == 0) {  // every body is empty: status 1 is a result, nothing to run
+		for (int b = 0; b < count; b++) empty_fit(out + b, 1, 0);
+		if (inlier_mask && n) memset(inlier_mask, 0, (size_t)n);
+		return SIFT3D_OK;
+	}
+	CallState &S = g_ransac[device];
+	std::lock_guard<std::mutex> lock(S.mu);
+	// device scratch: [fits count | mask n | list n | bounds count + 1 | pairs (host inputs)]; pinned host: the first four pieces at the
+	// same offsets, then the labels (device inputs)
+	const size_t fit_bytes = sizeof(sift3d_affine_fit) * (size_t)count, list_bytes = sizeof(int) * (size_t)n;
+	const size_t off_bytes = sizeof(int) * ((size_t)count + 1);
+	Layout L;
+	L.take(fit_bytes);
+	const size_t o_mask = L.take((size_t)n), o_list = L.take(list_bytes), o_off = L.take(off_bytes);
+	const size_t o_last = L.take(on_device ? 0 : sizeof(float) * 6 * (size_t)n);  // device: the pairs; pinned: the labels
+	if ((rc = S.ensure(L.end, o_last + (on_device ? list_bytes : 0)))) return rc;
+	hipStream_t st = S.stream;
+	char *D = S.d.p, *P = S.h.p;
+	const float *d_pairs = pairs6;
+	const int *lab = pair_label;
+	if (on_device) {
+		if ((rc = S.after_legacy_stream())) return rc;
+		S3D_HIP_ST(st, hipMemcpyAsync(P + o_last, pair_label, list_bytes, hipMemcpyDeviceToHost, st));
+		S3D_HIP_ST(st, hipStreamSynchronize(st));
+		lab = reinterpret_cast<const int *>(P + o_last);
+	} else {
+		d_pairs = reinterpret_cast<float *>(D + o_last);
+		S3D_HIP_ST(st, hipMemcpyAsync(D + o_last, pairs6, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice, st));
+	}
+	int *list = reinterpret_cast<int *>(P + o_list), *off = reinterpret_cast<int *>(P + o_off);
+	memset(off, 0, off_bytes);
+	for (int i = 0; i < n; i++)
+		if (lab[i] >= 1 && lab[i] <= count) off[lab[i]]++;
+	std::vector<int> at((size_t)count);
+	for (int b = 1; b <= count; b++) {
+		at[b - 1] = off[b - 1];
+		off[b] += off[b - 1];
+	}
+	for (int i = 0; i < n; i++)
+		if (lab[i] >= 1 && lab[i] <= count) list[at[lab[i] - 1]++] = i;
+	if (off[count]) S3D_HIP_ST(st, hipMemcpyAsync(D + o_list, list, sizeof(int) * (size_t)off[count], hipMemcpyHostToDevice, st));
+	S3D_HIP_ST(st, hipMemcpyAsync(D + o_off, off, off_bytes, hipMemcpyHostToDevice, st));
+	S3D_HIP_ST(st, hipEventRecord(S.e0, st));
+	S3D_HIP_ST(st, hipMemsetAsync(D + o_mask, 0, (size_t)n, st));
+	launch_rigid_bodies(d_pairs, reinterpret_cast<int *>(D + o_list), reinterpret_cast<int *>(D + o_off), count, H, s, tau2, min_det, model, refine,
+	                    reinterpret_cast<sift3d_affine_fit *>(D), reinterpret_cast<unsigned char *>(D + o_mask), st);
+	S3D_HIP_ST(st, hipGetLastError());
+	S3D_HIP_ST(st, hipMemcpyAsync(P, D, inlier_mask ? o_mask + n : fit_bytes, hipMemcpyDeviceToHost, st));
+	S3D_HIP_ST(st, hipEventRecord(S.e1, st));
+	if ((rc = S.finish(seconds))) return rc;
+	memcpy(out, P, fit_bytes);
+	if (inlier_mask) memcpy(inlier_mask, P + o_mask, (size_t)n);
+	return SIFT3D_OK;
 }
 
 extern "C" int sift3d_fit_rotation(const sift3d_affine_fit *fits, int m, double *quat4, double *scale, double *angle_deg) {

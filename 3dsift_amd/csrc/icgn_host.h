@@ -44,15 +44,23 @@ inline bool icgn_args_ok(const void *ref, int rnx, int rny, int rnz, const void 
 // sift3d_icgn_masked's own refusals, beside icgn_args_ok's with sift3d_icgn2's rules (max_interpolation 2, bspline 0)
 inline bool icgn_mask_args_ok(const void *mask, float min_fraction) { return mask && min_fraction >= 0.f && min_fraction <= 1.f; }  // (a NaN fails both)
 
+// sift3d_icgn_labelled's: the masked call's with the labels in the mask's place, and R's voxels must be counted by an int
+inline bool icgn_label_args_ok(const void *labels, float min_fraction, int rnx, int rny, int rnz) {
+	return icgn_mask_args_ok(labels, min_fraction) && (size_t)rnx * (size_t)rny <= (((size_t)1 << 31) - 1) / (size_t)rnz;
+}
+
 // device scratch of a call: [results m | state m | (host inputs) ref | tar | points | init | (prefilter) coefficients | the y pass's
 // output | (masked) the active bytes of R's voxels | the active counts m | (masked, host inputs) mask]; the pinned host block holds
 // the results and, 256-aligned behind them, the active counts.  o_opt (PairPlan) is the init table's offset.  The pieces of a masked
-// call come last: an unmasked call's layout does not know of them.
+// call come last: an unmasked call's layout does not know of them.  A labelled call (sift3d_icgn_labelled) appends its own behind
+// those: [the interior labels of R's voxels, 4 bytes each | the active counts m | the POI labels m | (host inputs) labels]; it has no
+// masked piece, and neither of the other layouts moves.  Its pinned block: the results, the counts, the POI labels, each 256-aligned.
 struct IcgnLayout : PairPlan {
 	size_t res_bytes, o_state, o_coef, o_tmp, o_act, o_count, o_mask, b_mask, count_bytes, end;
+	size_t o_interior, o_plabel, o_labels, b_labels;
 };
 inline IcgnLayout icgn_layout(int m, size_t nr, size_t nt, bool on_device, bool has_init, bool filter, size_t state_bytes, size_t result_bytes,
-                              int parameters, bool masked = false) {
+                              int parameters, bool masked = false, bool labelled = false) {
 	IcgnLayout g;
 	Layout L;
 	g.res_bytes = result_bytes * (size_t)m;
@@ -66,6 +74,14 @@ inline IcgnLayout icgn_layout(int m, size_t nr, size_t nt, bool on_device, bool 
 	g.o_act = L.take(masked ? nr : 0);
 	g.o_count = L.take(g.count_bytes);
 	g.o_mask = L.take(g.b_mask);
+	g.o_interior = L.take(labelled ? sizeof(int) * nr : 0);
+	if (labelled) {
+		g.count_bytes = sizeof(int) * (size_t)m;
+		g.o_count = L.take(g.count_bytes);
+	}
+	g.o_plabel = L.take(labelled ? sizeof(int) * (size_t)m : 0);
+	g.b_labels = labelled && !on_device ? sizeof(int) * nr : 0;
+	g.o_labels = L.take(g.b_labels);
 	g.end = L.end;
 	return g;
 }

@@ -118,9 +118,17 @@ __device__ inline float sample_shifted(const IcgnVol &T, const int ci[3], const 
 // MASKED (sift3d_icgn_masked): Aq is the active byte of the voxel q (the volume k_mask_active wrote, in R's layout); an inactive voxel
 // is skipped -- R is not read there -- while the walk advances as it does unmasked, and the mean is that of the *n active voxels: their
 // count, an integer sum in the wave (through red[][1], exact in fp64).  n = 0 returns NaN.  The unmasked form reads neither argument.
-template <int K, bool MASKED = false>
-__device__ __forceinline__ double subset_mean(const IcgnVol &R, const int q[3], int r, double (*red)[K], const unsigned char *Aq = nullptr,
-                                              int *n = nullptr) {
+// Labelled (sift3d_icgn_labelled): Aq points into the int volume of interior labels and a voxel is active where its entry equals
+// `want`, the POI's own label (> 0, uniform over the workgroup); voxel_on states both rules.
+template <class A>
+__device__ __forceinline__ bool voxel_on(A a, A want) {
+	if constexpr (sizeof(A) == 1) return a != 0;
+	else return a == want;
+}
+
+template <int K, bool MASKED = false, class A = unsigned char>
+__device__ __forceinline__ double subset_mean(const IcgnVol &R, const int q[3], int r, double (*red)[K], const A *Aq = nullptr,
+                                              int *n = nullptr, A want = 0) {
 	const int D = 2 * r + 1, N = D * D * D;
 	const SubsetWalk W(r);
 	const float *Rq = R.d + vidx(R, q[0], q[1], q[2]);
@@ -133,7 +141,7 @@ __device__ __forceinline__ double subset_mean(const IcgnVol &R, const int q[3], 
 		W.start(tid, dx, dy, dz);
 		for (int i = tid; i < N; i += kThreads) {
 			if constexpr (MASKED) {
-				if (Aq[dz * sz + dy * sy + dx]) {
+				if (voxel_on(Aq[dz * sz + dy * sy + dx], want)) {
 					s += (double)Rq[dz * sz + dy * sy + dx];
 					cnt++;
 				}

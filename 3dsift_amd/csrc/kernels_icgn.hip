@@ -18,9 +18,15 @@
 // active (one byte load per voxel and pass; a wave whose voxels are all inactive branches over the body), the walk is the unmasked
 // one, and the active count n of a POI -- an int per POI beside the state records, IcgnState keeps its size -- takes N's place.  The
 // unmasked instantiations are the kernels as they were: every masked piece stands under `if constexpr`.
+// sift3d_icgn_labelled runs the masked instantiations once more with an IcgnLabels in the IcgnMask's place: the volume read per
+// voxel and pass is the int volume of interior labels (k_label_interior) and the test is `== L_i`, the label under the POI's own
+// voxel, which the prepare kernel reads once, leaves beside the active counts and the iterate kernel reads back.  The kind of the
+// last kernel argument tells the two apart, so the byte-masked instantiations keep their names and their code.
 #include "icgn_subset.h"
 
 #include <math.h>
+
+#include <type_traits>
 
 namespace s3d {
 namespace {
@@ -92,13 +98,21 @@ __device__ inline int h_piece(int i, int j) {  // H(i, j) -> index into the 60 H
 // signature and kernel-argument segment are what they were.
 __device__ inline IcgnMask mask_of() { return IcgnMask{nullptr, nullptr, 0.f}; }
 __device__ inline IcgnMask mask_of(IcgnMask m) { return m; }
+__device__ inline IcgnLabels mask_of(IcgnLabels m) { return m; }
+// the volume a masked form tests per voxel: the active bytes, or the interior labels
+__device__ inline const unsigned char *active_of(const IcgnMask &m) { return m.act; }
+__device__ inline const int *active_of(const IcgnLabels &m) { return m.interior; }
+template <class... MASK>
+constexpr bool kLabelled = (std::is_same<MASK, IcgnLabels>::value || ...);
 
 template <bool MASKED, class... MASK>
 __global__ __launch_bounds__(kThreads) void k_icgn_prepare(IcgnVol R, IcgnVol T, const int *__restrict__ pts, const double *__restrict__ init,
                                                           int r, int cubic, IcgnState *__restrict__ state, sift3d_icgn_result *__restrict__ out,
                                                           MASK... mask) {
 	static_assert(sizeof...(MASK) == (MASKED ? 1 : 0), "the masked instantiation takes the IcgnMask");
-	const IcgnMask M = mask_of(mask...);
+	constexpr bool LABELLED = kLabelled<MASK...>;
+	const auto M = mask_of(mask...);
+	typedef typename std::remove_cv<typename std::remove_pointer<decltype(active_of(M))>::type>::type Act;  // a byte, or an int label
 	__shared__ double red[kWaves][kPrepSums];
 	__shared__ double A[12][13];
 	__shared__ int s_fail;
@@ -112,6 +126,11 @@ __global__ __launch_bounds__(kThreads) void k_icgn_prepare(IcgnVol R, IcgnVol T,
 		finite = finite && isfinite(p[k]);
 	}
 	IcgnState *S = state + poi;
+	Act want = 0;  // labelled: L_i, the label under q (0 outside R); uniform, one scalar load
+	if constexpr (LABELLED) {
+		if (q[0] >= 0 && q[0] < R.nx && q[1] >= 0 && q[1] < R.ny && q[2] >= 0 && q[2] < R.nz) want = M.labels[vidx(R, q[0], q[1], q[2])];
+		if (tid == 0) M.label[poi] = want;
+	}
 	int status = kRun;
 	if (!finite) status = 5;
 	else if (q[0] - r - 1 < 0 || q[0] + r + 1 > R.nx - 1 || q[1] - r - 1 < 0 || q[1] + r + 1 > R.ny - 1 || q[2] - r - 1 < 0 ||
@@ -130,9 +149,19 @@ __global__ __launch_bounds__(kThreads) void k_icgn_prepare(IcgnVol R, IcgnVol T,
 	const float *Rq = R.d + vidx(R, q[0], q[1], q[2]);
 	const int sy = R.nx, sz = R.nx * R.ny;
 	// pass 1: Rm (masked: and the active count, status 7)
-	const unsigned char *Aq = MASKED ? M.act + vidx(R, q[0], q[1], q[2]) : nullptr;
+	const Act *Aq = MASKED ? active_of(M) + vidx(R, q[0], q[1], q[2]) : nullptr;
 	int n = N;
-	const double Rm = subset_mean<kPrepSums, MASKED>(R, q, r, red, Aq, &n);
+	if constexpr (LABELLED) {
+		if (want <= 0) {  // uniform: no body under q, n = 0 and no voxel is read
+			if (tid == 0) {
+				M.n[poi] = 0;
+				S->status = 7;
+				write_result(out + poi, p, 0.0, 0.0, 0, 7);
+			}
+			return;
+		}
+	}
+	const double Rm = subset_mean<kPrepSums, MASKED, Act>(R, q, r, red, Aq, &n, want);
 	if constexpr (MASKED) {
 		const bool few = n == 0 || (double)n < (double)M.min_fraction * (double)N;  // uniform: every thread holds the same n
 		if (tid == 0) {
@@ -154,7 +183,7 @@ __global__ __launch_bounds__(kThreads) void k_icgn_prepare(IcgnVol R, IcgnVol T,
 		W.start(tid, dx, dy, dz);
 		for (int i = tid; i < N; i += kThreads) {
 			bool on = true;
-			if constexpr (MASKED) on = Aq[dz * sz + dy * sy + dx] != 0;
+			if constexpr (MASKED) on = voxel_on(Aq[dz * sz + dy * sy + dx], want);
 			if (on) {
 				const float *c = Rq + (dz * sz + dy * sy + dx);
 				const float gxf = 0.5f * (c[1] - c[-1]), gyf = 0.5f * (c[sy] - c[-sy]), gzf = 0.5f * (c[sz] - c[-sz]);
@@ -247,10 +276,11 @@ __global__ __launch_bounds__(kThreads) void k_icgn_prepare(IcgnVol R, IcgnVol T,
 // the taps leaves the interpolation's rounding.  Tc is one voxel: an outlier there (a hot voxel |Tc - Tm| >> dT) makes every T' large
 // and costs the fp32 sums that many ulps, as a T far brighter than R did under the shift by Rm; a mean of T would need a pass of its
 // own.  Returns Tc - (float)Rm, which turns the sums into those of T - Rm.
-// MASKED: Aq is the active byte of the voxel q; the body is skipped for an inactive voxel (neither R nor T is read there).
-template <int KIND, bool MASKED>
+// MASKED: Aq is the active byte of the voxel q; the body is skipped for an inactive voxel (neither R nor T is read there).  Labelled:
+// Aq is the interior label of the voxel q and `want` the POI's label (voxel_on, icgn_subset.h).
+template <int KIND, bool MASKED, class Act>
 __device__ inline double subset_pass(const IcgnVol &R, const IcgnVol &T, const int q[3], int r, float rmf, const double p[12],
-                                   double (*red)[kIterSums], double sums[kIterSums], const unsigned char *Aq) {
+                                   double (*red)[kIterSums], double sums[kIterSums], const Act *Aq, Act want) {
 	constexpr bool CUBIC = KIND != kLinear;  // 64 taps
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	const int D = 2 * r + 1, N = D * D * D;
@@ -282,7 +312,7 @@ __device__ inline double subset_pass(const IcgnVol &R, const IcgnVol &T, const i
 #pragma unroll 1
 	for (int i = tid; i < N; i += kThreads) {
 		bool on = true;
-		if constexpr (MASKED) on = Aq[dz * sz + dy * sy + dx] != 0;
+		if constexpr (MASKED) on = voxel_on(Aq[dz * sz + dy * sy + dx], want);
 		if (on) {
 			const float fx = (float)dx, fy = (float)dy, fz = (float)dz;
 			float o[3];
@@ -327,7 +357,8 @@ __global__ __launch_bounds__(kThreads) void k_icgn_iterate(IcgnVol R, IcgnVol T,
                                                           int r, int max_it, double tol, const IcgnState *__restrict__ state,
                                                           sift3d_icgn_result *__restrict__ out, MASK... mask) {
 	static_assert(sizeof...(MASK) == (MASKED ? 1 : 0), "the masked instantiation takes the IcgnMask");
-	const IcgnMask M = mask_of(mask...);
+	const auto M = mask_of(mask...);
+	typedef typename std::remove_cv<typename std::remove_pointer<decltype(active_of(M))>::type>::type Act;
 	__shared__ double red[2][kWaves][kIterSums];  // by pass parity: one barrier per pass
 	__shared__ double cst[168];                   // H^-1, c1, c2: read in the solve only (not held in registers across the passes)
 	const int poi = blockIdx.x;
@@ -341,14 +372,16 @@ __global__ __launch_bounds__(kThreads) void k_icgn_iterate(IcgnVol R, IcgnVol T,
 	for (int k = 0; k < 12; k++) p[k] = init ? init[12 * (size_t)poi + k] : 0.0;
 	// (masked: N is the POI's active count, which the prepare kernel left beside the state records)
 	const double N = MASKED ? (double)M.n[poi] : (double)((2 * r + 1) * (2 * r + 1) * (2 * r + 1)), dr = S->dr, sr = S->sr, r2 = (double)r * (double)r;
-	const unsigned char *Aq = MASKED ? M.act + vidx(R, q[0], q[1], q[2]) : nullptr;
+	const Act *Aq = MASKED ? active_of(M) + vidx(R, q[0], q[1], q[2]) : nullptr;
+	Act want = 0;
+	if constexpr (kLabelled<MASK...>) want = M.label[poi];  // (> 0: the prepare kernel ended every other POI)
 	const float rmf = S->rm;
 	int it = 0, status = kRun;
 	double last = 0.0;
 	bool done = false;
 	for (int pass = 0;; pass++) {
 		double s[kIterSums];
-		const double sh = subset_pass<KIND, MASKED>(R, T, q, r, rmf, p, red[pass & 1], s, Aq);
+		const double sh = subset_pass<KIND, MASKED, Act>(R, T, q, r, rmf, p, red[pass & 1], s, Aq, want);
 		// s: 0 sum T', 1 sum T'^2, 2..13 sum SD T', 14 sum R'T'
 		const double tm = s[0] / N;
 		const double dt2 = s[1] - s[0] * tm;
@@ -450,6 +483,14 @@ void launch_icgn_masked(IcgnVol R, IcgnVol T, const int *d_pts, int m, const dou
 	IcgnState *S = static_cast<IcgnState *>(d_state);
 	hipLaunchKernelGGL((k_icgn_prepare<true, IcgnMask>), dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, kind != kLinear, S, d_out, M);
 	hipLaunchKernelGGL(by_kind(kind, k_icgn_iterate<kKeys, true, IcgnMask>, k_icgn_iterate<kLinear, true, IcgnMask>, k_icgn_iterate<kBspline, true, IcgnMask>), dim3(m),
+	                   dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out, M);
+}
+
+void launch_icgn_labelled(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_init, int r, int max_it, double tol, int kind,
+                          void *d_state, sift3d_icgn_result *d_out, IcgnLabels M, hipStream_t st) {
+	IcgnState *S = static_cast<IcgnState *>(d_state);
+	hipLaunchKernelGGL((k_icgn_prepare<true, IcgnLabels>), dim3(m), dim3(kThreads), 0, st, R, T, d_pts, d_init, r, kind != kLinear, S, d_out, M);
+	hipLaunchKernelGGL(by_kind(kind, k_icgn_iterate<kKeys, true, IcgnLabels>, k_icgn_iterate<kLinear, true, IcgnLabels>, k_icgn_iterate<kBspline, true, IcgnLabels>), dim3(m),
 	                   dim3(kThreads), 0, st, R, T, d_pts, d_init, r, max_it, tol, S, d_out, M);
 }
 

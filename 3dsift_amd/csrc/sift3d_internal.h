@@ -341,6 +341,26 @@ void launch_rigid_global(const float *d_pairs, int n, int H, uint32_t s, double 
 void launch_rigid_local(const float *d_pairs, int n, const float *d_pts, int m, int k, float r2, int H, uint32_t s, double tau2, double min_det,
                         int model, int refine, sift3d_affine_fit *d_out, int *d_nbrs, hipStream_t st);
 
+// ---- kernels_bodyfit.hip: one rigid / similarity fit per body (sift3d_fit_rigid_bodies, sift3d_labels_at_positions) ---------------
+// d_list: the pair indices grouped by body, ascending inside a body; d_off: count + 1 ints, body L's segment is [off[L-1], off[L]);
+// d_out: count records; d_mask: n bytes, zero on entry (only an inlier test's result is written)
+void launch_rigid_bodies(const float *d_pairs, const int *d_list, const int *d_off, int count, int H, uint32_t s, double tau2, double min_det,
+                         int model, int refine, sift3d_affine_fit *d_out, unsigned char *d_mask, hipStream_t st);
+// the label at the voxel nearest to the fp32 position (x, y, z), 0 outside the volume: per axis the position is inside iff
+// -0.5 <= (double)x < n - 0.5 (a NaN or an infinity fails it), tested before the conversion i = floor((double)x + 0.5)
+__host__ __device__ inline int label_at_position(const int *labels, int nx, int ny, int nz, float x, float y, float z) {
+	const double p[3] = {(double)x, (double)y, (double)z};
+	const int n[3] = {nx, ny, nz};
+	long long v[3];
+	for (int a = 0; a < 3; a++) {
+		if (!(-0.5 <= p[a] && p[a] < (double)n[a] - 0.5)) return 0;
+		v[a] = (long long)floor(p[a] + 0.5);
+	}
+	return labels[((size_t)v[2] * ny + (size_t)v[1]) * nx + (size_t)v[0]];
+}
+// d_out[i] = label_at_position of the three floats at d_xyz + i * stride
+void launch_labels_at_positions(const int *d_labels, int nx, int ny, int nz, const float *d_xyz, int stride, int n, int *d_out, hipStream_t st);
+
 // ---- kernels_icgn.hip: IC-GN displacement refinement (sift3d_icgn, include/sift3d_hip.h) ---------------------------------------
 // a volume on the device: fp32 [z][y][x]
 struct IcgnVol {
@@ -360,13 +380,29 @@ struct IcgnMask {
 	int *n;
 	float min_fraction;
 };
+// what the labelled instantiations read in its place (sift3d_icgn_labelled): interior, an int per voxel of R (launch_label_interior's
+// output: the voxel's label where it and its six face neighbours agree on a positive label, else 0); labels, the caller's volume,
+// read at the POI's voxel alone; n as above; label, m ints: the POI's label L_i (0 outside R), written by the prepare kernel, read
+// by the iterate kernel and returned as `poi_label`.  A voxel is active for POI i iff interior == L_i > 0.
+struct IcgnLabels {
+	const int *interior;
+	const int *labels;
+	int *n;
+	int *label;
+	float min_fraction;
+};
 // launch_icgn limited to the active voxels
 void launch_icgn_masked(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_init, int r, int max_it, double tol, int kind, void *d_state,
                         sift3d_icgn_result *d_out, IcgnMask M, hipStream_t st);
+// launch_icgn with every POI limited to the interior voxels of its own label
+void launch_icgn_labelled(IcgnVol R, IcgnVol T, const int *d_pts, int m, const double *d_init, int r, int max_it, double tol, int kind,
+                          void *d_state, sift3d_icgn_result *d_out, IcgnLabels M, hipStream_t st);
 
 // ---- kernels_mask.hip: the byte volumes of the masked IC-GN (sift3d_icgn_masked, sift3d_mask_from_level) --------------------------
 // d_act[i] = 1 where voxel i and its six face neighbours lie in the volume and have a non-zero byte in d_mask, else 0; d_act != d_mask
 void launch_mask_active(const unsigned char *d_mask, int nx, int ny, int nz, unsigned char *d_act, hipStream_t st);
+// d_interior[i] = d_labels[i] where voxel i and its six face neighbours lie in the volume and carry the same positive label, else 0
+void launch_label_interior(const int *d_labels, int nx, int ny, int nz, int *d_interior, hipStream_t st);
 // d_mask[i] = 1 where (double)d_vol[i] >= level, else 0
 void launch_mask_threshold(const float *d_vol, size_t n, double level, unsigned char *d_mask, hipStream_t st);
 

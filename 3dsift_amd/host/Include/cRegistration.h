@@ -348,6 +348,27 @@ SIFT_LIBRARY_API bool LabelMask(const unsigned char *mask, int nx, int ny, int n
                                 double *seconds = nullptr);
 // the label at each point (0 for a point outside the volume); host only.  Empty when a coordinate is not integral
 SIFT_LIBRARY_API std::vector<int> LabelsAt(const int *labels, int nx, int ny, int nz, const std::vector<Cvec> &points);
+// One rigid (or similarity) fit per body of a labelled specimen (include/sift3d_hip.h, sift3d_fit_rigid_bodies): every matched pair is
+// given the label at the voxel nearest to its reference position (0 outside the volume) and body L = 1..count is fitted from its own
+// pairs alone; the result holds `count` fits, body L at index L - 1 (status 1: fewer than 3 pairs).  pairLabels (may be null): resized
+// to one label per pair; inlierMask (may be null): resized to one entry per pair, 1 where the pair is an inlier of its own body's fit.
+// opts.iterations 0 means 256.  Empty when the call failed (message on stderr).
+SIFT_LIBRARY_API std::vector<AffineFit> EstimateBodyRigid(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, const int *labels, int nx,
+                                                          int ny, int nz, int count, FitModel model = Rigid,
+                                                          const RansacOptions &opts = RansacOptions(), std::vector<int> *pairLabels = nullptr,
+                                                          std::vector<int> *inlierMask = nullptr);
+// starts of RefineDisplacements / RefineDisplacementsLabelled (their init) at `points`: the fit of the body each point lies in
+// (pointLabels: what LabelsAt returns; fits: what EstimateBodyRigid returns); a point of no body gets status 1 (no start)
+SIFT_LIBRARY_API std::vector<AffineFit> SeedsFromBodyFits(const std::vector<AffineFit> &fits, const std::vector<int> &pointLabels);
+// RefineDisplacementsMasked with every point limited to its own body, in one call: point i is treated as under the mask
+// labels == labels[point i] (include/sift3d_hip.h, sift3d_icgn_labelled); a point on a voxel whose label is <= 0 returns status 7.
+// active, pointLabels (may be null): resized to one count of active voxels and one label per point
+SIFT_LIBRARY_API std::vector<IcgnResult> RefineDisplacementsLabelled(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny,
+                                                                     int tnz, const int *labels, const std::vector<Cvec> &points,
+                                                                     const std::vector<AffineFit> *init = nullptr,
+                                                                     const IcgnOptions &opts = IcgnOptions(), float min_fraction = 0.f,
+                                                                     std::vector<int> *active = nullptr, std::vector<int> *pointLabels = nullptr,
+                                                                     bool tar_is_coefficients = false);
 // ComputeStrains, ValidateDisplacements and EvaluateField limited to a point's own body: a point is a neighbour of another only where
 // both have the same label > 0 (labels: one per point, what LabelsAt returns); a point or query whose label is <= 0 gets status 1 with no
 // neighbours.  keep (may be null): as for ComputeStrains with keep.  query_labels: one per query

@@ -1,4 +1,4 @@
-// cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine / PredictPositions / GuidedMatch / SearchDisplacements / RefineDisplacements / RefineDisplacementsMasked / MaskFromLevel / ValidateDisplacements /
+// cRegistration.cpp -- CPUSIFT::EstimateAffine / EstimateLocalAffine / PredictPositions / GuidedMatch / SearchDisplacements / RefineDisplacements / RefineDisplacementsMasked / RefineDisplacementsLabelled / EstimateBodyRigid / SeedsFromBodyFits / MaskFromLevel / ValidateDisplacements /
 // ComputeStrains over sift3d_fit_affine / sift3d_fit_affine_local / sift3d_predict_positions / sift3d_match_guided / sift3d_zncc_search / sift3d_icgn / sift3d_icgn_bspline / sift3d_icgn_masked /
 // sift3d_mask_from_level / sift3d_validate_displacements / sift3d_strain, CPUSIFT::LabelMask / LabelsAt and the labelled overloads over
 // sift3d_mask_label / sift3d_labels_at_points / sift3d_*_labelled, and
@@ -482,6 +482,74 @@ std::vector<int> LabelsAt(const int *labels, int nx, int ny, int nz, const std::
 	}
 	out.resize(m);
 	return out;
+}
+
+std::vector<AffineFit> EstimateBodyRigid(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, const int *labels, int nx, int ny, int nz,
+                                         int count, FitModel model, const RansacOptions &opts, std::vector<int> *pairLabels,
+                                         std::vector<int> *inlierMask) {
+	const size_t n = ref.size() < tar.size() ? ref.size() : tar.size();
+	if (pairLabels) pairLabels->assign(n, 0);
+	if (inlierMask) inlierMask->assign(n, 0);
+	const std::vector<float> p = pairs6(ref, tar, n);
+	std::vector<int> lab(n ? n : 1, 0);
+	int rc = sift3d_labels_at_positions(labels, nx, ny, nz, p.data(), 6, (int)n, lab.data(), 0, GetDevice());
+	const sift3d_ransac_options o = to_c(opts);
+	std::vector<sift3d_affine_fit> f(count > 0 ? count : 1);
+	std::vector<unsigned char> mask(n ? n : 1);
+	double sec = 0;
+	if (rc == SIFT3D_OK) rc = sift3d_fit_rigid_bodies(p.data(), (int)n, lab.data(), count, (int)model, &o, 0, GetDevice(), f.data(), mask.data(), &sec);
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] EstimateBodyRigid: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return std::vector<AffineFit>();
+	}
+	std::vector<AffineFit> res(count);
+	for (int b = 0; b < count; b++) from_c(f[b], sec, res[b]);
+	if (pairLabels) pairLabels->assign(lab.begin(), lab.begin() + n);
+	if (inlierMask) inlierMask->assign(mask.begin(), mask.begin() + n);
+	return res;
+}
+
+std::vector<AffineFit> SeedsFromBodyFits(const std::vector<AffineFit> &fits, const std::vector<int> &pointLabels) {
+	std::vector<AffineFit> res(pointLabels.size());
+	for (size_t i = 0; i < res.size(); i++) {
+		const int L = pointLabels[i];
+		if (L >= 1 && (size_t)L <= fits.size()) res[i] = fits[L - 1];
+		else res[i].status = 1;
+	}
+	return res;
+}
+
+std::vector<IcgnResult> RefineDisplacementsLabelled(const float *ref, int nx, int ny, int nz, const float *tar, int tnx, int tny, int tnz,
+                                                    const int *labels, const std::vector<Cvec> &points, const std::vector<AffineFit> *init,
+                                                    const IcgnOptions &opts, float min_fraction, std::vector<int> *active,
+                                                    std::vector<int> *pointLabels, bool tar_is_coefficients) {
+	const size_t m = points.size();
+	std::vector<IcgnResult> res(m);
+	if (active) active->assign(m, 0);
+	if (pointLabels) pointLabels->assign(m, 0);
+	std::vector<int> q;
+	if (!int_triples("RefineDisplacementsLabelled", "point", points, q)) return res;
+	if (init && init->size() != m) {
+		fprintf(stderr, "[3dsift_amd] RefineDisplacementsLabelled: %zu initial fits for %zu points\n", init->size(), m);
+		return res;
+	}
+	std::vector<double> p0;
+	if (init) icgn_init_rows(*init, nullptr, q, m, p0);
+	sift3d_icgn_options o = icgn_options_of(opts);
+	o.interpolation = opts.interpolation;  // 0, 1 or 2: one C entry for the three
+	std::vector<sift3d_icgn_result> r(m ? m : 1);
+	std::vector<int> n(m ? m : 1, 0), lab(m ? m : 1, 0);
+	double sec = 0;
+	const int rc = sift3d_icgn_labelled(ref, nx, ny, nz, tar, tnx, tny, tnz, labels, q.data(), (int)m, init ? p0.data() : nullptr, &o, min_fraction,
+	                                    tar_is_coefficients ? 1 : 0, 0, GetDevice(), r.data(), n.data(), lab.data(), &sec);
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] RefineDisplacementsLabelled: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return res;
+	}
+	icgn_records(r, sec, res);
+	if (active) active->assign(n.begin(), n.begin() + m);
+	if (pointLabels) pointLabels->assign(lab.begin(), lab.begin() + m);
+	return res;
 }
 
 // the strain call behind the ComputeStrains overloads: rc is what the input conversion returned; labels null: the unlabelled call

@@ -569,6 +569,28 @@ int sift3d_fit_rigid(const float *pairs6, int n, int model, const sift3d_ransac_
 int sift3d_fit_rigid_local(const float *pairs6, int n, const float *points3, int m, int k, float radius, int model,
                            const sift3d_ransac_options *o, int on_device, int device, sift3d_affine_fit *out,
                            int *neighbours, double *seconds);
+/* One fit per body (what "discrete DVC" of a granular specimen reports: the rigid motion of every grain, fitted from the grain's own
+ * matched keypoints).  pair_label[i] says which body pair i belongs to -- sift3d_labels_at_positions on the reference positions gives
+ * it from the labels of sift3d_mask_label.
+ *   Body L (1 <= L <= count) is one problem of the contract above with problem index p = L.  Its candidates are the pairs i with
+ *   pair_label[i] == L, in ascending i; c is their number.  A pair whose label is <= 0 or > count belongs to no body.
+ *   Everything else is sift3d_fit_rigid's contract word for word: draw<3> over c (u_j = fmix32(fmix32(s + L) + (4h + j))), the triad,
+ *   the scoring and the best hypothesis (the most inliers, ties to the smallest h), the Horn refit rounds, status 1 (c < 3), 2 and 3,
+ *   and how NaN and Inf travel.  o->iterations = 0 means 256, the local fits' default.
+ *   out[L-1] is body L's record, with candidates = c.  inlier_mask[i] (may be NULL) is 1 iff pair i is an inlier of its own body's
+ *   final A; it is 0 for a pair of no body and for a body with status 1 or 2.
+ *   Two calls return the same bytes.  Body L's record and mask bytes depend only on body L's pairs and their relative order: not on the
+ *   other bodies' pairs (non-finite ones included), nor on where in the list its own pairs stand.  A body's refit sums run in the
+ *   order of the global fit's on the same list.
+ * SIFT3D_ERR_ARG (checked before any device call): sift3d_fit_rigid's rules, count < 0, a NULL pair_label with n > 0, a NULL out with
+ * count > 0 (out may be NULL when count is 0).  n = 0 or count = 0 succeed (every record has status 1, every mask byte is 0).
+ * on_device != 0: pairs6 and pair_label are device pointers on `device`; out and inlier_mask are host memory.  The labels are brought
+ * to the host and the pairs' indices are grouped by body there (a stable counting sort), so the call holds 8 bytes per pair and 4 per
+ * body of pinned host memory beside the records; *seconds is the device time of the kernel. */
+int sift3d_fit_rigid_bodies(const float *pairs6, int n, const int *pair_label /* n */, int count, int model,
+                            const sift3d_ransac_options *o, int on_device, int device,
+                            sift3d_affine_fit *out /* count records, host */, unsigned char *inlier_mask /* n, host, may be NULL */,
+                            double *seconds);
 /* host only, no GPU: per fit the unit quaternion (w, x, y, z; w >= 0) of the rotation, the scale s = cbrt(det L) and the rotation
  * angle 2 atan2(sqrt(xx + yy + zz), w) in degrees of the linear part L of A: R = L / s, q from R by Shepperd's branch on the largest
  * of (trace, R00, R11, R22).  Meant for rigid and similarity fits; a fit with status != 0 gives NaN.  quat4: 4 m doubles, scale and
@@ -684,6 +706,10 @@ void sift3d_default_icgn_options(sift3d_icgn_options *o);
  * row (POI status 5).  SIFT3D_ERR_ARG: m < 0, or a NULL pointer with m > 0. */
 int sift3d_icgn_init_from_fits(const sift3d_affine_fit *fits, const int *points3, int m, double *init12);
 /* m POIs (x, y, z int triples) refined between ref (rnx x rny x rnz) and tar (tnx x tny x tnz); init12: m*12 or NULL (zero) */
+/* host only, no GPU: row i is what sift3d_icgn_init_from_fits writes for (fits[poi_label[i] - 1], point i); a label outside 1..count
+ * gives a NaN row, as a failed fit does.  fits: the count records of sift3d_fit_rigid_bodies.  SIFT3D_ERR_ARG: m < 0, count < 0, a NULL
+ * fits with count > 0, a NULL poi_label, points3 or init12 with m > 0. */
+int sift3d_icgn_init_from_body_fits(const sift3d_affine_fit *fits, int count, const int *poi_label, const int *points3, int m, double *init12);
 int sift3d_icgn(const float *ref, int rnx, int rny, int rnz, const float *tar, int tnx, int tny, int tnz, const int *points3, int m,
                 const double *init12, const sift3d_icgn_options *o, int on_device, int device, sift3d_icgn_result *out, double *seconds);
 
@@ -1260,6 +1286,14 @@ int sift3d_mask_from_level(const float *vol, int nx, int ny, int nz, double leve
  *   the legacy default stream; poi_label is host memory either way, filled by one kernel and one copy.  SIFT3D_ERR_ARG: NULL labels,
  *   a dimension < 1, nx * ny * nz >= 2^31, m < 0, NULL points3 or poi_label with m > 0.
  *
+ * sift3d_labels_at_positions: out_label[i] = labels at the voxel nearest to the fp32 position (x, y, z) = xyz[i * stride .. + 2], or 0
+ *   outside the volume.  Per axis the position is in the volume iff -0.5 <= (double)x && (double)x < n_axis - 0.5, tested before the
+ *   conversion (NaN and +-Inf fail the test); then i = (long long)floor((double)x + 0.5).  stride: floats between positions, >= 3;
+ *   stride = 6 labels the reference positions of pairs6 directly.  on_device == 0: a host loop, no GPU needed.  on_device != 0:
+ *   labels and xyz are device pointers on `device`, ordered behind the legacy default stream; out_label is host memory either way,
+ *   filled by one kernel and one copy.  SIFT3D_ERR_ARG: NULL labels, a dimension < 1, nx * ny * nz >= 2^31, n < 0, stride < 3, NULL xyz
+ *   or out_label with n > 0.
+ *
  * The labelled window calls: sift3d_strain, sift3d_validate_displacements and sift3d_field_eval with one sentence added to each
  * contract.  POI j is a neighbour (strain, validation) or a member (field) of centre i only if it is one under the unlabelled rule
  * and label[j] == label[i] and that label is > 0; for a field query k, query_label[k] takes the place of label[i].  A centre or query
@@ -1271,11 +1305,35 @@ int sift3d_mask_from_level(const float *vol, int nx, int ny, int nz, double leve
  * do not move a single fp64 sum -- as long as the bounding box of the contributing POIs, which places the cell grid and with it the
  * order of a window's entries, stays where it is (a validation record, which sums nothing, is independent without that).  label: m ints; query_label: nq ints; device pointers when on_device != 0.  SIFT3D_ERR_ARG: the unlabelled call's rules
  * with these, a NULL label, a NULL query_label with nq > 0.  A per-body mask for sift3d_icgn_masked is labels == L.
+ *
+ * sift3d_icgn_labelled: every POI correlated over its own body, in one call.  POI i is treated as sift3d_icgn_masked treats it under
+ * the mask labels == labels[q_i].
+ *   A voxel is active for POI i iff it and its six face neighbours lie in R and all seven carry the label L_i = labels[q_i], with
+ *   L_i > 0.  With L_i <= 0 the POI has n = 0 and therefore status 7; statuses 5 and 2 still come first.  Any positive int is a label:
+ *   the numbers need not be 1..count, so a watershed segmentation from elsewhere serves as well.
+ *   Everything else is the masked call's text: the statuses, min_fraction, the three interpolations, tar_is_coefficients, determinism,
+ *   the independence of a POI from the other POIs of the call, and R's values away from a POI's active voxels and their face
+ *   neighbours not being read for it.
+ *   Consequence (tests/test_gpu_icgn_labelled.py): for every label L, the records and the active counts of the POIs of L have the bits
+ *   of one sift3d_icgn_masked call on those POIs with the byte mask labels == L; with one positive label everywhere, those of
+ *   sift3d_icgn / sift3d_icgn_bspline.
+ *   poi_label[i] (may be NULL) = L_i, or 0 when q_i lies outside R; active[i] (may be NULL) as in the masked call.
+ * SIFT3D_ERR_ARG (checked before any device call): the masked call's rules with a NULL labels in the NULL mask's place, and
+ * rnx * rny * rnz >= 2^31.  on_device != 0: ref, tar, labels, points3 and init12 are device pointers on `device`; out, active and
+ * poi_label are host memory.  The call keeps 4 bytes per voxel of R (8 for host inputs) and 8 bytes per POI on the device beside
+ * sift3d_icgn's scratch; *seconds includes the pass that writes the interior labels.  sift3d_icgn2, the search and the screening
+ * stay unlabelled.
  * ------------------------------------------------------------------------------------------------------------ */
 int sift3d_mask_label(const unsigned char *mask, int nx, int ny, int nz, int connectivity /* 6 or 26 */, int min_voxels /* >= 1 */,
                       int *labels /* nx*ny*nz */, int *count, int on_device, int device, double *seconds);
 int sift3d_labels_at_points(const int *labels, int nx, int ny, int nz, const int *points3, int m, int *poi_label /* m, host */, int on_device,
                             int device);
+int sift3d_labels_at_positions(const int *labels, int nx, int ny, int nz, const float *xyz /* fp32 */, int stride /* floats, >= 3 */, int n,
+                               int *out_label /* n, host */, int on_device, int device);
+int sift3d_icgn_labelled(const float *ref, int rnx, int rny, int rnz, const float *tar, int tnx, int tny, int tnz,
+                         const int *labels /* rnx*rny*rnz */, const int *points3, int m, const double *init12,
+                         const sift3d_icgn_options *o, float min_fraction, int tar_is_coefficients, int on_device, int device,
+                         sift3d_icgn_result *out, int *active /* m, may be NULL */, int *poi_label /* m, may be NULL */, double *seconds);
 int sift3d_strain_labelled(const int *points3, const double *disp3, const unsigned char *valid, const int *label /* m */, int m,
                            const sift3d_strain_options *o, int on_device, int device, sift3d_strain_result *out, double *seconds);
 int sift3d_validate_displacements_labelled(const int *points3, const double *disp3, const double *grad9, const unsigned char *valid,
