@@ -69,6 +69,8 @@ SYMBOLS = [
     # several bodies: connected-component labels of a mask, and the three window calls limited to a POI's own body
     "sift3d_mask_label", "sift3d_labels_at_points", "sift3d_test_label_tile", "sift3d_strain_labelled",
     "sift3d_validate_displacements_labelled", "sift3d_field_eval_labelled",
+    # bodies that touch: the distance transform of a mask, exact erosion, and labels grown from the transform's cores
+    "sift3d_mask_distance", "sift3d_mask_from_distance", "sift3d_distance_at_points", "sift3d_default_split_options", "sift3d_mask_split",
     "sift3d_device_count", "sift3d_error_string", "sift3d_last_error",
     # typed input: 8 / 16-bit integer voxels uploaded at their own width and widened on the GPU
     "sift3d_dtype_bytes", "sift3d_create_typed", "sift3d_volume_to_device", "sift3d_test_ingest_launch",
@@ -228,6 +230,21 @@ SUBSET_DTYPE = np.dtype([("mean", "<f8"), ("dR", "<f8"), ("G", "<f8", (6,)), ("e
 assert SUBSET_DTYPE.itemsize == 104
 
 
+class SplitOptions(C.Structure):
+    """sift3d_split_options (include/sift3d_hip.h)"""
+    _fields_ = [("connectivity", C.c_int), ("core_dist2", C.c_int), ("min_core_voxels", C.c_int), ("border", C.c_int), ("max_rounds", C.c_int),
+                ("keep_unreached", C.c_int), ("min_voxels", C.c_int)]
+
+
+class SplitInfo(C.Structure):
+    """sift3d_split_info (include/sift3d_hip.h)"""
+    _fields_ = [("cores", C.c_int), ("unreached_bodies", C.c_int), ("rounds", C.c_int), ("unlabelled", C.c_int)]
+
+
+assert C.sizeof(SplitOptions) == 28 and C.sizeof(SplitInfo) == 16
+DIST2_NONE = 2 ** 31 - 1  # SIFT3D_DIST2_NONE
+
+
 class SlabDesc(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("z0", C.c_int), ("z1", C.c_int), ("halo", C.c_int),
                 ("noct_total", C.c_int), ("octave", C.c_int)]
@@ -359,6 +376,14 @@ def lib():
                                         C.POINTER(C.c_double)]
         L.sift3d_labels_at_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
         L.sift3d_test_label_tile.argtypes = [_ip]
+        L.sift3d_default_split_options.argtypes = [C.POINTER(SplitOptions)]
+        L.sift3d_default_split_options.restype = None
+        L.sift3d_mask_distance.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
+        L.sift3d_mask_from_distance.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                C.POINTER(C.c_double)]
+        L.sift3d_distance_at_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        L.sift3d_mask_split.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(SplitOptions), C.c_void_p, _ip, C.c_void_p,
+                                        C.POINTER(SplitInfo), C.c_int, C.c_int, C.POINTER(C.c_double)]
         L.sift3d_strain_labelled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(StrainOptions), C.c_int, C.c_int,
                                              C.c_void_p, C.POINTER(C.c_double)]
         L.sift3d_validate_displacements_labelled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -1107,6 +1132,107 @@ def labels_at_positions(labels, xyz, device=0):
     out = np.zeros(max(n, 1), np.int32)
     _check(lib().sift3d_labels_at_positions(lp, *tuple(lab.shape)[::-1], xp, stride, n, _p(out), int(on_dev), int(device)))
     return out[:n].copy()
+
+
+def _mask_input(mask):
+    """(pointer, the uint8 array / tensor, on_device) of an (nz, ny, nx) uint8 or bool mask"""
+    on_dev = _is_dev(mask)
+    if not on_dev:
+        mask = np.asarray(mask)
+    if len(mask.shape) != 3:
+        raise ValueError("mask: an (nz, ny, nx) volume is needed")
+    p, v = _mask(mask, mask.shape, on_dev)
+    return p, v, on_dev
+
+
+def _like(v, on_dev, dtype):
+    """(pointer, an uninitialised array / tensor of v's shape and kind)"""
+    if on_dev:
+        import torch
+
+        out = torch.empty(v.shape, dtype=getattr(torch, np.dtype(dtype).name), device=v.device)
+        return C.c_void_p(out.data_ptr()), out
+    out = np.empty(v.shape, dtype)
+    return _p(out), out
+
+
+def _device_of(v, on_dev, device):
+    return v.device.index if on_dev and v.device.index is not None else device
+
+
+def mask_distance(mask, border=1, device=0, with_seconds=False):
+    """sift3d_mask_distance: the exact squared Euclidean distance of every in-voxel of mask -- an (nz, ny, nx) uint8 (or bool) numpy
+    array or a contiguous uint8 device tensor; any non-zero byte is "in" -- to the nearest out-voxel, 0 for an out-voxel.  border 1: the
+    layer of voxels around the volume counts as out; border 0: only the volume's own out-voxels, DIST2_NONE everywhere when there is
+    none.  Returns an int32 array / tensor of the same shape and kind (with_seconds: and the device seconds)."""
+    vp, v, on_dev = _mask_input(mask)
+    op, out = _like(v, on_dev, np.int32)
+    sec = C.c_double(0)
+    _check(lib().sift3d_mask_distance(vp, *tuple(v.shape)[::-1], int(border), op, int(on_dev), int(_device_of(v, on_dev, device)), C.byref(sec)))
+    return (out, sec.value) if with_seconds else out
+
+
+def _dist_input(dist2):
+    """(pointer, the int32 array / tensor, on_device) of an (nz, ny, nx) int32 volume"""
+    on_dev = _is_dev(dist2)
+    if not on_dev:
+        dist2 = np.asarray(dist2)
+    if len(dist2.shape) != 3:
+        raise ValueError("dist2: an (nz, ny, nx) volume is needed")
+    p, v = _label_volume(dist2, dist2.shape, on_dev)
+    return p, v, on_dev
+
+
+def mask_from_distance(dist2, level2, device=0, with_seconds=False):
+    """sift3d_mask_from_distance: the uint8 mask dist2 >= level2 of mask_distance's output (an int32 numpy array or device tensor): with
+    level2 >= 1 the exact erosion of the mask by the open ball of squared radius level2.  Returns an array / a tensor of the same kind
+    (with_seconds: and the device seconds)."""
+    vp, v, on_dev = _dist_input(dist2)
+    op, out = _like(v, on_dev, np.uint8)
+    sec = C.c_double(0)
+    _check(lib().sift3d_mask_from_distance(vp, *tuple(v.shape)[::-1], int(level2), op, int(on_dev), int(_device_of(v, on_dev, device)),
+                                           C.byref(sec)))
+    return (out, sec.value) if with_seconds else out
+
+
+def distance_at(dist2, points, device=0):
+    """sift3d_distance_at_points: dist2 (m,) int32 at each point ((m, 3) int32 x, y, z) of mask_distance's output, an int32 numpy array or
+    device tensor; 0 for a point outside the volume.  With a host array it needs no GPU."""
+    vp, v, on_dev = _dist_input(dist2)
+    qp, m, q = _table(points, np.int32, 3, dist2)
+    out = np.zeros(max(m, 1), np.int32)
+    _check(lib().sift3d_distance_at_points(vp, *tuple(v.shape)[::-1], qp, m, _p(out), int(on_dev), int(_device_of(v, on_dev, device))))
+    return out[:m].copy()
+
+
+SPLIT_OPTIONS = ("connectivity", "core_dist2", "min_core_voxels", "border", "max_rounds", "keep_unreached", "min_voxels")
+SPLIT_INFO = ("cores", "unreached_bodies", "rounds", "unlabelled")
+
+
+def default_split_options():
+    """sift3d_default_split_options as a dict (needs no GPU)"""
+    o = _options(SplitOptions, "sift3d_default_split_options", SPLIT_OPTIONS, "split", {})
+    return {k: getattr(o, k) for k in SPLIT_OPTIONS}
+
+
+def mask_split(mask, device=0, with_seconds=False, return_distance=False, **opts):
+    """sift3d_mask_split: labels of bodies that may touch.  The cores -- the components of mask_distance(mask, border) >= core_dist2 --
+    are numbered as mask_label numbers them and grown back over the mask in synchronous rounds, a voxel taking the label of its labelled
+    neighbour with the largest distance (ties: the smallest label); with keep_unreached the components no core reaches are numbered
+    behind the cores.  mask: as for mask_label.  Options: SPLIT_OPTIONS (default_split_options()).  Returns labels (int32, the mask's
+    shape and kind), count and info, a dict of SPLIT_INFO (return_distance: then dist2, what mask_distance returns; with_seconds: then
+    the device seconds)."""
+    o = _options(SplitOptions, "sift3d_default_split_options", SPLIT_OPTIONS, "split", {k: int(v) for k, v in opts.items()})
+    vp, v, on_dev = _mask_input(mask)
+    op, out = _like(v, on_dev, np.int32)
+    dp, dist = _like(v, on_dev, np.int32) if return_distance else (None, None)
+    sec, count, info = C.c_double(0), C.c_int(0), SplitInfo()
+    _check(lib().sift3d_mask_split(vp, *tuple(v.shape)[::-1], C.byref(o), op, C.byref(count), dp, C.byref(info), int(on_dev),
+                                   int(_device_of(v, on_dev, device)), C.byref(sec)))
+    res = (out, count.value, {k: getattr(info, k) for k in SPLIT_INFO})
+    if return_distance:
+        res += (dist,)
+    return res + (sec.value,) if with_seconds else res
 
 
 SEARCH_OPTIONS = ("subset_radius", "search_radius")

@@ -417,6 +417,21 @@ void launch_mask_label(const unsigned char *d_mask, int nx, int ny, int nz, int 
 // d_out[i] = the label at voxel d_pts[i], 0 outside the volume
 void launch_labels_at(const int *d_labels, int nx, int ny, int nz, const int *d_pts, int m, int *d_out, hipStream_t st);
 
+// ---- kernels_edt.hip: the distance transform of a byte mask and the seeded growth of labels (sift3d_mask_distance, sift3d_mask_split) --
+constexpr int kEdtNone = 2147483647;  // SIFT3D_DIST2_NONE: no out-voxel anywhere
+// d_dist2 (n ints): the squared distance of every voxel of d_mask to the nearest out-voxel (border: the layer around the volume is
+// out); d_tmp: n ints.  n = nx ny nz < 2^31 and (nx + 1)^2 + (ny + 1)^2 + (nz + 1)^2 < 2^31.  Three launches.
+void launch_mask_distance(const unsigned char *d_mask, int nx, int ny, int nz, int border, int *d_dist2, int *d_tmp, hipStream_t st);
+// d_mask[i] = 1 where d_dist2[i] >= level2, else 0
+void launch_mask_from_distance(const int *d_dist2, size_t n, int level2, unsigned char *d_mask, hipStream_t st);
+// one round of the growth: d_dst = d_src with every unlabelled in-voxel (d_dist2 > 0) that has a labelled neighbour given the label of
+// the neighbour with the largest d_dist2 (ties: the smallest label); *d_grown += the voxels labelled.  d_dst != d_src
+void launch_split_grow(const int *d_dist2, const int *d_src, int *d_dst, int nx, int ny, int nz, int connectivity, int *d_grown, hipStream_t st);
+// d_rest[i] = 1 where d_dist2[i] > 0 and d_labels[i] == 0, else 0
+void launch_split_rest(const int *d_dist2, const int *d_labels, size_t n, unsigned char *d_rest, hipStream_t st);
+// an unlabelled in-voxel takes cores + d_extra[i] where that is > 0 (d_extra may be null); *d_unlabelled += the in-voxels left at 0
+void launch_split_finish(const int *d_dist2, int *d_labels, const int *d_extra, int cores, size_t n, int *d_unlabelled, hipStream_t st);
+
 // ---- kernels_icgn2.hip: second-order IC-GN (sift3d_icgn2, include/sift3d_hip.h) --------------------------------------------------
 size_t icgn2_state_bytes();  // per-POI scratch record of the prepare kernel
 // as launch_icgn, with m * 30 doubles in d_init and m * icgn2_state_bytes() in d_state

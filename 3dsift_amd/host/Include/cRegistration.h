@@ -348,6 +348,36 @@ SIFT_LIBRARY_API bool LabelMask(const unsigned char *mask, int nx, int ny, int n
                                 double *seconds = nullptr);
 // the label at each point (0 for a point outside the volume); host only.  Empty when a coordinate is not integral
 SIFT_LIBRARY_API std::vector<int> LabelsAt(const int *labels, int nx, int ny, int nz, const std::vector<Cvec> &points);
+// ---- bodies that touch (include/sift3d_hip.h, sift3d_mask_distance and sift3d_mask_split) ----------------------------------------------
+// dist2 (nx x ny x nz ints, host memory): the exact squared Euclidean distance of every in-voxel of mask to the nearest out-voxel, 0
+// for an out-voxel.  border: the layer of voxels around the volume counts as out; without it and without an out-voxel every entry is
+// SIFT3D_DIST2_NONE.  false: the call failed (message on stderr).  seconds (may be null): device time.
+SIFT_LIBRARY_API bool DistanceTransform(const unsigned char *mask, int nx, int ny, int nz, bool border, int *dist2, double *seconds = nullptr);
+// mask = dist2 >= level2: with level2 >= 1 the exact erosion by the open ball of squared radius level2 of the mask DistanceTransform saw
+SIFT_LIBRARY_API bool ErodeMask(const int *dist2, int nx, int ny, int nz, int level2, unsigned char *mask, double *seconds = nullptr);
+// dist2 at each point (0 for a point outside the volume): the squared distance of a point to its body's surface; host only.  Empty when
+// a coordinate is not integral
+SIFT_LIBRARY_API std::vector<int> DistancesAt(const int *dist2, int nx, int ny, int nz, const std::vector<Cvec> &points);
+struct SplitOptions {
+	int connectivity = 6;     // 6 or 26: of the cores' components and of the growth
+	int core_dist2 = 16;      // a core voxel has dist2 >= core_dist2: above the squared half-width of the widest neck between two grains,
+	                          // at most the squared inradius of the smallest grain to keep apart
+	int min_core_voxels = 1;  // smaller cores seed nothing
+	bool border = true;       // as DistanceTransform
+	int max_rounds = 0;       // growth rounds at most; 0: until a round labels nothing
+	bool keep_unreached = true;  // the components no core reaches become bodies too, numbered behind the cores
+	int min_voxels = 1;       // size cut of those components
+};
+struct SplitInfo {
+	int cores = 0, unreached_bodies = 0, rounds = 0, unlabelled = 0;
+};
+// LabelMask for bodies that touch: the components of dist2 >= core_dist2 are numbered as LabelMask numbers them and grown back over the
+// mask in synchronous rounds, a voxel taking the label of its labelled neighbour with the largest dist2 (ties: the smallest label).  A
+// grain too small to hold a core is a body of its own only where it stands alone; one that touches a grain with a core is absorbed.
+// dist2 (may be null): the transform; info (may be null).  false: the call failed (message on stderr)
+SIFT_LIBRARY_API bool SplitBodies(const unsigned char *mask, int nx, int ny, int nz, int *labels, int *count,
+                                  const SplitOptions &o = SplitOptions(), int *dist2 = nullptr, SplitInfo *info = nullptr,
+                                  double *seconds = nullptr);
 // One rigid (or similarity) fit per body of a labelled specimen (include/sift3d_hip.h, sift3d_fit_rigid_bodies): every matched pair is
 // given the label at the voxel nearest to its reference position (0 outside the volume) and body L = 1..count is fitted from its own
 // pairs alone; the result holds `count` fits, body L at index L - 1 (status 1: fewer than 3 pairs).  pairLabels (may be null): resized

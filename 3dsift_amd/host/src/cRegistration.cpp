@@ -484,6 +484,54 @@ std::vector<int> LabelsAt(const int *labels, int nx, int ny, int nz, const std::
 	return out;
 }
 
+bool DistanceTransform(const unsigned char *mask, int nx, int ny, int nz, bool border, int *dist2, double *seconds) {
+	const int rc = sift3d_mask_distance(mask, nx, ny, nz, border ? 1 : 0, dist2, 0, GetDevice(), seconds);
+	if (rc != SIFT3D_OK) fprintf(stderr, "[3dsift_amd] DistanceTransform: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+	return rc == SIFT3D_OK;
+}
+
+bool ErodeMask(const int *dist2, int nx, int ny, int nz, int level2, unsigned char *mask, double *seconds) {
+	const int rc = sift3d_mask_from_distance(dist2, nx, ny, nz, level2, mask, 0, GetDevice(), seconds);
+	if (rc != SIFT3D_OK) fprintf(stderr, "[3dsift_amd] ErodeMask: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+	return rc == SIFT3D_OK;
+}
+
+std::vector<int> DistancesAt(const int *dist2, int nx, int ny, int nz, const std::vector<Cvec> &points) {
+	const size_t m = points.size();
+	std::vector<int> q, out(m ? m : 1, 0);
+	if (!int_triples("DistancesAt", "point", points, q)) return std::vector<int>();
+	const int rc = sift3d_distance_at_points(dist2, nx, ny, nz, q.data(), (int)m, out.data(), 0, GetDevice());
+	if (rc != SIFT3D_OK) {
+		fprintf(stderr, "[3dsift_amd] DistancesAt: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+		return std::vector<int>();
+	}
+	out.resize(m);
+	return out;
+}
+
+bool SplitBodies(const unsigned char *mask, int nx, int ny, int nz, int *labels, int *count, const SplitOptions &o, int *dist2, SplitInfo *info,
+                 double *seconds) {
+	sift3d_split_options c;
+	sift3d_default_split_options(&c);
+	c.connectivity = o.connectivity;
+	c.core_dist2 = o.core_dist2;
+	c.min_core_voxels = o.min_core_voxels;
+	c.border = o.border ? 1 : 0;
+	c.max_rounds = o.max_rounds;
+	c.keep_unreached = o.keep_unreached ? 1 : 0;
+	c.min_voxels = o.min_voxels;
+	sift3d_split_info i = {0, 0, 0, 0};
+	const int rc = sift3d_mask_split(mask, nx, ny, nz, &c, labels, count, dist2, &i, 0, GetDevice(), seconds);
+	if (rc != SIFT3D_OK) fprintf(stderr, "[3dsift_amd] SplitBodies: %s (%s)\n", sift3d_error_string(rc), sift3d_last_error());
+	if (info && rc == SIFT3D_OK) {
+		info->cores = i.cores;
+		info->unreached_bodies = i.unreached_bodies;
+		info->rounds = i.rounds;
+		info->unlabelled = i.unlabelled;
+	}
+	return rc == SIFT3D_OK;
+}
+
 std::vector<AffineFit> EstimateBodyRigid(const std::vector<Cvec> &ref, const std::vector<Cvec> &tar, const int *labels, int nx, int ny, int nz,
                                          int count, FitModel model, const RansacOptions &opts, std::vector<int> *pairLabels,
                                          std::vector<int> *inlierMask) {

@@ -1343,6 +1343,89 @@ int sift3d_field_eval_labelled(const int *points3, const double *disp3, const un
                                const double *queries3, const int *query_label /* nq */, int nq, const sift3d_field_options *o, int on_device,
                                int device, sift3d_field_result *out, double *seconds);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Bodies that touch: the distance transform of a mask and labels grown from its cores (no reference counterpart: the marker-based
+ * separation of touching grains).  Grains that touch are one component of a threshold mask, so sift3d_mask_label returns one label for
+ * all of them; sift3d_mask_split gives every grain that is wide enough to hold a core a label of its own.  tests/split_ref.py restates
+ * both rules in NumPy.
+ *
+ * sift3d_mask_distance: the exact squared Euclidean distance of every in-voxel to the nearest out-voxel.
+ *   Layout [z][y][x], x fastest; any non-zero mask byte is "in".  dist2[i] = 0 for an out-voxel.  For an in-voxel i, dist2[i] is the
+ *   minimum over all out-voxels j of (xi - xj)^2 + (yi - yj)^2 + (zi - zj)^2, an exact integer.
+ *   border = 1: the voxels just outside the volume (a coordinate of -1 or n on any axis) count as out-voxels, so an in-voxel on a face
+ *   of the volume has dist2 = 1: what a specimen cut by the field of view needs.  border = 0: only the volume's own out-voxels count,
+ *   and where there is none every in-voxel gets SIFT3D_DIST2_NONE.
+ *   With border = 0 and at least one out-voxel the result is rint(scipy.ndimage.distance_transform_edt(mask) ** 2); with border = 1
+ *   the same of the mask padded by one layer of zeros, cropped back.
+ *   Determinism: the output is a function of the input alone (integer minima): two calls return the same bytes.
+ *   SIFT3D_ERR_ARG (checked before any device call): NULL mask or dist2, a dimension < 1, nx * ny * nz >= 2^31,
+ *   (nx + 1)^2 + (ny + 1)^2 + (nz + 1)^2 >= 2^31 (every distance fits an int), border outside 0..1.  SIFT3D_ERR_NO_DEVICE after that
+ *   check when no GPU is visible: there is no CPU fallback.  on_device != 0: mask and dist2 are device pointers on `device`, ordered
+ *   behind the legacy default stream; otherwise both are host memory.  *seconds (may be NULL): device time of the three kernels.
+ *   Device memory: beside dist2 the call keeps 4 bytes per voxel, and with host pointers 5 more (the mask and dist2), in a block that
+ *   grows with the largest call so far and stays allocated.
+ *
+ * sift3d_mask_from_distance: mask[i] = 1 where dist2[i] >= level2, else 0: with level2 >= 1 the exact erosion of the mask by the open
+ *   ball of squared radius level2.  SIFT3D_ERR_ARG (before any device call): NULL dist2 / mask, a dimension < 1, 2^39 voxels or more.
+ *   on_device, *seconds: as sift3d_mask_from_level.
+ *
+ * sift3d_distance_at_points: poi_dist2[i] = dist2 at voxel points3[i] (x, y, z), or 0 when that voxel lies outside the volume: the
+ *   squared distance of a POI to the surface of its body, by which a caller drops or down-weights the POIs whose subset reaches across
+ *   it.  Pointers, the host loop of on_device == 0 and SIFT3D_ERR_ARG: as sift3d_labels_at_points.
+ *
+ * sift3d_mask_split: labels of bodies that may touch.  The rule, with d = the transform and c = connectivity:
+ *   1. d = sift3d_mask_distance(mask, border).
+ *   2. Cores: L0 = sift3d_mask_label(d >= core_dist2, c, min_core_voxels), with that call's numbering (ascending lowest voxel of the
+ *      core); info->cores is its count.
+ *   3. Growth in synchronous rounds, from labels = L0.  In a round every in-voxel whose label was 0 at the start of the round looks at
+ *      its 6 or 26 neighbours inside the volume whose label was > 0 at the start of the round; if there is one, the voxel takes the
+ *      label of the neighbour with the largest d, and among neighbours of equal d the smallest label.  A labelled voxel never changes.
+ *      The growth stops after the first round that labels nothing, or after max_rounds rounds (max_rounds > 0); info->rounds is the
+ *      number of rounds that labelled at least one voxel.
+ *   4. keep_unreached = 1: the in-voxels still at 0 are labelled by sift3d_mask_label(that set, c, min_voxels) and numbered
+ *      cores + 1 ...; info->unreached_bodies is their count (0 with keep_unreached = 0).  A grain too small to hold a core keeps an
+ *      identity when it stands alone; one that touches a grain with a core is absorbed by it.
+ *   5. *count = cores + unreached_bodies; info->unlabelled = the in-voxels left at 0.  labels[i] = 0 for every out-voxel.
+ *   Consequences (tests/test_split_cpu.py, tests/test_gpu_split.py): (a) with core_dist2 = 1, and min_core_voxels = 1 or
+ *   keep_unreached = 0, labels and count are the bytes of sift3d_mask_label(mask, c, min_core_voxels) and rounds = 0; (b) two calls
+ *   return the same bytes (no result depends on the order of execution: a round reads one volume and writes another); (c) the voxels of
+ *   a label are connected under c; (d) two voxels with the same split label have the same sift3d_mask_label label: the split only
+ *   refines; (e) the labels on the core voxels are L0's.
+ *   Choosing core_dist2: above the squared half-width of the widest neck between two grains (or they share a core), and at most the
+ *   squared inradius of the smallest grain to keep apart (or it holds no core).
+ *   dist2 (may be NULL): the transform, as sift3d_mask_distance returns it.  info (may be NULL).
+ *   SIFT3D_ERR_ARG (checked before any device call): sift3d_mask_distance's and sift3d_mask_label's rules, NULL o, labels or count,
+ *   connectivity other than 6 or 26, core_dist2 < 1, min_core_voxels < 1, border outside 0..1, max_rounds < 0, keep_unreached outside
+ *   0..1, min_voxels < 1.  SIFT3D_ERR_NO_DEVICE after that check when no GPU is visible.  on_device != 0: mask, labels and dist2 are
+ *   device pointers on `device`, ordered behind the legacy default stream; otherwise host memory.  count and info are host memory.
+ *   *seconds (may be NULL): device time from the first kernel to the last, the read-backs of the round counters included (one per eight
+ *   rounds).  Device memory: beside labels 9 bytes per voxel and 4 bytes per 2048 voxels, 4 more per voxel when dist2 is NULL or host
+ *   memory, and with host pointers 5 more (the mask and the labels).
+ * ------------------------------------------------------------------------------------------------------------ */
+#define SIFT3D_DIST2_NONE 2147483647
+typedef struct {
+	int connectivity;    /* 6 or 26: of the cores' components and of the growth                                  default 6  */
+	int core_dist2;      /* >= 1: a core voxel has dist2 >= core_dist2                                           default 16 */
+	int min_core_voxels; /* >= 1: smaller cores seed nothing                                                     default 1  */
+	int border;          /* 0 or 1, as sift3d_mask_distance                                                      default 1  */
+	int max_rounds;      /* >= 0: growth rounds at most; 0 = until a round labels nothing                        default 0  */
+	int keep_unreached;  /* 0: in-voxels no core reaches stay 0; 1: their components become bodies too           default 1  */
+	int min_voxels;      /* >= 1: size cut of those components                                                   default 1  */
+} sift3d_split_options;
+typedef struct {
+	int cores, unreached_bodies, rounds, unlabelled;
+} sift3d_split_info;
+void sift3d_default_split_options(sift3d_split_options *o);
+int sift3d_mask_distance(const unsigned char *mask, int nx, int ny, int nz, int border /* 0 or 1 */, int *dist2 /* nx*ny*nz */, int on_device,
+                         int device, double *seconds);
+int sift3d_mask_from_distance(const int *dist2, int nx, int ny, int nz, int level2, unsigned char *mask, int on_device, int device,
+                              double *seconds);
+int sift3d_distance_at_points(const int *dist2, int nx, int ny, int nz, const int *points3, int m, int *poi_dist2 /* m, host */, int on_device,
+                              int device);
+int sift3d_mask_split(const unsigned char *mask, int nx, int ny, int nz, const sift3d_split_options *o, int *labels /* nx*ny*nz */, int *count,
+                      int *dist2 /* nx*ny*nz, may be NULL */, sift3d_split_info *info /* may be NULL */, int on_device, int device,
+                      double *seconds);
+
 /* Test hooks, rare-path counters and the unit-level debug entry points live in include/sift3d_hip_test.h: this header is the
  * product boundary only. */
 const char *sift3d_error_string(int code);
